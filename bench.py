@@ -10,10 +10,13 @@
 
 A step = one y4_predict over one batch of 32 float32 NHWC images already resident in HBM (the PCIe-inclusive rate is
 noted in DESIGN.md, it is never `value`) followed by ONE 77 KB device->host copy of the four NMS outputs (+ kept
-indices), as SURVEY.md section 8(d) defines the metric.  Timing: W untimed warm-up steps, then R (--blocks, default 5)
-blocks of EXACTLY K steps, each block bracketed by barrier + torch.cuda.synchronize() on both sides and reduced with MAX
-over ranks; `ms_per_step` / `value` are the MEDIAN block (one 0.13 s sample on a pool whose boxes differ by +-3 % was too
-noisy), every block is listed under `blocks_ms_per_step`.
+indices), as SURVEY.md section 8(d) defines the metric.  Timing: W untimed warm-up steps, then EXACTLY K timed steps,
+split into R (--blocks, default 1) blocks of near-equal size, each block bracketed by barrier + torch.cuda.synchronize() on
+both sides and reduced with MAX over ranks; `ms_per_step` is the summed block time / K and `value` the images of the K steps
+/ that time; every block is listed under `blocks_ms_per_step`.
+`--dump-outputs DIR` writes what the last timed step returned -- boxes, scores, classes, valid, kept (the global batch,
+every rank's shard) -- as DIR/<name>.npy in float32 / float64 after the timed steps; weights and images are seeded, so
+two builds run with the same arguments can be compared output for output.
 By default `--in-flight 2`: step i runs on HIP stream / activation workspace i % 2 (two independent batches overlap on the
 GPU; every step of a block still completes inside the block's bracket); `--in-flight 1` = every step on one stream, and
 `single_stream_value` in the line is that rate measured in the same process.
@@ -31,7 +34,6 @@ import argparse
 import json
 import os
 import socket
-import statistics
 import subprocess
 import sys
 import time
@@ -189,6 +191,40 @@ def committed_traffic(args, fused_stem, chained, staged, res_mask, tiles):
     return None, "null because: " + ("; ".join(reasons) if reasons else "no committed PMC pass exists")
 
 
+def block_sizes(steps, blocks):
+    """The K timed steps split into min(blocks, K) blocks whose sizes differ by at most one step (they sum to K)."""
+    b = min(blocks, steps)
+    return [steps // b + (i < steps % b) for i in range(b)]
+
+
+# what one step returns (Engine.alloc_outputs_flat order), and the dtype each is written in
+OUTPUT_NAMES = (("boxes", "float32"), ("scores", "float32"), ("classes", "float32"), ("valid", "float64"), ("kept", "float64"))
+
+
+def dump_outputs(out_dir, shards, T):
+    """Writes the outputs of one step as out_dir/<name>.npy: `shards` = every rank's int32 host block of that step
+    (Engine.alloc_outputs_flat layout; rank order = image order), T = detections per image.  The float outputs keep their
+    float32 bits, the integer ones (valid count, kept box indices) become float64, exactly."""
+    import numpy as np
+    parts = {name: [] for name, _ in OUTPUT_NAMES}
+    for block in shards:
+        block = np.asarray(block, dtype=np.int32)
+        n = block.size // (7 * T + 1)                         # boxes 4T + scores T + classes T + valid 1 + kept T per image
+        sizes = [n * T * 4, n * T, n * T, n, n * T]
+        offs = np.cumsum([0] + sizes)
+        shapes = [(n, T, 4), (n, T), (n, T), (n,), (n, T)]
+        for i, (name, _) in enumerate(OUTPUT_NAMES):
+            v = block[offs[i]:offs[i + 1]].reshape(shapes[i])
+            parts[name].append(v.view(np.float32) if i < 3 else v)
+    os.makedirs(out_dir, exist_ok=True)
+    written = {}
+    for name, dtype in OUTPUT_NAMES:
+        arr = np.ascontiguousarray(np.concatenate(parts[name], axis=0).astype(dtype))
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
+        written[name] = list(arr.shape)
+    return written
+
+
 def free_port():
     with socket.socket() as s:
         s.bind(("127.0.0.1", 0))
@@ -210,7 +246,8 @@ def parse_args(argv):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--blocks", type=int, default=5, help="timed blocks of --steps steps each; the median block is reported")
+    ap.add_argument("--blocks", type=int, default=1,
+                    help="split the --steps timed steps into this many barrier-bracketed blocks (at most one per step)")
     ap.add_argument("--size", type=int, default=608)
     ap.add_argument("--classes", type=int, default=80)
     ap.add_argument("--batch", type=int, default=32, help="images per GPU per step")
@@ -256,6 +293,8 @@ def parse_args(argv):
     ap.add_argument("--first-image", type=int, default=0,
                     help="global index of this run's first synthetic image (image i depends on (seed, i) only: a one-process run "
                          "with --first-image 32 computes what rank 1 of a two-rank run computes)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the last timed step's outputs (boxes, scores, classes, valid, kept) as DIR/<name>.npy")
     ap.add_argument("--dry-run", action="store_true",
                     help="launcher / protocol self-test on CPU (gloo, no engine, no GPU work): the line says so")
     return ap.parse_args(argv)
@@ -281,19 +320,19 @@ def dry_run(args):
         D.broadcast_bytes(blob, 0)
         assert int(blob[123]) == 7
     local, own = [], []
-    for _ in range(args.blocks):
+    for nb in block_sizes(args.steps, args.blocks):
         D.barrier()
         t0 = time.perf_counter()
-        for _ in range(args.steps):
+        for _ in range(nb):
             time.sleep(0.001 * (1 + (rank == world - 1 and os.environ.get("Y4_DRY_STRAGGLER") == "1")))
-        own.append(time.perf_counter() - t0)                 # this rank's own K steps, before it waits for the others
+        own.append(time.perf_counter() - t0)                 # this rank's own steps of the block, before it waits for the others
         D.barrier()
         local.append(time.perf_counter() - t0)
     blocks = D.max_over_ranks(local)
-    my_ms = statistics.median(own) / args.steps * 1e3
+    my_ms = sum(own) / args.steps * 1e3
     rank_ms, devices = D.gather_objects(my_ms), D.gather_objects(bound)
     if rank == 0:
-        dt = statistics.median(blocks)
+        dt = sum(blocks)
         print(json.dumps({"metric": METRIC + " [DRY RUN: no GPU work]", "value": round(args.batch * world * args.steps / dt, 2),
                           "unit": "images/sec", "n_gpus": dist.get_world_size() if dist.is_initialized() else 1,
                           "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 4),
@@ -455,20 +494,22 @@ def main():
         step()
     torch.cuda.synchronize()
     if depth == 1:                                           # one stream: the events sit in the timed blocks themselves
-        eng.timing_begin(min(args.steps * args.blocks, 4096), coarse=not args.per_op)
+        eng.timing_begin(min(args.steps, 4096), coarse=not args.per_op)
+    sizes = block_sizes(args.steps, args.blocks)             # the K timed steps, in barrier-bracketed blocks
     local, own = [], []
-    for _ in range(args.blocks):
+    for nb in sizes:
         D.barrier()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        for _ in range(args.steps):
+        for _ in range(nb):
             step()
         torch.cuda.synchronize()
-        own.append(time.perf_counter() - t0)               # this rank's own K steps, before it waits for the others
+        own.append(time.perf_counter() - t0)               # this rank's own steps of the block, before it waits for the others
         D.barrier()
         torch.cuda.synchronize()
-        local.append(time.perf_counter() - t0)              # nothing but the K steps between the two brackets
+        local.append(time.perf_counter() - t0)              # nothing but the block's steps between the two brackets
     blocks = D.max_over_ranks(local)                        # one reduction, after every timed region
+    last_step = slot_host[(counter[0] - 1) % depth].numpy().copy()   # what the last timed step returned (before any later pass)
     same = all(torch.equal(slot_host[0], h) for h in slot_host[1:])     # every slot ran the same batch: same outputs
     # ---- kernel-level attribution: HIP events on the launch stream need kernels that run one after the other, so the
     # per-kernel-family times behind `roofline` / `breakdown_ms_per_step` come from a single-stream pass of the same step
@@ -476,7 +517,7 @@ def main():
     # around one of them also spans its neighbour's work.  With D = 1 the events sit in the timed blocks themselves.
     if depth == 1:
         ops, nrec = eng.timing_end()
-        single_ms = statistics.median(blocks) / args.steps * 1e3
+        single_ms = sum(blocks) / args.steps * 1e3
     else:
         attrib_steps = min(args.steps, 4096)
         eng.timing_begin(attrib_steps, coarse=not args.per_op)   # 8 events per step unless --per-op
@@ -513,13 +554,18 @@ def main():
             ms = min(backbone_pass(nslots) for _ in range(3))        # best of 3 short passes (each K steps)
             backbone_wall[name] = {"ms_per_step": round(ms, 4), "frac": round(bb_flops / (ms * 1e-3) / 1e12 / peak_tf, 4)}
     # every rank's own median block (a straggler must be visible the first time this runs on a real node)
-    my_ms = statistics.median(own) / args.steps * 1e3
+    my_ms = sum(own) / args.steps * 1e3
     rank_ms = [float(v) for v in D.gather_objects(my_ms)]
+    dumped = None
+    if args.dump_outputs:
+        shards = D.gather_objects(last_step)                 # every rank's shard, in image order
+        if rank == 0:
+            dumped = dump_outputs(args.dump_outputs, shards, eng.T)
     rank_digests = D.gather_objects(digest)                  # every rank's outputs of its last step (its own shard of the batch)
     rank_tiles = D.gather_objects(hashlib.sha256(json.dumps(eng.get_tiles()).encode()).hexdigest()[:16])   # ... and its tile set
 
     if rank == 0:
-        dt = statistics.median(blocks)
+        dt = sum(blocks)
         n_img = args.batch * world * args.steps
         is_conv = lambda name: name.startswith("c") and name != "c0"
         conv_ms = sum(ms for name, ms in ops if is_conv(name))
@@ -556,15 +602,17 @@ def main():
                        "batch_per_gpu": args.batch, "global_batch": args.batch * world,
                        "sharding": f"batch split over {world} rank(s), no data-path collective"},
             "outputs_sha256": digest,
+            "dumped_outputs": ({"dir": args.dump_outputs, "shapes": dumped, "step": "the last timed step"} if dumped else None),
             "rank_outputs_sha256": rank_digests if world > 1 else None,
             "rank_tiles_sha256": rank_tiles if world > 1 else None,
             "first_image": lo,
-            "blocks_ms_per_step": [round(b / args.steps * 1e3, 4) for b in blocks],
+            "blocks_ms_per_step": [round(b / nb * 1e3, 4) for b, nb in zip(blocks, sizes)],
             "rank_ms_per_step": {"min": round(min(rank_ms), 4), "max": round(max(rank_ms), 4),
                                  "per_rank": [round(v, 4) for v in rank_ms],
-                                 "what": "each rank's own K steps (median block, stopped BEFORE the closing barrier) / K; ms_per_step above is "
-                                         "the barrier-bracketed block, max over ranks"},
-            "timing": f"median of {args.blocks} blocks of {args.steps} steps, each barrier+synchronize bracketed, max over ranks; "
+                                 "what": "each rank's own K steps (every block stopped BEFORE its closing barrier) / K; ms_per_step above "
+                                         "is the barrier-bracketed blocks, max over ranks"},
+            "timing": f"{args.steps} timed steps in {len(sizes)} block(s) of {'/'.join(map(str, sizes))} steps, each "
+                      f"barrier+synchronize bracketed, max over ranks, summed / {args.steps}; "
                       f"{depth} batch(es) in flight per GPU (step i on HIP stream / workspace i % {depth}, shared weights)",
             "in_flight": depth, "schedule": schedule_src,
             "activation_workspace_bytes": int(eng.act_bytes), "workspace_aliasing": bool(args.alias_workspace),

@@ -160,6 +160,12 @@ def gather_objects(obj):
 
 
 def barrier():
+    import torch
     import torch.distributed as dist
     if dist.is_available() and dist.is_initialized():
-        dist.barrier()
+        if dist.get_backend() == "nccl":
+            dist.barrier()
+        else:
+            # gloo: a one-element all_reduce on the host is the barrier.  dist.barrier() probes the accelerator first
+            # (torch._C._get_accelerator), which starts the HIP runtime -- and opens the GPU -- in every CPU-only rank
+            dist.all_reduce(torch.zeros(1), op=dist.ReduceOp.SUM)
