@@ -48,7 +48,7 @@ typedef struct y4_ctx* y4_handle;
 
 /* Mirrors what `Yolov4.__init__` reads from `yolo_config` (reference models.py:26-37, config.py:1-17). */
 typedef struct y4_config {
-    int32_t img_size;          /* square input side, multiple of 32 (reference models.py:23-24) */
+    int32_t img_size;          /* square input side, multiple of 32 (reference models.py:23-24); y4_create_hw takes H and W instead */
     int32_t num_classes;       /* len(class_names) (reference models.py:25,27) */
     int32_t max_batch;         /* largest n any call will pass */
     int32_t dtype;             /* Y4_F32 | Y4_BF16 | Y4_F16: storage/MFMA-input type; accumulation is fp32 */
@@ -63,7 +63,7 @@ typedef struct y4_config {
 
 /* One row of the 110-conv plan, as built by the C++ runtime. */
 typedef struct y4_layer_desc {
-    int32_t idx, ksize, stride, cin, cout, act, has_bn, in_side, out_side;
+    int32_t idx, ksize, stride, cin, cout, act, has_bn, in_side, out_side;   /* sides: -1 on a non-square handle (y4_layer_dims) */
     int64_t weight_offset;     /* float offset of this layer's record in the Darknet stream (bn/bias first) */
 } y4_layer_desc;
 
@@ -73,6 +73,17 @@ const char* y4_version(void);
 /* Replaces Yolov4.__init__ -> build_model (inference half), reference models.py:18-52,67-73: builds the
  * 110-conv CSPDarknet53+SPP+PANet plan, the decode and the NMS stages for this config.  Host-only. */
 int y4_create(const y4_config* cfg, y4_handle* out);
+/* Rectangular input: images are [n, img_h, img_w, 3] (the Keras Input shape, height first), each side a positive multiple of 32;
+ * cfg->img_size is not read.  Scale s has gh = img_h / stride rows and gw = img_w / stride columns, raw heads are
+ * [n, gh, gw, 3*(C+5)], cells row-major (row over H, column over W), and num_boxes = 3 * sum(gh * gw).  Boxes are normalised
+ * x / img_w, y / img_h (the reference divides all four coordinates by input_shape[0], custom_layers.py:284: the same float32
+ * division for a square input, so y4_create(cfg) == y4_create_hw(cfg, cfg->img_size, cfg->img_size) bit for bit).  Stem fusion
+ * (y4_set_stem_fusion) is square-only; every other kernel and knob takes either shape. */
+int y4_create_hw(const y4_config* cfg, int32_t img_h, int32_t img_w, y4_handle* out);
+/* The handle's input rows / columns. */
+int y4_input_dims(y4_handle h, int32_t* img_h, int32_t* img_w);
+/* dims = {in_h, in_w, out_h, out_w} of layer `idx` (the stored tensor for the upsampling convs 78 / 85 is 2 out_h x 2 out_w). */
+int y4_layer_dims(y4_handle h, int idx, int32_t dims[4]);
 int y4_destroy(y4_handle h);
 
 int y4_num_layers(y4_handle h);
@@ -116,9 +127,9 @@ int y4_forward_u8(y4_handle h, const uint8_t* imgs_nhwc_u8_dev, int n, void* str
  * SPP block's convs -- which bench.py times on its own (`backbone` in its line).  Y4_EINVAL when the conv does not end a launch
  * under the current fusion settings (a run that continues behind it is never cut). */
 int y4_forward_until(y4_handle h, const float* imgs_nhwc_dev, int n, int last_conv, void* stream);
-/* Dense float32 copies of the three raw heads, [n,g,g,3*(C+5)] each, as Keras returns them. */
+/* Dense float32 copies of the three raw heads, [n,gh,gw,3*(C+5)] each, as Keras returns them. */
 int y4_get_heads(y4_handle h, int n, float* out_s_dev, float* out_m_dev, float* out_l_dev, void* stream);
-/* Inverse of y4_get_heads: load dense float32 raw heads [n,g,g,3*(C+5)] into the workspace, so that
+/* Inverse of y4_get_heads: load dense float32 raw heads [n,gh,gw,3*(C+5)] into the workspace, so that
  * y4_decode_nms can be driven with arbitrary logits (decode/NMS known-answer tests; reference
  * predict_nonms feeds yolov4_head/nms with precomputed heads the same way, models.py:521-523). */
 int y4_set_heads(y4_handle h, int n, const float* in_s_dev, const float* in_m_dev, const float* in_l_dev,
@@ -129,9 +140,9 @@ int y4_get_conv_output(y4_handle h, int conv_idx, int n, float* out_dev, size_t 
 
 /* Replaces yolov4_head/get_boxes + nms (reference custom_layers.py:201-298, i.e.
  * tf.image.combined_non_max_suppression) on the heads left by y4_forward.
- * boxes [n,max_total,4] (x1,y1,x2,y2 / img_size, clipped to [0,1], zero padded), scores [n,max_total],
+ * boxes [n,max_total,4] (x1/W, y1/H, x2/W, y2/H, clipped to [0,1], zero padded; W = H = img_size when square), scores [n,max_total],
  * classes [n,max_total] (class id as float), valid [n] int32, kept_idx [n,max_total] int32 (box index
- * n = scale_offset + (row*g+col)*3 + anchor, -1 padded; may be NULL).  iou/score thresholds < 0 mean
+ * n = scale_offset + (row*gw+col)*3 + anchor, -1 padded; may be NULL).  iou/score thresholds < 0 mean
  * "use the config's" (predict_nonms passes its own, reference models.py:516-523). */
 int y4_decode_nms(y4_handle h, int n, float iou_threshold, float score_threshold, float* boxes_dev,
                   float* scores_dev, float* classes_dev, int32_t* valid_dev, int32_t* kept_idx_dev,
@@ -314,6 +325,8 @@ int y4_resize_u8(const uint8_t* imgs_dev, int n, int h, int w, uint8_t* out_dev,
 /* SPP (custom_layers.py:130-134): x = buf[..., 3c:4c] -> buf[..., 0:c]=maxpool13, [c:2c]=maxpool9,
  * [2c:3c]=maxpool5 (stride 1, 'same'), buf is [n,side,side,4c] */
 int y4_spp(int dtype, void* buf_dev, int n, int side, int c, void* stream);
+/* The same on an h x w plane (buf is [n,h,w,4c]); y4_spp(..., side, ...) == y4_spp_hw(..., side, side, ...). */
+int y4_spp_hw(int dtype, void* buf_dev, int n, int h, int w, int c, void* stream);
 
 #ifdef __cplusplus
 }

@@ -98,8 +98,8 @@ struct CspStageK {
     const char* blob;            // CS_BLOB_BYTES: fragment-ordered weights + affine (pack_csp_stage)
     int in_cstride, in_coff, out_cstride, out_coff;
     unsigned in_bytes;
-    int N, S;                    // images, side of the stage's tensors (a multiple of 16)
-    int tiles_x, tiles_per_img, ntiles;
+    int N, H, W;                 // images, rows / columns of the stage's tensors (multiples of 16)
+    int tiles_x, tiles_y, tiles_per_img, ntiles;
 };
 
 // this lane's scale / shift of channels (4c + g)*8 .. +7, c < NC, from the LDS affine table of one conv
@@ -174,13 +174,13 @@ __global__ __launch_bounds__(64 * CS_WAVES, 1) void csp_stage_kernel(const CspSt
         const int hp = (wave + CS_WAVES * k) * 8 + (lane >> 3);
         const int hy = hp / CS_H, hx = hp - hy * CS_H;
         const int flags = hp >= CS_H * CS_H ? 15 : ((hy == 0) | ((hy == CS_H - 1) << 1) | ((hx == 0) << 2) | ((hx == CS_H - 1) << 3));
-        lx_rel[k] = (((hy * p.S + hx) * p.in_cstride + (((lane & 7) ^ (hp & 7)) * 8)) * 2) | flags;
+        lx_rel[k] = (((hy * p.W + hx) * p.in_cstride + (((lane & 7) ^ (hp & 7)) * 8)) * 2) | flags;
     }
     auto load_x = [&](int tile) {
         const int n = tile / p.tiles_per_img, rem = tile - n * p.tiles_per_img;
         const int ty = rem / p.tiles_x, tx = rem - ty * p.tiles_x;
-        const int base = (((n * p.S + ty * CS_T - 1) * p.S + tx * CS_T - 1) * p.in_cstride + p.in_coff) * 2;
-        const int tmask = (ty == 0) | ((ty == p.tiles_x - 1) << 1) | ((tx == 0) << 2) | ((tx == p.tiles_x - 1) << 3);
+        const int base = (((n * p.H + ty * CS_T - 1) * p.W + tx * CS_T - 1) * p.in_cstride + p.in_coff) * 2;
+        const int tmask = (ty == 0) | ((ty == p.tiles_y - 1) << 1) | ((tx == 0) << 2) | ((tx == p.tiles_x - 1) << 3);
 #pragma unroll
         for (int k = 0; k < CS_NPIECE; ++k) {
             const int u = wave + CS_WAVES * k;
@@ -198,8 +198,8 @@ __global__ __launch_bounds__(64 * CS_WAVES, 1) void csp_stage_kernel(const CspSt
             const int hp = u * 8 + (lane >> 3);
             const int hy = hp / CS_H, hx = hp - hy * CS_H;
             const int gy = y0 + hy, gx = x0 + hx;
-            const bool ok = hp < CS_H * CS_H && (unsigned)gy < (unsigned)p.S && (unsigned)gx < (unsigned)p.S;
-            const int off = (((n * p.S + gy) * p.S + gx) * p.in_cstride + p.in_coff + (((lane & 7) ^ (hp & 7)) * 8)) * 2;
+            const bool ok = hp < CS_H * CS_H && (unsigned)gy < (unsigned)p.H && (unsigned)gx < (unsigned)p.W;
+            const int off = (((n * p.H + gy) * p.W + gx) * p.in_cstride + p.in_coff + (((lane & 7) ^ (hp & 7)) * 8)) * 2;
             buffer_load16_lds(rs_in, X1 + __builtin_amdgcn_readfirstlane(u * 1024), ok ? off : (int)0x80000000, 0);
         }
     };
@@ -302,7 +302,7 @@ __global__ __launch_bounds__(64 * CS_WAVES, 1) void csp_stage_kernel(const CspSt
                 u32x4 pk;
                 cs_act_pack<DT, 2>(a4, sc4, sh4, &pk);
                 const int gy = ty * CS_T - 1 + hy, gx = tx * CS_T - 1 + hx;
-                if (!((unsigned)gy < (unsigned)p.S && (unsigned)gx < (unsigned)p.S)) pk = u32x4{0u, 0u, 0u, 0u};
+                if (!((unsigned)gy < (unsigned)p.H && (unsigned)gx < (unsigned)p.W)) pk = u32x4{0u, 0u, 0u, 0u};
                 *(u32x4*)(X4 + xr * 64 + ((g ^ ((xr >> 1) & 3)) * 16)) = pk;
             };
             // conv3 -> conv4 of the halo-ring fragment(s)
@@ -431,7 +431,7 @@ __global__ __launch_bounds__(64 * CS_WAVES, 1) void csp_stage_kernel(const CspSt
                 for (int i = 0; i < 2; ++i) {
                     u32x4 Z[2];
                     cs_act_pack<DT, 4>(a7[i], sc7, sh7, Z);
-                    const int64_t pix = ((int64_t)n * p.S + ty * CS_T + 2 * wave + i) * p.S + tx * CS_T + q;
+                    const int64_t pix = ((int64_t)n * p.H + ty * CS_T + 2 * wave + i) * p.W + tx * CS_T + q;
                     T* op = (T*)p.out + pix * p.out_cstride + p.out_coff;
 #pragma unroll
                     for (int c = 0; c < 2; ++c)
@@ -459,23 +459,25 @@ namespace y4 {
 #endif
 
 // ------------------------------------------------------------------------------------------------ launch
-bool csp_stage_supported(int dtype, int side) { return dtype != Y4_F32 && side % CS_T == 0 && side >= CS_T; }
+bool csp_stage_supported(int dtype, int h, int w) {
+    return dtype != Y4_F32 && h % CS_T == 0 && w % CS_T == 0 && h >= CS_T && w >= CS_T;
+}
 size_t csp_stage_blob_bytes() { return CS_BLOB_BYTES; }
 
-int csp_stage_launch(int dtype, const void* in, int n, int side, int in_cstride, int in_coff, const void* blob, void* out,
+int csp_stage_launch(int dtype, const void* in, int n, int h, int w, int in_cstride, int in_coff, const void* blob, void* out,
                      int out_cstride, int out_coff, hipStream_t stream) {
-    Y4_REQUIRE(csp_stage_supported(dtype, side), Y4_EINVAL, "csp_stage: dtype %d / side %d not supported", dtype, side);
+    Y4_REQUIRE(csp_stage_supported(dtype, h, w), Y4_EINVAL, "csp_stage: dtype %d / %d x %d map not supported", dtype, h, w);
     Y4_REQUIRE(in && blob && out && n > 0, Y4_EINVAL, "csp_stage: null pointer / empty batch");
     Y4_REQUIRE(in_cstride % 8 == 0 && in_coff % 8 == 0 && out_cstride % 8 == 0 && out_coff % 8 == 0, Y4_EINVAL,
                "csp_stage: views not 16-byte aligned");
-    const int64_t in_bytes = (int64_t)n * side * side * in_cstride * 2;
+    const int64_t in_bytes = (int64_t)n * h * w * in_cstride * 2;
     Y4_REQUIRE(in_bytes < (1ll << 31), Y4_EINVAL, "csp_stage: input (%lld B) exceeds the 2 GiB buffer-descriptor range", (long long)in_bytes);
     CspStageK k{};
     k.in = (const char*)in; k.out = (char*)out; k.blob = (const char*)blob;
     k.in_cstride = in_cstride; k.in_coff = in_coff; k.out_cstride = out_cstride; k.out_coff = out_coff;
     k.in_bytes = (unsigned)in_bytes;
-    k.N = n; k.S = side;
-    k.tiles_x = side / CS_T; k.tiles_per_img = k.tiles_x * k.tiles_x; k.ntiles = n * k.tiles_per_img;
+    k.N = n; k.H = h; k.W = w;
+    k.tiles_x = w / CS_T; k.tiles_y = h / CS_T; k.tiles_per_img = k.tiles_x * k.tiles_y; k.ntiles = n * k.tiles_per_img;
     static int n_cus[64] = {0};
     int dev = 0;
     Y4_CHECK_HIP(hipGetDevice(&dev));

@@ -8,6 +8,9 @@
 // score > score_threshold (strict) to the image's candidate list with ONE wave-aggregated atomic per pass
 // (ballot + popcount).  Only surviving boxes are decoded to coordinates.  A candidate is a 64-bit key  (score bits << 32) | ~(box_index*C + class): sorting keys
 // descending gives (score desc, box index asc, class asc) -- the tie order this build defines.
+// Rectangular inputs (H x W): scale s has gh = H / stride rows and gw = W / stride columns, cells row-major; box index =
+// box_off[s] + (row * gw + col) * 3 + anchor.  x1 and x2 are divided by W, y1 and y2 by H (the reference divides all four by
+// input_shape[0], custom_layers.py:284 -- for a square input the same float32 division, bit for bit).
 //
 // nms_kernel: one workgroup per image.  Class-aware greedy NMS is done in ONE pass over the globally
 // sorted candidates (suppression only against kept boxes of the same class): this visits every class's
@@ -45,11 +48,10 @@ __global__ __launch_bounds__(256) void decode_kernel(const DecodeK p) {
     if (in_range) {
         const int c3 = b / 3;
         a = b - c3 * 3;
-        const int n0 = p.g[0] * p.g[0], n1 = n0 + p.g[1] * p.g[1];
+        const int n0 = p.gh[0] * p.gw[0], n1 = n0 + p.gh[1] * p.gw[1];
         s = c3 >= n1 ? 2 : (c3 >= n0 ? 1 : 0);
         cell = c3 - (s == 2 ? n1 : (s == 1 ? n0 : 0));
-        const int g = p.g[s];
-        cellp = p.head[s] + ((int64_t)n * g * g + cell) * p.hcs + a * nf;
+        cellp = p.head[s] + ((int64_t)n * p.gh[s] * p.gw[s] + cell) * p.hcs + a * nf;
         s_obj = sigmoid_f(cellp[4]);
     }
     unsigned long long todo = __ballot(in_range && s_obj > p.score_thr);
@@ -90,17 +92,17 @@ __global__ __launch_bounds__(256) void decode_kernel(const DecodeK p) {
         }
         if (lane == j) {
             // custom_layers.py:251-256 (only boxes that can be candidates are ever read back by the NMS stage)
-            const int g = p.g[s];
-            const int row = cell / g, col = cell - row * g;
+            const int gw = p.gw[s];
+            const int row = cell / gw, col = cell - row * gw;          // cells are row-major: row over H, column over W
             const float bx = ((sigmoid_f(cellp[0]) * p.xyscale[s]) - p.xyoff[s] + (float)col) * (float)p.stride[s];
             const float by = ((sigmoid_f(cellp[1]) * p.xyscale[s]) - p.xyoff[s] + (float)row) * (float)p.stride[s];
             const float bw = expf(cellp[2]) * p.anchors[(s * 3 + a) * 2 + 0];
             const float bh = expf(cellp[3]) * p.anchors[(s * 3 + a) * 2 + 1];
             float4 o;
-            o.x = (bx - bw / 2.0f) / p.img_size;
-            o.y = (by - bh / 2.0f) / p.img_size;
-            o.z = (bx + bw / 2.0f) / p.img_size;
-            o.w = (by + bh / 2.0f) / p.img_size;
+            o.x = (bx - bw / 2.0f) / p.img_w;
+            o.y = (by - bh / 2.0f) / p.img_h;
+            o.z = (bx + bw / 2.0f) / p.img_w;
+            o.w = (by + bh / 2.0f) / p.img_h;
             *(float4*)(p.dboxes + ((int64_t)n * p.nbox + b) * 4) = o;
         }
     }
@@ -118,9 +120,9 @@ __device__ __forceinline__ DecodeCell decode_locate(const DecodeK& p, int64_t ce
     c.n = (int)fastdiv((uint32_t)cellid, p.div_cells);
     c.rem = (int)cellid - c.n * p.cells_per_img;
     c.s = 0;
-    if (c.rem >= p.g[0] * p.g[0]) { c.rem -= p.g[0] * p.g[0]; c.s = 1; if (c.rem >= p.g[1] * p.g[1]) { c.rem -= p.g[1] * p.g[1]; c.s = 2; } }
-    const int g = p.g[c.s];
-    c.src = p.head[c.s] + ((int64_t)c.n * g * g + c.rem) * p.hcs;
+    const int c0 = p.gh[0] * p.gw[0], c1 = p.gh[1] * p.gw[1];
+    if (c.rem >= c0) { c.rem -= c0; c.s = 1; if (c.rem >= c1) { c.rem -= c1; c.s = 2; } }
+    c.src = p.head[c.s] + ((int64_t)c.n * p.gh[c.s] * p.gw[c.s] + c.rem) * p.hcs;
     return c;
 }
 
@@ -145,7 +147,6 @@ __device__ __forceinline__ void decode_flush(const DecodeK& p, DecodeStage& st, 
 __device__ __forceinline__ void decode_one_cell(const DecodeK& p, const DecodeCell& cl, const float (&v)[4], const float (&so)[3], int lane,
                                                 DecodeStage& st) {
     const int n = cl.n, s = cl.s, rem = cl.rem;
-    const int g = p.g[s];
     const int nf = 5 + p.C, nval = 3 * nf;
     // so[a] = sigmoid(objectness of anchor a): the screen's value for this cell (the same float32 logit through the same sigmoid_f)
     const int box0 = p.box_off[s] + rem * 3;
@@ -222,19 +223,19 @@ __global__ __launch_bounds__(256) void decode_cell_kernel(const DecodeK p) {
     // the four box logits come from the cell: its lines are read by the full-cell load anyway)
     if (pass) {
         const DecodeCell cl = decode_locate(p, cell0 + c);
-        const int s = cl.s, g = p.g[s];
+        const int s = cl.s, gw = p.gw[s];
         const float* tp = cl.src + a * nf;
         const float t0 = tp[0], t1 = tp[1], t2 = tp[2], t3 = tp[3];
-        const int row = (int)fastdiv((uint32_t)cl.rem, p.div_g[s]), col = cl.rem - row * g;
+        const int row = (int)fastdiv((uint32_t)cl.rem, p.div_gw[s]), col = cl.rem - row * gw;
         const float bx = ((sigmoid_f(t0) * p.xyscale[s]) - p.xyoff[s] + (float)col) * (float)p.stride[s];
         const float by = ((sigmoid_f(t1) * p.xyscale[s]) - p.xyoff[s] + (float)row) * (float)p.stride[s];
         const float bw = expf(t2) * p.anchors[(s * 3 + a) * 2 + 0];
         const float bh = expf(t3) * p.anchors[(s * 3 + a) * 2 + 1];
         float4 o;
-        o.x = (bx - bw / 2.0f) / p.img_size;
-        o.y = (by - bh / 2.0f) / p.img_size;
-        o.z = (bx + bw / 2.0f) / p.img_size;
-        o.w = (by + bh / 2.0f) / p.img_size;
+        o.x = (bx - bw / 2.0f) / p.img_w;
+        o.y = (by - bh / 2.0f) / p.img_h;
+        o.z = (bx + bw / 2.0f) / p.img_w;
+        o.w = (by + bh / 2.0f) / p.img_h;
         *(float4*)(p.dboxes + ((int64_t)cl.n * p.nbox + p.box_off[s] + cl.rem * 3 + a) * 4) = o;
     }
     unsigned long long m = __ballot(pass);

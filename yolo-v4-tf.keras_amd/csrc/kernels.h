@@ -55,7 +55,7 @@ int stem_conv_launch(int dtype, const void* imgs, int img_u8, int n, int h, int 
 int resize_u8_launch(const uint8_t* img, int n, int h, int w, uint8_t* out, int H, int W, hipStream_t stream);
 int pack_stem_weights(const float* w_oihw, float* wk, int cout, hipStream_t stream);
 int preprocess_u8_launch(const uint8_t* img, int h, int w, float* out, int H, int W, hipStream_t stream);
-int spp_launch(int dtype, void* buf, int n, int side, int c, hipStream_t stream);
+int spp_launch(int dtype, void* buf, int n, int h, int w, int c, hipStream_t stream);
 int view_to_f32_launch(int dtype, const void* src, float* dst, int64_t pixels, int cstride, int coff, int c,
                        hipStream_t stream);
 int f32_to_view_launch(const float* src, float* dst, int64_t pixels, int cstride, int c, hipStream_t stream);
@@ -68,11 +68,11 @@ int stem_down_launch(int dtype, const void* imgs, int img_u8, int n, int S, cons
                      int act1, void* out, int out_cstride, int out_coff, hipStream_t stream);
 
 // csp_stage.hip: convs 2..7 (the first CSP stage) as one spatially tiled persistent kernel (16-bit dtypes)
-bool csp_stage_supported(int dtype, int side);
+bool csp_stage_supported(int dtype, int h, int w);
 size_t csp_stage_blob_bytes();
 int pack_csp_stage(int dtype, const float* const* w, const float* const* scale, const float* const* shift, void* blob,
                    hipStream_t stream);
-int csp_stage_launch(int dtype, const void* in, int n, int side, int in_cstride, int in_coff, const void* blob, void* out,
+int csp_stage_launch(int dtype, const void* in, int n, int h, int w, int in_cstride, int in_coff, const void* blob, void* out,
                      int out_cstride, int out_coff, hipStream_t stream);
 
 // resblock.hip: "1x1 conv -> 3x3 conv + Add" residual blocks with 64 / 128 channels as one spatially tiled kernel
@@ -80,7 +80,7 @@ bool resblock_supported(int dtype, int c);
 size_t resblock_blob_bytes(int c);
 int pack_resblock(int dtype, int c, const float* w1, const float* scale1, const float* shift1, const float* w3, const float* scale3,
                   const float* shift3, void* blob, hipStream_t stream);
-int resblock_launch(int dtype, int c, const void* in, int n, int side, int in_cstride, int in_coff, const void* blob, void* out,
+int resblock_launch(int dtype, int c, const void* in, int n, int h, int w, int in_cstride, int in_coff, const void* blob, void* out,
                     int out_cstride, int out_coff, hipStream_t stream);
 
 // decode_nms.hip
@@ -89,17 +89,17 @@ int resblock_launch(int dtype, int c, const void* in, int n, int side, int in_cs
 constexpr int COUNT_STRIDE = 64;     // uint32 words
 struct DecodeK {
     const float* head[3];
-    int g[3], stride[3], box_off[3];
+    int gh[3], gw[3], stride[3], box_off[3];   // grid rows (over H) / columns (over W) per scale
     float xyscale[3], xyoff[3];      // xyoff = float(0.5*(xyscale-1)) computed in double like the reference
     float anchors[18];
-    int cells_per_img;               // g0^2 + g1^2 + g2^2
+    int cells_per_img;               // gh0*gw0 + gh1*gw1 + gh2*gw2
     int N, C, hcs, nbox;
-    float img_size, score_thr;
+    float img_h, img_w, score_thr;   // x1, x2 are divided by img_w, y1, y2 by img_h
     float* dboxes;                   // [N, nbox, 4] normalised x1,y1,x2,y2
     unsigned long long* keys;        // [N, cap]
     uint32_t* counts;                // [N * COUNT_STRIDE]: one counter per image, each on its own 256-byte line
     uint32_t cap;
-    FastDiv div_cells, div_g[3];     // cell id -> image, cell -> row (ids < 2^31: checked at y4_create)
+    FastDiv div_cells, div_gw[3];    // cell id -> image, cell -> row (ids < 2^31: checked at y4_create)
     const float* obj;                // [N * cells_per_img][4]: the cells' objectness logits as the head convs left them (ConvObjDesc), or null
 };
 struct NmsK {

@@ -202,38 +202,38 @@ int stem_conv_launch(int dtype, const void* imgs, int img_u8, int n, int h, int 
 }
 
 // ------------------------------------------------------------------------------------------- SPP
-// buf [n, side, side, 4c]: x lives in channels [3c,4c); writes maxpool13 -> [0,c), maxpool9 -> [c,2c),
+// buf [n, h, w, 4c]: x lives in channels [3c,4c); writes maxpool13 -> [0,c), maxpool9 -> [c,2c),
 // maxpool5 -> [2c,3c).  stride 1, 'same': windows are clipped at the border (Keras pads with -inf).
 // The 5/9/13 windows are nested, so one sweep of the 13x13 neighbourhood yields all three maxima.
 template <int DT>
-__global__ __launch_bounds__(256) void spp_kernel(typename Elem<DT>::type* __restrict__ buf, int N, int S, int C) {
+__global__ __launch_bounds__(256) void spp_kernel(typename Elem<DT>::type* __restrict__ buf, int N, int H, int W, int C) {
     using E = Elem<DT>;
     using T = typename E::type;
     constexpr int EPC = 16 / (int)sizeof(T);
     const int cchunks = C / EPC;
-    const int64_t total = (int64_t)N * S * S * cchunks;
+    const int64_t total = (int64_t)N * H * W * cchunks;
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= total) return;
     const int cc = (int)(i % cchunks);
     int64_t r = i / cchunks;
-    const int x = (int)(r % S); r /= S;
-    const int y = (int)(r % S);
-    const int n = (int)(r / S);
+    const int x = (int)(r % W); r /= W;
+    const int y = (int)(r % H);
+    const int n = (int)(r / H);
     const int cs = 4 * C;
     float m5[EPC], m9[EPC], m13[EPC];
 #pragma unroll
     for (int e = 0; e < EPC; ++e) m5[e] = m9[e] = m13[e] = -INFINITY;
-    const T* base = buf + (int64_t)n * S * S * cs + 3 * C + cc * EPC;
+    const T* base = buf + (int64_t)n * H * W * cs + 3 * C + cc * EPC;
     for (int dy = -6; dy <= 6; ++dy) {
         const int yy = y + dy;
-        if ((unsigned)yy >= (unsigned)S) continue;
+        if ((unsigned)yy >= (unsigned)H) continue;
         const int ady = dy < 0 ? -dy : dy;
         for (int dx = -6; dx <= 6; ++dx) {
             const int xx = x + dx;
-            if ((unsigned)xx >= (unsigned)S) continue;
+            if ((unsigned)xx >= (unsigned)W) continue;
             const int adx = dx < 0 ? -dx : dx;
             const int rad = ady > adx ? ady : adx;
-            const u32x4 raw = *(const u32x4*)(base + ((int64_t)yy * S + xx) * cs);
+            const u32x4 raw = *(const u32x4*)(base + ((int64_t)yy * W + xx) * cs);
             const T* v = (const T*)&raw;
 #pragma unroll
             for (int e = 0; e < EPC; ++e) {
@@ -244,7 +244,7 @@ __global__ __launch_bounds__(256) void spp_kernel(typename Elem<DT>::type* __res
             }
         }
     }
-    T* op = buf + (((int64_t)n * S + y) * S + x) * cs + cc * EPC;
+    T* op = buf + (((int64_t)n * H + y) * W + x) * cs + cc * EPC;
     u32x4 o13, o9, o5;
 #pragma unroll
     for (int e = 0; e < EPC; ++e) {
@@ -297,13 +297,13 @@ template <> struct PMax<Y4_F32> {
 };
 
 template <int DT, int CPG>
-__global__ __launch_bounds__(256) void spp_lds_kernel(typename Elem<DT>::type* __restrict__ buf, int N, int S, int C) {
+__global__ __launch_bounds__(256) void spp_lds_kernel(typename Elem<DT>::type* __restrict__ buf, int N, int H, int W, int C) {
     using E = Elem<DT>;
     using T = typename E::type;
     using M = PMax<DT>;
     constexpr int EPC = E::EPC;
     extern __shared__ __attribute__((aligned(16))) char ssm[];
-    const int P = S * S;
+    const int P = H * W;
     u32x4* X = (u32x4*)ssm;             // [P][CPG]
     u32x4* H2 = X + P * CPG;
     u32x4* H4 = H2 + P * CPG;
@@ -320,32 +320,32 @@ __global__ __launch_bounds__(256) void spp_lds_kernel(typename Elem<DT>::type* _
     __syncthreads();
     for (int t = threadIdx.x; t < P * CPG; t += 256) {
         const int px = t / CPG, q = t - px * CPG;
-        const int y = px / S, x = px - y * S;
+        const int y = px / W, x = px - y * W;
         u32x4 m = M::lowest();
-        const u32x4* row = X + (y * S) * CPG + q;
+        const u32x4* row = X + (y * W) * CPG + q;
         for (int dx = -2; dx <= 2; ++dx)
-            if ((unsigned)(x + dx) < (unsigned)S) m = M::mx(m, row[(x + dx) * CPG]);
+            if ((unsigned)(x + dx) < (unsigned)W) m = M::mx(m, row[(x + dx) * CPG]);
         H2[t] = m;
         for (int k = 3; k <= 4; ++k) {
             if (x - k >= 0) m = M::mx(m, row[(x - k) * CPG]);
-            if (x + k < S) m = M::mx(m, row[(x + k) * CPG]);
+            if (x + k < W) m = M::mx(m, row[(x + k) * CPG]);
         }
         H4[t] = m;
         for (int k = 5; k <= 6; ++k) {
             if (x - k >= 0) m = M::mx(m, row[(x - k) * CPG]);
-            if (x + k < S) m = M::mx(m, row[(x + k) * CPG]);
+            if (x + k < W) m = M::mx(m, row[(x + k) * CPG]);
         }
         H6[t] = m;
     }
     __syncthreads();
     for (int t = threadIdx.x; t < P * CPG; t += 256) {
         const int px = t / CPG, q = t - px * CPG;
-        const int y = px / S, x = px - y * S;
+        const int y = px / W, x = px - y * W;
         u32x4 m5 = M::lowest(), m9 = m5, m13 = m5;
         for (int dy = -6; dy <= 6; ++dy) {
             const int yy = y + dy;
-            if ((unsigned)yy >= (unsigned)S) continue;
-            const int o = (yy * S + x) * CPG + q;
+            if ((unsigned)yy >= (unsigned)H) continue;
+            const int o = (yy * W + x) * CPG + q;
             const int ady = dy < 0 ? -dy : dy;
             m13 = M::mx(m13, H6[o]);
             if (ady <= 4) m9 = M::mx(m9, H4[o]);
@@ -359,34 +359,34 @@ __global__ __launch_bounds__(256) void spp_lds_kernel(typename Elem<DT>::type* _
 }
 
 template <int DT>
-static int spp_dispatch(void* buf, int n, int side, int c, hipStream_t stream) {
+static int spp_dispatch(void* buf, int n, int h, int w, int c, hipStream_t stream) {
     using T = typename Elem<DT>::type;
     constexpr int EPC = Elem<DT>::EPC;
     constexpr int CPG = 2;
-    const size_t lds = (size_t)side * side * CPG * 16 * 4;
+    const size_t lds = (size_t)h * w * CPG * 16 * 4;
     if (c % (CPG * EPC) == 0 && lds <= 150 * 1024) {
         static PerDeviceOnce once;
         if (const uint64_t bit = once.due()) {
             Y4_CHECK_HIP(hipFuncSetAttribute((const void*)spp_lds_kernel<DT, CPG>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
             once.mark(bit);
         }
-        hipLaunchKernelGGL((spp_lds_kernel<DT, CPG>), dim3(n * (c / (CPG * EPC))), dim3(256), lds, stream, (T*)buf, n, side, c);
+        hipLaunchKernelGGL((spp_lds_kernel<DT, CPG>), dim3(n * (c / (CPG * EPC))), dim3(256), lds, stream, (T*)buf, n, h, w, c);
     } else {
-        const int64_t total = (int64_t)n * side * side * (c / EPC);
-        hipLaunchKernelGGL(spp_kernel<DT>, dim3((int)((total + 255) / 256)), dim3(256), 0, stream, (T*)buf, n, side, c);
+        const int64_t total = (int64_t)n * h * w * (c / EPC);
+        hipLaunchKernelGGL(spp_kernel<DT>, dim3((int)((total + 255) / 256)), dim3(256), 0, stream, (T*)buf, n, h, w, c);
     }
     Y4_CHECK_HIP(hipGetLastError());
     return Y4_OK;
 }
 
-int spp_launch(int dtype, void* buf, int n, int side, int c, hipStream_t stream) {
-    Y4_REQUIRE(buf && n > 0 && side > 0, Y4_EINVAL, "spp: bad arguments");
+int spp_launch(int dtype, void* buf, int n, int h, int w, int c, hipStream_t stream) {
+    Y4_REQUIRE(buf && n > 0 && h > 0 && w > 0, Y4_EINVAL, "spp: bad arguments");
     const int epc = 16 / elem_size(dtype);
     Y4_REQUIRE(c % epc == 0, Y4_EINVAL, "spp: channels %d not a multiple of %d", c, epc);
     switch (dtype) {
-        case Y4_F32: return spp_dispatch<Y4_F32>(buf, n, side, c, stream);
-        case Y4_BF16: return spp_dispatch<Y4_BF16>(buf, n, side, c, stream);
-        case Y4_F16: return spp_dispatch<Y4_F16>(buf, n, side, c, stream);
+        case Y4_F32: return spp_dispatch<Y4_F32>(buf, n, h, w, c, stream);
+        case Y4_BF16: return spp_dispatch<Y4_BF16>(buf, n, h, w, c, stream);
+        case Y4_F16: return spp_dispatch<Y4_F16>(buf, n, h, w, c, stream);
     }
     set_error("spp: bad dtype %d", dtype);
     return Y4_EINVAL;

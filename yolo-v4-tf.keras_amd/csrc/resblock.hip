@@ -10,7 +10,7 @@
 // pixel operand for all 9 taps straight from that tile at shifted rows -- nothing but the 3x3 weights (C*C*2 bytes per
 // tap, fragment ordered, lane-linear LDS-DMA through a 2-stage ring) is streamed during the K loop, and the 1x1's
 // output never exists in HBM.  Cost: the 1-pixel halo ring of the 1x1 conv is recomputed (1.27x of 10 % of the FLOPs),
-// and tensors whose side is not a multiple of 16 (76, 52) have partially filled edge tiles.
+// and a tensor whose height or width is not a multiple of 16 (76, 52, 44) has partially filled edge tiles in that direction.
 //
 // Numerics: every conv issues the same MFMAs (v_mfma_f32_16x16x32, K ascending in the canonical order of common.h: 64-channel block, tap, channel) on the
 // same 16-bit inputs as its conv_igemm kernel and the same fp32 epilogue -> bit-identical to the unfused path.
@@ -109,8 +109,8 @@ struct ResBlockK {
     const char* blob;            // RbGeom<C>::BLOB_BYTES (pack_resblock)
     int in_cstride, in_coff, out_cstride, out_coff;
     unsigned in_bytes, out_bytes;
-    int N, S;
-    int tiles_x, tiles_per_img, ntiles;
+    int N, H, W;                 // images, rows / columns of the block's tensors
+    int tiles_x, tiles_y, tiles_per_img, ntiles;
     int t_begin, t_end;          // this launch's range of PART tiles: part tile u = 16x16 tile u / (16 / TY), rows (u % (16 / TY)) * TY .. + TY
     int touch;                   // weight touch (conv_common.h) of the block's blob at kernel start
 };
@@ -178,14 +178,14 @@ __global__ __launch_bounds__(64 * RB_WAVES, C == 64 ? 4 : 2) void resblock_kerne
         const int hp0 = slot0 / SPR;
         int ch = slot0 - hp0 * SPR, hy = hp0 / RB_H;
         int hx = hp0 - hy * RB_H;
-        const int pix_b = p.in_cstride * 2, row_b = p.S * pix_b;           // bytes per pixel / per image row of the view
-        int off = (((n * p.S + y0) * p.S + x0) * p.in_cstride + p.in_coff) * 2 + hy * row_b + hx * pix_b + ch * 16;
+        const int pix_b = p.in_cstride * 2, row_b = p.W * pix_b;           // bytes per pixel / per image row of the view
+        int off = (((n * p.H + y0) * p.W + x0) * p.in_cstride + p.in_coff) * 2 + hy * row_b + hx * pix_b + ch * 16;
         const int d_off = DHY * row_b + DHX * pix_b + DCH * 16, c_ch = pix_b - SPR * 16, c_hx = row_b - RB_H * pix_b;
 #pragma unroll
         for (int k = 0; k * RB_WAVES < G::XT_PIECES; ++k) {
             const int u = wave + k * RB_WAVES;
             if (u < G::XT_PIECES) {                                         // (wave-uniform; false for some waves' last piece only)
-                const bool ok = ch < CPR && hy < G::HR && (unsigned)(y0 + hy) < (unsigned)p.S && (unsigned)(x0 + hx) < (unsigned)p.S;
+                const bool ok = ch < CPR && hy < G::HR && (unsigned)(y0 + hy) < (unsigned)p.H && (unsigned)(x0 + hx) < (unsigned)p.W;
                 const int off_x = (RB_ABL & 128) ? (off & ~63) + (lane & 3) * 16 : off;      // (timing experiment: 64-byte aligned quads, wrong data)
                 buffer_load16_lds(rs_in, XT + __builtin_amdgcn_readfirstlane(u * 1024), ok ? off_x : (int)0x80000000, 0);
             }
@@ -238,7 +238,7 @@ __global__ __launch_bounds__(64 * RB_WAVES, C == 64 ? 4 : 2) void resblock_kerne
                 const int r = hy * RB_H + hx;
                 row[k] = XT + r * ROWB;
                 const int gy = y_out0 - 1 + hy, gx = tx * RB_T - 1 + hx;
-                inside[k] = (unsigned)gy < (unsigned)p.S && (unsigned)gx < (unsigned)p.S;
+                inside[k] = (unsigned)gy < (unsigned)p.H && (unsigned)gx < (unsigned)p.W;
             }
             f32x4 acc[NFR][NF];
 #pragma unroll
@@ -300,7 +300,7 @@ __global__ __launch_bounds__(64 * RB_WAVES, C == 64 ? 4 : 2) void resblock_kerne
 #pragma unroll
             for (int i = 0; i < MREP; ++i) {
                 const int gy = y_out0 + wm * MREP + i, gx = tx * RB_T + q;
-                pix[i] = gy < p.S && gx < p.S ? (n * p.S + gy) * p.S + gx : -1;
+                pix[i] = gy < p.H && gx < p.W ? (n * p.H + gy) * p.W + gx : -1;
             }
             auto load_res = [&]() {
 #pragma unroll
@@ -503,23 +503,23 @@ static int resblock_dispatch(ResBlockK& k, hipStream_t stream) {
     return Y4_EINVAL;
 }
 
-int resblock_launch(int dtype, int c, const void* in, int n, int side, int in_cstride, int in_coff, const void* blob, void* out,
+int resblock_launch(int dtype, int c, const void* in, int n, int h, int w, int in_cstride, int in_coff, const void* blob, void* out,
                     int out_cstride, int out_coff, hipStream_t stream) {
     Y4_REQUIRE(resblock_supported(dtype, c), Y4_EINVAL, "resblock: dtype %d / %d channels not supported", dtype, c);
-    Y4_REQUIRE(in && blob && out && n > 0 && side > 0, Y4_EINVAL, "resblock: null pointer / empty batch");
+    Y4_REQUIRE(in && blob && out && n > 0 && h > 0 && w > 0, Y4_EINVAL, "resblock: null pointer / empty batch");
     Y4_REQUIRE(in_cstride % 8 == 0 && in_coff % 8 == 0 && out_cstride % 8 == 0 && out_coff % 8 == 0, Y4_EINVAL,
                "resblock: views not 16-byte aligned");
-    const int64_t in_bytes = (int64_t)n * side * side * in_cstride * 2;
-    const int64_t out_bytes = (int64_t)n * side * side * out_cstride * 2;
+    const int64_t in_bytes = (int64_t)n * h * w * in_cstride * 2;
+    const int64_t out_bytes = (int64_t)n * h * w * out_cstride * 2;
     Y4_REQUIRE(in_bytes < (1ll << 31) && out_bytes < (1ll << 31), Y4_EINVAL,
                "resblock: input (%lld B) or output (%lld B) exceeds the 2 GiB buffer-descriptor range", (long long)in_bytes, (long long)out_bytes);
     ResBlockK k{};
     k.in = (const char*)in; k.out = (char*)out; k.blob = (const char*)blob;
     k.in_cstride = in_cstride; k.in_coff = in_coff; k.out_cstride = out_cstride; k.out_coff = out_coff;
     k.in_bytes = (unsigned)in_bytes; k.out_bytes = (unsigned)out_bytes;
-    k.N = n; k.S = side;
+    k.N = n; k.H = h; k.W = w;
     k.touch = weight_touch_enabled() ? 1 : 0;
-    k.tiles_x = (side + RB_T - 1) / RB_T; k.tiles_per_img = k.tiles_x * k.tiles_x; k.ntiles = n * k.tiles_per_img;
+    k.tiles_x = (w + RB_T - 1) / RB_T; k.tiles_y = (h + RB_T - 1) / RB_T; k.tiles_per_img = k.tiles_x * k.tiles_y; k.ntiles = n * k.tiles_per_img;
     if (c == 128) return dtype == Y4_BF16 ? resblock_dispatch<Y4_BF16, 128>(k, stream) : resblock_dispatch<Y4_F16, 128>(k, stream);
     return dtype == Y4_BF16 ? resblock_dispatch<Y4_BF16, 64>(k, stream) : resblock_dispatch<Y4_F16, 64>(k, stream);
 }

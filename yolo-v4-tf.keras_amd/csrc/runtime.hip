@@ -28,10 +28,10 @@ void set_error(const char* fmt, ...) {
 
 struct View {
     int buf = -1;          // buffer id
-    int side = 0, cstride = 0, coff = 0, c = 0;
+    int h = 0, w = 0, cstride = 0, coff = 0, c = 0;     // rows (over the input's H) and columns (over W)
 };
 struct Buffer {
-    int side, channels;
+    int h, w, channels;
     bool f32;              // raw heads are float32 whatever the compute dtype
     size_t offset = 0;     // byte offset in the act workspace (for max_batch images)
     size_t bytes = 0;
@@ -49,7 +49,8 @@ struct Op {
     char name[16];
 };
 struct Layer {
-    y4_layer_desc d;
+    y4_layer_desc d;       // (in_side / out_side: -1 on a non-square handle)
+    int in_h, in_w, out_h, out_w;
     int cout_pad;
     int fused_with = -1;   // >= 0: this layer's rows live in layer `fused_with`'s packed matrix at row `fused_row`
     int fused_row = 0;
@@ -89,7 +90,7 @@ using namespace y4;
 struct y4_ctx {
     y4_config cfg;
     int es;                           // element size of the compute dtype
-    int S;                            // img side
+    int H, W;                         // input rows / columns (multiples of 32)
     int hcs;                          // padded channels of a raw head
     int nbox;
     int64_t flops_per_image = 0;
@@ -169,11 +170,11 @@ struct Builder {
     y4_ctx& c;
     explicit Builder(y4_ctx& ctx) : c(ctx) {}
 
-    View alloc(int side, int ch, bool f32 = false) {
-        Buffer b{side, ch, f32};
+    View alloc(int h, int w, int ch, bool f32 = false) {
+        Buffer b{h, w, ch, f32};
         c.bufs.push_back(b);
         View v;
-        v.buf = (int)c.bufs.size() - 1; v.side = side; v.cstride = ch; v.coff = 0; v.c = ch;
+        v.buf = (int)c.bufs.size() - 1; v.h = h; v.w = w; v.cstride = ch; v.coff = 0; v.c = ch;
         return v;
     }
     static View slice(View t, int off, int ch) {
@@ -187,10 +188,13 @@ struct Builder {
         Layer L{};
         const int idx = (int)c.layers.size();
         L.d.idx = idx; L.d.ksize = k; L.d.stride = down ? 2 : 1; L.d.cin = in.c; L.d.cout = filters;
-        L.d.act = act; L.d.has_bn = bn ? 1 : 0; L.d.in_side = in.side; L.d.out_side = down ? in.side / 2 : in.side;
+        L.d.act = act; L.d.has_bn = bn ? 1 : 0;
+        L.in_h = in.h; L.in_w = in.w; L.out_h = down ? in.h / 2 : in.h; L.out_w = down ? in.w / 2 : in.w;
+        const bool square = c.H == c.W;
+        L.d.in_side = square ? L.in_h : -1; L.d.out_side = square ? L.out_h : -1;
         L.d.weight_offset = c.weight_floats;
         c.weight_floats += (bn ? 4 : 1) * (int64_t)filters + (int64_t)filters * in.c * k * k;
-        c.flops_per_image += 2ll * k * k * in.c * filters * L.d.out_side * L.d.out_side;
+        c.flops_per_image += 2ll * k * k * in.c * filters * L.out_h * L.out_w;
         L.cout_pad = (int)round_up(filters, COUT_PAD);
         c.layers.push_back(L);
         Op op{};
@@ -201,13 +205,13 @@ struct Builder {
         c.ops.push_back(op);
     }
     View conv_new(View in, int filters, int k, bool down, int act) {
-        View out = alloc(down ? in.side / 2 : in.side, filters);
+        View out = down ? alloc(in.h / 2, in.w / 2, filters) : alloc(in.h, in.w, filters);
         conv(in, out, filters, k, down, act);
         return out;
     }
     // csp_block (reference custom_layers.py:47-69): returns the [x, route] concat buffer
     View csp(View din, int width, int repeat, bool bottleneck) {
-        View cat = alloc(din.side, 2 * width);
+        View cat = alloc(din.h, din.w, 2 * width);
         // route conv (created first) and main-in conv read the same tensor: ONE GEMM with 2*width output
         // channels, [0,width) -> the route slice of the concat buffer, [width,2*width) -> x
         conv(din, slice(cat, width, width), width, 1, false, Y4_ACT_MISH);          // route
@@ -224,7 +228,7 @@ struct Builder {
         }
         for (int r = 0; r < repeat; ++r) {                                           // residual_block :34-44
             View t = conv_new(x, bottleneck ? width / 2 : width, 1, false, Y4_ACT_MISH);
-            View x2 = alloc(din.side, width);
+            View x2 = alloc(din.h, din.w, width);
             conv(t, x2, width, 3, false, Y4_ACT_MISH, true, &x);                     // 3x3 + Add
             x = x2;
         }
@@ -243,9 +247,9 @@ struct Builder {
     }
 
     void build() {
-        const int S = c.S, M = Y4_ACT_MISH, L = Y4_ACT_LEAKY;
+        const int M = Y4_ACT_MISH, L = Y4_ACT_LEAKY;
         const int nout = 3 * (c.cfg.num_classes + 5);
-        View img; img.buf = -1; img.side = S; img.cstride = 3; img.coff = 0; img.c = 3;     // caller's images
+        View img; img.buf = -1; img.h = c.H; img.w = c.W; img.cstride = 3; img.coff = 0; img.c = 3;     // caller's images
         // ---- cspdarknet53, reference custom_layers.py:100-138
         View x = conv_new(img, 32, 3, false, L);                 // c0  (leaky, as the reference)
         x = conv_new(x, 64, 3, true, L);                         // c1  (leaky, as the reference)
@@ -265,7 +269,7 @@ struct Builder {
         x = conv_new(x, 1024, 1, false, M);                      // c71
         x = conv_new(x, 512, 1, false, L);
         x = conv_new(x, 1024, 3, false, L);
-        View cat_spp = alloc(x.side, 2048);                      // [mp13 | mp9 | mp5 | x]
+        View cat_spp = alloc(x.h, x.w, 2048);                     // [mp13 | mp9 | mp5 | x]
         conv(x, slice(cat_spp, 1536, 512), 512, 1, false, L);    // c74
         {
             Op op{};
@@ -275,31 +279,31 @@ struct Builder {
         }
         x = conv_new(cat_spp, 512, 1, false, L);
         x = conv_new(x, 1024, 3, false, L);
-        View cat_bu2 = alloc(x.side, 1024);                      // [down(route1'') | route2]
+        View cat_bu2 = alloc(x.h, x.w, 1024);                     // [down(route1'') | route2]
         View route2 = slice(cat_bu2, 512, 512);
         conv(x, route2, 512, 1, false, L);                       // c77
         // ---- yolov4_neck, reference custom_layers.py:141-198
-        View cat_td1 = alloc(route1.side, 512);                  // [lateral(route1) | up(route2)]
+        View cat_td1 = alloc(route1.h, route1.w, 512);                 // [lateral(route1) | up(route2)]
         conv(route2, slice(cat_td1, 256, 256), 256, 1, false, L, true, nullptr, /*upsample=*/true);   // c78
         conv(route1, slice(cat_td1, 0, 256), 256, 1, false, L);                                       // c79
-        View cat_bu1 = alloc(route1.side, 512);                  // [down(route0') | route1']
+        View cat_bu1 = alloc(route1.h, route1.w, 512);                 // [down(route0') | route1']
         View route1p = five(cat_td1, 256, slice(cat_bu1, 256, 256));                                  // c80-c84
-        View cat_td0 = alloc(route0.side, 256);                  // [lateral(route0) | up(route1')]
+        View cat_td0 = alloc(route0.h, route0.w, 256);                 // [lateral(route0) | up(route1')]
         conv(route1p, slice(cat_td0, 128, 128), 128, 1, false, L, true, nullptr, /*upsample=*/true);  // c85
         conv(route0, slice(cat_td0, 0, 128), 128, 1, false, L);                                       // c86
-        View route0p = five(cat_td0, 128, alloc(route0.side, 128));                                   // c87-c91
+        View route0p = five(cat_td0, 128, alloc(route0.h, route0.w, 128));                                   // c87-c91
         x = conv_new(route0p, 256, 3, false, L);                                                      // c92
-        c.heads[0] = alloc(route0.side, c.hcs, true); c.heads[0].c = nout;
+        c.heads[0] = alloc(route0.h, route0.w, c.hcs, true); c.heads[0].c = nout;
         conv(x, c.heads[0], nout, 1, false, Y4_ACT_LINEAR, false, nullptr, false, true);              // c93
         conv(route0p, slice(cat_bu1, 0, 256), 256, 3, true, L);                                       // c94
-        View route1pp = five(cat_bu1, 256, alloc(route1.side, 256));                                  // c95-c99
+        View route1pp = five(cat_bu1, 256, alloc(route1.h, route1.w, 256));                                  // c95-c99
         x = conv_new(route1pp, 512, 3, false, L);                                                     // c100
-        c.heads[1] = alloc(route1.side, c.hcs, true); c.heads[1].c = nout;
+        c.heads[1] = alloc(route1.h, route1.w, c.hcs, true); c.heads[1].c = nout;
         conv(x, c.heads[1], nout, 1, false, Y4_ACT_LINEAR, false, nullptr, false, true);              // c101
         conv(route1pp, slice(cat_bu2, 0, 512), 512, 3, true, L);                                      // c102
-        x = five(cat_bu2, 512, alloc(cat_bu2.side, 512));                                             // c103-c107
+        x = five(cat_bu2, 512, alloc(cat_bu2.h, cat_bu2.w, 512));                                             // c103-c107
         x = conv_new(x, 1024, 3, false, L);                                                           // c108
-        c.heads[2] = alloc(cat_bu2.side, c.hcs, true); c.heads[2].c = nout;
+        c.heads[2] = alloc(cat_bu2.h, cat_bu2.w, c.hcs, true); c.heads[2].c = nout;
         conv(x, c.heads[2], nout, 1, false, Y4_ACT_LINEAR, false, nullptr, false, true);              // c109
     }
 };
@@ -429,7 +433,7 @@ void find_stage(y4_ctx& c) {
         // dataflow: b reads a's main-in half, d reads b and adds a's main-in half, e reads d, f reads [e | a's route half]
         if (!(same_view(b.in, a.out2) && same_view(d.in, b.out) && same_view(d.res, a.out2) && same_view(e.in, d.out))) continue;
         if (!(f.in.buf == e.out.buf && f.in.buf == a.out.buf && e.out.coff == f.in.coff && a.out.coff == f.in.coff + 64 && f.in.c == 128)) continue;
-        if (a.upsample || f.upsample || f.out_f32 || a.in.side % 16 != 0) continue;
+        if (a.upsample || f.upsample || f.out_f32 || !csp_stage_supported(c.cfg.dtype, a.in.h, a.in.w)) continue;
         // no other op may read the tensors that stop existing
         bool leak = false;
         for (int k = 0; k < nops; ++k) {
@@ -506,7 +510,7 @@ void layout(y4_ctx& c) {
     size_t off = 0;
     c.zero_off = off; off += ZERO_PAGE_BYTES;
     const size_t nb = (size_t)c.cfg.max_batch;
-    for (auto& b : c.bufs) b.bytes = nb * b.side * b.side * b.channels * (b.f32 ? 4 : c.es);
+    for (auto& b : c.bufs) b.bytes = nb * b.h * b.w * b.channels * (b.f32 ? 4 : c.es);
     if (!c.alias_bufs) {
         for (auto& b : c.bufs) {
             b.offset = off;
@@ -550,7 +554,7 @@ void layout(y4_ctx& c) {
     c.scratch_off = off; off = align256(off + nb * (size_t)c.cfg.max_total * 28 + nb * 4);
     c.splitk_off = off; off = align256(off + SPLITK_WS_BYTES);
     c.cells_per_img = 0;
-    for (int i = 0; i < 3; ++i) { c.cell_base[i] = c.cells_per_img; c.cells_per_img += c.heads[i].side * c.heads[i].side; }
+    for (int i = 0; i < 3; ++i) { c.cell_base[i] = c.cells_per_img; c.cells_per_img += c.heads[i].h * c.heads[i].w; }
     c.obj_off = off; off = align256(off + nb * (size_t)c.cells_per_img * 16);
     c.act_bytes = off;
     // ---- weights
@@ -584,13 +588,13 @@ int check_ready(y4_handle h, int n) {
 
 char* buf_ptr(y4_handle h, const View& v, int img0 = 0) {
     const Buffer& b = h->bufs[v.buf];
-    return h->act + b.offset + (size_t)img0 * b.side * b.side * b.channels * (b.f32 ? 4 : h->es);
+    return h->act + b.offset + (size_t)img0 * b.h * b.w * b.channels * (b.f32 ? 4 : h->es);
 }
 
 // image `img0` of the caller's batch (float32 or uint8 elements, see y4_ctx::img_u8)
 const void* img_at(y4_handle h, const void* imgs, int img0) {
     if (!imgs) return imgs;
-    return (const char*)imgs + (size_t)img0 * h->S * h->S * 3 * (h->img_u8 ? 1 : 4);
+    return (const char*)imgs + (size_t)img0 * h->H * h->W * 3 * (h->img_u8 ? 1 : 4);
 }
 
 struct Launch {
@@ -610,14 +614,14 @@ void build_schedule(y4_handle h, int n, std::vector<Launch>& out) {
 }
 
 int run_op(y4_handle h, const Op& op, const void* imgs, int n, hipStream_t s, int img0 = 0, bool allow_chain = true) {
-    if (op.kind == OP_SPP) return spp_launch(h->cfg.dtype, buf_ptr(h, op.in, img0), n, op.in.side, op.in.cstride / 4, s);
+    if (op.kind == OP_SPP) return spp_launch(h->cfg.dtype, buf_ptr(h, op.in, img0), n, op.in.h, op.in.w, op.in.cstride / 4, s);
     const Layer& L = h->layers[op.conv];
     const float* scale = (const float*)(h->wts + L.scale_off);
     const float* shift = (const float*)(h->wts + L.shift_off);
     if (op.kind == OP_STEM && h->fuse_stem) {
         const Op& o1 = h->ops[1];
         const Layer& L1 = h->layers[1];
-        return stem_down_launch(h->cfg.dtype, img_at(h, imgs, img0), h->img_u8 ? 1 : 0, n, h->S,
+        return stem_down_launch(h->cfg.dtype, img_at(h, imgs, img0), h->img_u8 ? 1 : 0, n, h->H,      // (square only: y4_set_stem_fusion)
                                 h->wts + L.w_off, scale, shift, L.d.act, h->wts + L1.w_off,
                                 (const float*)(h->wts + L1.scale_off), (const float*)(h->wts + L1.shift_off), L1.d.act,
                                 buf_ptr(h, o1.out, img0), o1.out.cstride, o1.out.coff, s);
@@ -628,12 +632,12 @@ int run_op(y4_handle h, const Op& op, const void* imgs, int n, hipStream_t s, in
         if (const ResRun* rr = h->res_of((int)(&op - h->ops.data()), &is_head)) {
             if (!is_head) return Y4_OK;                          // the 3x3 conv ran inside its block's kernel
             const Op& last = h->ops[rr->tail];
-            const int64_t per_img = (int64_t)op.in.side * op.in.side * op.in.cstride * h->es;
+            const int64_t per_img = (int64_t)op.in.h * op.in.w * op.in.cstride * h->es;
             const int max_n = (int)(((1ll << 31) - 1) / per_img);
             Y4_REQUIRE(max_n >= 1, Y4_EINVAL, "residual block: one image of the input view (%lld B) exceeds the 2 GiB buffer range", (long long)per_img);
             for (int i0 = 0; i0 < n; i0 += max_n) {
                 const int cnt = n - i0 < max_n ? n - i0 : max_n;
-                if (int r = resblock_launch(h->cfg.dtype, rr->c, buf_ptr(h, op.in, img0 + i0), cnt, op.in.side, op.in.cstride, op.in.coff,
+                if (int r = resblock_launch(h->cfg.dtype, rr->c, buf_ptr(h, op.in, img0 + i0), cnt, op.in.h, op.in.w, op.in.cstride, op.in.coff,
                                             h->wts + rr->blob_off, buf_ptr(h, last.out, img0 + i0), last.out.cstride, last.out.coff, s))
                     return r;
             }
@@ -645,12 +649,12 @@ int run_op(y4_handle h, const Op& op, const void* imgs, int n, hipStream_t s, in
         if (oi > h->stage_first && oi <= h->stage_last) return Y4_OK;      // ran inside the stage kernel
         if (oi == h->stage_first) {
             const Op& last = h->ops[h->stage_last];
-            const int64_t per_img = (int64_t)op.in.side * op.in.side * op.in.cstride * h->es;
+            const int64_t per_img = (int64_t)op.in.h * op.in.w * op.in.cstride * h->es;
             const int max_n = (int)(((1ll << 31) - 1) / per_img);
             Y4_REQUIRE(max_n >= 1, Y4_EINVAL, "stage kernel: one image of the input view (%lld B) exceeds the 2 GiB buffer range", (long long)per_img);
             for (int i0 = 0; i0 < n; i0 += max_n) {           // 2 GiB buffer-descriptor range: image chunks
                 const int cnt = n - i0 < max_n ? n - i0 : max_n;
-                if (int r = csp_stage_launch(h->cfg.dtype, buf_ptr(h, op.in, img0 + i0), cnt, op.in.side, op.in.cstride, op.in.coff,
+                if (int r = csp_stage_launch(h->cfg.dtype, buf_ptr(h, op.in, img0 + i0), cnt, op.in.h, op.in.w, op.in.cstride, op.in.coff,
                                              h->wts + h->stage_blob_off, buf_ptr(h, last.out, img0 + i0), last.out.cstride,
                                              last.out.coff, s))
                     return r;
@@ -666,15 +670,15 @@ int run_op(y4_handle h, const Op& op, const void* imgs, int n, hipStream_t s, in
             else if (&h->ops[ch.tail[0]] == &op || (ch.tail[1] >= 0 && &h->ops[ch.tail[1]] == &op)) return Y4_OK;   // ran with its head
         }
     if (op.kind == OP_STEM)
-        return stem_conv_launch(h->cfg.dtype, img_at(h, imgs, img0), h->img_u8 ? 1 : 0, n, h->S, h->S,
+        return stem_conv_launch(h->cfg.dtype, img_at(h, imgs, img0), h->img_u8 ? 1 : 0, n, h->H, h->W,
                                 (const float*)(h->wts + L.w_off), scale, shift, L.d.cout, L.d.act,
                                 buf_ptr(h, op.out, img0), op.out.cstride, op.out.coff, s);
     {
         // the conv kernels address their input through a raw buffer descriptor (2 GiB range, conv_igemm.hip): a batch
         // whose input view is larger runs as consecutive image chunks of this same op (images are independent)
-        const int64_t per_img = (int64_t)op.in.side * op.in.side * op.in.cstride * h->es;
+        const int64_t per_img = (int64_t)op.in.h * op.in.w * op.in.cstride * h->es;
         // (minus the reach of a 3x3 kernel's biased tap offsets: conv2d_launch's own check)
-        const int64_t tap_span = L.d.ksize == 3 ? ((int64_t)3 * op.in.side + 3) * op.in.cstride * h->es + (int64_t)op.in.c * h->es : 0;
+        const int64_t tap_span = L.d.ksize == 3 ? ((int64_t)3 * op.in.w + 3) * op.in.cstride * h->es + (int64_t)op.in.c * h->es : 0;
         const int max_n = (int)(((1ll << 31) - 1 - tap_span) / per_img);
         Y4_REQUIRE(max_n >= 1, Y4_EINVAL, "conv %d: one image's input (%lld B) exceeds the 2 GiB buffer-descriptor range",
                    op.conv, (long long)per_img);
@@ -686,7 +690,7 @@ int run_op(y4_handle h, const Op& op, const void* imgs, int n, hipStream_t s, in
     }
     y4_conv_desc d{};
     d.dtype = h->cfg.dtype;
-    d.n = n; d.h = op.in.side; d.w = op.in.side; d.cin = op.in.c;
+    d.n = n; d.h = op.in.h; d.w = op.in.w; d.cin = op.in.c;
     d.cout = op.conv2 >= 0 ? 2 * L.d.cout : L.d.cout; d.ksize = L.d.ksize; d.stride = L.d.stride; d.act = L.d.act;
     d.upsample = op.upsample ? 1 : 0; d.out_f32 = op.out_f32 ? 1 : 0;
     d.in_cstride = op.in.cstride; d.in_coff = op.in.coff;
@@ -782,16 +786,16 @@ int run_decode_nms(y4_handle h, int n, float iou_thr, float score_thr, float* bo
         int off = 0, cells = 0;
         for (int i = 0; i < 3; ++i) {
             k.head[i] = (const float*)buf_ptr(h, h->heads[i]);
-            k.g[i] = h->heads[i].side; k.stride[i] = cfg.strides[i]; k.box_off[i] = off;
-            off += 3 * k.g[i] * k.g[i]; cells += k.g[i] * k.g[i];
+            k.gh[i] = h->heads[i].h; k.gw[i] = h->heads[i].w; k.stride[i] = cfg.strides[i]; k.box_off[i] = off;
+            off += 3 * k.gh[i] * k.gw[i]; cells += k.gh[i] * k.gw[i];
             k.xyscale[i] = cfg.xyscale[i];
             k.xyoff[i] = (float)(0.5 * ((double)cfg.xyscale[i] - 1.0));
         }
         memcpy(k.anchors, cfg.anchors, sizeof(k.anchors));
         k.cells_per_img = cells; k.N = n; k.C = cfg.num_classes; k.hcs = h->hcs; k.nbox = h->nbox;
         k.div_cells = fastdiv_make((uint32_t)cells);
-        for (int i = 0; i < 3; ++i) k.div_g[i] = fastdiv_make((uint32_t)k.g[i]);
-        k.img_size = (float)cfg.img_size; k.score_thr = score_thr;
+        for (int i = 0; i < 3; ++i) k.div_gw[i] = fastdiv_make((uint32_t)k.gw[i]);
+        k.img_h = (float)h->H; k.img_w = (float)h->W; k.score_thr = score_thr;
         k.dboxes = (float*)(h->act + h->dbox_off);
         k.keys = (unsigned long long*)(h->act + h->keys_off);
         k.counts = (uint32_t*)(h->act + h->counts_off);
@@ -822,13 +826,18 @@ int run_decode_nms(y4_handle h, int n, float iou_thr, float score_thr, float* bo
 extern "C" {
 
 const char* y4_last_error(void) { return g_err; }
-const char* y4_version(void) { return "yolo4hip 0.3 (gfx950)"; }
+const char* y4_version(void) { return "yolo4hip 0.4 (gfx950)"; }
 
 int y4_create(const y4_config* cfg, y4_handle* out) {
     Y4_REQUIRE(cfg && out, Y4_EINVAL, "y4_create: null argument");
-    // the reference's asserts (models.py:23-24,38); non-square inputs are 'not support yet' there too
-    Y4_REQUIRE(cfg->img_size > 0 && cfg->img_size % 32 == 0, Y4_EINVAL,
-               "img_size %d must be a positive multiple of the last stride (32)", cfg->img_size);
+    return y4_create_hw(cfg, cfg->img_size, cfg->img_size, out);
+}
+
+int y4_create_hw(const y4_config* cfg, int32_t img_h, int32_t img_w, y4_handle* out) {
+    Y4_REQUIRE(cfg && out, Y4_EINVAL, "y4_create_hw: null argument");
+    // the reference's asserts (models.py:24,38), for each side; the reference's 'not support yet' for H != W is lifted
+    Y4_REQUIRE(img_h > 0 && img_h % 32 == 0 && img_w > 0 && img_w % 32 == 0, Y4_EINVAL,
+               "img_size %d x %d: each side must be a positive multiple of the last stride (32)", img_h, img_w);
     Y4_REQUIRE(cfg->num_classes > 0, Y4_EINVAL, "no classes detected!");
     Y4_REQUIRE(cfg->num_classes <= 4096, Y4_EINVAL, "num_classes %d too large", cfg->num_classes);
     Y4_REQUIRE(cfg->max_batch >= 1, Y4_EINVAL, "max_batch %d", cfg->max_batch);
@@ -838,11 +847,12 @@ int y4_create(const y4_config* cfg, y4_handle* out) {
     Y4_REQUIRE(cfg->max_total >= 1 && cfg->max_total <= 1024 && cfg->max_per_class >= 1, Y4_EINVAL, "max_total/max_per_class");
     y4_ctx* c = new y4_ctx();
     c->cfg = *cfg;
+    c->cfg.img_size = img_h == img_w ? img_h : -1;    // (a rectangle has no one side: H and W below)
     c->es = elem_size(cfg->dtype);
-    c->S = cfg->img_size;
+    c->H = img_h; c->W = img_w;
     c->hcs = (int)round_up(3 * (cfg->num_classes + 5), 8);
     c->nbox = 0;
-    for (int i = 0; i < 3; ++i) { const int g = c->S / cfg->strides[i]; c->nbox += 3 * g * g; }
+    for (int i = 0; i < 3; ++i) c->nbox += 3 * (c->H / cfg->strides[i]) * (c->W / cfg->strides[i]);
     if ((int64_t)c->nbox * cfg->num_classes >= (1ll << 31)) {
         delete c;
         set_error("num_boxes*num_classes overflows the 32-bit candidate id");
@@ -868,6 +878,21 @@ int y4_layer_info(y4_handle h, int idx, y4_layer_desc* out) {
     if (int r = check_handle(h)) return r;
     Y4_REQUIRE(out && idx >= 0 && idx < (int)h->layers.size(), Y4_EINVAL, "layer index %d", idx);
     *out = h->layers[idx].d;
+    return Y4_OK;
+}
+
+int y4_input_dims(y4_handle h, int32_t* img_h, int32_t* img_w) {
+    if (int r = check_handle(h)) return r;
+    if (img_h) *img_h = h->H;
+    if (img_w) *img_w = h->W;
+    return Y4_OK;
+}
+
+int y4_layer_dims(y4_handle h, int idx, int32_t dims[4]) {
+    if (int r = check_handle(h)) return r;
+    Y4_REQUIRE(dims && idx >= 0 && idx < (int)h->layers.size(), Y4_EINVAL, "layer index %d", idx);
+    const Layer& L = h->layers[idx];
+    dims[0] = L.in_h; dims[1] = L.in_w; dims[2] = L.out_h; dims[3] = L.out_w;
     return Y4_OK;
 }
 
@@ -1033,7 +1058,7 @@ int y4_get_heads(y4_handle h, int n, float* out_s, float* out_m, float* out_l, v
     for (int i = 0; i < 3; ++i) {
         if (!outs[i]) continue;
         const View& v = h->heads[i];
-        if (int r = view_to_f32_launch(Y4_F32, buf_ptr(h, v), outs[i], (int64_t)n * v.side * v.side, v.cstride, v.coff,
+        if (int r = view_to_f32_launch(Y4_F32, buf_ptr(h, v), outs[i], (int64_t)n * v.h * v.w, v.cstride, v.coff,
                                        v.c, (hipStream_t)stream))
             return r;
     }
@@ -1047,7 +1072,7 @@ int y4_set_heads(y4_handle h, int n, const float* in_s, const float* in_m, const
         Y4_REQUIRE(ins[i], Y4_EINVAL, "y4_set_heads: null head %d", i);
         h->obj_n[i] = -1;
         const View& v = h->heads[i];
-        if (int r = f32_to_view_launch(ins[i], (float*)buf_ptr(h, v), (int64_t)n * v.side * v.side, v.cstride, v.c,
+        if (int r = f32_to_view_launch(ins[i], (float*)buf_ptr(h, v), (int64_t)n * v.h * v.w, v.cstride, v.c,
                                        (hipStream_t)stream))
             return r;
     }
@@ -1069,7 +1094,7 @@ int y4_get_conv_output(y4_handle h, int conv_idx, int n, float* out, size_t out_
                        "conv %d is not materialised while the residual-block fusion is on", conv_idx);
         }
         const View& v = op.conv == conv_idx ? op.out : op.out2;
-        const int64_t px = (int64_t)n * v.side * v.side;   // for an upsampling conv: the upsampled tensor
+        const int64_t px = (int64_t)n * v.h * v.w;   // for an upsampling conv: the upsampled tensor
         Y4_REQUIRE((int64_t)out_floats >= px * v.c, Y4_EINVAL, "output buffer too small: %zu < %lld", out_floats,
                    (long long)(px * v.c));
         return view_to_f32_launch(op.out_f32 ? Y4_F32 : h->cfg.dtype, buf_ptr(h, v), out, px, v.cstride, v.coff, v.c,
@@ -1173,7 +1198,7 @@ static int autotune_impl(y4_handle h, y4_handle h2, int n, int reps, hipStream_t
         if (int r = check_ready(h2, n)) return r;
     Y4_REQUIRE(reps >= 1 && reps <= 100, Y4_EINVAL, "y4_autotune: reps %d", reps);
     Y4_REQUIRE(!h2 || (h2 != h && h2->ops.size() == h->ops.size() && h2->chains.size() == h->chains.size() &&
-                       h2->cfg.dtype == h->cfg.dtype && h2->S == h->S && s2 != s),
+                       h2->cfg.dtype == h->cfg.dtype && h2->H == h->H && h2->W == h->W && s2 != s),
                Y4_EINVAL, "y4_autotune_pair: the second handle must be a sibling of the first (same plan) on another stream");
     hipEvent_t e0, e1, e2;
     Y4_CHECK_HIP(hipEventCreate(&e0));
@@ -1465,8 +1490,11 @@ int y4_set_stem_fusion(y4_handle h, int on) {
                               h->ops[1].conv == 1 && h->ops[1].conv2 < 0 && !h->ops[1].has_res &&
                               h->layers[0].d.cout == 32 && h->layers[1].d.cout == 64 && h->layers[1].d.ksize == 3 &&
                               h->layers[1].d.stride == 2;
-        Y4_REQUIRE(shape_ok && stem_down_supported(h->cfg.dtype, h->S), Y4_EINVAL,
-                   "y4_set_stem_fusion: needs a 16-bit dtype and img_size <= 640 (dtype %d, img_size %d)", h->cfg.dtype, h->S);
+        // stem_down.hip walks a square image (one side S for rows and columns): a rectangular handle runs convs 0 and 1 apart
+        Y4_REQUIRE(h->H == h->W, Y4_EINVAL, "y4_set_stem_fusion: square inputs only (this handle is %d x %d); convs 0 and 1 run as "
+                   "separate kernels", h->H, h->W);
+        Y4_REQUIRE(shape_ok && stem_down_supported(h->cfg.dtype, h->H), Y4_EINVAL,
+                   "y4_set_stem_fusion: needs a 16-bit dtype and img_size <= 640 (dtype %d, img_size %d)", h->cfg.dtype, h->H);
     }
     h->fuse_stem = on != 0;
     return Y4_OK;
@@ -1560,7 +1588,7 @@ int y4_copy_schedule(y4_handle src, y4_handle dst) {
     Y4_REQUIRE(src != dst, Y4_EINVAL, "y4_copy_schedule: source and destination are the same handle");
     Y4_REQUIRE(dst->t_max_steps == 0, Y4_ESTATE, "y4_copy_schedule: a timing session is open on the destination");
     Y4_REQUIRE(src->ops.size() == dst->ops.size() && src->chains.size() == dst->chains.size() &&
-               src->resruns.size() == dst->resruns.size() && src->cfg.dtype == dst->cfg.dtype && src->S == dst->S &&
+               src->resruns.size() == dst->resruns.size() && src->cfg.dtype == dst->cfg.dtype && src->H == dst->H && src->W == dst->W &&
                src->cfg.num_classes == dst->cfg.num_classes && src->cfg.max_batch == dst->cfg.max_batch, Y4_EINVAL,
                "y4_copy_schedule: the handles were not created from the same configuration");
     Y4_REQUIRE(src->sub_images <= 0 || !dst->alias_bufs, Y4_ESTATE,
@@ -1736,7 +1764,11 @@ int y4_preprocess_u8(const uint8_t* img_dev, int h, int w, float* out_dev, int o
 }
 
 int y4_spp(int dtype, void* buf_dev, int n, int side, int c, void* stream) {
-    return spp_launch(dtype, buf_dev, n, side, c, (hipStream_t)stream);
+    return spp_launch(dtype, buf_dev, n, side, side, c, (hipStream_t)stream);
+}
+
+int y4_spp_hw(int dtype, void* buf_dev, int n, int h, int w, int c, void* stream) {
+    return spp_launch(dtype, buf_dev, n, h, w, c, (hipStream_t)stream);
 }
 
 }  // extern "C"

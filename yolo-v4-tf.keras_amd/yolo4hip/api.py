@@ -6,7 +6,8 @@ weight_path, max_boxes`), `.yolo_model.predict(imgs)` -> 3 raw heads, `.inferenc
 `[boxes, scores, classes, valid_detections]`, `.predict / .predict_img / .predict_raw / .predict_nonms`
 with their prints (`img shape:`, `# of bboxes:`) and DataFrame layout.
 Differences, all supersets: the passed `config` is honoured (the reference reads the module global,
-models.py:26-37); grid sizes follow img_size (the reference hard-codes 52/26/13); extra keyword-only
+models.py:26-37); grid sizes follow img_size (the reference hard-codes 52/26/13) and img_size may be a rectangle (H, W, 3) --
+the reference's 'not support yet' assert is lifted, boxes are normalised x / W, y / H; extra keyword-only
 arguments pick the compute dtype / batch capacity.  `save_model` / `load_model` (models.py:86-93) are stand-ins on a
 self-describing checkpoint of this framework (Keras' SavedModel / H5 needs TensorFlow); `eval_map` (models.py:182-507)
 is the VOC mAP tool over the exported text files (yolo4hip/evalmap.py).  Training (`fit`, `training_model`) is out of
@@ -38,8 +39,9 @@ class _KerasLikeModel:
 class Yolov4(object):
     def __init__(self, weight_path=None, class_name_path='coco_classes.txt', config=yolo_config, *,
                  dtype='f32', max_batch=32, synth_seed=0, device=None, device_preprocess=True, tune=None, share_schedule=None):
-        assert config['img_size'][0] == config['img_size'][1], 'not support yet'
+        # (reference models.py:23 also asserts img_size[0] == img_size[1], 'not support yet': rectangles are supported here)
         assert config['img_size'][0] % config['strides'][-1] == 0, 'must be a multiple of last stride'
+        assert config['img_size'][1] % config['strides'][-1] == 0, 'must be a multiple of last stride'
         self.class_names = [line.strip() for line in open(class_name_path).readlines()]
         self.img_size = tuple(config['img_size'])
         self.num_classes = len(self.class_names)
@@ -47,7 +49,9 @@ class Yolov4(object):
         self.anchors = np.array(config['anchors']).reshape((3, 3, 2))
         self.xyscale = config['xyscale']
         self.strides = config['strides']
-        self.output_sizes = [self.img_size[0] // s for s in self.strides]
+        H, W = self.img_size[0], self.img_size[1]
+        # square: one grid side per scale (as the reference); rectangle: (rows, columns) per scale
+        self.output_sizes = [H // s for s in self.strides] if H == W else [(H // s, W // s) for s in self.strides]
         self.class_color = {name: list(np.random.random(size=3) * 255) for name in self.class_names}
         self.max_boxes = config['max_boxes']
         self.iou_loss_thresh = config.get('iou_loss_thresh', 0.5)
@@ -70,7 +74,7 @@ class Yolov4(object):
         self.build_model(load_pretrained=True if self.weight_path else False)
 
     def build_model(self, load_pretrained=True):
-        self.plan = build_plan(self.img_size[0], self.num_classes)
+        self.plan = build_plan(self.img_size[:2], self.num_classes)
         # alias_workspace: like the reference's Keras model, the facade keeps no intermediate activations (2.7x less HBM)
         self.engine = Engine(self.num_classes, self.config, max_batch=self._max_batch, dtype=self._dtype,
                              device=self._device, alias_workspace=True)

@@ -26,8 +26,12 @@ yolo_config = {
 
 
 def make_config(img_size=416, **overrides):
-    """Copy of `yolo_config` at another square resolution (e.g. 608 for the headline configs)."""
+    """Copy of `yolo_config` at another resolution: a square side (e.g. 608 for the headline configs) or (H, W), height
+    first like the Keras Input shape (e.g. (352, 608) for 16:9 frames) -> img_size (H, W, 3)."""
     cfg = dict(yolo_config)
-    cfg['img_size'] = (int(img_size), int(img_size), 3)
+    if isinstance(img_size, (tuple, list)):
+        cfg['img_size'] = (int(img_size[0]), int(img_size[1]), 3)
+    else:
+        cfg['img_size'] = (int(img_size), int(img_size), 3)
     cfg.update(overrides)
     return cfg

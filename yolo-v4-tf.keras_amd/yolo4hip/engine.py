@@ -12,13 +12,19 @@ from . import ext
 from .config import yolo_config
 
 
+def _img_hw(config):
+    """(H, W) of config['img_size'] = (H, W, 3), the Keras Input shape (height first)."""
+    size = config["img_size"]
+    return int(size[0]), int(size[1])
+
+
 def _cfg_struct(config, num_classes, max_batch, dtype):
     c = ext.y4_config()
-    size = config["img_size"]
-    assert size[0] == size[1], "not support yet"                      # reference models.py:23
-    assert size[0] % config["strides"][-1] == 0, "must be a multiple of last stride"   # models.py:24
+    H, W = _img_hw(config)
+    # reference models.py:24, for each side (its models.py:23 'not support yet' for H != W is lifted: y4_create_hw)
+    assert H % config["strides"][-1] == 0 and W % config["strides"][-1] == 0, "must be a multiple of last stride"
     assert num_classes > 0, "no classes detected!"                   # models.py:38
-    c.img_size = int(size[0]); c.num_classes = int(num_classes); c.max_batch = int(max_batch)
+    c.img_size = H; c.num_classes = int(num_classes); c.max_batch = int(max_batch)     # (img_size: y4_create only)
     c.dtype = ext.DTYPE_IDS[dtype] if isinstance(dtype, str) else int(dtype)
     anchors = np.asarray(config["anchors"], dtype=np.float32).reshape(-1)
     assert anchors.size == 18, "9 anchors (w,h) expected"
@@ -48,9 +54,11 @@ class Engine:
         self.max_batch = int(max_batch)
         self.cfg = _cfg_struct(self.config, num_classes, max_batch, dtype)
         self.dtype = ext.DTYPE_NAMES[self.cfg.dtype]
-        self.img_size = self.cfg.img_size
+        # img_size: the side of a square engine (as before), (H, W) of a rectangular one; img_hw is (H, W) either way
+        self.img_hw = _img_hw(self.config)
+        self.img_size = self.img_hw[0] if self.img_hw[0] == self.img_hw[1] else self.img_hw
         self.handle = C.c_void_p()
-        ext.check(self.lib.y4_create(C.byref(self.cfg), C.byref(self.handle)))
+        ext.check(self.lib.y4_create_hw(C.byref(self.cfg), self.img_hw[0], self.img_hw[1], C.byref(self.handle)))
         flops, nbox, hcs, wfl = C.c_int64(), C.c_int32(), C.c_int32(), C.c_int64()
         ext.check(self.lib.y4_model_info(self.handle, C.byref(flops), C.byref(nbox), C.byref(hcs), C.byref(wfl)))
         self.flops_per_image, self.num_boxes = flops.value, nbox.value
@@ -68,7 +76,8 @@ class Engine:
             self.wts = torch.zeros(self.wts_bytes, dtype=torch.uint8, device=self.device)
             ext.check(self.lib.y4_bind_workspace(self.handle, ext.ptr(self.act), self.act_bytes, ext.ptr(self.wts),
                                                  self.wts_bytes))
-        self.grids = [self.img_size // s for s in self.config["strides"]]
+        self.grids_hw = [(self.img_hw[0] // s, self.img_hw[1] // s) for s in self.config["strides"]]
+        self.grids = [g[0] for g in self.grids_hw] if self.img_hw[0] == self.img_hw[1] else list(self.grids_hw)
         self.nout = 3 * (self.num_classes + 5)
         self.T = self.cfg.max_total
         self.halo2 = False
@@ -85,8 +94,9 @@ class Engine:
         e = Engine.__new__(Engine)
         e.torch, e.lib, e.config, e.device = torch, self.lib, dict(self.config), self.device
         e.num_classes, e.max_batch, e.cfg, e.dtype, e.img_size = self.num_classes, self.max_batch, self.cfg, self.dtype, self.img_size
+        e.img_hw = self.img_hw
         e.handle = C.c_void_p()
-        ext.check(self.lib.y4_create(C.byref(e.cfg), C.byref(e.handle)))
+        ext.check(self.lib.y4_create_hw(C.byref(e.cfg), e.img_hw[0], e.img_hw[1], C.byref(e.handle)))
         e.alias_workspace = getattr(self, "alias_workspace", False)
         if e.alias_workspace:
             ext.check(self.lib.y4_set_workspace_aliasing(e.handle, 1))
@@ -97,7 +107,7 @@ class Engine:
             e.act = torch.empty(e.act_bytes, dtype=torch.uint8, device=self.device)
             e.wts = self.wts                                   # the SAME tensor: packed weights are never written after packing
             ext.check(self.lib.y4_bind_workspace(e.handle, ext.ptr(e.act), e.act_bytes, ext.ptr(e.wts), e.wts_bytes))
-        e.grids, e.nout, e.T = list(self.grids), self.nout, self.T
+        e.grids, e.grids_hw, e.nout, e.T = list(self.grids), list(self.grids_hw), self.nout, self.T
         e.adopt_packed()
         self.copy_schedule_to(e)
         return e
@@ -199,20 +209,21 @@ class Engine:
                 if a.dtype != np.float32:
                     a = a.astype(np.float32)
                 t = torch.from_numpy(np.ascontiguousarray(a)).to(self.device)
-        if t.dim() != 4 or t.shape[1] != self.img_size or t.shape[2] != self.img_size or t.shape[3] != 3:
-            raise ValueError(f"expected images of shape [N,{self.img_size},{self.img_size},3], got {tuple(t.shape)}")
+        H, W = self.img_hw
+        if t.dim() != 4 or t.shape[1] != H or t.shape[2] != W or t.shape[3] != 3:
+            raise ValueError(f"expected images of shape [N,{H},{W},3], got {tuple(t.shape)}")
         return t.contiguous()
 
     def preprocess_u8(self, raw_imgs, as_float=False):
         """Device-side `Yolov4.preprocess_img` (reference models.py:95-98) for one uint8 RGB image [h,w,3] or a list of
-        them (any sizes).  Returns the tensor `forward_device` / `predict` take: by default a uint8 cuda tensor [n,S,S,3]
+        them (any sizes).  Returns the tensor `forward_device` / `predict` take: by default a uint8 cuda tensor [n,H,W,3]
         (the resize done with cv2's uint8 arithmetic; the `/ 255.` then happens inside the stem's operand load), with
         as_float=True the float32 tensor in [0,1] (`y4_preprocess_u8`).  Both give bit-identical network outputs."""
         torch = self.torch
         if isinstance(raw_imgs, np.ndarray) and raw_imgs.ndim == 3:
             raw_imgs = [raw_imgs]
-        S = self.img_size
-        out = torch.empty((len(raw_imgs), S, S, 3), dtype=torch.float32 if as_float else torch.uint8, device=self.device)
+        H, W = self.img_hw
+        out = torch.empty((len(raw_imgs), H, W, 3), dtype=torch.float32 if as_float else torch.uint8, device=self.device)
         with torch.cuda.device(self.device):
             for i, im in enumerate(raw_imgs):
                 a = np.ascontiguousarray(im)
@@ -220,32 +231,32 @@ class Engine:
                     raise ValueError(f"expected uint8 [h,w,3] images, got {a.dtype} {a.shape}")
                 d = torch.from_numpy(a.copy() if not a.flags.writeable else a).to(self.device)
                 if as_float:
-                    ext.check(self.lib.y4_preprocess_u8(ext.ptr(d), a.shape[0], a.shape[1], ext.ptr(out[i]), S, S, ext.stream_ptr()))
+                    ext.check(self.lib.y4_preprocess_u8(ext.ptr(d), a.shape[0], a.shape[1], ext.ptr(out[i]), H, W, ext.stream_ptr()))
                 else:
-                    ext.check(self.lib.y4_resize_u8(ext.ptr(d), 1, a.shape[0], a.shape[1], ext.ptr(out[i]), S, S, ext.stream_ptr()))
+                    ext.check(self.lib.y4_resize_u8(ext.ptr(d), 1, a.shape[0], a.shape[1], ext.ptr(out[i]), H, W, ext.stream_ptr()))
             torch.cuda.current_stream().synchronize()       # the uint8 staging tensors may be freed now
         return out
 
     def resize_u8(self, frames_dev, out=None):
-        """Device-side `cv2.resize(img, img_size)` on a uint8 cuda batch [n,h,w,3] -> uint8 [n,S,S,3] (cv2's uint8
-        INTER_LINEAR arithmetic); frames already at network size are returned as they are."""
+        """Device-side stretch resize (cv2.resize to width W, height H) on a uint8 cuda batch [n,h,w,3] -> uint8 [n,H,W,3]
+        (cv2's uint8 INTER_LINEAR arithmetic); frames already at network size are returned as they are."""
         torch = self.torch
         n, h, w, _ = frames_dev.shape
-        S = self.img_size
-        if h == S and w == S:
+        H, W = self.img_hw
+        if h == H and w == W:
             return frames_dev
         if out is None:
-            out = torch.empty((n, S, S, 3), dtype=torch.uint8, device=self.device)
+            out = torch.empty((n, H, W, 3), dtype=torch.uint8, device=self.device)
         with torch.cuda.device(self.device):
-            ext.check(self.lib.y4_resize_u8(ext.ptr(frames_dev), n, h, w, ext.ptr(out), S, S, ext.stream_ptr()))
+            ext.check(self.lib.y4_resize_u8(ext.ptr(frames_dev), n, h, w, ext.ptr(out), H, W, ext.stream_ptr()))
         return out[:n]
 
     def _check_device_images(self, imgs_dev):
         torch = self.torch
-        S = self.img_size
-        if imgs_dev.dtype not in (torch.float32, torch.uint8) or imgs_dev.dim() != 4 or tuple(imgs_dev.shape[1:]) != (S, S, 3) \
+        H, W = self.img_hw
+        if imgs_dev.dtype not in (torch.float32, torch.uint8) or imgs_dev.dim() != 4 or tuple(imgs_dev.shape[1:]) != (H, W, 3) \
                 or not imgs_dev.is_contiguous():
-            raise ValueError(f"expected a contiguous float32 or uint8 cuda tensor [n,{S},{S},3], got {imgs_dev.dtype} {tuple(imgs_dev.shape)}")
+            raise ValueError(f"expected a contiguous float32 or uint8 cuda tensor [n,{H},{W},3], got {imgs_dev.dtype} {tuple(imgs_dev.shape)}")
         return imgs_dev.dtype == torch.uint8
 
     def forward_device(self, imgs_dev):
@@ -268,20 +279,20 @@ class Engine:
 
     def heads_device(self, n):
         torch = self.torch
-        outs = [torch.empty((n, g, g, self.nout), dtype=torch.float32, device=self.device) for g in self.grids]
+        outs = [torch.empty((n, gh, gw, self.nout), dtype=torch.float32, device=self.device) for gh, gw in self.grids_hw]
         with torch.cuda.device(self.device):
             ext.check(self.lib.y4_get_heads(self.handle, n, ext.ptr(outs[0]), ext.ptr(outs[1]), ext.ptr(outs[2]),
                                             ext.stream_ptr()))
         return outs
 
     def set_heads(self, heads):
-        """Load dense float32 raw heads (3 arrays [n,g,g,3(C+5)]) into the workspace (decode/NMS tests)."""
+        """Load dense float32 raw heads (3 arrays [n,gh,gw,3(C+5)]) into the workspace (decode/NMS tests)."""
         torch = self.torch
         ts = [torch.from_numpy(np.ascontiguousarray(h, dtype=np.float32)).to(self.device) for h in heads]
         n = ts[0].shape[0]
-        for t, g in zip(ts, self.grids):
-            if tuple(t.shape) != (n, g, g, self.nout):
-                raise ValueError(f"head shape {tuple(t.shape)} != {(n, g, g, self.nout)}")
+        for t, (gh, gw) in zip(ts, self.grids_hw):
+            if tuple(t.shape) != (n, gh, gw, self.nout):
+                raise ValueError(f"head shape {tuple(t.shape)} != {(n, gh, gw, self.nout)}")
         with torch.cuda.device(self.device):
             ext.check(self.lib.y4_set_heads(self.handle, n, ext.ptr(ts[0]), ext.ptr(ts[1]), ext.ptr(ts[2]),
                                             ext.stream_ptr()))
@@ -434,8 +445,8 @@ class Engine:
                     sl["pin_np"] = sl["pin"].numpy()
                     sl["u8"] = torch.empty(shape, dtype=torch.uint8, device=dev)
                     # frames of another size are resized uint8 -> uint8 on the device; the /255 happens in the stem's load
-                    sl["net"] = None if shape[1:3] == (self.img_size, self.img_size) else \
-                        torch.empty((self.max_batch, self.img_size, self.img_size, 3), dtype=torch.uint8, device=dev)
+                    sl["net"] = None if shape[1:3] == tuple(self.img_hw) else \
+                        torch.empty((self.max_batch, self.img_hw[0], self.img_hw[1], 3), dtype=torch.uint8, device=dev)
                     sl["flat"] = torch.empty(int(offs[-1]), dtype=torch.int32, device=dev)
                     sl["flat_host"] = torch.empty(int(offs[-1]), dtype=torch.int32).pin_memory()
                     sl["outs"], sl["host"] = views(sl["flat"]), views(sl["flat_host"])
@@ -476,9 +487,11 @@ class Engine:
         """Dense float32 NHWC copy of conv `conv_idx`'s output from the last forward (parity tap)."""
         torch = self.torch
         lt = self.layer_table()[conv_idx]
+        dims = (C.c_int32 * 4)()
+        ext.check(self.lib.y4_layer_dims(self.handle, conv_idx, dims))
         # upsampling convs (78, 85) store the 2x-upsampled tensor
-        side = lt["out_side"] * (2 if conv_idx in (78, 85) else 1)
-        out = torch.empty((n, side, side, lt["cout"]), dtype=torch.float32, device=self.device)
+        up = 2 if conv_idx in (78, 85) else 1
+        out = torch.empty((n, dims[2] * up, dims[3] * up, lt["cout"]), dtype=torch.float32, device=self.device)
         with torch.cuda.device(self.device):
             ext.check(self.lib.y4_get_conv_output(self.handle, conv_idx, n, ext.ptr(out), out.numel(), ext.stream_ptr()))
         return out.cpu().numpy()
@@ -508,6 +521,12 @@ class Engine:
         return self.get_tiles()
 
     # ---------------------------------------------------------------- shipped schedules
+    @property
+    def shape_key(self):
+        """The image-size part of schedule file names: the side of a square engine, '<H>x<W>' of a rectangular one."""
+        H, W = self.img_hw
+        return str(H) if H == W else f"{H}x{W}"
+
     def shipped_schedule(self):
         """The tuned schedule that ships with the package for this (image side, classes, batch, dtype), or None: the
         per-launch tile ids, the stage-kernel switch and the residual-block mask one `autotune` run chose on an MI355X
@@ -520,7 +539,7 @@ class Engine:
         import json
         import os
         path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "schedules",
-                            f"{self.img_size}_{self.num_classes}_{self.max_batch}_{self.dtype}.json")
+                            f"{self.shape_key}_{self.num_classes}_{self.max_batch}_{self.dtype}.json")
         try:
             saved = json.load(open(path))
         except (OSError, ValueError):
@@ -533,12 +552,12 @@ class Engine:
 
     def schedule_cache_path(self):
         """Where a schedule tuned on first use is kept: $YOLO4HIP_CACHE (default ~/.cache/yolo4hip) / schedules /
-        <side>_<classes>_<batch>_<dtype>_<gfx arch>_<library version>.json."""
+        <side>_<classes>_<batch>_<dtype>_<gfx arch>_<library version>.json (<H>x<W>_... for a rectangular engine)."""
         import os
         root = os.environ.get("YOLO4HIP_CACHE") or os.path.join(os.path.expanduser("~"), ".cache", "yolo4hip")
         arch = self.torch.cuda.get_device_properties(self.device).gcnArchName.split(":")[0]
         ver = self.lib.y4_version().decode().replace(" ", "_").replace("/", "_")
-        return os.path.join(root, "schedules", f"{self.img_size}_{self.num_classes}_{self.max_batch}_{self.dtype}_{arch}_{ver}.json")
+        return os.path.join(root, "schedules", f"{self.shape_key}_{self.num_classes}_{self.max_batch}_{self.dtype}_{arch}_{ver}.json")
 
     def ensure_schedule(self, tune=True, verbose=True, share=False):
         """Make sure this engine runs a TUNED schedule, and say which: (1) the one that ships with the package for this (image side,
@@ -557,7 +576,8 @@ class Engine:
         from . import dist as D
         rank, world = D.group_rank_world() if share else (0, 1)
         src, path, saved, err = "heuristic", None, None, None
-        mine = [int(self.img_size), int(self.num_classes), int(self.max_batch), str(self.dtype)]
+        mine = [self.img_size if isinstance(self.img_size, int) else list(self.img_size), int(self.num_classes), int(self.max_batch),
+                str(self.dtype)]
         if rank == 0:
             try:
                 src, path, saved = self._resolve_schedule(tune)
@@ -592,7 +612,7 @@ class Engine:
 
     def _all_fusions_on(self):
         if self.dtype != "f32":
-            if self.img_size <= 640:
+            if self.img_hw[0] == self.img_hw[1] and self.img_hw[0] <= 640:      # (stem_down.hip: square inputs only)
                 self.set_stem_fusion(True)
             self.set_chain_fusion(True)
             self.set_stage_fusion(True)
@@ -629,11 +649,11 @@ class Engine:
         splitk = self.max_batch <= self.LATENCY_BATCH and os.environ.get("YOLO4HIP_LATENCY", "0") == "1"
         self.set_splitk(splitk)
         from . import weights as W
-        imgs = torch.from_numpy(W.synth_images(self.max_batch, self.img_size, seed=0)).to(self.device)
+        imgs = torch.from_numpy(W.synth_images(self.max_batch, self.img_hw, seed=0)).to(self.device)
         self.predict_device(imgs)                      # real activations in the workspace
         tiles = self.autotune(self.max_batch, reps=3)
         self.set_splitk(False)
-        saved = {"size": self.img_size, "classes": self.num_classes, "batch": self.max_batch, "dtype": self.dtype,
+        saved = {"size": self.img_size if isinstance(self.img_size, int) else list(self.img_size), "classes": self.num_classes, "batch": self.max_batch, "dtype": self.dtype,
                  "tiles": tiles, "stage_fusion": bool(self.stage_fusion_active()) if self.dtype != "f32" else False,
                  "res_fusion_mask": int(self.res_fusion_mask()) if self.dtype != "f32" else 0, "in_flight": 1,
                  "splitk": any(abs(t) % 1000 >= 100 or abs(t) // 1000 >= 100 for t in tiles),
@@ -683,7 +703,7 @@ class Engine:
         self._subbatch = (int(images), int(last_conv)) if images > 0 else None
 
     def set_stem_fusion(self, on=True):
-        """Convs 0+1 as one kernel with conv 0's output kept in LDS (16-bit dtypes, img_size <= 640).  Results are
+        """Convs 0+1 as one kernel with conv 0's output kept in LDS (16-bit dtypes, square img_size <= 640).  Results are
         unchanged; conv_output(0) is unavailable while on."""
         ext.check(self.lib.y4_set_stem_fusion(self.handle, int(bool(on))))
         self.stem_fusion = bool(on)

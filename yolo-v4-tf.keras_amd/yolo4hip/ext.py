@@ -54,6 +54,9 @@ SYMBOLS = {
     "y4_last_error": (C.c_char_p, []),
     "y4_version": (C.c_char_p, []),
     "y4_create": (_I, [C.POINTER(y4_config), C.POINTER(_VP)]),
+    "y4_create_hw": (_I, [C.POINTER(y4_config), C.c_int32, C.c_int32, C.POINTER(_VP)]),
+    "y4_input_dims": (_I, [_VP, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "y4_layer_dims": (_I, [_VP, _I, C.POINTER(C.c_int32)]),
     "y4_destroy": (_I, [_VP]),
     "y4_num_layers": (_I, [_VP]),
     "y4_layer_info": (_I, [_VP, _I, C.POINTER(y4_layer_desc)]),
@@ -103,6 +106,7 @@ SYMBOLS = {
     "y4_preprocess_u8": (_I, [_VP, _I, _I, _VP, _I, _I, _VP]),
     "y4_resize_u8": (_I, [_VP, _I, _I, _I, _VP, _I, _I, _VP]),
     "y4_spp": (_I, [_I, _VP, _I, _I, _I, _VP]),
+    "y4_spp_hw": (_I, [_I, _VP, _I, _I, _I, _I, _VP]),
 }
 
 _lib = None

@@ -13,7 +13,8 @@ Reference behaviours reproduced on purpose:
   * concat orders: CSP [x, route] (:68); SPP [mp13, mp9, mp5, x] (:130-134); top-down
     [lateral, upsampled] (:149,:161); bottom-up [downsampled, route] (:174,:187)
 Generalised on purpose: grid sizes are img_size // stride instead of the hard-coded 52/26/13
-(`custom_layers.py:204,208,212`), which is what lets the 608x608 configs exist at all.
+(`custom_layers.py:204,208,212`), which is what lets the 608x608 configs exist at all; and the input may be a
+rectangle (H, W) -- the Keras Input shape, height first -- with gh = H // stride rows and gw = W // stride columns.
 
 The C++ runtime (csrc/runtime.hip: build_plan) builds the same table independently; tests compare the two through
 `y4_layer_info`.
@@ -37,12 +38,16 @@ class ConvSpec:
     cout: int
     act: int            # ACT_*
     bn: bool            # False only for the 3 head convs (bias instead), custom_layers.py:20
-    in_side: int = 0
+    in_side: int = 0    # -1 on a rectangular plan (as y4_layer_info reports it): read in_h / in_w there
     out_side: int = 0
+    in_h: int = 0
+    in_w: int = 0
+    out_h: int = 0
+    out_w: int = 0
 
     @property
     def flops_per_image(self) -> int:
-        return 2 * self.k * self.k * self.cin * self.cout * self.out_side * self.out_side
+        return 2 * self.k * self.k * self.cin * self.cout * self.out_h * self.out_w
 
     @property
     def n_weights(self) -> int:
@@ -60,11 +65,11 @@ class Op:
 
 @dataclass
 class Plan:
-    img_size: int
+    img_size: object                               # int side of a square plan, (H, W) of a rectangular one
     num_classes: int
     convs: List[ConvSpec] = field(default_factory=list)
     ops: List[Op] = field(default_factory=list)
-    sides: dict = field(default_factory=dict)      # tensor name -> spatial side
+    sides: dict = field(default_factory=dict)      # tensor name -> spatial side (square) or (h, w) (rectangle)
     chans: dict = field(default_factory=dict)      # tensor name -> channels
     heads: Tuple[str, str, str] = ("", "", "")     # conv_sbbox, conv_mbbox, conv_lbbox tensor names
 
@@ -73,12 +78,27 @@ class Plan:
         return (8, 16, 32)
 
     @property
+    def img_hw(self):
+        return tuple(self.img_size) if isinstance(self.img_size, tuple) else (self.img_size, self.img_size)
+
+    @property
+    def square(self) -> bool:
+        return not isinstance(self.img_size, tuple)
+
+    @property
+    def grids_hw(self):
+        """((gh, gw) per scale), whatever the shape."""
+        H, W = self.img_hw
+        return tuple((H // s, W // s) for s in self.strides)
+
+    @property
     def grids(self):
-        return tuple(self.img_size // s for s in self.strides)
+        """Grid side per scale of a square plan; (gh, gw) pairs for a rectangle."""
+        return tuple(g[0] for g in self.grids_hw) if self.square else self.grids_hw
 
     @property
     def num_boxes(self) -> int:
-        return sum(3 * g * g for g in self.grids)
+        return sum(3 * gh * gw for gh, gw in self.grids_hw)
 
     @property
     def flops_per_image(self) -> int:
@@ -90,11 +110,16 @@ class Plan:
 
 
 class _Builder:
-    def __init__(self, img_size: int, num_classes: int):
+    def __init__(self, img_size, num_classes: int):
         self.p = Plan(img_size=img_size, num_classes=num_classes)
-        self.p.sides["input"] = img_size
-        self.p.chans["input"] = 3
+        self.hw = {}                               # tensor name -> (h, w)
+        self._set("input", self.p.img_hw, 3)
         self._tmp = 0
+
+    def _set(self, dst, hw, ch):
+        self.hw[dst] = hw
+        self.p.sides[dst] = hw[0] if self.p.square else hw
+        self.p.chans[dst] = ch
 
     def _name(self, stem):
         self._tmp += 1
@@ -103,37 +128,39 @@ class _Builder:
     def conv(self, x, filters, k, down=False, act=ACT_LEAKY, bn=True):
         p = self.p
         idx = len(p.convs)
-        side = p.sides[x]
-        out_side = side // 2 if down else side
-        p.convs.append(ConvSpec(idx, k, 2 if down else 1, p.chans[x], filters, act, bn, side, out_side))
+        ih, iw = self.hw[x]
+        oh, ow = (ih // 2, iw // 2) if down else (ih, iw)
+        sq = p.square
+        p.convs.append(ConvSpec(idx, k, 2 if down else 1, p.chans[x], filters, act, bn, ih if sq else -1, oh if sq else -1,
+                                ih, iw, oh, ow))
         dst = f"c{idx}"
         p.ops.append(Op("conv", dst, (x,), conv=idx))
-        p.sides[dst], p.chans[dst] = out_side, filters
+        self._set(dst, (oh, ow), filters)
         return dst
 
     def add(self, a, b):
         dst = self._name("add")
         self.p.ops.append(Op("add", dst, (a, b)))
-        self.p.sides[dst], self.p.chans[dst] = self.p.sides[a], self.p.chans[a]
+        self._set(dst, self.hw[a], self.p.chans[a])
         return dst
 
     def concat(self, *xs):
         dst = self._name("cat")
         self.p.ops.append(Op("concat", dst, tuple(xs)))
-        self.p.sides[dst] = self.p.sides[xs[0]]
-        self.p.chans[dst] = sum(self.p.chans[x] for x in xs)
+        self._set(dst, self.hw[xs[0]], sum(self.p.chans[x] for x in xs))
         return dst
 
     def maxpool(self, x, k):
         dst = self._name(f"mp{k}_")
         self.p.ops.append(Op("maxpool", dst, (x,), k=k))
-        self.p.sides[dst], self.p.chans[dst] = self.p.sides[x], self.p.chans[x]
+        self._set(dst, self.hw[x], self.p.chans[x])
         return dst
 
     def upsample(self, x):
         dst = self._name("up")
         self.p.ops.append(Op("upsample", dst, (x,)))
-        self.p.sides[dst], self.p.chans[dst] = 2 * self.p.sides[x], self.p.chans[x]
+        h, w = self.hw[x]
+        self._set(dst, (2 * h, 2 * w), self.p.chans[x])
         return dst
 
     # custom_layers.py:34-44
@@ -152,9 +179,16 @@ class _Builder:
         return self.concat(x, route)
 
 
-def build_plan(img_size: int = 416, num_classes: int = 80) -> Plan:
-    """Build the plan for a square `img_size` (multiple of 32, `models.py:23-24`)."""
-    assert img_size % 32 == 0, "must be a multiple of last stride"
+def build_plan(img_size=416, num_classes: int = 80) -> Plan:
+    """Build the plan for a square `img_size` or a rectangle `(H, W)` (each side a multiple of 32, `models.py:24`).
+    A square given as (S, S) is the square plan of side S."""
+    if isinstance(img_size, (tuple, list)):
+        H, W = (int(v) for v in tuple(img_size)[:2])
+        img_size = H if H == W else (H, W)
+    else:
+        H = W = int(img_size)
+        img_size = H
+    assert H > 0 and W > 0 and H % 32 == 0 and W % 32 == 0, "must be a multiple of last stride"
     assert num_classes > 0, "no classes detected!"
     b = _Builder(img_size, num_classes)
     M = ACT_MISH

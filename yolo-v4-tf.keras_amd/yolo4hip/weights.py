@@ -194,13 +194,14 @@ def synth_weights(plan: Plan, seed: int = 0) -> WeightSet:
     return ws  # type: ignore[return-value]
 
 
-def synth_images(n: int, img_size: int, seed: int = 0, first_index: int = 0) -> np.ndarray:
-    """U[0,1) float32 [n, H, W, 3]; the stream of image i depends only on (seed, first_index + i), so a
-    rank's shard of a multi-GPU batch is bit-identical to the same rows of the single-GPU batch."""
-    out = np.empty((n, img_size, img_size, 3), np.float32)
+def synth_images(n: int, img_size, seed: int = 0, first_index: int = 0) -> np.ndarray:
+    """U[0,1) float32 [n, H, W, 3] (img_size: a square side or (H, W)); the stream of image i depends only on
+    (seed, first_index + i), so a rank's shard of a multi-GPU batch is bit-identical to the same rows of the single-GPU batch."""
+    H, W = (int(img_size[0]), int(img_size[1])) if isinstance(img_size, (tuple, list)) else (int(img_size), int(img_size))
+    out = np.empty((n, H, W, 3), np.float32)
     for i in range(n):
         rng = np.random.default_rng([seed, 0x1A6E, first_index + i])
-        out[i] = rng.random((img_size, img_size, 3), dtype=np.float32)
+        out[i] = rng.random((H, W, 3), dtype=np.float32)
     return out
 
 
