@@ -147,6 +147,16 @@ int y4_get_conv_output(y4_handle h, int conv_idx, int n, float* out_dev, size_t 
 int y4_decode_nms(y4_handle h, int n, float iou_threshold, float score_threshold, float* boxes_dev,
                   float* scores_dev, float* classes_dev, int32_t* valid_dev, int32_t* kept_idx_dev,
                   void* stream);
+/* y4_decode_nms with the boxes mapped back to each SOURCE image (letterbox input, see y4_resize_u8_ragged).  The reference
+ * normalises boxes by the network input (custom_layers.py:284) and clips them to [0,1] (:297, clip_boxes=True); here each kept
+ * box of image i is first mapped with box_map_dev[i] = {ax, bx, ay, by}: x1, x2 -> fmaf(x, ax, bx), y1, y2 -> fmaf(y, ay, by),
+ * and then clipped to [0,1] -- to the image, not to the canvas.  The kept set, scores, classes, valid and kept_idx are those of
+ * y4_decode_nms bit for bit (the map applies in the output stage, after NMS); box_map_dev == NULL is y4_decode_nms exactly.
+ * Same handle-state rules (candidate counters, head notes, stream order) as y4_decode_nms.  Stretch input (reference
+ * models.py:95-98) has the identity map {1, 0, 1, 0}. */
+int y4_decode_nms_mapped(y4_handle h, int n, float iou_threshold, float score_threshold, const float* box_map_dev,
+                         float* boxes_dev, float* scores_dev, float* classes_dev, int32_t* valid_dev, int32_t* kept_idx_dev,
+                         void* stream);
 /* Replaces inference_model.predict(imgs) (reference models.py:69-73,113,159) = forward + decode + NMS. */
 int y4_predict(y4_handle h, const float* imgs_nhwc_dev, int n, float* boxes_dev, float* scores_dev,
                float* classes_dev, int32_t* valid_dev, int32_t* kept_idx_dev, void* stream);
@@ -322,6 +332,23 @@ int y4_preprocess_u8(const uint8_t* img_dev, int h, int w, float* out_dev, int o
 /* The resize half of preprocess_img alone, batched: uint8 [n,h,w,3] -> uint8 [n,out_h,out_w,3] with cv2.resize's
  * uint8 INTER_LINEAR fixed-point arithmetic (what cv2.resize itself returns for a uint8 image). */
 int y4_resize_u8(const uint8_t* imgs_dev, int n, int h, int w, uint8_t* out_dev, int out_h, int out_w, void* stream);
+/* One image of a ragged batch for y4_resize_u8_ragged: a packed uint8 [h,w,3] source at byte `offset` of the source buffer,
+ * resized to out_h x out_w and placed at (pad_top, pad_left) of the network canvas. */
+typedef struct y4_image_desc {
+    int64_t offset;
+    int32_t h, w, out_h, out_w, pad_top, pad_left;
+} y4_image_desc;
+/* The resize half of preprocess_img over a batch of images of DIFFERENT sizes, in one launch: image i (desc_dev[i], a device
+ * array of n descriptors) -> slot i of the uint8 [n,H,W,3] batch y4_forward_u8 / y4_predict_u8 take.  Canvas pixels inside
+ * [pad_top, pad_top + out_h) x [pad_left, pad_left + out_w) are cv2.resize's uint8 INTER_LINEAR resize of the source to
+ * out_w x out_h (the arithmetic of y4_resize_u8); every other pixel is `pad_value` (0..255) in all three channels.
+ *   stretch   (reference models.py:95-98): out_h = H, out_w = W, pads 0 -- the same bytes as y4_resize_u8 on that image;
+ *   letterbox (Darknet's letterbox_image geometry): the aspect-keeping rectangle, centred -- yolo4hip/prepost.py: letterbox_rect.
+ * The arguments are checked on the host (NULL pointers, n, H, W, pad_value, an output of 2^31 bytes or more: Y4_EINVAL before
+ * any launch), but the descriptors live on the device and are NOT checked: the caller owns the table's correctness (offsets
+ * and sizes inside the source buffer, h, w, out_h, out_w >= 1, the rectangle inside the canvas). */
+int y4_resize_u8_ragged(const uint8_t* src_dev, const y4_image_desc* desc_dev, int n, uint8_t* out_dev, int H, int W,
+                        int pad_value, void* stream);
 /* SPP (custom_layers.py:130-134): x = buf[..., 3c:4c] -> buf[..., 0:c]=maxpool13, [c:2c]=maxpool9,
  * [2c:3c]=maxpool5 (stride 1, 'same'), buf is [n,side,side,4c] */
 int y4_spp(int dtype, void* buf_dev, int n, int side, int c, void* stream);

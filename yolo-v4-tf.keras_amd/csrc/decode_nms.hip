@@ -669,14 +669,22 @@ __global__ __launch_bounds__(NMS_THREADS) void nms_kernel(const NmsK p) {
         __syncthreads();
     }
     __syncthreads();
-    // ---- outputs: clipped boxes, zero padded (clip_boxes=True, pad to max_total)
+    // ---- outputs: clipped boxes, zero padded (clip_boxes=True, pad to max_total); with a box map (y4_decode_nms_mapped) each
+    // kept box is first mapped from the canvas to its source image, x -> fmaf(x, ax, bx), y -> fmaf(y, ay, by), so the clip is to
+    // the image.  Only the written boxes change: which boxes are kept was decided above on the canvas boxes.
     const int kept = (int)sh[1];
+    float ax = 1.f, bx = 0.f, ay = 1.f, by = 0.f;
+    if (p.box_map) { ax = p.box_map[4 * n]; bx = p.box_map[4 * n + 1]; ay = p.box_map[4 * n + 2]; by = p.box_map[4 * n + 3]; }
     for (int i = tid; i < p.max_total; i += NMS_THREADS) {
         float4 b = make_float4(0.f, 0.f, 0.f, 0.f);
         float s = 0.f, c = 0.f;
         int id = -1;
         if (i < kept) {
             b = kbox[i];
+            if (p.box_map) {
+                b.x = fmaf(b.x, ax, bx); b.y = fmaf(b.y, ay, by);
+                b.z = fmaf(b.z, ax, bx); b.w = fmaf(b.w, ay, by);
+            }
             b.x = fmaxf(fminf(b.x, 1.f), 0.f); b.y = fmaxf(fminf(b.y, 1.f), 0.f);
             b.z = fmaxf(fminf(b.z, 1.f), 0.f); b.w = fmaxf(fminf(b.w, 1.f), 0.f);
             s = kscore[i]; c = (float)kcls[i]; id = kidx[i];

@@ -53,6 +53,8 @@ int pack_conv_frag32(int dtype, int cout, int cin, const void* packed, void* fra
 int stem_conv_launch(int dtype, const void* imgs, int img_u8, int n, int h, int w, const float* wk, const float* scale,
                      const float* shift, int cout, int act, void* out, int out_cstride, int out_coff, hipStream_t stream);
 int resize_u8_launch(const uint8_t* img, int n, int h, int w, uint8_t* out, int H, int W, hipStream_t stream);
+int resize_u8_ragged_launch(const uint8_t* src, const y4_image_desc* desc, int n, uint8_t* out, int H, int W, int pad,
+                            hipStream_t stream);
 int pack_stem_weights(const float* w_oihw, float* wk, int cout, hipStream_t stream);
 int preprocess_u8_launch(const uint8_t* img, int h, int w, float* out, int H, int W, hipStream_t stream);
 int spp_launch(int dtype, void* buf, int n, int h, int w, int c, hipStream_t stream);
@@ -116,6 +118,7 @@ struct NmsK {
     int32_t* out_idx;                // [N, max_total] or null
     uint32_t* status;                // [1] bit0: candidate list overflowed its capacity
     FastDiv div_c;                   // id -> (box, class) without integer division (ids < 2^31 checked at y4_create)
+    const float* box_map;            // [N][4] {ax, bx, ay, by} applied to the kept boxes before the clip, or null (identity)
 };
 int decode_launch(const DecodeK& k, hipStream_t stream, int clear_images);
 // tuner aid (latency schedules): streams `bytes` of `p` through the L2s so that the next launch starts on cold weights

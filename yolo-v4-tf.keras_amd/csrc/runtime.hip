@@ -779,7 +779,8 @@ int run_op(y4_handle h, const Op& op, const void* imgs, int n, hipStream_t s, in
 }
 
 int run_decode_nms(y4_handle h, int n, float iou_thr, float score_thr, float* boxes, float* scores, float* classes,
-                   int32_t* valid, int32_t* kept_idx, hipStream_t s, int stage /*0 both, 1 decode, 2 nms*/) {
+                   int32_t* valid, int32_t* kept_idx, hipStream_t s, int stage /*0 both, 1 decode, 2 nms*/,
+                   const float* box_map = nullptr /*[n][4] per image, NMS output stage (y4_decode_nms_mapped)*/) {
     const y4_config& cfg = h->cfg;
     if (stage != 2) {
         DecodeK k{};
@@ -815,6 +816,7 @@ int run_decode_nms(y4_handle h, int n, float iou_thr, float score_thr, float* bo
         k.out_boxes = boxes; k.out_scores = scores; k.out_classes = classes; k.out_valid = valid; k.out_idx = kept_idx;
         k.status = (uint32_t*)(h->act + h->status_off);
         k.div_c = fastdiv_make((uint32_t)cfg.num_classes);
+        k.box_map = box_map;
         if (int r = nms_launch(k, s)) return r;
         h->counts_clean = h->counts_n <= n;               // (an NMS over fewer images than were decoded leaves counters behind)
     }
@@ -826,7 +828,7 @@ int run_decode_nms(y4_handle h, int n, float iou_thr, float score_thr, float* bo
 extern "C" {
 
 const char* y4_last_error(void) { return g_err; }
-const char* y4_version(void) { return "yolo4hip 0.4 (gfx950)"; }
+const char* y4_version(void) { return "yolo4hip 0.5 (gfx950)"; }
 
 int y4_create(const y4_config* cfg, y4_handle* out) {
     Y4_REQUIRE(cfg && out, Y4_EINVAL, "y4_create: null argument");
@@ -1106,11 +1108,16 @@ int y4_get_conv_output(y4_handle h, int conv_idx, int n, float* out, size_t out_
 
 int y4_decode_nms(y4_handle h, int n, float iou_threshold, float score_threshold, float* boxes, float* scores,
                   float* classes, int32_t* valid, int32_t* kept_idx, void* stream) {
+    return y4_decode_nms_mapped(h, n, iou_threshold, score_threshold, nullptr, boxes, scores, classes, valid, kept_idx, stream);
+}
+
+int y4_decode_nms_mapped(y4_handle h, int n, float iou_threshold, float score_threshold, const float* box_map, float* boxes,
+                         float* scores, float* classes, int32_t* valid, int32_t* kept_idx, void* stream) {
     if (int r = check_ready(h, n)) return r;
     Y4_REQUIRE(boxes && scores && classes && valid, Y4_EINVAL, "y4_decode_nms: null output");
     const float iou = iou_threshold < 0.f ? h->cfg.iou_threshold : iou_threshold;
     const float sc = score_threshold < 0.f ? h->cfg.score_threshold : score_threshold;
-    return run_decode_nms(h, n, iou, sc, boxes, scores, classes, valid, kept_idx, (hipStream_t)stream, 0);
+    return run_decode_nms(h, n, iou, sc, boxes, scores, classes, valid, kept_idx, (hipStream_t)stream, 0, box_map);
 }
 
 // forward + decode + NMS; when `ev` is given, ev[0] is recorded before the first op and ev[i+1] after op i
@@ -1757,6 +1764,11 @@ int y4_stem_conv(int dtype, const float* imgs_dev, int n, int h, int w, const fl
 
 int y4_resize_u8(const uint8_t* imgs_dev, int n, int h, int w, uint8_t* out_dev, int out_h, int out_w, void* stream) {
     return resize_u8_launch(imgs_dev, n, h, w, out_dev, out_h, out_w, (hipStream_t)stream);
+}
+
+int y4_resize_u8_ragged(const uint8_t* src_dev, const y4_image_desc* desc_dev, int n, uint8_t* out_dev, int H, int W,
+                        int pad_value, void* stream) {
+    return resize_u8_ragged_launch(src_dev, desc_dev, n, out_dev, H, W, pad_value, (hipStream_t)stream);
 }
 
 int y4_preprocess_u8(const uint8_t* img_dev, int h, int w, float* out_dev, int out_h, int out_w, void* stream) {

@@ -8,7 +8,8 @@ with their prints (`img shape:`, `# of bboxes:`) and DataFrame layout.
 Differences, all supersets: the passed `config` is honoured (the reference reads the module global,
 models.py:26-37); grid sizes follow img_size (the reference hard-codes 52/26/13) and img_size may be a rectangle (H, W, 3) --
 the reference's 'not support yet' assert is lifted, boxes are normalised x / W, y / H; extra keyword-only
-arguments pick the compute dtype / batch capacity.  `save_model` / `load_model` (models.py:86-93) are stand-ins on a
+arguments pick the compute dtype / batch capacity, and `letterbox=True` (keyword-only, off by default) letterboxes the input
+instead of the reference's stretch (Darknet's letter_box=1 geometry) with boxes returned in each raw image's pixels.  `save_model` / `load_model` (models.py:86-93) are stand-ins on a
 self-describing checkpoint of this framework (Keras' SavedModel / H5 needs TensorFlow); `eval_map` (models.py:182-507)
 is the VOC mAP tool over the exported text files (yolo4hip/evalmap.py).  Training (`fit`, `training_model`) is out of
 scope for this inference framework and raises.
@@ -38,7 +39,8 @@ class _KerasLikeModel:
 
 class Yolov4(object):
     def __init__(self, weight_path=None, class_name_path='coco_classes.txt', config=yolo_config, *,
-                 dtype='f32', max_batch=32, synth_seed=0, device=None, device_preprocess=True, tune=None, share_schedule=None):
+                 dtype='f32', max_batch=32, synth_seed=0, device=None, device_preprocess=True, tune=None, share_schedule=None,
+                 letterbox=False, pad_value=128):
         # (reference models.py:23 also asserts img_size[0] == img_size[1], 'not support yet': rectangles are supported here)
         assert config['img_size'][0] % config['strides'][-1] == 0, 'must be a multiple of last stride'
         assert config['img_size'][1] % config['strides'][-1] == 0, 'must be a multiple of last stride'
@@ -59,6 +61,15 @@ class Yolov4(object):
         assert self.num_classes > 0, 'no classes detected!'
         self._dtype, self._max_batch, self._synth_seed, self._device = dtype, max_batch, synth_seed, device
         self._device_preprocess = device_preprocess
+        # letterbox=True: predict_img / predict / export_prediction resize each image with its aspect ratio kept, centred on a
+        # canvas of uint8 level `pad_value` (Darknet's letterbox_image geometry; the resize is still cv2's uint8 arithmetic and the
+        # pad a uint8 level, 128 = 0.502, where Darknet pads 0.5), and the boxes are mapped back to each raw image on the device.
+        # inference_model.predict(imgs) keeps the reference's meaning (preprocessed images in, canvas-normalised boxes out), and
+        # predict_raw / predict_nonms stay stretch-only.
+        self._letterbox = bool(letterbox)
+        self._pad_value = int(pad_value)
+        if not 0 <= self._pad_value <= 255:
+            raise ValueError(f'pad_value must be a uint8 level 0..255, got {pad_value}')
         # A shape without a shipped / cached schedule is tuned ONCE (a full-size predict + y4_autotune on `max_batch` synthetic
         # images: seconds at 160^2, ~20 s at 608^2 x 32; written to $YOLO4HIP_CACHE, default ~/.cache/yolo4hip):
         #   tune=None (default)  on the first predict of this object, not in the constructor; YOLO4HIP_TUNE=0: never
@@ -80,6 +91,7 @@ class Yolov4(object):
                              device=self._device, alias_workspace=True)
         self.yolo_model = _KerasLikeModel(self._tuned_first(self.engine.forward_heads), 'yolo_model')
         print(f"nms iou: {self.config['iou_threshold']} score: {self.config['score_threshold']}")
+        self._thresholds = (-1.0, -1.0)  # what inference_model runs with (-1: the config's); load_model changes them
         self.inference_model = _KerasLikeModel(self._tuned_first(self.engine.predict), 'inference_model')
         self.training_model = None      # training is out of scope (inference-only framework)
         if load_pretrained and self.weight_path and self.weight_path.endswith('.weights'):
@@ -165,6 +177,7 @@ class Yolov4(object):
         self.yolo_model = _KerasLikeModel(self._tuned_first(self.engine.forward_heads), 'yolo_model')
         self.inference_model = _KerasLikeModel(
             self._tuned_first(lambda x: self.engine.predict(x, iou_threshold=0.413, score_threshold=0.3)), 'inference_model')
+        self._thresholds = (0.413, 0.3)
 
     # ---- out of scope (training)
     def fit(self, *a, **k):
@@ -174,17 +187,37 @@ class Yolov4(object):
     def preprocess_img(self, img):
         return prepost.preprocess_img(img, self.img_size)
 
+    def _letterboxed(self, raws):
+        """Letterboxed network input for a list of raw images -> (images for engine.predict, box map [n,4]): on the device
+        (one upload, one ragged resize) for uint8 images when device_preprocess is on, else prepost.letterbox on the host."""
+        if self._device_preprocess and all(getattr(r, 'dtype', None) == np.uint8 for r in raws):
+            return self.engine.preprocess_u8_batch(raws, letterbox=True, pad_value=self._pad_value)
+        H, W = self.img_size[0], self.img_size[1]
+        imgs = np.stack([prepost.letterbox(r, (H, W), self._pad_value) / 255. for r in raws])
+        maps = np.stack([prepost.box_map(r.shape[0], r.shape[1], H, W) for r in raws])
+        return imgs, maps
+
+    def _predict_mapped(self, imgs, box_map):
+        """inference_model.predict with boxes normalised to each raw image (box_map from `_letterboxed`)."""
+        self._ensure_tuned()
+        iou, score = self._thresholds
+        return self.engine.predict(imgs, iou_threshold=iou, score_threshold=score, box_map=box_map)
+
     # ---- reference models.py:109-123 (raw_img: RGB)
     def predict_img(self, raw_img, random_color=True, plot_img=True, figsize=(10, 10), show_text=True,
                     return_output=False):
         print('img shape: ', raw_img.shape)
-        if self._device_preprocess and getattr(raw_img, 'dtype', None) == np.uint8:
+        if self._letterbox:
+            imgs, box_map = self._letterboxed([raw_img])
+            pred_output = self._predict_mapped(imgs, box_map)
+        elif self._device_preprocess and getattr(raw_img, 'dtype', None) == np.uint8:
             # same arithmetic as preprocess_img (tests: bit-identical), on the GPU: the uint8 image crosses PCIe
             imgs = self.engine.preprocess_u8(np.ascontiguousarray(raw_img))
+            pred_output = self.inference_model.predict(imgs)
         else:
             img = self.preprocess_img(raw_img)
             imgs = np.expand_dims(img, axis=0)
-        pred_output = self.inference_model.predict(imgs)
+            pred_output = self.inference_model.predict(imgs)
         detections = prepost.get_detection_data(img=raw_img, model_outputs=pred_output, class_names=self.class_names)
         output_img = prepost.draw_bbox(raw_img, detections, cmap=self.class_color, random_color=random_color,
                                        figsize=figsize, show_text=show_text, show_img=plot_img)
@@ -222,11 +255,15 @@ class Yolov4(object):
         for start in tqdm(range(0, len(img_paths), bs)):
             paths = img_paths[start:start + bs]
             raws = [prepost.imread_rgb(pth)[:, :, ::-1] for pth in paths]
-            if self._device_preprocess:
-                imgs = self.engine.preprocess_u8([np.ascontiguousarray(r) for r in raws])
+            if self._letterbox:                   # boxes come back normalised to each raw image: the * w, * h below hold
+                imgs, box_map = self._letterboxed(raws)
+                b_boxes, b_scores, b_classes, b_valid = self._predict_mapped(imgs, box_map)
             else:
-                imgs = np.stack([self.preprocess_img(r) for r in raws])
-            b_boxes, b_scores, b_classes, b_valid = self.inference_model.predict(imgs)
+                if self._device_preprocess:       # one upload + one ragged stretch launch: the bytes of preprocess_u8
+                    imgs, _ = self.engine.preprocess_u8_batch(raws)
+                else:
+                    imgs = np.stack([self.preprocess_img(r) for r in raws])
+                b_boxes, b_scores, b_classes, b_valid = self.inference_model.predict(imgs)
             for k, pth in enumerate(paths):
                 nb = int(b_valid[k])
                 h, w = raws[k].shape[:2]

@@ -5,6 +5,7 @@ and `Yolov4.inference_model.predict` (reference models.py:113,159,514) end up in
 / `Engine.predict`.  No compute happens in Python and nothing here falls back to a CPU path.
 """
 import ctypes as C
+import os
 
 import numpy as np
 
@@ -125,6 +126,10 @@ class Engine:
             e.close()
         self._stream_siblings = []
         self._stream_slots = None                          # predict_stream's pinned staging buffers
+        self._batch_pin = None                             # preprocess_u8_batch's staging buffer and packing threads
+        if getattr(self, "_pack_pool", None) is not None:
+            self._pack_pool.shutdown(wait=True)
+            self._pack_pool = None
         if getattr(self, "handle", None) is not None and self.handle:
             self.lib.y4_destroy(self.handle)
             self.handle = C.c_void_p()
@@ -237,6 +242,91 @@ class Engine:
             torch.cuda.current_stream().synchronize()       # the uint8 staging tensors may be freed now
         return out
 
+    def preprocess_u8_batch(self, raw_imgs, letterbox=False, pad_value=128):
+        """Device-side preprocessing of uint8 RGB images [h,w,3] of ANY mix of sizes in one upload and one launch: the images
+        and their descriptor table are packed into one pinned staging buffer (kept across calls), cross PCIe in one copy, and
+        `y4_resize_u8_ragged` writes the uint8 network batch.  letterbox=False: the stretch of `Yolov4.preprocess_img`
+        (reference models.py:95-98), the same bytes as `preprocess_u8`; letterbox=True: each image resized with its aspect
+        kept and centred on a `pad_value` canvas (prepost.letterbox_rect / prepost.letterbox, bit for bit).
+        -> (uint8 cuda tensor [n,H,W,3], float32 cuda tensor [n,4] box map for `predict(..., box_map=)`: the identity rows
+        for stretch, prepost.box_map for letterbox).  Asynchronous on the current stream."""
+        torch = self.torch
+        from . import prepost
+        if isinstance(raw_imgs, np.ndarray) and raw_imgs.ndim == 3:
+            raw_imgs = [raw_imgs]
+        raw_imgs = list(raw_imgs)
+        n = len(raw_imgs)
+        if n == 0:
+            raise ValueError("preprocess_u8_batch: no images")
+        pad_value = int(pad_value)
+        if not 0 <= pad_value <= 255:
+            raise ValueError(f"pad_value must be a uint8 level 0..255, got {pad_value}")
+        H, W = self.img_hw
+        for a in raw_imgs:
+            if getattr(a, "dtype", None) != np.uint8 or a.ndim != 3 or a.shape[2] != 3 or a.shape[0] < 1 or a.shape[1] < 1:
+                raise ValueError(f"expected uint8 [h,w,3] images, got {getattr(a, 'dtype', type(a))} {getattr(a, 'shape', '')}")
+        # staging layout: descriptors [n] (32 B each) | box map float32 [n,4] | the images, packed; descriptor offsets count from
+        # the first image byte
+        desc_bytes, map_bytes = n * C.sizeof(ext.y4_image_desc), n * 16
+        head = desc_bytes + map_bytes
+        desc = (ext.y4_image_desc * n)()
+        maps = np.empty((n, 4), np.float32)
+        off = 0
+        for i, a in enumerate(raw_imgs):
+            h, w = a.shape[:2]
+            rect = prepost.letterbox_rect(h, w, H, W) if letterbox else (H, W, 0, 0)
+            d = desc[i]
+            d.offset, d.h, d.w = off, h, w
+            d.out_h, d.out_w, d.pad_top, d.pad_left = rect
+            maps[i] = prepost.box_map(h, w, H, W, rect)
+            off += h * w * 3
+        total = head + off
+        pin = getattr(self, "_batch_pin", None)
+        if pin is None or pin.numel() < total:
+            if pin is not None:
+                self._batch_pin_free.synchronize()
+            pin = self._batch_pin = torch.empty(max(total, 1 << 20), dtype=torch.uint8).pin_memory()
+            self._batch_pin_np = pin.numpy()
+            self._batch_pin_free = torch.cuda.Event()
+        else:
+            self._batch_pin_free.synchronize()              # the previous call's upload has left the buffer
+        buf = self._batch_pin_np
+        buf[:desc_bytes] = np.frombuffer(desc, dtype=np.uint8)
+        buf[desc_bytes:head] = maps.view(np.uint8).reshape(-1)
+
+        def pack(i):
+            a, o = raw_imgs[i], head + desc[i].offset
+            np.copyto(buf[o:o + a.size].reshape(a.shape), a)   # (any strides: BGR views included; releases the GIL)
+
+        if off >= (8 << 20) and n > 1:
+            # tens of MB of photos: one thread's memcpy into the staging buffer would cost more than the upload itself
+            # (measured), so the images are packed by a few worker threads (they block when idle, they do not spin)
+            if getattr(self, "_pack_pool", None) is None:
+                from concurrent.futures import ThreadPoolExecutor
+                self._pack_pool = ThreadPoolExecutor(max_workers=min(8, os.cpu_count() or 1))
+            list(self._pack_pool.map(pack, range(n)))
+        else:
+            for i in range(n):
+                pack(i)
+        with torch.cuda.device(self.device):
+            # a fresh device block per call (torch's caching allocator): the returned box map is a view of it and stays valid
+            dev = torch.empty(total, dtype=torch.uint8, device=self.device)
+            dev.copy_(pin[:total], non_blocking=True)
+            self._batch_pin_free.record()
+            out = torch.empty((n, H, W, 3), dtype=torch.uint8, device=self.device)
+            ext.check(self.lib.y4_resize_u8_ragged(C.c_void_p(dev.data_ptr() + head), ext.ptr(dev), n, ext.ptr(out), H, W,
+                                                   pad_value, ext.stream_ptr()))
+        return out, dev[desc_bytes:head].view(torch.float32).view(n, 4)
+
+    def resize_u8_ragged(self, src_dev, desc_dev, n, out, pad_value=128):
+        """y4_resize_u8_ragged on device buffers: `desc_dev` holds n y4_image_desc rows (offsets into `src_dev`), `out` is a
+        uint8 cuda tensor of at least [n,H,W,3].  Asynchronous on the current stream; returns out[:n]."""
+        H, W = self.img_hw
+        with self.torch.cuda.device(self.device):
+            ext.check(self.lib.y4_resize_u8_ragged(ext.ptr(src_dev), ext.ptr(desc_dev), int(n), ext.ptr(out), H, W,
+                                                   int(pad_value), ext.stream_ptr()))
+        return out[:n]
+
     def resize_u8(self, frames_dev, out=None):
         """Device-side stretch resize (cv2.resize to width W, height H) on a uint8 cuda batch [n,h,w,3] -> uint8 [n,H,W,3]
         (cv2's uint8 INTER_LINEAR arithmetic); frames already at network size are returned as they are."""
@@ -320,12 +410,22 @@ class Engine:
         return flat, (v[0].view(torch.float32).view(n, T, 4), v[1].view(torch.float32).view(n, T),
                       v[2].view(torch.float32).view(n, T), v[3], v[4].view(n, T))
 
-    def decode_nms_device(self, n, outs=None, iou_threshold=-1.0, score_threshold=-1.0):
+    def decode_nms_device(self, n, outs=None, iou_threshold=-1.0, score_threshold=-1.0, box_map=None):
+        """Decode + NMS of the heads in the workspace.  box_map: a contiguous float32 cuda tensor [n,4] of (ax, bx, ay, by) rows
+        (`preprocess_u8_batch`, prepost.box_map) -- the kept boxes are then mapped to each source image before the clip
+        (y4_decode_nms_mapped); everything but the boxes is unchanged."""
         outs = outs or self.alloc_outputs(n)
         b, s, c, v, k = outs
         with self.torch.cuda.device(self.device):
-            ext.check(self.lib.y4_decode_nms(self.handle, n, float(iou_threshold), float(score_threshold), ext.ptr(b),
-                                             ext.ptr(s), ext.ptr(c), ext.ptr(v), ext.ptr(k), ext.stream_ptr()))
+            if box_map is None:
+                ext.check(self.lib.y4_decode_nms(self.handle, n, float(iou_threshold), float(score_threshold), ext.ptr(b),
+                                                 ext.ptr(s), ext.ptr(c), ext.ptr(v), ext.ptr(k), ext.stream_ptr()))
+            else:
+                if tuple(box_map.shape) != (n, 4) or box_map.dtype != self.torch.float32 or not box_map.is_contiguous():
+                    raise ValueError(f"box_map must be a contiguous float32 tensor [{n},4], got {box_map.dtype} {tuple(box_map.shape)}")
+                ext.check(self.lib.y4_decode_nms_mapped(self.handle, n, float(iou_threshold), float(score_threshold),
+                                                        ext.ptr(box_map), ext.ptr(b), ext.ptr(s), ext.ptr(c), ext.ptr(v),
+                                                        ext.ptr(k), ext.stream_ptr()))
         return outs
 
     def predict_device(self, imgs_dev, outs=None):
@@ -356,20 +456,33 @@ class Engine:
                 parts[i].append(o.cpu().numpy())
         return [np.concatenate(p, axis=0) for p in parts]
 
-    def predict(self, imgs, with_indices=False, iou_threshold=-1.0, score_threshold=-1.0):
+    def predict(self, imgs, with_indices=False, iou_threshold=-1.0, score_threshold=-1.0, box_map=None):
         """inference_model.predict(imgs): [boxes [N,100,4], scores [N,100], classes [N,100], valid [N] int32]
         as fresh, writable host numpy arrays (the reference's export_prediction mutates them in place,
-        models.py:167-168)."""
+        models.py:167-168).  box_map [N,4] (a cuda tensor or an array; `preprocess_u8_batch`, prepost.box_map): the boxes
+        come back normalised to each SOURCE image instead of the canvas (letterbox input); None: canvas-normalised."""
         acc = [[], [], [], [], []]
+        if box_map is not None:
+            torch = self.torch
+            bm = box_map if isinstance(box_map, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(box_map, np.float32))
+            box_map = bm.to(self.device, dtype=torch.float32).contiguous()
+        i0 = 0
         for chunk in self._chunks(imgs):
+            n = chunk.shape[0]
             self.forward_device(chunk)
-            outs = self.decode_nms_device(chunk.shape[0], None, iou_threshold, score_threshold)
+            bm = None if box_map is None else box_map[i0:i0 + n]
+            if bm is not None and bm.shape[0] != n:
+                raise ValueError(f"box_map has {box_map.shape[0]} rows, the images are more")
+            outs = self.decode_nms_device(n, None, iou_threshold, score_threshold, box_map=bm)
+            i0 += n
             for i, o in enumerate(outs):
                 acc[i].append(o.cpu().numpy())
+        if box_map is not None and i0 != box_map.shape[0]:
+            raise ValueError(f"box_map has {box_map.shape[0]} rows for {i0} images")
         res = [np.concatenate(p, axis=0) for p in acc]
         return res if with_indices else res[:4]
 
-    def predict_stream(self, batches, with_indices=False, in_flight=None):
+    def predict_stream(self, batches, with_indices=False, in_flight=None, letterbox=False, pad_value=128):
         """Pipelined `inference_model.predict` over an iterable of uint8 batches ([n,h,w,3] numpy arrays or pinned torch
         tensors, n <= max_batch, any h,w): yields one result list per batch, in order.  A pinned tensor is uploaded from where
         it lies and may be refilled as soon as the generator yields (its upload is waited for before every yield).  While batch i computes, batch i+1 crosses PCIe as uint8
@@ -381,7 +494,10 @@ class Engine:
         packed weights), so that one batch's idle compute units are the other's (see `InFlight`); results are unchanged and still
         come in order.  Every batch in flight beyond the first costs one more activation workspace for the engine's lifetime
         (`act_bytes`: 2.9 GB at 608x608 / batch 32 / bf16 with `alias_workspace`, 8.0 GB without), so the default is 2 with an
-        aliased workspace and 1 with the plain one; pass `in_flight` to choose."""
+        aliased workspace and 1 with the plain one; pass `in_flight` to choose.
+        letterbox=True: frames are letterboxed instead of stretched (`y4_resize_u8_ragged` with one descriptor per frame, all the
+        same rectangle) and the boxes come back normalised to the frame (`y4_decode_nms_mapped`): what
+        `preprocess_u8_batch(letterbox=True)` + `predict(..., box_map=)` give, batch by batch."""
         torch = self.torch
         dev = self.device
         copy_stream = torch.cuda.Stream(device=dev)        # uploads
@@ -437,16 +553,31 @@ class Engine:
                 sl = slots[bi % nslots]
                 eng, compute = engines[bi % in_flight], cstreams[bi % in_flight]     # batches alternate engines; slots rotate on their own
                 shape = tuple(a.shape)
-                if sl.get("shape") != shape:               # (re)allocate this slot's staging for the frame geometry
+                key = (shape, bool(letterbox), int(pad_value))
+                if sl.get("key") != key:                   # (re)allocate this slot's staging for the frame geometry
                     if "done" in sl:
                         sl["done"].synchronize()
-                    sl["shape"] = shape
+                    sl["key"] = key
                     sl["pin"] = torch.empty(shape, dtype=torch.uint8).pin_memory()
                     sl["pin_np"] = sl["pin"].numpy()
                     sl["u8"] = torch.empty(shape, dtype=torch.uint8, device=dev)
                     # frames of another size are resized uint8 -> uint8 on the device; the /255 happens in the stem's load
                     sl["net"] = None if shape[1:3] == tuple(self.img_hw) else \
                         torch.empty((self.max_batch, self.img_hw[0], self.img_hw[1], 3), dtype=torch.uint8, device=dev)
+                    sl["desc"] = sl["map"] = None
+                    if letterbox and sl["net"] is not None:
+                        # every frame of the slot has the same rectangle: one descriptor per frame, frame j at j * h * w * 3
+                        from . import prepost
+                        fh, fw = shape[1], shape[2]
+                        H, W = self.img_hw
+                        rect = prepost.letterbox_rect(fh, fw, H, W)
+                        desc = (ext.y4_image_desc * self.max_batch)()
+                        for j in range(self.max_batch):
+                            desc[j].offset, desc[j].h, desc[j].w = j * fh * fw * 3, fh, fw
+                            desc[j].out_h, desc[j].out_w, desc[j].pad_top, desc[j].pad_left = rect
+                        sl["desc"] = torch.from_numpy(np.frombuffer(desc, dtype=np.uint8).copy()).to(dev)
+                        sl["map"] = torch.from_numpy(np.tile(prepost.box_map(fh, fw, H, W, rect), (self.max_batch, 1))).to(dev)
+                        torch.cuda.current_stream().synchronize()   # (read by the compute streams)
                     sl["flat"] = torch.empty(int(offs[-1]), dtype=torch.int32, device=dev)
                     sl["flat_host"] = torch.empty(int(offs[-1]), dtype=torch.int32).pin_memory()
                     sl["outs"], sl["host"] = views(sl["flat"]), views(sl["flat_host"])
@@ -465,8 +596,13 @@ class Engine:
                     sl["up"].record(copy_stream)
                 compute.wait_event(sl["up"])
                 with torch.cuda.stream(compute):
-                    frames = sl["u8"] if sl["net"] is None else eng.resize_u8(sl["u8"], sl["net"])
-                    eng.predict_device(frames[:n], tuple(t[:n] for t in sl["outs"]))
+                    if sl["desc"] is not None:             # letterbox: ragged resize, boxes mapped back to the frame in the NMS output
+                        frames = eng.resize_u8_ragged(sl["u8"], sl["desc"], n, sl["net"], pad_value)
+                        eng.forward_device(frames)
+                        eng.decode_nms_device(n, tuple(t[:n] for t in sl["outs"]), box_map=sl["map"][:n])
+                    else:
+                        frames = sl["u8"] if sl["net"] is None else eng.resize_u8(sl["u8"], sl["net"])
+                        eng.predict_device(frames[:n], tuple(t[:n] for t in sl["outs"]))
                 sl["free"].record(compute)                 # the stem has consumed the uint8 frames
                 sl["ran"].record(compute)
                 with torch.cuda.stream(down_stream):       # results leave on a third stream: compute and uploads never wait

@@ -48,6 +48,11 @@ class y4_conv_desc(C.Structure):
                 ("split", C.c_int32), ("splitk_ws", C.c_void_p), ("splitk_ws_bytes", C.c_size_t), ("wt_frag", C.c_void_p)]
 
 
+class y4_image_desc(C.Structure):
+    _fields_ = [("offset", C.c_int64), ("h", C.c_int32), ("w", C.c_int32), ("out_h", C.c_int32), ("out_w", C.c_int32),
+                ("pad_top", C.c_int32), ("pad_left", C.c_int32)]
+
+
 # every symbol include/yolo4hip.h declares: name -> (restype, argtypes)
 _VP, _I, _F = C.c_void_p, C.c_int, C.c_float
 SYMBOLS = {
@@ -73,6 +78,7 @@ SYMBOLS = {
     "y4_set_heads": (_I, [_VP, _I, _VP, _VP, _VP, _VP]),
     "y4_get_conv_output": (_I, [_VP, _I, _I, _VP, C.c_size_t, _VP]),
     "y4_decode_nms": (_I, [_VP, _I, _F, _F, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "y4_decode_nms_mapped": (_I, [_VP, _I, _F, _F, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "y4_predict": (_I, [_VP, _VP, _I, _VP, _VP, _VP, _VP, _VP, _VP]),
     "y4_predict_u8": (_I, [_VP, _VP, _I, _VP, _VP, _VP, _VP, _VP, _VP]),
     "y4_profile": (_I, [_VP, _VP, _I, _VP, _VP, _I, C.POINTER(_I), _VP]),
@@ -105,6 +111,7 @@ SYMBOLS = {
     "y4_stem_conv": (_I, [_I, _VP, _I, _I, _I, _VP, _VP, _VP, _I, _I, _VP, _I, _I, _VP]),
     "y4_preprocess_u8": (_I, [_VP, _I, _I, _VP, _I, _I, _VP]),
     "y4_resize_u8": (_I, [_VP, _I, _I, _I, _VP, _I, _I, _VP]),
+    "y4_resize_u8_ragged": (_I, [_VP, _VP, _I, _VP, _I, _I, _I, _VP]),
     "y4_spp": (_I, [_I, _VP, _I, _I, _I, _VP]),
     "y4_spp_hw": (_I, [_I, _VP, _I, _I, _I, _I, _VP]),
 }

@@ -6,6 +6,9 @@ installed on the build or GPU machines; these are PIL/NumPy counterparts with th
   imread_rgb          reference models.py:126   cv2.imread(path)[:, :, ::-1]  -> RGB uint8 [h,w,3]
   resize_bilinear     reference models.py:96    cv2.resize(img, (W,H)) (INTER_LINEAR, plain stretch)
   preprocess_img      reference models.py:95-98 resize, then img / 255. (float64 in [0,1])
+  letterbox_rect      -- (no reference counterpart) Darknet's letterbox_image geometry: aspect kept, centred, padded
+  letterbox           -- the letterbox restated in NumPy (the device path, y4_resize_u8_ragged, is bit-identical to it)
+  box_map             -- per-image affine map canvas-normalised -> image-normalised boxes (y4_decode_nms_mapped)
   get_detection_data  reference utils.py:56-78  element 0 of the 4 NMS outputs -> pandas DataFrame
   draw_bbox           reference utils.py:88-118 rectangles + labels (+ plt.imshow when show_img)
 
@@ -74,6 +77,54 @@ def preprocess_img(img, img_size):
     """reference models.py:95-98: stretch-resize to img_size[:2] (no letterbox), scale to [0,1] float64."""
     img = resize_bilinear(img, (img_size[1], img_size[0]))
     return img / 255.
+
+
+def letterbox_rect(h, w, H, W):
+    """Where an h x w image goes on an H x W canvas with its aspect ratio kept: (out_h, out_w, pad_top, pad_left).  Darknet's
+    integer rule (letterbox_image): the side that limits is filled, the other is scaled down and truncated, and the rectangle
+    is centred (an odd margin leaves the extra row / column at the bottom / right).  Stretch is (H, W, 0, 0)."""
+    h, w, H, W = int(h), int(w), int(H), int(W)
+    if h <= 0 or w <= 0 or H <= 0 or W <= 0:
+        raise ValueError(f"letterbox_rect: sizes must be positive, got image {h}x{w}, canvas {H}x{W}")
+    if W * h <= H * w:
+        out_w, out_h = W, max(1, (h * W) // w)
+    else:
+        out_h, out_w = H, max(1, (w * H) // h)
+    return out_h, out_w, (H - out_h) // 2, (W - out_w) // 2
+
+
+def letterbox(img, size_hw, pad_value=128):
+    """Letterbox preprocessing on the host: an H x W canvas filled with `pad_value`, the image resized with its aspect kept
+    (`resize_bilinear`: cv2's uint8 fixed point, or its float variant for float images) and placed at the centre.  Only the
+    geometry follows Darknet (which pads with 0.5 and has its own bilinear); the pad is a uint8 level (128 = 0.502 after the
+    /255) and the resize is cv2's.  Returns an array of the image's dtype [H, W, c]."""
+    img = np.asarray(img)
+    H, W = int(size_hw[0]), int(size_hw[1])
+    out_h, out_w, top, left = letterbox_rect(img.shape[0], img.shape[1], H, W)
+    canvas = np.full((H, W) + img.shape[2:], pad_value, dtype=img.dtype)
+    canvas[top:top + out_h, left:left + out_w] = resize_bilinear(img, (out_w, out_h))
+    return canvas
+
+
+def box_map(h, w, H, W, rect=None):
+    """float32 (ax, bx, ay, by) with x_img = x_canvas * ax + bx, y_img = y_canvas * ay + by on normalised coordinates, for an
+    h x w image placed at rect = (out_h, out_w, pad_top, pad_left) of an H x W canvas (the corners of the rectangle go to 0 and
+    1).  Computed in float64, stored as float32; stretch, rect = (H, W, 0, 0), gives the identity (1, 0, 1, 0); rect=None is
+    the letterbox rectangle letterbox_rect(h, w, H, W)."""
+    if rect is None:
+        rect = letterbox_rect(h, w, H, W)
+    out_h, out_w, top, left = (int(v) for v in rect)
+    return np.array([W / out_w, -left / out_w, H / out_h, -top / out_h], dtype=np.float64).astype(np.float32)
+
+
+def map_boxes(boxes, m):
+    """NumPy counterpart of y4_decode_nms_mapped's output stage for one image: canvas-normalised [k,4] (x1,y1,x2,y2) boxes ->
+    image-normalised, clipped to [0,1] (float32 multiply-add; the device fuses it, so the two agree to an ulp)."""
+    b = np.asarray(boxes, np.float32).copy()
+    m = np.asarray(m, np.float32)
+    b[:, [0, 2]] = b[:, [0, 2]] * m[0] + m[1]
+    b[:, [1, 3]] = b[:, [1, 3]] * m[2] + m[3]
+    return np.clip(b, 0.0, 1.0).astype(np.float32)
 
 
 def get_detection_data(img, model_outputs, class_names):
