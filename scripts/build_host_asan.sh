@@ -9,13 +9,14 @@ here=$(cd "$(dirname "$0")/.." && pwd)
 src=$here/yolo-v4-tf.keras_amd/csrc
 out=$here/scratch/hostasan; mkdir -p $out
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-omit-frame-pointer -Xarch_host -fno-sanitize-recover=undefined -Xarch_host -g -w"
+# the translation units are those of the library build (csrc/build.py UNITS), so this list cannot fall behind it
+units=$(cd $src && python3 -B -c 'import build; print(" ".join(build.UNITS))')
 pids=""
-# (four compiles at a time: the device passes are the expensive part)
-for u in conv_igemm_bf16 conv_igemm_f16 conv_p8_bf16 conv_p8_f16 conv_halo_bf16 conv_halo_f16 conv_igemm_bf16_fused conv_igemm_f16_fused conv_igemm_f32 resblock csp_stage stem_down misc_kernels decode_nms runtime conv_igemm; do
+for u in $units; do
   ( cd $src && hipcc $FLAGS -c $u.hip -o $out/$u.o ) &
   pids="$pids $!"
 done
 for p in $pids; do wait $p; done
-hipcc -shared -fPIC -fsanitize=address,undefined -shared-libsan -o $here/scratch/libyolo4hip_hostasan.so $out/*.o
+hipcc -shared -fPIC -fsanitize=address,undefined -shared-libsan -o $here/scratch/libyolo4hip_hostasan.so $(for u in $units; do echo $out/$u.o; done)
 echo "$(/opt/rocm/lib/llvm/bin/clang -print-file-name=libclang_rt.asan-x86_64.so)" > $here/scratch/hostasan_runtime.txt
 ls -la $here/scratch/libyolo4hip_hostasan.so

@@ -99,10 +99,37 @@ def test_workspace_aliasing_layout_host_only():
         lib.y4_destroy(h)
 
 
+# y4_launch_counts -> (conv-family launches, all launches of a predict) under each shipped schedule ...
+SHIPPED_LAUNCHES = {"416_3_64_f16.json": (76, 80), "416_80_1_bf16.json": (87, 91), "416_80_1_f32.json": (104, 108),
+                    "416_80_32_bf16.json": (81, 85), "416_80_32_f32.json": (104, 108), "608_80_1_bf16.json": (87, 91),
+                    "608_80_1_f32.json": (104, 108), "608_80_32_bf16.json": (75, 79), "608_80_32_f16.json": (75, 79),
+                    "608_80_32_f32.json": (104, 108)}
+# ... and on a fresh 16-bit square handle, by (stem, chain, stage fusion) for residual masks 0, 1, 2, 3
+FRESH_LAUNCHES = {
+    (0, 0, 0): [(104, 108), (96, 100), (102, 106), (94, 98)],
+    (0, 0, 1): [(100, 104), (92, 96), (98, 102), (90, 94)],
+    (0, 1, 0): [(77, 81), (77, 81), (77, 81), (77, 81)],
+    (0, 1, 1): [(76, 80), (76, 80), (76, 80), (76, 80)],
+    (1, 0, 0): [(103, 107), (95, 99), (101, 105), (93, 97)],
+    (1, 0, 1): [(99, 103), (91, 95), (97, 101), (89, 93)],
+    (1, 1, 0): [(76, 80), (76, 80), (76, 80), (76, 80)],
+    (1, 1, 1): [(75, 79), (75, 79), (75, 79), (75, 79)],
+}
+
+
+def _launch_counts(lib, h):
+    from yolo4hip import ext
+    convs, total = C.c_int32(), C.c_int32()
+    ext.check(lib.y4_launch_counts(h, C.byref(convs), C.byref(total)))
+    return convs.value, total.value
+
+
 def test_every_shipped_schedule_is_accepted_by_the_library():
     """yolo4hip/schedules/*.json (what bench.py and the facade load instead of tuning) against the library's own rules, host
     only: right length, every tile id known, chained heads (negative ids) only where the plan has a chain, stage / residual
-    switches settable -- y4_set_tiles and friends validate all of that without a GPU."""
+    switches settable -- y4_set_tiles and friends validate all of that without a GPU.  The launches a predict issues under each
+    schedule, and under every fusion switch on fresh handles, are pinned (y4_launch_counts: which ops run, fused or skipped)."""
+    import itertools
     import glob
     import json
     from yolo4hip import ext
@@ -167,4 +194,19 @@ def test_every_shipped_schedule_is_accepted_by_the_library():
             assert lib.y4_set_stage_fusion(h, int(s["stage_fusion"])) == int(s["stage_fusion"])
             ext.check(lib.y4_set_res_fusion_mask(h, int(s["res_fusion_mask"])))
             assert lib.y4_get_res_fusion(h) == s["res_fusion_mask"]
+        assert _launch_counts(lib, h) == SHIPPED_LAUNCHES[os.path.basename(f)], f
         lib.y4_destroy(h)
+    # every switch combination on fresh handles; stem fusion is refused on a rectangle, which then counts as stem off
+    for (H, W), dtype in [((416, 416), "bf16"), ((416, 416), "f16"), ((608, 608), "bf16"), ((608, 608), "f16"),
+                          ((352, 608), "bf16")]:
+        for stem, chain, stage, res in itertools.product((0, 1), (0, 1), (0, 1), range(4)):
+            cfg = _cfg_struct(make_config((H, W)), 80, 1, dtype)
+            h = C.c_void_p()
+            ext.check(lib.y4_create_hw(C.byref(cfg), H, W, C.byref(h)))
+            assert lib.y4_set_stem_fusion(h, stem) == (-22 if stem and H != W else 0)
+            assert lib.y4_set_chain_fusion(h, chain) == (26 if chain else 0)
+            assert lib.y4_set_stage_fusion(h, stage) == stage
+            ext.check(lib.y4_set_res_fusion_mask(h, res))
+            key = (int(stem and H == W), chain, stage)
+            assert _launch_counts(lib, h) == FRESH_LAUNCHES[key][res], (H, W, dtype, stem, chain, stage, res)
+            lib.y4_destroy(h)

@@ -312,19 +312,20 @@ size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 bool same_view(const View& a, const View& b) { return a.buf == b.buf && a.coff == b.coff && a.c == b.c; }
 
+// does an op outside [lo, hi] read buffer `buf` (as its input or its residual)?
+bool read_outside(const y4_ctx& c, int buf, int lo, int hi) {
+    for (int k = 0; k < (int)c.ops.size(); ++k) {
+        const Op& o = c.ops[k];
+        if ((k < lo || k > hi) && (o.in.buf == buf || (o.has_res && o.res.buf == buf))) return true;
+    }
+    return false;
+}
+
 // Find the 3x3+Add -> 1x1 [-> 1x1 over Concatenate([., route])] runs of the plan that conv_chain.h can execute as one
 // kernel (16-bit dtypes): head cout 64, Mish everywhere, tails 64 -> 64 and 128 -> 64|128.
 void find_chains(y4_ctx& c) {
     if (c.cfg.dtype == Y4_F32) return;
     const int nops = (int)c.ops.size();
-    auto readers = [&](int buf, int except_a, int except_b) {     // does any other op read this buffer?
-        for (int i = 0; i < nops; ++i) {
-            if (i == except_a || i == except_b) continue;
-            const Op& o = c.ops[i];
-            if (o.in.buf == buf || (o.has_res && o.res.buf == buf)) return true;
-        }
-        return false;
-    };
     auto in_chain = [&](int oi) {
         for (const Chain& ch : c.chains)
             if (ch.head == oi || ch.tail[0] == oi || ch.tail[1] == oi) return true;
@@ -343,7 +344,7 @@ void find_chains(y4_ctx& c) {
         if (!(lb.d.ksize == 1 && lb.d.cin == la.d.cout && 2 * lb.d.cout == la.d.cout && b.split == lb.d.cout && !b.has_res &&
               same_view(b.in, a.out)))
             continue;
-        Chain ch{i, {i + 1, -1}, readers(a.out.buf, i + 1, -1)};
+        Chain ch{i, {i + 1, -1}, read_outside(c, a.out.buf, i + 1, i + 1)};
         ch.lds_pair = true;
         c.chains.push_back(ch);
     }
@@ -371,7 +372,7 @@ void find_chains(y4_ctx& c) {
         if (!(lb.d.ksize == 1 && lb.d.cin == 64 && lb.d.cout == 64 && lb.d.act == Y4_ACT_MISH && !b.has_res && !b.upsample &&
               !b.out_f32 && same_view(b.in, a.out)))
             continue;
-        Chain ch{i, {i + 1, -1}, readers(a.out.buf, i + 1, -1)};
+        Chain ch{i, {i + 1, -1}, read_outside(c, a.out.buf, i + 1, i + 1)};
         if (i + 2 < nops) {
             const Op& d = c.ops[i + 2];
             if (d.kind == OP_CONV && d.conv2 < 0) {
@@ -379,7 +380,7 @@ void find_chains(y4_ctx& c) {
                 // d reads the whole concat buffer whose first 64 channels are b's output
                 if (ld.d.ksize == 1 && ld.d.cin == 128 && (ld.d.cout == 64 || ld.d.cout == 128) && ld.d.act == Y4_ACT_MISH &&
                     !d.has_res && !d.upsample && !d.out_f32 && d.in.buf == b.out.buf && d.in.coff == 0 && b.out.coff == 0 &&
-                    d.in.cstride == 128 && !readers(b.out.buf, i + 2, -1))
+                    d.in.cstride == 128 && !read_outside(c, b.out.buf, i + 2, i + 2))
                     ch.tail[1] = i + 2;
             }
         }
@@ -406,7 +407,7 @@ void find_chains(y4_ctx& c) {
         if ((la.d.cout != 128 && la.d.cout != 256) || a.upsample || a.out_f32) continue;
         if (!(lb.d.ksize == 1 && lb.d.cin == la.d.cout && lb.d.cout <= la.d.cout && !b.has_res && !b.upsample && same_view(b.in, a.out)))
             continue;
-        Chain ch{i, {i + 1, -1}, readers(a.out.buf, i + 1, -1)};
+        Chain ch{i, {i + 1, -1}, read_outside(c, a.out.buf, i + 1, i + 1)};
         ch.lds_pair = true;
         c.chains.push_back(ch);
     }
@@ -436,12 +437,7 @@ void find_stage(y4_ctx& c) {
         if (a.upsample || f.upsample || f.out_f32 || !csp_stage_supported(c.cfg.dtype, a.in.h, a.in.w)) continue;
         // no other op may read the tensors that stop existing
         bool leak = false;
-        for (int k = 0; k < nops; ++k) {
-            if (k >= i && k <= i + 4) continue;
-            const Op& o = c.ops[k];
-            for (int bufid : {a.out.buf, a.out2.buf, b.out.buf, d.out.buf})
-                if (o.in.buf == bufid || (o.has_res && o.res.buf == bufid)) leak = true;
-        }
+        for (int bufid : {a.out.buf, a.out2.buf, b.out.buf, d.out.buf}) leak = leak || read_outside(c, bufid, i, i + 4);
         if (leak) continue;
         c.stage_first = i; c.stage_last = i + 4;
         return;
@@ -462,10 +458,7 @@ void find_resruns(y4_ctx& c) {
               lb.d.cin == ch && lb.d.cout == ch && lb.d.act == Y4_ACT_MISH && lb.d.has_bn))
             continue;
         if (!(same_view(b.in, a.out) && same_view(b.res, a.in)) || a.upsample || b.upsample || a.out_f32 || b.out_f32) continue;
-        bool leak = false;                         // the 1x1 conv's output must have no other reader
-        for (int k = 0; k < nops; ++k)
-            if (k != i + 1 && (c.ops[k].in.buf == a.out.buf || (c.ops[k].has_res && c.ops[k].res.buf == a.out.buf))) leak = true;
-        if (leak) continue;
+        if (read_outside(c, a.out.buf, i + 1, i + 1)) continue;      // the 1x1 conv's output must have no other reader
         c.resruns.push_back(ResRun{i, i + 1, ch});
     }
 }
@@ -613,169 +606,191 @@ void build_schedule(y4_handle h, int n, std::vector<Launch>& out) {
     for (int i = first_full; i < nops; ++i) out.push_back({i, 0, n});
 }
 
-int run_op(y4_handle h, const Op& op, const void* imgs, int n, hipStream_t s, int img0 = 0, bool allow_chain = true) {
-    if (op.kind == OP_SPP) return spp_launch(h->cfg.dtype, buf_ptr(h, op.in, img0), n, op.in.h, op.in.w, op.in.cstride / 4, s);
-    const Layer& L = h->layers[op.conv];
-    const float* scale = (const float*)(h->wts + L.scale_off);
-    const float* shift = (const float*)(h->wts + L.shift_off);
-    if (op.kind == OP_STEM && h->fuse_stem) {
+// What op `oi` does under the handle's current switches: the one place that decides it (run_op executes the answer,
+// y4_launch_counts counts it).  allow_chain = false (the tuner timing a conv as its own kernel): only the stem's fusion applies.
+enum ExecKind { EX_SKIP, EX_SPP, EX_STEM, EX_STEM_DOWN, EX_RESBLOCK, EX_STAGE, EX_CHAIN, EX_LDS_PAIR, EX_ALT_CHAIN, EX_PLAIN };
+struct OpExec {
+    ExecKind kind;
+    const ResRun* res = nullptr;      // EX_RESBLOCK
+    const Chain* chain = nullptr;     // EX_CHAIN, EX_LDS_PAIR, EX_ALT_CHAIN
+};
+OpExec resolve_op(y4_handle h, int oi, bool allow_chain) {
+    const Op& op = h->ops[oi];
+    if (op.kind == OP_SPP) return {EX_SPP};
+    if (op.kind == OP_STEM) return {h->fuse_stem ? EX_STEM_DOWN : EX_STEM};
+    if (h->fuse_stem && op.conv == 1) return {EX_SKIP};                   // ran inside stem_down
+    if (!allow_chain) return {EX_PLAIN};
+    bool is_head = false;
+    if (const ResRun* rr = h->res_of(oi, &is_head)) return is_head ? OpExec{EX_RESBLOCK, rr} : OpExec{EX_SKIP};
+    if (h->stage_active() && oi >= h->stage_first && oi <= h->stage_last) return {oi == h->stage_first ? EX_STAGE : EX_SKIP};
+    const Chain* chain = nullptr;
+    for (const Chain& ch : h->chains) {
+        if (!h->chain_active(ch)) continue;     // (a head inside a residual-block kernel: its tails run alone or as the alternative run)
+        if (ch.tail[0] == oi || ch.tail[1] == oi) return {EX_SKIP};       // ran with its head
+        if (ch.head == oi) chain = &ch;
+    }
+    if (!chain) return {EX_PLAIN};
+    return {chain->lds_pair ? EX_LDS_PAIR : chain->alt_of >= 0 ? EX_ALT_CHAIN : EX_CHAIN, nullptr, chain};
+}
+
+// The kernels address their input through a raw buffer descriptor (2 GiB range, conv_igemm.hip): a batch whose input view is
+// larger runs as consecutive image chunks (images are independent), `launch(first image, count)` each.  `reach`: what a 3x3
+// conv's biased tap offsets add to the range (conv2d_launch's own check).  `fmt, args...` word the error; the bytes of one image
+// are its last argument.
+template <class F, class... A>
+int for_image_chunks(y4_handle h, const View& in, int64_t reach, int n, int img0, const F& launch, const char* fmt, A... args) {
+    const int64_t per_img = (int64_t)in.h * in.w * in.cstride * h->es;
+    const int max_n = (int)(((1ll << 31) - 1 - reach) / per_img);
+    if (max_n < 1) {
+        set_error(fmt, args..., (long long)per_img);
+        return Y4_EINVAL;
+    }
+    for (int i0 = 0; i0 < n; i0 += max_n)
+        if (int r = launch(img0 + i0, n - i0 < max_n ? n - i0 : max_n)) return r;
+    return Y4_OK;
+}
+
+int run_op(y4_handle h, int oi, const void* imgs, int n, hipStream_t s, int img0 = 0, bool allow_chain = true) {
+    const Op& op = h->ops[oi];
+    const OpExec ex = resolve_op(h, oi, allow_chain);
+    switch (ex.kind) {
+    case EX_SKIP:
+        return Y4_OK;
+    case EX_SPP:
+        return spp_launch(h->cfg.dtype, buf_ptr(h, op.in, img0), n, op.in.h, op.in.w, op.in.cstride / 4, s);
+    case EX_STEM_DOWN: {
         const Op& o1 = h->ops[1];
-        const Layer& L1 = h->layers[1];
+        const Layer &L = h->layers[0], &L1 = h->layers[1];
         return stem_down_launch(h->cfg.dtype, img_at(h, imgs, img0), h->img_u8 ? 1 : 0, n, h->H,      // (square only: y4_set_stem_fusion)
-                                h->wts + L.w_off, scale, shift, L.d.act, h->wts + L1.w_off,
-                                (const float*)(h->wts + L1.scale_off), (const float*)(h->wts + L1.shift_off), L1.d.act,
+                                h->wts + L.w_off, (const float*)(h->wts + L.scale_off), (const float*)(h->wts + L.shift_off), L.d.act,
+                                h->wts + L1.w_off, (const float*)(h->wts + L1.scale_off), (const float*)(h->wts + L1.shift_off), L1.d.act,
                                 buf_ptr(h, o1.out, img0), o1.out.cstride, o1.out.coff, s);
     }
-    if (h->fuse_stem && op.kind == OP_CONV && op.conv == 1) return Y4_OK;
-    if (allow_chain && op.kind == OP_CONV) {
-        bool is_head = false;
-        if (const ResRun* rr = h->res_of((int)(&op - h->ops.data()), &is_head)) {
-            if (!is_head) return Y4_OK;                          // the 3x3 conv ran inside its block's kernel
-            const Op& last = h->ops[rr->tail];
-            const int64_t per_img = (int64_t)op.in.h * op.in.w * op.in.cstride * h->es;
-            const int max_n = (int)(((1ll << 31) - 1) / per_img);
-            Y4_REQUIRE(max_n >= 1, Y4_EINVAL, "residual block: one image of the input view (%lld B) exceeds the 2 GiB buffer range", (long long)per_img);
-            for (int i0 = 0; i0 < n; i0 += max_n) {
-                const int cnt = n - i0 < max_n ? n - i0 : max_n;
-                if (int r = resblock_launch(h->cfg.dtype, rr->c, buf_ptr(h, op.in, img0 + i0), cnt, op.in.h, op.in.w, op.in.cstride, op.in.coff,
-                                            h->wts + rr->blob_off, buf_ptr(h, last.out, img0 + i0), last.out.cstride, last.out.coff, s))
-                    return r;
-            }
-            return Y4_OK;
-        }
-    }
-    if (allow_chain && h->stage_active() && op.kind == OP_CONV) {
-        const int oi = (int)(&op - h->ops.data());
-        if (oi > h->stage_first && oi <= h->stage_last) return Y4_OK;      // ran inside the stage kernel
-        if (oi == h->stage_first) {
-            const Op& last = h->ops[h->stage_last];
-            const int64_t per_img = (int64_t)op.in.h * op.in.w * op.in.cstride * h->es;
-            const int max_n = (int)(((1ll << 31) - 1) / per_img);
-            Y4_REQUIRE(max_n >= 1, Y4_EINVAL, "stage kernel: one image of the input view (%lld B) exceeds the 2 GiB buffer range", (long long)per_img);
-            for (int i0 = 0; i0 < n; i0 += max_n) {           // 2 GiB buffer-descriptor range: image chunks
-                const int cnt = n - i0 < max_n ? n - i0 : max_n;
-                if (int r = csp_stage_launch(h->cfg.dtype, buf_ptr(h, op.in, img0 + i0), cnt, op.in.h, op.in.w, op.in.cstride, op.in.coff,
-                                             h->wts + h->stage_blob_off, buf_ptr(h, last.out, img0 + i0), last.out.cstride,
-                                             last.out.coff, s))
-                    return r;
-            }
-            return Y4_OK;
-        }
-    }
-    const Chain* chain = nullptr;
-    if (h->fuse_chains && allow_chain && op.kind == OP_CONV)
-        for (const Chain& ch : h->chains) {
-            if (!h->chain_active(ch)) continue;     // (a head inside a residual-block kernel: its tails run alone or as the alternative run)
-            if (&h->ops[ch.head] == &op) chain = &ch;
-            else if (&h->ops[ch.tail[0]] == &op || (ch.tail[1] >= 0 && &h->ops[ch.tail[1]] == &op)) return Y4_OK;   // ran with its head
-        }
-    if (op.kind == OP_STEM)
+    case EX_STEM: {
+        const Layer& L = h->layers[0];
         return stem_conv_launch(h->cfg.dtype, img_at(h, imgs, img0), h->img_u8 ? 1 : 0, n, h->H, h->W,
-                                (const float*)(h->wts + L.w_off), scale, shift, L.d.cout, L.d.act,
-                                buf_ptr(h, op.out, img0), op.out.cstride, op.out.coff, s);
-    {
-        // the conv kernels address their input through a raw buffer descriptor (2 GiB range, conv_igemm.hip): a batch
-        // whose input view is larger runs as consecutive image chunks of this same op (images are independent)
-        const int64_t per_img = (int64_t)op.in.h * op.in.w * op.in.cstride * h->es;
-        // (minus the reach of a 3x3 kernel's biased tap offsets: conv2d_launch's own check)
-        const int64_t tap_span = L.d.ksize == 3 ? ((int64_t)3 * op.in.w + 3) * op.in.cstride * h->es + (int64_t)op.in.c * h->es : 0;
-        const int max_n = (int)(((1ll << 31) - 1 - tap_span) / per_img);
-        Y4_REQUIRE(max_n >= 1, Y4_EINVAL, "conv %d: one image's input (%lld B) exceeds the 2 GiB buffer-descriptor range",
-                   op.conv, (long long)per_img);
-        if (n > max_n) {
-            for (int i0 = 0; i0 < n; i0 += max_n)
-                if (int r = run_op(h, op, imgs, n - i0 < max_n ? n - i0 : max_n, s, img0 + i0, allow_chain)) return r;
-            return Y4_OK;
+                                (const float*)(h->wts + L.w_off), (const float*)(h->wts + L.scale_off),
+                                (const float*)(h->wts + L.shift_off), L.d.cout, L.d.act, buf_ptr(h, op.out, img0), op.out.cstride,
+                                op.out.coff, s);
+    }
+    case EX_RESBLOCK: {
+        const Op& last = h->ops[ex.res->tail];
+        auto launch = [&](int i0, int cnt) {
+            return resblock_launch(h->cfg.dtype, ex.res->c, buf_ptr(h, op.in, i0), cnt, op.in.h, op.in.w, op.in.cstride, op.in.coff,
+                                   h->wts + ex.res->blob_off, buf_ptr(h, last.out, i0), last.out.cstride, last.out.coff, s);
+        };
+        return for_image_chunks(h, op.in, 0, n, img0, launch,
+                                "residual block: one image of the input view (%lld B) exceeds the 2 GiB buffer range");
+    }
+    case EX_STAGE: {
+        const Op& last = h->ops[h->stage_last];
+        auto launch = [&](int i0, int cnt) {
+            return csp_stage_launch(h->cfg.dtype, buf_ptr(h, op.in, i0), cnt, op.in.h, op.in.w, op.in.cstride, op.in.coff,
+                                    h->wts + h->stage_blob_off, buf_ptr(h, last.out, i0), last.out.cstride, last.out.coff, s);
+        };
+        return for_image_chunks(h, op.in, 0, n, img0, launch,
+                                "stage kernel: one image of the input view (%lld B) exceeds the 2 GiB buffer range");
+    }
+    case EX_PLAIN: case EX_CHAIN: case EX_LDS_PAIR: case EX_ALT_CHAIN:
+        break;
+    }
+    // the conv family: one conv2d_launch, carrying the run's tails when op heads one
+    const Layer& L = h->layers[op.conv];
+    const Chain* chain = ex.chain;
+    auto launch = [&](int i0, int cnt) -> int {
+        y4_conv_desc d{};
+        d.dtype = h->cfg.dtype;
+        d.n = cnt; d.h = op.in.h; d.w = op.in.w; d.cin = op.in.c;
+        d.cout = op.conv2 >= 0 ? 2 * L.d.cout : L.d.cout; d.ksize = L.d.ksize; d.stride = L.d.stride; d.act = L.d.act;
+        d.upsample = op.upsample ? 1 : 0; d.out_f32 = op.out_f32 ? 1 : 0;
+        d.in_cstride = op.in.cstride; d.in_coff = op.in.coff;
+        d.out_cstride = op.out.cstride; d.out_coff = op.out.coff;
+        d.in = buf_ptr(h, op.in, i0); d.wt = h->wts + L.w_off;
+        d.scale = (const float*)(h->wts + L.scale_off); d.shift = (const float*)(h->wts + L.shift_off);
+        d.wt_frag = L.has_frag ? h->wts + L.frag_off : nullptr;
+        d.out = buf_ptr(h, op.out, i0);
+        if (op.has_res) { d.res = buf_ptr(h, op.res, i0); d.res_cstride = op.res.cstride; d.res_coff = op.res.coff; }
+        if (op.conv2 >= 0) { d.out2 = buf_ptr(h, op.out2, i0); d.out2_cstride = op.out2.cstride; d.out2_coff = op.out2.coff; d.split = op.split; }
+        d.tile = chain ? chain->tile : op.tile;
+        d.splitk_ws = h->act + h->splitk_off; d.splitk_ws_bytes = SPLITK_WS_BYTES;
+        // a float32 head (as a plain launch or as the tail of an LDS pair) also fills its cells' slots of the objectness array
+        ConvObjDesc od{};
+        const ConvObjDesc* odp = nullptr;
+        int obj_head = -1;
+        {
+            const Op* ho = op.out_f32 ? &op : (ex.kind == EX_LDS_PAIR && h->ops[chain->tail[0]].out_f32 ? &h->ops[chain->tail[0]] : nullptr);
+            if (ho)
+                for (int i = 0; i < 3; ++i)
+                    if (h->heads[i].buf == ho->out.buf) {
+                        od.obj = (float*)(h->act + h->obj_off) + (size_t)i0 * h->cells_per_img * 4;
+                        od.nf = 5 + h->cfg.num_classes; od.cells_per_img = h->cells_per_img; od.cell_base = h->cell_base[i];
+                        odp = &od;
+                        obj_head = i;
+                        h->obj_n[i] = -1;                     // (valid again once the launch below has been enqueued)
+                    }
         }
-    }
-    y4_conv_desc d{};
-    d.dtype = h->cfg.dtype;
-    d.n = n; d.h = op.in.h; d.w = op.in.w; d.cin = op.in.c;
-    d.cout = op.conv2 >= 0 ? 2 * L.d.cout : L.d.cout; d.ksize = L.d.ksize; d.stride = L.d.stride; d.act = L.d.act;
-    d.upsample = op.upsample ? 1 : 0; d.out_f32 = op.out_f32 ? 1 : 0;
-    d.in_cstride = op.in.cstride; d.in_coff = op.in.coff;
-    d.out_cstride = op.out.cstride; d.out_coff = op.out.coff;
-    d.in = buf_ptr(h, op.in, img0); d.wt = h->wts + L.w_off; d.scale = scale; d.shift = shift;
-    d.wt_frag = L.has_frag ? h->wts + L.frag_off : nullptr;
-    d.out = buf_ptr(h, op.out, img0);
-    if (op.has_res) { d.res = buf_ptr(h, op.res, img0); d.res_cstride = op.res.cstride; d.res_coff = op.res.coff; }
-    if (op.conv2 >= 0) { d.out2 = buf_ptr(h, op.out2, img0); d.out2_cstride = op.out2.cstride; d.out2_coff = op.out2.coff; d.split = op.split; }
-    d.tile = chain ? chain->tile : op.tile;
-    d.splitk_ws = h->act + h->splitk_off; d.splitk_ws_bytes = SPLITK_WS_BYTES;
-    // a float32 head (as a plain launch or as the tail of an LDS pair) also fills its cells' slots of the objectness array
-    ConvObjDesc od{};
-    const ConvObjDesc* odp = nullptr;
-    int obj_head = -1;
-    {
-        const Op* ho = op.out_f32 ? &op : (chain && chain->lds_pair && h->ops[chain->tail[0]].out_f32 ? &h->ops[chain->tail[0]] : nullptr);
-        if (ho)
-            for (int i = 0; i < 3; ++i)
-                if (h->heads[i].buf == ho->out.buf) {
-                    od.obj = (float*)(h->act + h->obj_off) + (size_t)img0 * h->cells_per_img * 4;
-                    od.nf = 5 + h->cfg.num_classes; od.cells_per_img = h->cells_per_img; od.cell_base = h->cell_base[i];
-                    odp = &od;
-                    obj_head = i;
-                    h->obj_n[i] = -1;                     // (valid again once the launch below has been enqueued)
-                }
-    }
-    auto launched = [&](int rc) {                          // the side array counts only after a successful enqueue
-        if (rc == Y4_OK && obj_head >= 0) h->obj_n[obj_head] = img0 + n;
-        return rc;
-    };
-    if (chain && chain->lds_pair) {
-        const Op& to = h->ops[chain->tail[0]];
-        const Layer& TL = h->layers[to.conv];
-        ConvPairDesc pd{};
-        pd.w = h->wts + TL.w_off;
-        pd.scale = (const float*)(h->wts + TL.scale_off);
-        pd.shift = (const float*)(h->wts + TL.shift_off);
-        pd.act = TL.d.act; pd.cout = TL.d.cout; pd.out_f32 = to.out_f32 ? 1 : 0; pd.store_x = chain->store_x ? 1 : 0;
-        pd.fin = buf_ptr(h, to.out, img0); pd.fin_cstride = to.out.cstride; pd.fin_coff = to.out.coff;
-        if (to.conv2 >= 0) {          // the tail is a fused CSP pair: both convs' rows, split over two views
-            pd.cout = 2 * TL.d.cout; pd.split = to.split;
-            pd.fin2 = buf_ptr(h, to.out2, img0); pd.fin2_cstride = to.out2.cstride; pd.fin2_coff = to.out2.coff;
-        }
-        return launched(conv2d_launch(&d, h->act + h->zero_off, s, nullptr, &pd, odp));
-    }
-    if (chain && chain->alt_of >= 0) {
-        // this op (64 -> 64) feeds the conv over Concatenate([its output, route]) in registers; its own output is not stored
-        const Op& to = h->ops[chain->tail[0]];
-        const Layer& TL = h->layers[to.conv];
-        ConvChainDesc cd{};
-        cd.ntail = 2; cd.concat_only = 1; cd.store_x = 0;
-        cd.tail[1].w = h->wts + TL.tail_off;
-        cd.tail[1].scale = (const float*)(h->wts + TL.scale_off);
-        cd.tail[1].shift = (const float*)(h->wts + TL.shift_off);
-        cd.tail[1].cout = TL.d.cout;
-        cd.tail[1].src2 = buf_ptr(h, to.in, img0);
-        cd.tail[1].src2_cstride = to.in.cstride;
-        cd.tail[1].src2_coff = to.in.coff + 64;
-        cd.fin = buf_ptr(h, to.out, img0); cd.fin_cstride = to.out.cstride; cd.fin_coff = to.out.coff;
-        return conv2d_launch(&d, h->act + h->zero_off, s, &cd);
-    }
-    if (chain) {
-        ConvChainDesc cd{};
-        cd.store_x = chain->store_x ? 1 : 0;
-        const Op* last = &op;
-        for (int t = 0; t < 2 && chain->tail[t] >= 0; ++t) {
-            const Op& to = h->ops[chain->tail[t]];
+        auto launched = [&](int rc) {                          // the side array counts only after a successful enqueue
+            if (rc == Y4_OK && obj_head >= 0) h->obj_n[obj_head] = i0 + cnt;
+            return rc;
+        };
+        if (ex.kind == EX_LDS_PAIR) {
+            const Op& to = h->ops[chain->tail[0]];
             const Layer& TL = h->layers[to.conv];
-            cd.tail[t].w = h->wts + TL.tail_off;
-            cd.tail[t].scale = (const float*)(h->wts + TL.scale_off);
-            cd.tail[t].shift = (const float*)(h->wts + TL.shift_off);
-            cd.tail[t].cout = TL.d.cout;
-            if (t == 1) {                       // the concat partner: channels [64, 128) of the buffer the first tail writes into
-                cd.tail[t].src2 = buf_ptr(h, to.in, img0);
-                cd.tail[t].src2_cstride = to.in.cstride;
-                cd.tail[t].src2_coff = to.in.coff + 64;
+            ConvPairDesc pd{};
+            pd.w = h->wts + TL.w_off;
+            pd.scale = (const float*)(h->wts + TL.scale_off);
+            pd.shift = (const float*)(h->wts + TL.shift_off);
+            pd.act = TL.d.act; pd.cout = TL.d.cout; pd.out_f32 = to.out_f32 ? 1 : 0; pd.store_x = chain->store_x ? 1 : 0;
+            pd.fin = buf_ptr(h, to.out, i0); pd.fin_cstride = to.out.cstride; pd.fin_coff = to.out.coff;
+            if (to.conv2 >= 0) {          // the tail is a fused CSP pair: both convs' rows, split over two views
+                pd.cout = 2 * TL.d.cout; pd.split = to.split;
+                pd.fin2 = buf_ptr(h, to.out2, i0); pd.fin2_cstride = to.out2.cstride; pd.fin2_coff = to.out2.coff;
             }
-            cd.ntail = t + 1;
-            last = &to;
+            return launched(conv2d_launch(&d, h->act + h->zero_off, s, nullptr, &pd, odp));
         }
-        cd.fin = buf_ptr(h, last->out, img0); cd.fin_cstride = last->out.cstride; cd.fin_coff = last->out.coff;
-        return conv2d_launch(&d, h->act + h->zero_off, s, &cd);
-    }
-    return launched(conv2d_launch(&d, h->act + h->zero_off, s, nullptr, nullptr, odp));
+        if (ex.kind == EX_ALT_CHAIN) {
+            // this op (64 -> 64) feeds the conv over Concatenate([its output, route]) in registers; its own output is not stored
+            const Op& to = h->ops[chain->tail[0]];
+            const Layer& TL = h->layers[to.conv];
+            ConvChainDesc cd{};
+            cd.ntail = 2; cd.concat_only = 1; cd.store_x = 0;
+            cd.tail[1].w = h->wts + TL.tail_off;
+            cd.tail[1].scale = (const float*)(h->wts + TL.scale_off);
+            cd.tail[1].shift = (const float*)(h->wts + TL.shift_off);
+            cd.tail[1].cout = TL.d.cout;
+            cd.tail[1].src2 = buf_ptr(h, to.in, i0);
+            cd.tail[1].src2_cstride = to.in.cstride;
+            cd.tail[1].src2_coff = to.in.coff + 64;
+            cd.fin = buf_ptr(h, to.out, i0); cd.fin_cstride = to.out.cstride; cd.fin_coff = to.out.coff;
+            return conv2d_launch(&d, h->act + h->zero_off, s, &cd);
+        }
+        if (ex.kind == EX_CHAIN) {
+            ConvChainDesc cd{};
+            cd.store_x = chain->store_x ? 1 : 0;
+            const Op* last = &op;
+            for (int t = 0; t < 2 && chain->tail[t] >= 0; ++t) {
+                const Op& to = h->ops[chain->tail[t]];
+                const Layer& TL = h->layers[to.conv];
+                cd.tail[t].w = h->wts + TL.tail_off;
+                cd.tail[t].scale = (const float*)(h->wts + TL.scale_off);
+                cd.tail[t].shift = (const float*)(h->wts + TL.shift_off);
+                cd.tail[t].cout = TL.d.cout;
+                if (t == 1) {                       // the concat partner: channels [64, 128) of the buffer the first tail writes into
+                    cd.tail[t].src2 = buf_ptr(h, to.in, i0);
+                    cd.tail[t].src2_cstride = to.in.cstride;
+                    cd.tail[t].src2_coff = to.in.coff + 64;
+                }
+                cd.ntail = t + 1;
+                last = &to;
+            }
+            cd.fin = buf_ptr(h, last->out, i0); cd.fin_cstride = last->out.cstride; cd.fin_coff = last->out.coff;
+            return conv2d_launch(&d, h->act + h->zero_off, s, &cd);
+        }
+        return launched(conv2d_launch(&d, h->act + h->zero_off, s, nullptr, nullptr, odp));
+    };
+    const int64_t reach = L.d.ksize == 3 ? ((int64_t)3 * op.in.w + 3) * op.in.cstride * h->es + (int64_t)op.in.c * h->es : 0;
+    return for_image_chunks(h, op.in, reach, n, img0, launch,
+                            "conv %d: one image's input (%lld B) exceeds the 2 GiB buffer-descriptor range", op.conv);
 }
 
 int run_decode_nms(y4_handle h, int n, float iou_thr, float score_thr, float* boxes, float* scores, float* classes,
@@ -1015,7 +1030,7 @@ static int forward_impl(y4_handle h, const void* imgs, bool u8, int n, void* str
     build_schedule(h, n, sched);
     int rc = Y4_OK;
     for (const Launch& l : sched)
-        if ((rc = run_op(h, h->ops[l.op], imgs, l.cnt, (hipStream_t)stream, l.img0))) break;
+        if ((rc = run_op(h, l.op, imgs, l.cnt, (hipStream_t)stream, l.img0))) break;
     h->img_u8 = false;
     return rc;
 }
@@ -1047,7 +1062,7 @@ int y4_forward_until(y4_handle h, const float* imgs, int n, int last_conv, void*
     build_schedule(h, n, sched);
     int rc = Y4_OK;
     for (const Launch& l : sched)
-        if (l.op <= last_op && (rc = run_op(h, h->ops[l.op], imgs, l.cnt, (hipStream_t)stream, l.img0))) break;
+        if (l.op <= last_op && (rc = run_op(h, l.op, imgs, l.cnt, (hipStream_t)stream, l.img0))) break;
     return rc;
 }
 
@@ -1158,7 +1173,7 @@ static int predict_impl(y4_handle h, const void* imgs, int n, float* boxes, floa
     if (ev) Y4_CHECK_HIP(hipEventRecord(ev[0], s));
     for (size_t k = 0; k < sched.size(); ++k) {
         const Launch& l = sched[k];
-        if (int r = run_op(h, h->ops[l.op], imgs, l.cnt, s, l.img0)) return r;
+        if (int r = run_op(h, l.op, imgs, l.cnt, s, l.img0)) return r;
         if (ev && h->t_rec[k]) Y4_CHECK_HIP(hipEventRecord(ev[++i], s));
     }
     for (int stage = 1; stage <= 2; ++stage) {
@@ -1217,8 +1232,8 @@ static int autotune_impl(y4_handle h, y4_handle h2, int n, int reps, hipStream_t
     // (pair_passes bit 0: tiles, 1: chains / LDS pairs, 2: stage kernel, 3: residual-block kernels)
     bool two = false;
     auto run_both = [&](int oi, int ne, bool chained) -> int {
-        int r = run_op(h, h->ops[oi], nullptr, ne, s, 0, chained);
-        if (r == Y4_OK && two) r = run_op(h2, h2->ops[oi], nullptr, ne, s2, 0, chained);
+        int r = run_op(h, oi, nullptr, ne, s, 0, chained);
+        if (r == Y4_OK && two) r = run_op(h2, oi, nullptr, ne, s2, 0, chained);
         return r;
     };
     // the timed region: e0 on s (s2 starts behind it), the launches, then s waits for s2's tail and e1 closes it
@@ -1260,15 +1275,50 @@ static int autotune_impl(y4_handle h, y4_handle h2, int n, int reps, hipStream_t
         float ms = 0.f;
         return t_end(&ms) ? ms : -2.f;
     };
-    auto set_tile = [&](int oi, int tile) { h->ops[oi].tile = tile; if (h2) h2->ops[oi].tile = tile; };
+    // Final decision of passes 2-4, head to head, each variant as the executor would run it: `once(fused)` issues the variant's
+    // launches once (the separate kernels in their real order, not the same kernel back to back, which runs warmer than it ever
+    // does in a step).  One untimed block of max(reps, 3) of them each way (both start equally warm), then 4 alternating timed
+    // blocks.  Comparing a fused probe with the SUM of per-tile minima instead is biased towards "separate" (a minimum of noisy
+    // samples is low, and several of them add up) and flipped the 8 % wins of the 76^2 pairs run to run.
+    // -> Y4_EHIP (an event failure is not "fused lost"), Y4_EINVAL when the separate kernels themselves fail (their launch's
+    // message stays, y4_last_error), else Y4_OK and the verdict; a failing fused launch loses rather than "win" with ~0 ms.
+    const int per_block = reps > 3 ? reps : 3;
+    auto head_to_head = [&](const auto& once, bool* fused_wins) -> int {
+        auto block = [&](bool fused) -> float {            // ms; -2: HIP failure, -1: a launch failed
+            if (!t_begin()) return -2.f;
+            for (int i = 0; i < per_block; ++i)
+                if (once(fused) != Y4_OK) return -1.f;
+            float ms = 0.f;
+            return t_end(&ms) ? ms : -2.f;
+        };
+        const float w_f = block(true), w_s = block(false);
+        if (w_f == -2.f || w_s == -2.f) return Y4_EHIP;
+        bool fused_ok = w_f >= 0.f, sep_ok = w_s >= 0.f;
+        float t_fused = 0.f, t_sep = 0.f;
+        for (int r = 0; r < 4 && fused_ok && sep_ok; ++r) {
+            const float a = block(true), b = block(false);
+            if (a == -2.f || b == -2.f) return Y4_EHIP;
+            fused_ok = a >= 0.f; sep_ok = b >= 0.f;
+            t_fused += a; t_sep += b;
+        }
+        if (!sep_ok) return Y4_EINVAL;
+        *fused_wins = fused_ok && t_fused < t_sep;
+        return Y4_OK;
+    };
+    // every choice is made on both handles: the sibling ends up with the same schedule
+    auto on_both = [&](const auto& set) {
+        for (y4_handle x : {h, h2})
+            if (x) set(x);
+    };
+    auto set_tile = [&](int oi, int tile) { on_both([&](y4_handle x) { x->ops[oi].tile = tile; }); };
+    auto set_chain = [&](int ci, int tile, bool on) { on_both([&](y4_handle x) { x->chains[ci].tile = tile; x->chains[ci].enabled = on; }); };
+    auto set_stage = [&](bool on) { on_both([&](y4_handle x) { x->stage_enabled = on; }); };
+    auto set_res = [&](int grp, bool on) { on_both([&](y4_handle x) { x->res_enabled[grp] = on; }); };
     auto images_of = [&](int oi) { return (h->sub_images > 0 && oi <= h->sub_last_op && n > h->sub_images) ? h->sub_images : n; };
-    auto set_stage = [&](bool on) { h->stage_enabled = on; if (h2) h2->stage_enabled = on; };
-    auto set_res = [&](int grp, bool on) { h->res_enabled[grp] = on; if (h2) h2->res_enabled[grp] = on; };
     set_stage(false);                  // passes 1 and 2 tune the stage's convs as separate kernels; pass 3 decides
     set_res(0, false); set_res(1, false);               // likewise the residual-block kernels: pass 4
     // pass 1: every conv as its own kernel
     two = h2 && (pair_passes & 1);
-    std::vector<float> best_ms(h->ops.size(), 0.f);
     for (int oi = 0; oi < (int)h->ops.size() && rc == Y4_OK; ++oi) {
         Op& op = h->ops[oi];
         if (op.kind != OP_CONV || (h->fuse_stem && op.conv == 1)) continue;
@@ -1297,100 +1347,46 @@ static int autotune_impl(y4_handle h, y4_handle h2, int n, int reps, hipStream_t
                 }
             }
         set_tile(oi, best_tile);
-        best_ms[oi] = best;
     }
-    // pass 2: each chain as one kernel against the sum of its separate kernels
+    // pass 2: each chain as one kernel against its separate kernels
     two = h2 && (pair_passes & 2);
-    if (h->fuse_chains)
-        for (size_t ci = 0; ci < h->chains.size(); ++ci) {
-            Chain& ch = h->chains[ci];
-            auto mirror = [&]() { if (h2) { h2->chains[ci].tile = ch.tile; h2->chains[ci].enabled = ch.enabled; } };
-            if (rc != Y4_OK) break;
-            // an alternative run is timed as if its parent's head sat in a residual-block kernel (those are off until pass 4)
-            h->force_chain = ch.alt_of >= 0 ? (int)ci : -1;
-            if (h2) h2->force_chain = h->force_chain;
-            float separate = best_ms[ch.head] + best_ms[ch.tail[0]] + (ch.tail[1] >= 0 ? best_ms[ch.tail[1]] : 0.f);
-            float best = 1e30f;
-            int best_tile = 0;
-            ch.enabled = true;
-            for (int tile = 1; tile <= ntiles; ++tile) {
-                ch.tile = tile;
-                mirror();
-                const float ms = time_op(ch.head, images_of(ch.head), true);
-                if (ms == -2.f) { rc = Y4_EHIP; break; }
-                if (ms >= 0.f && ms < best) { best = ms; best_tile = tile; }
-            }
-            ch.tile = best_tile;
-            ch.enabled = best_tile > 0;
-            mirror();
-            if (!ch.enabled) continue;
-            // Final decision head to head, each variant as the executor would run it: the separate kernels in their real
-            // order (head, tail, tail -- not the same kernel back to back, which runs warmer than it ever does in a step)
-            // against the one fused launch, in alternating blocks and with several times the launches of a tile probe.
-            // Comparing `best` with the SUM of three per-tile minima instead is biased towards "separate" (a minimum of
-            // noisy samples is low, and three of them add up) and flipped the 8 % wins of the 76^2 pairs run to run.
-            (void)separate;
-            const int rounds = 4, per_round = reps > 3 ? reps : 3;
-            auto block = [&](bool fused) -> float {
-                if (!t_begin()) return -2.f;
-                for (int i = 0; i < per_round; ++i) {
-                    int r = Y4_OK;
-                    if (fused) {
-                        r = run_both(ch.head, images_of(ch.head), true);
-                    } else {
-                        r = run_both(ch.head, images_of(ch.head), false);
-                        if (r == Y4_OK) r = run_both(ch.tail[0], images_of(ch.tail[0]), false);
-                        if (r == Y4_OK && ch.tail[1] >= 0) r = run_both(ch.tail[1], images_of(ch.tail[1]), false);
-                    }
-                    if (r != Y4_OK) return fused ? -3.f : -4.f;      // a failed launch must not "win" with ~0 ms
-                }
-                float ms = 0.f;
-                return t_end(&ms) ? ms : -2.f;
-            };
-            float t_fused = 0.f, t_sep = 0.f;
-            const float w_f = block(true), w_s = block(false);                 // one untimed block each: both start equally warm
-            if (w_f == -2.f || w_s == -2.f) { rc = Y4_EHIP; break; }           // (an event failure is not "fused lost")
-            bool fused_ok = w_f >= 0.f, sep_ok = w_s >= 0.f;
-            for (int r = 0; r < rounds && rc == Y4_OK && fused_ok && sep_ok; ++r) {
-                const float a = block(true), b = block(false);
-                if (a == -2.f || b == -2.f) { rc = Y4_EHIP; break; }
-                if (a < 0.f) fused_ok = false;
-                if (b < 0.f) sep_ok = false;
-                t_fused += a; t_sep += b;
-            }
-            if (!sep_ok) { rc = Y4_EINVAL; break; }                   // the plain kernels themselves fail: report it (y4_last_error)
-            ch.enabled = fused_ok && t_fused < t_sep;
-            mirror();
+    for (int ci = 0; h->fuse_chains && ci < (int)h->chains.size() && rc == Y4_OK; ++ci) {
+        const Chain& ch = h->chains[ci];
+        // an alternative run is timed as if its parent's head sat in a residual-block kernel (those are off until pass 4)
+        on_both([&](y4_handle x) { x->force_chain = ch.alt_of >= 0 ? ci : -1; });
+        float best = 1e30f;
+        int best_tile = 0;
+        for (int tile = 1; tile <= ntiles; ++tile) {
+            set_chain(ci, tile, true);
+            const float ms = time_op(ch.head, images_of(ch.head), true);
+            if (ms == -2.f) { rc = Y4_EHIP; break; }
+            if (ms >= 0.f && ms < best) { best = ms; best_tile = tile; }
         }
-    h->force_chain = -1;
-    if (h2) h2->force_chain = -1;
+        set_chain(ci, best_tile, best_tile > 0);
+        if (!ch.enabled || rc != Y4_OK) continue;
+        bool wins = false;
+        rc = head_to_head([&](bool fused) -> int {
+            if (fused) return run_both(ch.head, images_of(ch.head), true);
+            for (int oi : {ch.head, ch.tail[0], ch.tail[1]})
+                if (oi >= 0)
+                    if (int r = run_both(oi, images_of(oi), false)) return r;
+            return Y4_OK;
+        }, &wins);
+        if (rc == Y4_OK) set_chain(ci, ch.tile, wins);     // (on a failure the run stays as its tile probe left it)
+    }
+    on_both([](y4_handle x) { x->force_chain = -1; });
     // pass 3: the stage kernel (convs 2..7 in one launch) head to head against the same ops as tuned above
     two = h2 && (pair_passes & 4);
     if (rc == Y4_OK && h->stage_first >= 0 && h->stage_on) {
         const int ne = images_of(h->stage_first);
-        const int rounds = 4, per_round = reps > 3 ? reps : 3;
-        auto block = [&](bool fused) -> float {
+        bool wins = false;
+        rc = head_to_head([&](bool fused) -> int {
             set_stage(fused);
-            if (!t_begin()) return -2.f;
-            for (int i = 0; i < per_round; ++i)
-                for (int oi = h->stage_first; oi <= h->stage_last; ++oi)
-                    if (run_both(oi, ne, true) != Y4_OK) return fused ? -3.f : -4.f;
-            float ms = 0.f;
-            return t_end(&ms) ? ms : -2.f;
-        };
-        float t_fused = 0.f, t_sep = 0.f;
-        const float w_f = block(true), w_s = block(false);
-        if (w_f == -2.f || w_s == -2.f) rc = Y4_EHIP;
-        bool fused_ok = w_f >= 0.f, sep_ok = w_s >= 0.f;
-        for (int r = 0; r < rounds && rc == Y4_OK && fused_ok && sep_ok; ++r) {
-            const float a = block(true), b = block(false);
-            if (a == -2.f || b == -2.f) { rc = Y4_EHIP; break; }
-            if (a < 0.f) fused_ok = false;
-            if (b < 0.f) sep_ok = false;
-            t_fused += a; t_sep += b;
-        }
-        if (!sep_ok && rc == Y4_OK) rc = Y4_EINVAL;
-        set_stage(rc == Y4_OK && fused_ok && t_fused < t_sep);
+            for (int oi = h->stage_first; oi <= h->stage_last; ++oi)
+                if (int r = run_both(oi, ne, true)) return r;
+            return Y4_OK;
+        }, &wins);
+        set_stage(rc == Y4_OK && wins);
     }
     // pass 4: per channel group, the residual blocks as one kernel each against the same op range as tuned above
     two = h2 && (pair_passes & 8);
@@ -1403,29 +1399,14 @@ static int autotune_impl(y4_handle h, y4_handle h2, int n, int reps, hipStream_t
         for (const Chain& ch : h->chains)
             if (ch.head >= lo && ch.head <= hi) { if (ch.tail[0] > hi) hi = ch.tail[0]; if (ch.tail[1] > hi) hi = ch.tail[1]; }
         const int ne = images_of(lo);
-        const int rounds = 4, per_round = reps > 3 ? reps : 3;
-        auto block = [&](bool fused) -> float {
+        bool wins = false;
+        rc = head_to_head([&](bool fused) -> int {
             set_res(grp, fused);
-            if (!t_begin()) return -2.f;
-            for (int i = 0; i < per_round; ++i)
-                for (int oi = lo; oi <= hi; ++oi)
-                    if (run_both(oi, ne, true) != Y4_OK) return fused ? -3.f : -4.f;
-            float ms = 0.f;
-            return t_end(&ms) ? ms : -2.f;
-        };
-        float t_fused = 0.f, t_sep = 0.f;
-        const float w_f = block(true), w_s = block(false);
-        if (w_f == -2.f || w_s == -2.f) rc = Y4_EHIP;
-        bool fused_ok = w_f >= 0.f, sep_ok = w_s >= 0.f;
-        for (int r = 0; r < rounds && rc == Y4_OK && fused_ok && sep_ok; ++r) {
-            const float a = block(true), b = block(false);
-            if (a == -2.f || b == -2.f) { rc = Y4_EHIP; break; }
-            if (a < 0.f) fused_ok = false;
-            if (b < 0.f) sep_ok = false;
-            t_fused += a; t_sep += b;
-        }
-        if (!sep_ok && rc == Y4_OK) rc = Y4_EINVAL;
-        set_res(grp, rc == Y4_OK && fused_ok && t_fused < t_sep);
+            for (int oi = lo; oi <= hi; ++oi)
+                if (int r = run_both(oi, ne, true)) return r;
+            return Y4_OK;
+        }, &wins);
+        set_res(grp, rc == Y4_OK && wins);
     }
     (void)hipEventDestroy(e0);
     (void)hipEventDestroy(e1);
@@ -1613,27 +1594,11 @@ int y4_copy_schedule(y4_handle src, y4_handle dst) {
     return Y4_OK;
 }
 
-// does op `oi` launch a kernel of its own under the current fusion settings?  (mirrors run_op's skip logic)
-static bool op_launches(y4_handle h, int oi) {
-    const Op& op = h->ops[oi];
-    if (op.kind != OP_CONV) return true;
-    if (h->fuse_stem && op.conv == 1) return false;
-    {
-        bool is_head = false;
-        if (h->res_of(oi, &is_head)) return is_head;
-    }
-    if (h->stage_active() && oi >= h->stage_first && oi <= h->stage_last) return oi == h->stage_first;
-    if (h->fuse_chains)
-        for (const Chain& ch : h->chains)
-            if (h->chain_active(ch) && (ch.tail[0] == oi || ch.tail[1] == oi)) return false;
-    return true;
-}
-
 int y4_launch_counts(y4_handle h, int32_t* conv_family, int32_t* total) {
     if (int r = check_handle(h)) return r;
     int convs = 0, all = 2;                                  // decode + nms
     for (int oi = 0; oi < (int)h->ops.size(); ++oi) {
-        if (!op_launches(h, oi)) continue;
+        if (resolve_op(h, oi, true).kind == EX_SKIP) continue;
         ++all;
         if (h->ops[oi].kind == OP_CONV) ++convs;
     }
