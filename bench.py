@@ -2,7 +2,7 @@
 """Headline benchmark: images/sec of the whole predict() hot path (forward + decode + NMS + results to the host) at
 608x608, 80 classes, batch 32 per GPU, bf16 storage / fp32 accumulate, synthetic data.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--full]
       N > 1 without a torchrun environment: this process -- before it touches any GPU -- starts
       `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py <same args>`
       as a child, relays its output (rank 0's JSON line) and exits with its return code.  Under torchrun
@@ -23,12 +23,15 @@ GPU; every step of a block still completes inside the block's bracket); `--in-fl
 Schedule (tile per launch, fusion kernels on / off -- every choice gives the same bits): the tuned one that ships for the
 shape (yolo4hip/schedules/, the kernel mix profiles/r05 was profiled with) if there is one, else a one-off autotune on this
 box; `--retune` forces the autotune, `--load-tiles` a file; `schedule` in the line says which ran.
+A plain run sets up, warms up, times the K steps, writes `--dump-outputs` and prints its line: nothing else.  `--full` adds
+what takes passes of its own after the timed blocks: the single-stream pass behind `roofline` / `breakdown_ms_per_step` /
+`single_stream_*` when more than one batch is in flight, `roofline.backbone_wall`, `latency` and `cpu_baseline`.
 `roofline` is for the dominant kernel family (the conv kernels: convs 2..109 with the stem fusion, else 1..109):
 algorithmic conv FLOPs of one step / its summed device time, measured with HIP events recorded on the launch stream
-(y4_timing_begin/end) -- inside the timed blocks with one stream, in a single-stream pass right after them with two
-(`roofline.measured_in`); `roofline.traffic` quotes the committed PMC passes when the schedule is the profiled one, else
-null with the reason.  `cpu_baseline` times the oracle (a torch-CPU/NumPy restatement; the reference's tf.keras path cannot
-run here) on a bounded sample on rank 0 at N=1.
+(y4_timing_begin/end) -- inside the timed blocks with one stream (so `--in-flight 1` reports it without `--full`), in a
+single-stream pass right after them with two (`roofline.measured_in`); `roofline.traffic` quotes the committed PMC passes
+when the schedule is the profiled one, else null with the reason.  `cpu_baseline` times the oracle (a torch-CPU/NumPy
+restatement; the reference's tf.keras path cannot run here) on a bounded sample on rank 0 at N=1.
 """
 import argparse
 import json
@@ -252,14 +255,17 @@ def parse_args(argv):
     ap.add_argument("--classes", type=int, default=80)
     ap.add_argument("--batch", type=int, default=32, help="images per GPU per step")
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "f16", "f32"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what takes passes of its own after the timed blocks: the single-stream pass behind `roofline` "
+                         "with --in-flight > 1, the backbone-only passes, `latency` and `cpu_baseline` (a plain run does none of them)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip `cpu_baseline`")
     ap.add_argument("--no-latency", action="store_true",
-                    help="skip the `latency` block (one-image y4_predict at 608 / 416, bf16 / fp32, and the facade's predict)")
+                    help="with --full: skip the `latency` block (one-image y4_predict at 608 / 416, bf16 / fp32, and the facade's predict)")
     ap.add_argument("--cpu-batch", type=int, default=32,
                     help="batch of the CPU proxy baseline (SURVEY.md 8(d): 32 and 1; 1 warm-up + 3 timed runs each, ~55 s of host time)")
     ap.add_argument("--stop-after-conv", type=int, default=71,
-                    help="last conv of the backbone-only passes (`roofline.backbone_wall`): the forward cut behind this conv "
-                         "(y4_forward_until), wall-clock timed with one stream and with --in-flight batches in flight; 71 = "
+                    help="with --full: last conv of the backbone-only passes (`roofline.backbone_wall`): the forward cut behind this "
+                         "conv (y4_forward_until), wall-clock timed with one stream and with --in-flight batches in flight; 71 = "
                          "CSPDarknet53 proper (reference custom_layers.py:100-124); -1 skips the passes")
 
     ap.add_argument("--no-autotune", action="store_true", help="use the built-in tile heuristic instead of measuring")
@@ -289,7 +295,8 @@ def parse_args(argv):
     ap.add_argument("--alias-workspace", action=argparse.BooleanOptionalAction, default=True,
                     help="activation buffers with disjoint lifetimes share memory (y4_set_workspace_aliasing): 8.0 -> 2.9 GB "
                          "per batch in flight at the headline shape, same bits, +1 %% single-stream")
-    ap.add_argument("--per-op", action="store_true", help="also print the per-op time table to stderr")
+    ap.add_argument("--per-op", action="store_true",
+                    help="also print the per-op time table to stderr (needs --full unless --in-flight 1)")
     ap.add_argument("--first-image", type=int, default=0,
                     help="global index of this run's first synthetic image (image i depends on (seed, i) only: a one-process run "
                          "with --first-image 32 computes what rank 1 of a two-rank run computes)")
@@ -354,6 +361,9 @@ def main():
         sys.exit(self_launch(args.gpus, argv))
     if args.batch < 1 or args.steps < 1 or args.blocks < 1 or args.gpus < 1:
         raise SystemExit("bench.py: --batch, --steps, --blocks and --gpus must be >= 1")
+    if args.per_op and args.in_flight > 1 and not args.full:
+        raise SystemExit("bench.py: --per-op with more than one batch in flight needs --full (the per-op times come from its "
+                         "single-stream pass)")
     if args.subbatch > 0:
         args.alias_workspace = False       # see --subbatch
     if args.dry_run:
@@ -513,12 +523,13 @@ def main():
     same = all(torch.equal(slot_host[0], h) for h in slot_host[1:])     # every slot ran the same batch: same outputs
     # ---- kernel-level attribution: HIP events on the launch stream need kernels that run one after the other, so the
     # per-kernel-family times behind `roofline` / `breakdown_ms_per_step` come from a single-stream pass of the same step
-    # (`--steps` steps, right here, same engine, same tiles) when D > 1: kernels of two streams overlap and an event pair
-    # around one of them also spans its neighbour's work.  With D = 1 the events sit in the timed blocks themselves.
+    # (`--steps` steps, right here, same engine, same tiles) when D > 1 and --full: kernels of two streams overlap and an event
+    # pair around one of them also spans its neighbour's work.  With D = 1 the events sit in the timed blocks themselves.
+    ops, nrec, single_ms = None, 0, None
     if depth == 1:
         ops, nrec = eng.timing_end()
         single_ms = sum(blocks) / args.steps * 1e3
-    else:
+    elif args.full:
         attrib_steps = min(args.steps, 4096)
         eng.timing_begin(attrib_steps, coarse=not args.per_op)   # 8 events per step unless --per-op
         t0 = time.perf_counter()
@@ -530,10 +541,10 @@ def main():
         ops, nrec = eng.timing_end()
     import hashlib
     digest = hashlib.sha256(host.numpy().tobytes()).hexdigest() if same else "SLOTS DIFFER"   # outputs of the last step
-    # ---- the backbone on its own, from WALL time, in both regimes: the forward cut behind conv
+    # ---- --full: the backbone on its own, from WALL time, in both regimes: the forward cut behind conv
     # --stop-after-conv (71: CSPDarknet53 proper), K steps with one stream, then K steps with `depth` batches in flight
     backbone_wall = None
-    if args.stop_after_conv >= 0:
+    if args.full and args.stop_after_conv >= 0:
         def backbone_pass(nslots):
             for k in range(nslots):                                  # warm-up, one per slot
                 with torch.cuda.stream(fl.streams[k]):
@@ -567,27 +578,6 @@ def main():
     if rank == 0:
         dt = sum(blocks)
         n_img = args.batch * world * args.steps
-        is_conv = lambda name: name.startswith("c") and name != "c0"
-        conv_ms = sum(ms for name, ms in ops if is_conv(name))
-        conv_flops = sum(c.flops_per_image for c in plan.convs[first_conv:]) * (hi - lo)
-        other = {name: ms for name, ms in ops if not is_conv(name)}
-        total_ms = sum(ms for _, ms in ops)
-        achieved = conv_flops / (conv_ms * 1e-3) / 1e12 if conv_ms > 0 else 0.0
-        peak = MFMA_PEAK_TFLOPS[args.dtype]
-        conv_launches = eng.conv_launches_per_step()
-        traffic, traffic_source = committed_traffic(args, fused_stem, chained, staged, res_mask, tiles)
-        # the other fractions of the same peak: the backbone north_star names (convs 0..71, from the coarse
-        # segment that ends behind conv 71, plus the stem), the whole forward (every conv FLOP over stem + convs + SPP), and
-        # end to end (every conv FLOP over the wall-clock step incl. decode, NMS and the results' copy to the host)
-        op_ms = dict(ops)
-        seg_names = [name for name, ms in ops if is_conv(name) and ms > 0]
-        backbone_ms = other.get("c0", 0.0) + (op_ms.get(seg_names[0], 0.0) if seg_names else 0.0)
-        if args.per_op:
-            backbone_ms = sum(ms for name, ms in ops if name.startswith("c") and all(int(i) <= 71 for i in name[1:].split("+")))
-        backbone_flops = sum(c.flops_per_image for c in plan.convs[:72]) * (hi - lo)
-        fwd_ms = conv_ms + other.get("c0", 0.0) + other.get("spp", 0.0)
-        fwd_flops = plan.flops_per_image * (hi - lo)
-        frac_of = lambda flops, ms: round(flops / (ms * 1e-3) / 1e12 / peak, 4) if ms > 0 else None
         line = {
             "metric": METRIC,
             "value": round(n_img / dt, 2), "unit": "images/sec",
@@ -616,59 +606,84 @@ def main():
                       f"{depth} batch(es) in flight per GPU (step i on HIP stream / workspace i % {depth}, shared weights)",
             "in_flight": depth, "schedule": schedule_src,
             "activation_workspace_bytes": int(eng.act_bytes), "workspace_aliasing": bool(args.alias_workspace),
-            "single_stream_ms_per_step": round(single_ms, 4),
-            "single_stream_value": round(args.batch * world / (single_ms * 1e-3), 2) if world == 1 else None,
-            "roofline": {"bound": "mfma", "achieved": round(achieved, 2), "peak": peak, "unit": "TFLOP/s",
-                         "frac": round(achieved / peak, 4),
-                         "backbone_frac": frac_of(backbone_flops, backbone_ms),
-                         "backbone_ms_per_step": round(backbone_ms, 4),
-                         "backbone_wall": backbone_wall,
-                         "whole_forward_frac": frac_of(fwd_flops, fwd_ms),
-                         "end_to_end_frac": round(n_img / dt * plan.flops_per_image / 1e12 / peak / world, 4),
-                         "timed_region_frac": round(conv_flops / (dt / args.steps) / 1e12 / peak, 4),
-                         "frac_definitions": "frac: conv family FLOPs / its HIP-event time; backbone_frac: convs 0..71 (CSPDarknet53, "
-                                             "73.696 GFLOP/image at 608) / stem + conv segment up to conv 71 (HIP events, one stream); "
-                                             "backbone_wall: the same FLOPs / WALL time of y4_forward_until(conv 71) alone, one stream and "
-                                             "with the timed region's batches in flight; whole_forward_frac: all 110 "
-                                             "convs / stem + convs + SPP; end_to_end_frac: all 110 convs x images/s (per GPU) / peak; timed_region_frac: the conv "
-                                             "family's FLOPs / the WALL time of a step in the timed blocks (a lower bound on the family inside the "
-                                             "timed region: that time also holds stem, SPP, decode, NMS and the copy of the results)",
-                         # what the matrix pipes SUSTAIN on random 16-bit operands (round 6: a register-only MFMA loop, no memory):
-                         # the power management lowers the clock to ~1.64 GHz under it -- `peak` stays the spec figure
-                         "sustained_on_random_data": ({"peak": SUSTAINED_TFLOPS, "unit": "TFLOP/s", "frac": round(achieved / SUSTAINED_TFLOPS, 4),
-                                                       "source": "scripts/ubench/mfma_power.hip, profiles/r06/mfma_power.txt: back-to-back "
-                                                                 "v_mfma_f32_32x32x16_bf16 from registers on random normal operands, all 256 CUs: "
-                                                                 "1617-1677 TFLOP/s at 1.64-1.70 GHz (zeros: 2157 at 2.17 GHz); DESIGN.md section 6a"}
-                                                      if args.dtype != "f32" else None),
-                         "traffic": traffic, "traffic_unit": "HBM bytes per step (all launches of the family)",
-                         "traffic_source": traffic_source,
-                         "kernel": "conv kernel family (convs %d..109, %d launches/step%s)" %
-                                   (first_conv, conv_launches, (", convs 2..7 in csp_stage_kernel" if staged else "") +
-                                    (", residual blocks of the %s-channel stages in resblock_kernel" %
-                                     "/".join(c for b, c in ((1, "128"), (2, "64")) if res_mask & b) if res_mask else "")),
-                         "flops_per_step": conv_flops, "kernel_ms_per_step": round(conv_ms, 4),
-                         "timed_steps": nrec,
-                         "measured_in": "HIP events on the launch stream over %d single-stream steps run right after the timed "
-                                        "blocks in this process (kernels of overlapping streams cannot be attributed to one "
-                                        "kernel); end_to_end_frac is from the timed blocks themselves" % nrec
-                                        if depth > 1 else "HIP events on the launch stream over the timed blocks"},
-            "breakdown_ms_per_step": {"conv_family": round(conv_ms, 4), ("stem_c0+c1_fused" if fused_stem else "stem_c0"): round(other.get("c0", 0.0), 4),
-                                      "spp": round(other.get("spp", 0.0), 4),
-                                      "decode": round(other.get("decode", 0.0), 4),
-                                      "nms": round(other.get("nms", 0.0), 4), "sum_of_ops": round(total_ms, 4),
-                                      "decode_nms_frac": round((other.get("decode", 0.0) + other.get("nms", 0.0)) /
-                                                               max(total_ms, 1e-9), 4)},
+            "full": bool(args.full),
         }
+        if ops is not None:      # per-kernel HIP-event times: the timed blocks' own with one stream, else --full's pass
+            is_conv = lambda name: name.startswith("c") and name != "c0"
+            conv_ms = sum(ms for name, ms in ops if is_conv(name))
+            conv_flops = sum(c.flops_per_image for c in plan.convs[first_conv:]) * (hi - lo)
+            other = {name: ms for name, ms in ops if not is_conv(name)}
+            total_ms = sum(ms for _, ms in ops)
+            achieved = conv_flops / (conv_ms * 1e-3) / 1e12 if conv_ms > 0 else 0.0
+            peak = MFMA_PEAK_TFLOPS[args.dtype]
+            conv_launches = eng.conv_launches_per_step()
+            traffic, traffic_source = committed_traffic(args, fused_stem, chained, staged, res_mask, tiles)
+            # the other fractions of the same peak: the backbone north_star names (convs 0..71, from the coarse
+            # segment that ends behind conv 71, plus the stem), the whole forward (every conv FLOP over stem + convs + SPP), and
+            # end to end (every conv FLOP over the wall-clock step incl. decode, NMS and the results' copy to the host)
+            op_ms = dict(ops)
+            seg_names = [name for name, ms in ops if is_conv(name) and ms > 0]
+            backbone_ms = other.get("c0", 0.0) + (op_ms.get(seg_names[0], 0.0) if seg_names else 0.0)
+            if args.per_op:
+                backbone_ms = sum(ms for name, ms in ops if name.startswith("c") and all(int(i) <= 71 for i in name[1:].split("+")))
+            backbone_flops = sum(c.flops_per_image for c in plan.convs[:72]) * (hi - lo)
+            fwd_ms = conv_ms + other.get("c0", 0.0) + other.get("spp", 0.0)
+            fwd_flops = plan.flops_per_image * (hi - lo)
+            frac_of = lambda flops, ms: round(flops / (ms * 1e-3) / 1e12 / peak, 4) if ms > 0 else None
+            line.update({
+                "single_stream_ms_per_step": round(single_ms, 4),
+                "single_stream_value": round(args.batch * world / (single_ms * 1e-3), 2) if world == 1 else None,
+                "roofline": {"bound": "mfma", "achieved": round(achieved, 2), "peak": peak, "unit": "TFLOP/s",
+                             "frac": round(achieved / peak, 4),
+                             "backbone_frac": frac_of(backbone_flops, backbone_ms),
+                             "backbone_ms_per_step": round(backbone_ms, 4),
+                             "backbone_wall": backbone_wall,
+                             "whole_forward_frac": frac_of(fwd_flops, fwd_ms),
+                             "end_to_end_frac": round(n_img / dt * plan.flops_per_image / 1e12 / peak / world, 4),
+                             "timed_region_frac": round(conv_flops / (dt / args.steps) / 1e12 / peak, 4),
+                             "frac_definitions": "frac: conv family FLOPs / its HIP-event time; backbone_frac: convs 0..71 (CSPDarknet53, "
+                                                 "73.696 GFLOP/image at 608) / stem + conv segment up to conv 71 (HIP events, one stream); "
+                                                 "backbone_wall: the same FLOPs / WALL time of y4_forward_until(conv 71) alone, one stream and "
+                                                 "with the timed region's batches in flight; whole_forward_frac: all 110 "
+                                                 "convs / stem + convs + SPP; end_to_end_frac: all 110 convs x images/s (per GPU) / peak; timed_region_frac: the conv "
+                                                 "family's FLOPs / the WALL time of a step in the timed blocks (a lower bound on the family inside the "
+                                                 "timed region: that time also holds stem, SPP, decode, NMS and the copy of the results)",
+                             # what the matrix pipes SUSTAIN on random 16-bit operands (round 6: a register-only MFMA loop, no memory):
+                             # the power management lowers the clock to ~1.64 GHz under it -- `peak` stays the spec figure
+                             "sustained_on_random_data": ({"peak": SUSTAINED_TFLOPS, "unit": "TFLOP/s", "frac": round(achieved / SUSTAINED_TFLOPS, 4),
+                                                           "source": "scripts/ubench/mfma_power.hip, profiles/r06/mfma_power.txt: back-to-back "
+                                                                     "v_mfma_f32_32x32x16_bf16 from registers on random normal operands, all 256 CUs: "
+                                                                     "1617-1677 TFLOP/s at 1.64-1.70 GHz (zeros: 2157 at 2.17 GHz); DESIGN.md section 6a"}
+                                                          if args.dtype != "f32" else None),
+                             "traffic": traffic, "traffic_unit": "HBM bytes per step (all launches of the family)",
+                             "traffic_source": traffic_source,
+                             "kernel": "conv kernel family (convs %d..109, %d launches/step%s)" %
+                                       (first_conv, conv_launches, (", convs 2..7 in csp_stage_kernel" if staged else "") +
+                                        (", residual blocks of the %s-channel stages in resblock_kernel" %
+                                         "/".join(c for b, c in ((1, "128"), (2, "64")) if res_mask & b) if res_mask else "")),
+                             "flops_per_step": conv_flops, "kernel_ms_per_step": round(conv_ms, 4),
+                             "timed_steps": nrec,
+                             "measured_in": "HIP events on the launch stream over %d single-stream steps run right after the timed "
+                                            "blocks in this process (kernels of overlapping streams cannot be attributed to one "
+                                            "kernel); end_to_end_frac is from the timed blocks themselves" % nrec
+                                            if depth > 1 else "HIP events on the launch stream over the timed blocks"},
+                "breakdown_ms_per_step": {"conv_family": round(conv_ms, 4), ("stem_c0+c1_fused" if fused_stem else "stem_c0"): round(other.get("c0", 0.0), 4),
+                                          "spp": round(other.get("spp", 0.0), 4),
+                                          "decode": round(other.get("decode", 0.0), 4),
+                                          "nms": round(other.get("nms", 0.0), 4), "sum_of_ops": round(total_ms, 4),
+                                          "decode_nms_frac": round((other.get("decode", 0.0) + other.get("nms", 0.0)) /
+                                                                   max(total_ms, 1e-9), 4)},
+            })
         if args.per_op:
             print("tiles:", tiles, file=sys.stderr)
             for name, ms in ops:
                 fl = sum(plan.convs[int(i)].flops_per_image for i in name[1:].split("+")) * (hi - lo) if name.startswith("c") else 0
                 print(f"{name:8s} {ms:8.4f} ms  {fl / (ms * 1e-3) / 1e12 if ms > 0 else 0:8.1f} TFLOP/s", file=sys.stderr)
-        if world == 1 and not args.no_latency and args.classes == 80:
+        if args.full and world == 1 and not args.no_latency and args.classes == 80:
             pkg = os.path.join(ROOT, "yolo-v4-tf.keras_amd")
             line["latency"] = latency_block(args.classes, W.flatten(ws_holder.get("ws") or W.synth_weights(plan, seed=0)),
                                             os.path.join(pkg, "class_names", "coco_classes.txt"), os.path.join(pkg, "img", "street.jpeg"))
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             ws = ws_holder.get("ws") or W.synth_weights(plan, seed=0)
             line["cpu_baseline"] = cpu_baseline(args.size, args.classes, ws, cfg, batch=args.cpu_batch)
         print(json.dumps(line), flush=True)

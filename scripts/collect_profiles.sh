@@ -20,17 +20,17 @@ SMI="rocm-smi --showclocks --showpower --showtemp --showperflevel --showmaxpower
 $SMI > $O/smi_idle.txt 2>&1
 # the schedule of the whole set: $Y4_COLLECT_TILES (a schedule file, e.g. scripts/instep_select.py's) if given, else a fresh autotune on THIS box;
 # afterwards tiles.json is what ships as yolo4hip/schedules/608_80_32_bf16.json
-if [ -n "$Y4_COLLECT_TILES" ]; then cp "$Y4_COLLECT_TILES" $O/tiles.json; python bench.py --load-tiles $O/tiles.json > $O/bench.json 2> $O/bench.err
-else python bench.py --retune --save-tiles $O/tiles.json > $O/bench.json 2> $O/bench.err; fi
+if [ -n "$Y4_COLLECT_TILES" ]; then cp "$Y4_COLLECT_TILES" $O/tiles.json; python bench.py --full --load-tiles $O/tiles.json > $O/bench.json 2> $O/bench.err
+else python bench.py --full --retune --save-tiles $O/tiles.json > $O/bench.json 2> $O/bench.err; fi
 # steady single-stream load for ~45 s; the sampler starts once the engine is up and the steps are running
-python bench.py --no-cpu-baseline --no-latency --load-tiles $O/tiles.json --in-flight 1 --steps 1500 --blocks 5 > $O/bench_single_stream.json 2> $O/bench_single_stream.err &
+python bench.py --full --no-cpu-baseline --no-latency --load-tiles $O/tiles.json --in-flight 1 --steps 1500 --blocks 5 > $O/bench_single_stream.json 2> $O/bench_single_stream.err &
 BPID=$!
 sleep 22
 ( for i in $(seq 1 24); do echo "== sample $i $(date +%s.%N)"; rocm-smi --showclocks --showpower --showtemp 2>/dev/null | grep -E "sclk|mclk|Power \(W\)|junction"; sleep 0.4; done ) > $O/smi_load.txt 2>&1
 wait $BPID
 for s in 1 2 3; do python scripts/two_batches.py $s 2>/dev/null | tail -1; done > $O/in_flight_sweep.txt
 B1="python3 bench.py --no-cpu-baseline --no-latency --stop-after-conv -1 --load-tiles $O/tiles.json --blocks 1 --in-flight 1"
-B2="python3 bench.py --no-cpu-baseline --no-latency --stop-after-conv -1 --load-tiles $O/tiles.json --blocks 1"
+B2="python3 bench.py --full --no-cpu-baseline --no-latency --stop-after-conv -1 --load-tiles $O/tiles.json --blocks 1"
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- $B1 --steps 5 --warmup 2 > $O/stats_bench.json 2> $O/stats.err
 python scripts/trace_gaps.py $(ls $O/stats/*/*kernel_trace.csv | head -1) $O/gaps.json
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats2 -- $B2 --steps 6 --warmup 2 > $O/stats2_bench.json 2> $O/stats2.err
@@ -46,11 +46,11 @@ done
 python scripts/pmc_summary.py 4 $O/hbm_traffic.json $O/pmc/pass1 $O/pmc/pass2
 python scripts/pmc_kernels.py $O/pmc_kernels.json $O/pmc/pass3 $O/pmc/pass4 $O/pmc/pass5 > $O/pmc_kernels.txt
 python scripts/mfma_util.py $O/pmc_kernels.json - $O/mfma_util.json $O/sq_wait_breakdown.json > $O/mfma_util.txt
-python bench.py --size 416 --classes 3 --batch 64 --dtype f16 --no-cpu-baseline --no-latency > $O/bench_cfg5.json 2>/dev/null
-python bench.py --batch 1 --dtype f32 --no-cpu-baseline --no-latency --steps 50 > $O/bench_cfg2.json 2>/dev/null
+python bench.py --full --size 416 --classes 3 --batch 64 --dtype f16 --no-cpu-baseline --no-latency > $O/bench_cfg5.json 2>/dev/null
+python bench.py --full --batch 1 --dtype f32 --no-cpu-baseline --no-latency --steps 50 > $O/bench_cfg2.json 2>/dev/null
 # round 5: fp16 at the headline shape, the halo tiles against the implicit-GEMM tiles layer by layer, the determinism hunt
-python bench.py --dtype f16 --no-cpu-baseline --no-latency > $O/bench_608_80_32_f16.json 2>/dev/null
-python bench.py --dtype f16 --no-cpu-baseline --no-latency --in-flight 1 > $O/bench_608_80_32_f16_single_stream.json 2>/dev/null
+python bench.py --full --dtype f16 --no-cpu-baseline --no-latency > $O/bench_608_80_32_f16.json 2>/dev/null
+python bench.py --full --dtype f16 --no-cpu-baseline --no-latency --in-flight 1 > $O/bench_608_80_32_f16_single_stream.json 2>/dev/null
 python scripts/halo_bench.py > $O/halo_bench_bf16.txt 2>&1
 python scripts/halo_bench.py --dtype f16 > $O/halo_bench_f16.txt 2>&1
 timeout 600 python scripts/determinism_hunt.py --sweep --iters 500 > $O/determinism_hunt.txt 2>&1
@@ -65,7 +65,7 @@ for dt in bf16 f16; do for act in 1 2; do echo "== $dt act $act"; python scripts
 for dt in bf16 f16; do python scripts/h2_det.py --dtype $dt --forwards 200 2>&1 | grep -v amdgpu.ids | tail -3; done > $O/h2_det.txt 2>&1
 # one image: the kernel timeline of a step on the shipped latency schedules (rocprofv3 --kernel-trace), bf16 and fp32
 for dt in bf16 f32; do
-  rocprofv3 --kernel-trace --output-format csv -d $O/b1_$dt -- python3 bench.py --batch 1 --dtype $dt --no-cpu-baseline --no-latency --in-flight 1 --steps 40 --warmup 5 --blocks 1 > $O/b1_$dt.json 2> $O/b1_$dt.err
+  rocprofv3 --kernel-trace --output-format csv -d $O/b1_$dt -- python3 bench.py --full --batch 1 --dtype $dt --no-cpu-baseline --no-latency --in-flight 1 --steps 40 --warmup 5 --blocks 1 > $O/b1_$dt.json 2> $O/b1_$dt.err
   python scripts/step_timeline.py $(ls $O/b1_$dt/*/*kernel_trace.csv | head -1) > $O/b1_${dt}_timeline.txt 2>&1
   rm -rf $O/b1_$dt
 done

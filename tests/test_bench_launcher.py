@@ -56,3 +56,12 @@ def test_eight_ranks_uneven_shards_slow_rank0_and_a_straggler():
     per = line["rank_ms_per_step"]["per_rank"]
     assert len(per) == 8 and per.index(max(per)) == 7 and max(per) > 1.5 * min(per)
     assert line["ms_per_step"] >= 0.95 * line["rank_ms_per_step"]["max"]
+
+
+def test_per_op_with_batches_in_flight_needs_full():
+    """With two batches in flight the per-op times come from --full's single-stream pass: a plain run refuses --per-op before it
+    touches anything (no torch import, no GPU) instead of printing a table it has no times for."""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--per-op", "--steps", "1"],
+                       capture_output=True, text=True, timeout=120)
+    assert r.returncode != 0 and "--full" in r.stderr
+    assert not [l for l in r.stdout.splitlines() if l.startswith("{")]

@@ -48,8 +48,8 @@ def test_bench_under_torchrun_one_rank_and_adopted_weights():
 
 def test_headline_shape_under_torchrun():
     """The same at the headline shape (608x608, 80 classes, batch 32, bf16): the 129 MB packed workspace through the RCCL
-    broadcast, the default fusions, one block of two steps."""
-    line = _run_child({}, size=608, classes=80, batch=32)
+    broadcast, the default fusions, one block of two steps; --full for the roofline's single-stream and backbone passes."""
+    line = _run_child({}, size=608, classes=80, batch=32, extra_args=["--full"])
     assert line["n_gpus"] == 1 and line["config"]["global_batch"] == 32 and line["dtype"] == "bf16"
     assert 0.05 < line["roofline"]["frac"] < 1.0 and line["roofline"]["backbone_frac"] and line["roofline"]["end_to_end_frac"]
 
@@ -84,3 +84,32 @@ def test_two_ranks_run_rank_zeros_tuned_schedule():
     plain = _run_child(share, ranks=2, extra_args=["--in-flight", "1"])
     assert plain["rank_tiles_sha256"][0] == plain["rank_tiles_sha256"][1] != tuned["rank_tiles_sha256"][0]
     assert plain["rank_outputs_sha256"] == tuned["rank_outputs_sha256"]
+
+
+def _run_plain(extra_args=()):
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--size", "160",
+           "--classes", "3", "--batch", "4", "--no-autotune"] + list(extra_args)
+    r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    return json.loads(lines[0])
+
+
+def test_plain_run_leaves_the_extra_passes_to_full():
+    """A plain run (no --full) times its steps and prints the headline fields, nothing that needs passes of its own: no
+    single-stream attribution pass with two batches in flight, no backbone passes, no CPU baseline.  --full adds them back
+    and computes the same outputs.  (`latency` runs only at 80 classes; the headline test above covers the roofline.)"""
+    plain = _run_plain()
+    assert plain["full"] is False and plain["in_flight"] == 2 and plain["steps"] == 2 and plain["value"] > 0
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "outputs_sha256"):
+        assert key in plain, key
+    for key in ("roofline", "breakdown_ms_per_step", "single_stream_value", "latency", "cpu_baseline"):
+        assert key not in plain, key
+    one = _run_plain(["--in-flight", "1"])                 # one stream: the events sit in the timed blocks, no extra pass needed
+    assert one["roofline"]["backbone_wall"] is None and one["single_stream_ms_per_step"] == one["ms_per_step"]
+    full = _run_plain(["--full", "--cpu-batch", "1"])
+    assert full["full"] is True and full["roofline"]["backbone_wall"]["in_flight_2"]["ms_per_step"] > 0
+    assert full["single_stream_value"] > 0 and full["cpu_baseline"]["batch"] == 1
+    assert full["outputs_sha256"] == plain["outputs_sha256"] == one["outputs_sha256"]
