@@ -157,6 +157,33 @@ int y4_decode_nms(y4_handle h, int n, float iou_threshold, float score_threshold
 int y4_decode_nms_mapped(y4_handle h, int n, float iou_threshold, float score_threshold, const float* box_map_dev,
                          float* boxes_dev, float* scores_dev, float* classes_dev, int32_t* valid_dev, int32_t* kept_idx_dev,
                          void* stream);
+/* ---- Validation loss: the forward of the reference's yolo_loss (loss.py:119-212; training_model, models.py:54-65) over the raw
+ * heads y4_forward / y4_set_heads left in the workspace.  Forward only: nothing here computes a gradient.
+ *
+ * A responsible-cell RECORD is words = 8 + ceil(num_classes / 32) int32 values
+ *     [scale, row, col, anchor, bits(x), bits(y), bits(w), bits(h), class mask word 0, ...]
+ * (label xywh in network-input pixels as float32 bit patterns; class c is bit c % 32 of mask word c / 32).  An image has at
+ * most max_boxes records, sorted by (scale, row, col, anchor); records_dev is [n, max_boxes, words], counts_dev [n].
+ *
+ * y4_loss_assign: the label assignment of preprocess_true_boxes (utils.py:215-303) for boxes_dev [n, max_boxes, 5] float32
+ * (x1, y1, x2, y2, class in network-input pixels; max_boxes <= 256) -> xywh_dev [n, max_boxes, 4] (its y_true_boxes_xywh) and
+ * the records of every image: rows with w <= 0 dropped by compaction, the k-th valid row's (w, h) picking the anchor and row k
+ * the cell, the later of two rows on one (cell, anchor) keeping its xywh while the class bits of both stay set.  Unused record
+ * slots are zeroed.  counts_dev[i] = -1 flags an image with a used row whose centre is off the grid or whose class id is
+ * outside [0, num_classes) (the reference's IndexError); that row makes no record. */
+int y4_loss_assign(y4_handle h, int n, const float* boxes_dev, int max_boxes, float* xywh_dev, int32_t* records_dev,
+                   int32_t* counts_dev, void* stream);
+/* floats of scratch y4_loss needs for n images (caller-provided, like the decode outputs; no workspace growth) */
+int y4_loss_scratch_floats(y4_handle h, int n, size_t* floats);
+/* out_dev [n, 3 scales, 3] float32: per image and scale the sums over all cells and anchors of the box term (GIoU), the
+ * confidence term and the class term, as loss.py runs them (decode without xyscale, epsilon 1e-7, divide_no_nan, the ignore
+ * mask max IoU(pred, every row of xywh_dev) < iou_loss_thresh); the caller combines them 3.54 / 64.3 / 1 and averages over the
+ * batch (loss.py:136-140).  iou_loss_thresh < 0 is refused.  Reduced without floating-point atomics in an order fixed by
+ * the image's geometry: image i's nine values do not depend on n or on its position in the batch.  Records that point
+ * outside the grids are ignored. */
+int y4_loss(y4_handle h, int n, const int32_t* records_dev, const int32_t* counts_dev, const float* xywh_dev, int max_boxes,
+            float iou_loss_thresh, float* scratch_dev, size_t scratch_floats, float* out_dev, void* stream);
+
 /* Replaces inference_model.predict(imgs) (reference models.py:69-73,113,159) = forward + decode + NMS. */
 int y4_predict(y4_handle h, const float* imgs_nhwc_dev, int n, float* boxes_dev, float* scores_dev,
                float* classes_dev, int32_t* valid_dev, int32_t* kept_idx_dev, void* stream);

@@ -125,4 +125,32 @@ int decode_launch(const DecodeK& k, hipStream_t stream, int clear_images);
 int l2_flush_launch(const void* p, size_t bytes, void* sink, hipStream_t stream);
 int nms_launch(const NmsK& k, hipStream_t stream);
 
+// loss.hip: the reference's yolo_loss forward over the raw heads, and the label assignment as responsible-cell records
+// (record: int32 words [scale, row, col, anchor, bits of x, y, w, h, class mask words]; sorted by (scale, row, col, anchor))
+struct LossAssignK {
+    const float* boxes;              // [n, mb, 5] x1, y1, x2, y2, class in network-input pixels
+    float* xywh;                     // [n, mb, 4] floor-centre x, y and w, h of every row
+    int32_t* records;                // [n, mb, rw]
+    int32_t* counts;                 // [n] records of the image, or -1: a used row is off the grid / has no such class
+    int mb, rw, mw, C;
+    int img_h, img_w;
+    int gh[3], gw[3], lane_base[3];  // lane_base: first (cell, anchor) index of a scale among the image's 3 * cells lanes
+    float anchors[18];
+};
+struct LossK {
+    const float* head[3];
+    int gh[3], gw[3], strip_base[3], strips;   // strips: 256-lane workgroups per image, strip_base: the first one of a scale
+    float stride[3], anchors[18];
+    int C, hcs, mb, rw;
+    float thresh, input_area;
+    const int32_t* records;          // [n, mb, rw]
+    const int32_t* counts;           // [n]
+    const float* xywh;               // [n, mb, 4]
+    float* partials;                 // [n, strips, 3]
+    float* out;                      // [n, 3 scales, 3] box, confidence, class sums
+};
+int loss_strips(const int* gh, const int* gw, int* strip_base);
+int loss_assign_launch(const LossAssignK& k, int n, hipStream_t stream);
+int loss_launch(const LossK& k, int n, hipStream_t stream);
+
 }  // namespace y4

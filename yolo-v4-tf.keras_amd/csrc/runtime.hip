@@ -843,7 +843,7 @@ int run_decode_nms(y4_handle h, int n, float iou_thr, float score_thr, float* bo
 extern "C" {
 
 const char* y4_last_error(void) { return g_err; }
-const char* y4_version(void) { return "yolo4hip 0.5 (gfx950)"; }
+const char* y4_version(void) { return "yolo4hip 0.5.1 (gfx950)"; }
 
 int y4_create(const y4_config* cfg, y4_handle* out) {
     Y4_REQUIRE(cfg && out, Y4_EINVAL, "y4_create: null argument");
@@ -1133,6 +1133,60 @@ int y4_decode_nms_mapped(y4_handle h, int n, float iou_threshold, float score_th
     const float iou = iou_threshold < 0.f ? h->cfg.iou_threshold : iou_threshold;
     const float sc = score_threshold < 0.f ? h->cfg.score_threshold : score_threshold;
     return run_decode_nms(h, n, iou, sc, boxes, scores, classes, valid, kept_idx, (hipStream_t)stream, 0, box_map);
+}
+
+static void loss_geometry(y4_handle h, int* gh, int* gw, int* lane_base) {
+    int lanes = 0;
+    for (int i = 0; i < 3; ++i) {
+        gh[i] = h->heads[i].h; gw[i] = h->heads[i].w;
+        if (lane_base) lane_base[i] = lanes;
+        lanes += 3 * gh[i] * gw[i];
+    }
+}
+
+int y4_loss_assign(y4_handle h, int n, const float* boxes, int max_boxes, float* xywh, int32_t* records, int32_t* counts,
+                   void* stream) {
+    if (int r = check_handle(h)) return r;
+    Y4_REQUIRE(n >= 1, Y4_EINVAL, "y4_loss_assign: batch %d", n);
+    Y4_REQUIRE(boxes && xywh && records && counts, Y4_EINVAL, "y4_loss_assign: null argument");
+    LossAssignK k{};
+    k.boxes = boxes; k.xywh = xywh; k.records = records; k.counts = counts;
+    k.mb = max_boxes; k.C = h->cfg.num_classes; k.mw = (k.C + 31) / 32; k.rw = 8 + k.mw;
+    k.img_h = h->H; k.img_w = h->W;
+    loss_geometry(h, k.gh, k.gw, k.lane_base);
+    memcpy(k.anchors, h->cfg.anchors, sizeof(k.anchors));
+    return loss_assign_launch(k, n, (hipStream_t)stream);
+}
+
+int y4_loss_scratch_floats(y4_handle h, int n, size_t* floats) {
+    if (int r = check_handle(h)) return r;
+    Y4_REQUIRE(n >= 1 && floats, Y4_EINVAL, "y4_loss_scratch_floats: bad argument");
+    int gh[3], gw[3];
+    loss_geometry(h, gh, gw, nullptr);
+    *floats = (size_t)n * loss_strips(gh, gw, nullptr) * 3;
+    return Y4_OK;
+}
+
+int y4_loss(y4_handle h, int n, const int32_t* records, const int32_t* counts, const float* xywh, int max_boxes,
+            float iou_loss_thresh, float* scratch, size_t scratch_floats, float* out, void* stream) {
+    if (int r = check_ready(h, n)) return r;
+    Y4_REQUIRE(records && counts && xywh && scratch && out, Y4_EINVAL, "y4_loss: null argument");
+    Y4_REQUIRE(iou_loss_thresh >= 0.f, Y4_EINVAL, "y4_loss: iou_loss_thresh %g", (double)iou_loss_thresh);
+    LossK k{};
+    loss_geometry(h, k.gh, k.gw, nullptr);
+    k.strips = loss_strips(k.gh, k.gw, k.strip_base);
+    Y4_REQUIRE(scratch_floats >= (size_t)n * k.strips * 3, Y4_ENOMEM, "y4_loss: scratch %zu < %zu floats", scratch_floats,
+               (size_t)n * k.strips * 3);
+    for (int i = 0; i < 3; ++i) {
+        k.head[i] = (const float*)buf_ptr(h, h->heads[i]);
+        k.stride[i] = (float)h->cfg.strides[i];
+    }
+    memcpy(k.anchors, h->cfg.anchors, sizeof(k.anchors));
+    k.C = h->cfg.num_classes; k.hcs = h->hcs; k.mb = max_boxes; k.rw = 8 + (k.C + 31) / 32;
+    k.thresh = iou_loss_thresh;
+    k.input_area = (float)h->H * (float)h->W;          // input_size ** 2 of the reference (loss.py:158); H * W for a rectangle
+    k.records = records; k.counts = counts; k.xywh = xywh; k.partials = scratch; k.out = out;
+    return loss_launch(k, n, (hipStream_t)stream);
 }
 
 // forward + decode + NMS; when `ev` is given, ev[0] is recorded before the first op and ev[i+1] after op i

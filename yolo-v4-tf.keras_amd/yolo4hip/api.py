@@ -11,8 +11,9 @@ the reference's 'not support yet' assert is lifted, boxes are normalised x / W, 
 arguments pick the compute dtype / batch capacity, and `letterbox=True` (keyword-only, off by default) letterboxes the input
 instead of the reference's stretch (Darknet's letter_box=1 geometry) with boxes returned in each raw image's pixels.  `save_model` / `load_model` (models.py:86-93) are stand-ins on a
 self-describing checkpoint of this framework (Keras' SavedModel / H5 needs TensorFlow); `eval_map` (models.py:182-507)
-is the VOC mAP tool over the exported text files (yolo4hip/evalmap.py).  Training (`fit`, `training_model`) is out of
-scope for this inference framework and raises.
+is the VOC mAP tool over the exported text files (yolo4hip/evalmap.py).  `training_model.predict([X, y_s, y_m, y_l, true_xywh])`
+is the reference's yolo_loss FORWARD (models.py:54-65, loss.py) on the device and `evaluate(data_gen)` the validation loss over
+a `DataGenerator`; training itself (`fit`) is out of scope and raises.
 """
 import json
 import os
@@ -93,7 +94,8 @@ class Yolov4(object):
         print(f"nms iou: {self.config['iou_threshold']} score: {self.config['score_threshold']}")
         self._thresholds = (-1.0, -1.0)  # what inference_model runs with (-1: the config's); load_model changes them
         self.inference_model = _KerasLikeModel(self._tuned_first(self.engine.predict), 'inference_model')
-        self.training_model = None      # training is out of scope (inference-only framework)
+        # the reference's other model (models.py:54-65): yolo_loss over the raw heads and the labels, forward only
+        self.training_model = _KerasLikeModel(self._tuned_first(self._loss_of_dense), 'training_model')
         if load_pretrained and self.weight_path and self.weight_path.endswith('.weights'):
             load_weights(self, self.weight_path)
             print(f'load from {self.weight_path}')
@@ -179,9 +181,45 @@ class Yolov4(object):
             self._tuned_first(lambda x: self.engine.predict(x, iou_threshold=0.413, score_threshold=0.3)), 'inference_model')
         self._thresholds = (0.413, 0.3)
 
-    # ---- out of scope (training)
+    # ---- out of scope (training).  The loss FORWARD is there (training_model.predict, evaluate): no gradients.
     def fit(self, *a, **k):
         raise NotImplementedError('training is out of scope of the MI355X inference path')
+
+    # ---- reference models.py:57-65: training_model's inputs [X, y_s, y_m, y_l, true_xywh] -> the yolo_loss Lambda's scalar
+    def _loss_of_dense(self, inputs):
+        """The dense labels never reach the device: their responsible cells (label[..., 4] == 1) are extracted on the host into
+        the sparse records `y4_loss` reads.  Label values other than 0 / 1 (smoothed labels) raise ValueError."""
+        from .data import records_from_dense
+        from .engine import combine_loss
+        if len(inputs) != 5:
+            raise ValueError('training_model.predict takes [X, y_small, y_medium, y_large, true_boxes_xywh]')
+        X, y_s, y_m, y_l, xywh = inputs
+        for y, g in zip((y_s, y_m, y_l), self.engine.grids_hw):
+            if tuple(np.shape(y)[1:3]) != tuple(g):
+                raise ValueError(f'label grid {tuple(np.shape(y)[1:3])} != {tuple(g)}')
+        records = records_from_dense([y_s, y_m, y_l], self.num_classes)
+        parts = self.engine.loss(X, records=records, true_xywh=xywh, iou_loss_thresh=self.iou_loss_thresh)
+        return np.float32(combine_loss(parts)[0].mean())
+
+    def evaluate(self, data_gen):
+        """The validation loss over a `DataGenerator` (yolo4hip.data / the drop-in utils): per batch the images and the
+        [n, max_boxes, 5] boxes are uploaded, labels are assigned on the device (y4_loss_assign) and the loss is one read of the
+        heads (y4_loss).  -> {'loss', 'box', 'conf', 'class', 'images'}: means over all images of the weighted terms
+        (loss = box + conf + class, weights 3.54 / 64.3 / 1 as loss.py:136-140), and the image count."""
+        from .engine import combine_loss
+        self._ensure_tuned()
+        if getattr(data_gen, 'max_boxes', self.max_boxes) != self.max_boxes:
+            raise ValueError(f"the generator's max_boxes {data_gen.max_boxes} != config['max_boxes'] {self.max_boxes}")
+        sums, images = np.zeros(4), 0
+        for i in range(len(data_gen)):
+            X, boxes = data_gen.boxes(i)
+            parts = self.engine.loss(X, boxes=boxes, iou_loss_thresh=self.iou_loss_thresh)
+            sums += np.array([t.sum() for t in combine_loss(parts)])
+            images += len(parts)
+        if images == 0:
+            raise ValueError('evaluate: the generator is empty')
+        mean = sums / images
+        return {'loss': float(mean[0]), 'box': float(mean[1]), 'conf': float(mean[2]), 'class': float(mean[3]), 'images': images}
 
     # ---- reference models.py:95-98
     def preprocess_img(self, img):

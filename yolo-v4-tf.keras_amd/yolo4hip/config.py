@@ -1,8 +1,8 @@
 """Inference constants of the path (mirror of the reference's module-global dict, `config.py:1-17`).
 
-Only the keys the inference path reads are kept; the training knobs (`iou_loss_thresh`,
-`batch_size`) are carried so that code doing `yolo_config['batch_size']` keeps working, but nothing
-here consumes them.  Unlike the reference (`models.py:26-37` ignores the ctor's `config=` argument),
+The inference path reads the Basic and Inference keys.  Of the training keys, `iou_loss_thresh` is the ignore
+threshold of the validation loss (`Yolov4.training_model`, `Yolov4.evaluate`), and `batch_size` x `num_gpu` is the
+batch of `DataGenerator`; nothing here trains.  Unlike the reference (`models.py:26-37` ignores the ctor's `config=` argument),
 `Yolov4(config=...)` honours a passed dict.
 """
 
@@ -13,7 +13,7 @@ yolo_config = {
     'strides': [8, 16, 32],
     'xyscale': [1.2, 1.1, 1.05],
 
-    # Training (unused by this inference-only framework)
+    # Training (the validation loss and DataGenerator read them; there is no fit)
     'iou_loss_thresh': 0.5,
     'batch_size': 8,
     'num_gpu': 1,

@@ -482,6 +482,113 @@ class Engine:
         res = [np.concatenate(p, axis=0) for p in acc]
         return res if with_indices else res[:4]
 
+    # ---------------------------------------------------------------- validation loss (forward only)
+    def _loss_max_boxes(self):
+        return int(self.config.get("max_boxes", 100))
+
+    def assign_device(self, boxes_dev):
+        """y4_loss_assign: boxes_dev, a contiguous float32 cuda tensor [n, max_boxes, 5] (x1, y1, x2, y2, class in network-input
+        pixels) -> (records int32 [n, max_boxes, 8 + mw], counts int32 [n], xywh float32 [n, max_boxes, 4]) on the device
+        (yolo4hip/data.py describes the record).  counts[i] == -1: image i has a box off the grid or an unknown class."""
+        torch = self.torch
+        mb = self._loss_max_boxes()
+        if boxes_dev.dtype != torch.float32 or boxes_dev.dim() != 3 or tuple(boxes_dev.shape[1:]) != (mb, 5) \
+                or not boxes_dev.is_contiguous():
+            raise ValueError(f"boxes must be a contiguous float32 tensor [n, max_boxes={mb}, 5], got {boxes_dev.dtype} "
+                             f"{tuple(boxes_dev.shape)}")
+        from .data import record_words
+        n = boxes_dev.shape[0]
+        rec = torch.empty((n, mb, record_words(self.num_classes)), dtype=torch.int32, device=self.device)
+        cnt = torch.empty((n,), dtype=torch.int32, device=self.device)
+        xywh = torch.empty((n, mb, 4), dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            ext.check(self.lib.y4_loss_assign(self.handle, n, ext.ptr(boxes_dev), mb, ext.ptr(xywh), ext.ptr(rec), ext.ptr(cnt),
+                                              ext.stream_ptr()))
+        return rec, cnt, xywh
+
+    def upload_records(self, records, true_xywh):
+        """Host records (a list of per-image int32 arrays, data.records_from_dense / records_from_boxes) and the
+        [n, max_boxes, 4] xywh array -> the device triple `loss_device` takes."""
+        from .data import pad_records
+        torch = self.torch
+        mb = self._loss_max_boxes()
+        xywh = np.ascontiguousarray(true_xywh, dtype=np.float32)
+        if xywh.ndim != 3 or xywh.shape != (len(records), mb, 4):
+            raise ValueError(f"true boxes must be [{len(records)}, max_boxes={mb}, 4], got {xywh.shape}")
+        rec, cnt = pad_records(records, mb, self.num_classes)
+        return (torch.from_numpy(rec).to(self.device), torch.from_numpy(cnt).to(self.device),
+                torch.from_numpy(xywh).to(self.device))
+
+    def loss_device(self, n, boxes_dev=None, records=None, iou_loss_thresh=None):
+        """The loss terms of the heads in the workspace (forward_device / set_heads): float32 cuda tensor [n, 3 scales, 3]
+        = per image and scale the box, confidence and class sums (y4_loss).  Labels: `boxes_dev` [n, max_boxes, 5] (assigned
+        on the device), or `records` = the (records, counts, xywh) triple of `assign_device` / `upload_records`."""
+        torch = self.torch
+        if (boxes_dev is None) == (records is None):
+            raise ValueError("loss_device: give boxes_dev or records")
+        rec, cnt, xywh = self.assign_device(boxes_dev) if records is None else records
+        if rec.shape[0] != n or cnt.shape[0] != n or xywh.shape[0] != n:
+            raise ValueError(f"labels are for {rec.shape[0]} images, the batch has {n}")
+        thr = float(self.config.get("iou_loss_thresh", 0.5) if iou_loss_thresh is None else iou_loss_thresh)
+        fl = C.c_size_t()
+        ext.check(self.lib.y4_loss_scratch_floats(self.handle, n, C.byref(fl)))
+        scratch = torch.empty((fl.value,), dtype=torch.float32, device=self.device)
+        out = torch.empty((n, 3, 3), dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            ext.check(self.lib.y4_loss(self.handle, n, ext.ptr(rec), ext.ptr(cnt), ext.ptr(xywh), self._loss_max_boxes(), thr,
+                                       ext.ptr(scratch), fl.value, ext.ptr(out), ext.stream_ptr()))
+        return out
+
+    def _check_boxes(self, boxes):
+        """Host-side refusal of what the reference fails on (a centre off the grid, a class id without a class) before upload."""
+        mb = self._loss_max_boxes()
+        b = np.ascontiguousarray(boxes, dtype=np.float32)
+        if b.ndim != 3 or b.shape[1:] != (mb, 5):
+            raise ValueError(f"boxes must be [n, max_boxes={mb}, 5], got {b.shape}")
+        H, W = self.img_hw
+        used = np.arange(mb)[None, :] < (b[..., 2] - b[..., 0] > 0).sum(axis=1)[:, None]     # rows 0 .. (valid rows - 1)
+        norm = np.empty(b.shape[:2] + (2,), dtype=np.float32)
+        norm[...] = ((b[..., 0:2] + b[..., 2:4]) // 2) / np.array([W, H], dtype=np.int32)
+        off = used & ~((norm >= 0) & (norm < 1)).all(axis=-1)
+        cls = b[..., 4].astype(np.int32)
+        bad_cls = used & ~((cls >= 0) & (cls < self.num_classes))
+        if off.any():
+            i, k = np.argwhere(off)[0]
+            raise ValueError(f"image {i} box {k}: centre is outside the {H} x {W} input")
+        if bad_cls.any():
+            i, k = np.argwhere(bad_cls)[0]
+            raise ValueError(f"image {i} box {k}: class id {cls[i, k]} outside [0, {self.num_classes})")
+        return b
+
+    def loss(self, imgs, boxes=None, records=None, true_xywh=None, iou_loss_thresh=None):
+        """Forward + label assignment + loss, chunked by max_batch like `predict`: float32 numpy [N, 3, 3] per image and scale
+        (box, confidence, class sums; `combine_loss` weighs them).  Labels: `boxes` [N, max_boxes, 5], assigned on the device,
+        or host `records` (one int32 array per image) with `true_xywh` [N, max_boxes, 4]."""
+        torch = self.torch
+        if (boxes is None) == (records is None):
+            raise ValueError("loss: give boxes or records")
+        if boxes is not None:
+            boxes_dev = torch.from_numpy(self._check_boxes(boxes)).to(self.device)
+            count = boxes_dev.shape[0]
+        else:
+            triple = self.upload_records(records, true_xywh)
+            count = len(records)
+        parts, i0 = [], 0
+        for chunk in self._chunks(imgs):
+            n = chunk.shape[0]
+            if i0 + n > count:
+                raise ValueError(f"labels for {count} images, the images are more")
+            self.forward_device(chunk)
+            if boxes is not None:
+                out = self.loss_device(n, boxes_dev=boxes_dev[i0:i0 + n], iou_loss_thresh=iou_loss_thresh)
+            else:
+                out = self.loss_device(n, records=tuple(t[i0:i0 + n] for t in triple), iou_loss_thresh=iou_loss_thresh)
+            parts.append(out.cpu().numpy())
+            i0 += n
+        if i0 != count:
+            raise ValueError(f"labels for {count} images, but {i0} images")
+        return np.concatenate(parts, axis=0)
+
     def predict_stream(self, batches, with_indices=False, in_flight=None, letterbox=False, pad_value=128):
         """Pipelined `inference_model.predict` over an iterable of uint8 batches ([n,h,w,3] numpy arrays or pinned torch
         tensors, n <= max_batch, any h,w): yields one result list per batch, in order.  A pinned tensor is uploaded from where
@@ -920,6 +1027,16 @@ class Engine:
                                           ext.stream_ptr()))
         raw = names.raw
         return [(raw[16 * i:16 * i + 16].split(b"\0")[0].decode(), float(ms[i])) for i in range(nops.value)]
+
+
+LOSS_WEIGHTS = (3.54, 64.3, 1.0)      # reference loss.py:136-138: box (GIoU), confidence, class
+
+
+def combine_loss(parts):
+    """[N, 3 scales, 3 terms] -> (loss, box, conf, class) per image, float64 [N] each, weighted as the reference does
+    (loss.py:136-140); the reference's scalar is `loss.mean()`."""
+    terms = np.asarray(parts, dtype=np.float64).sum(axis=1) * np.array(LOSS_WEIGHTS)
+    return terms.sum(axis=1), terms[:, 0], terms[:, 1], terms[:, 2]
 
 
 class InFlight:

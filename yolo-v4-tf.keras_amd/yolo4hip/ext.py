@@ -79,6 +79,9 @@ SYMBOLS = {
     "y4_get_conv_output": (_I, [_VP, _I, _I, _VP, C.c_size_t, _VP]),
     "y4_decode_nms": (_I, [_VP, _I, _F, _F, _VP, _VP, _VP, _VP, _VP, _VP]),
     "y4_decode_nms_mapped": (_I, [_VP, _I, _F, _F, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "y4_loss_assign": (_I, [_VP, _I, _VP, _I, _VP, _VP, _VP, _VP]),
+    "y4_loss_scratch_floats": (_I, [_VP, _I, C.POINTER(C.c_size_t)]),
+    "y4_loss": (_I, [_VP, _I, _VP, _VP, _VP, _I, _F, _VP, C.c_size_t, _VP, _VP]),
     "y4_predict": (_I, [_VP, _VP, _I, _VP, _VP, _VP, _VP, _VP, _VP]),
     "y4_predict_u8": (_I, [_VP, _VP, _I, _VP, _VP, _VP, _VP, _VP, _VP]),
     "y4_profile": (_I, [_VP, _VP, _I, _VP, _VP, _I, C.POINTER(_I), _VP]),
