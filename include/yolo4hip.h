@@ -158,7 +158,7 @@ int y4_decode_nms_mapped(y4_handle h, int n, float iou_threshold, float score_th
                          float* boxes_dev, float* scores_dev, float* classes_dev, int32_t* valid_dev, int32_t* kept_idx_dev,
                          void* stream);
 /* ---- Validation loss: the forward of the reference's yolo_loss (loss.py:119-212; training_model, models.py:54-65) over the raw
- * heads y4_forward / y4_set_heads left in the workspace.  Forward only: nothing here computes a gradient.
+ * heads y4_forward / y4_set_heads left in the workspace.  (Its gradient: "Head fine-tuning" below.)
  *
  * A responsible-cell RECORD is words = 8 + ceil(num_classes / 32) int32 values
  *     [scale, row, col, anchor, bits(x), bits(y), bits(w), bits(h), class mask word 0, ...]
@@ -183,6 +183,56 @@ int y4_loss_scratch_floats(y4_handle h, int n, size_t* floats);
  * outside the grids are ignored. */
 int y4_loss(y4_handle h, int n, const int32_t* records_dev, const int32_t* counts_dev, const float* xywh_dev, int max_boxes,
             float iou_loss_thresh, float* scratch_dev, size_t scratch_floats, float* out_dev, void* stream);
+
+/* ---- Head fine-tuning: the three detection convs (93 / 101 / 109; reference custom_layers.py yolov4_neck, the three
+ * conv(..., activation=None, batch_norm=False) calls) trained on a frozen backbone and neck -- in Keras terms every layer
+ * trainable = False except those three, then Model.fit on training_model (reference models.py:54-65,79-84,100-107).  No other
+ * layer has a gradient here.
+ *
+ * The objective is  sum_i img_weight[i] * (3.54 box_i + 64.3 conf_i + 1 class_i)  (loss.py:131-135; img_weight = 1 / N gives
+ * the batch mean of loss.py:184-186).  Its derivative w.r.t. a raw head value is what TensorFlow's autodiff of loss.py gives:
+ * through decode without xyscale (loss.py:206-207), through GIoU w.r.t. all four predicted values including the enclosing box and
+ * divide_no_nan (loss.py:34-60), through BOTH factors of the confidence term (conf_focal is not a constant, loss.py:176-182),
+ * sigmoid(x) - z for the class logits of responsible lanes (loss.py:165), and none through the ignore mask (a cast of a
+ * comparison, loss.py:173).  At a tie of a maximum / minimum inside GIoU autodiff's choice is unspecified; here the strict
+ * comparison decides.  Records that point outside the grids are ignored, as in y4_loss.  Same determinism rule as y4_loss: no
+ * floating-point atomics, every sum in an order fixed by the geometry, the same call gives the same bits.
+ *
+ * The head convs' weights, their gradient, the float32 master copy and the Adam moments all use ONE layout: the three layers'
+ * records one after the other (conv 93, 101, 109), each as it lies in the Darknet stream at y4_layer_info(...).weight_offset:
+ * [cout biases][cout * cin weights in (out, in) order], cout = 3 * (5 + num_classes). */
+
+/* BEFORE y4_workspace_bytes / y4_bind_workspace, default off: the outputs of convs 92 / 100 / 108 (the head convs' inputs) are
+ * written to the workspace and live to the end of the forward also under workspace aliasing; with chain fusion on, the LDS pair
+ * conv 92 -> conv 93 -- which otherwise keeps conv 92's output on chip -- stores it as well.  Results are unchanged; off leaves
+ * y4_workspace_bytes, y4_launch_counts and every result exactly as they are. */
+int y4_set_retain_head_inputs(y4_handle h, int on);
+/* Parity / debugging entry, dense on purpose: the derivative above for the heads in the workspace, as three float32 tensors
+ * [n, gh, gw, 3 * (5 + C)] (the layout of y4_get_heads).  Labels as y4_loss; img_weight_dev [n] float32. */
+int y4_loss_grad(y4_handle h, int n, const int32_t* records_dev, const int32_t* counts_dev, const float* xywh_dev, int max_boxes,
+                 float iou_loss_thresh, const float* img_weight_dev, float* out_s_dev, float* out_m_dev, float* out_l_dev,
+                 void* stream);
+/* floats of scratch y4_head_grad needs for n images */
+int y4_head_grad_scratch_floats(y4_handle h, int n, size_t* floats);
+/* The training path: the loss gradient fused with the weight gradient of the head convs, for the n images of the last y4_forward
+ * (their raw heads AND the head convs' inputs are read from the workspace: Y4_ESTATE unless y4_set_retain_head_inputs is on).
+ * dw_dev (layout above, dw_floats >= the three records) is written, or with accumulate != 0 added to:
+ *     dW[o, c] = sum over images and cells of g[p, o] * X[p, c],   db[o] = sum g[p, o]
+ * with g the derivative above, recomputed in registers and never stored: the three confidence rows of each layer in one pass
+ * over X in strips of 64 cells, every other row from the at most max_boxes records per image.  X is converted up to float32
+ * exactly; products and sums are float32 (fused multiply-add). */
+int y4_head_grad(y4_handle h, int n, const int32_t* records_dev, const int32_t* counts_dev, const float* xywh_dev, int max_boxes,
+                 float iou_loss_thresh, const float* img_weight_dev, float* scratch_dev, size_t scratch_floats, float* dw_dev,
+                 size_t dw_floats, int accumulate, void* stream);
+/* One step of Keras' Adam as the reference compiles it (models.py:83: Adam(learning_rate=1e-4), beta 0.9 / 0.999, epsilon 1e-7)
+ * on the three records, t = 1, 2, ...:
+ *     lr_t = lr * sqrt(1 - beta2^t) / (1 - beta1^t),  m = beta1 m + (1 - beta1) g,  v = beta2 v + (1 - beta2) g^2,
+ *     w -= lr_t * m / (sqrt(v) + epsilon)
+ * on the caller's float32 master weights w_dev and moments m_dev, v_dev (n_floats = the three records exactly), followed by the
+ * re-pack: the new weights go into the bound packed-weight workspace in the handle's dtype and canonical K order and the biases
+ * into the layers' shift, by the kernels of y4_pack_weights -- a handle that loads the updated stream afresh holds the same bytes. */
+int y4_head_adam(y4_handle h, const float* dw_dev, float* w_dev, float* m_dev, float* v_dev, size_t n_floats, float lr,
+                 float beta1, float beta2, float epsilon, int t, void* stream);
 
 /* Replaces inference_model.predict(imgs) (reference models.py:69-73,113,159) = forward + decode + NMS. */
 int y4_predict(y4_handle h, const float* imgs_nhwc_dev, int n, float* boxes_dev, float* scores_dev,

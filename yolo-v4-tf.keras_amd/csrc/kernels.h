@@ -153,4 +153,33 @@ int loss_strips(const int* gh, const int* gw, int* strip_base);
 int loss_assign_launch(const LossAssignK& k, int n, hipStream_t stream);
 int loss_launch(const LossK& k, int n, hipStream_t stream);
 
+// head_train.hip: the gradient of yolo_loss w.r.t. the raw heads, the weight gradient of the three head convs, Adam
+struct GradK {
+    const float* head[3];
+    int gh[3], gw[3], strip_base[3], strips;   // 256-lane strips as LossK (the dense gradient)
+    float stride[3], anchors[18];
+    int C, hcs, mb, rw;
+    float thresh, input_area;
+    const int32_t* records;          // [n, mb, rw]
+    const int32_t* counts;           // [n]
+    const float* xywh;               // [n, mb, 4]
+    const float* imgw;               // [n] weight of each image's loss (1 / N: the batch mean)
+    float* dense[3];                 // y4_loss_grad: [n, gh, gw, 3 (5 + C)] per scale
+    // y4_head_grad
+    const void* x[3];                // the head convs' inputs, dense NHWC [n, gh, gw, cin] in the handle's dtype
+    int cin[3];
+    int pstrip_base[3], pstrips[3];  // 64-cell strips of one image: the first one of a scale, their number per scale
+    size_t part_base[3];             // float offset of a scale's strip partials [n, pstrips, 3 cin + 4] in `partials`
+    float* partials;
+    float* dw;                       // the three records [cout biases][cout x cin], conv 93 / 101 / 109 at dw_off
+    size_t dw_off[3];
+    int accumulate;
+};
+int head_grad_strips(const int* gh, const int* gw, int* pstrip_base, int* pstrips);
+size_t head_grad_scratch_floats(const int* gh, const int* gw, const int* cin, int n, size_t* part_base);
+int loss_grad_launch(const GradK& k, int n, hipStream_t stream);
+int head_grad_launch(int dtype, const GradK& k, int n, hipStream_t stream);
+int head_adam_launch(const float* g, float* w, float* m, float* v, size_t count, float lr_t, float b1, float b2, float eps,
+                     hipStream_t stream);
+
 }  // namespace y4

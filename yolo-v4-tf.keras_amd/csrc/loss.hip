@@ -6,26 +6,11 @@
 // strip order.  The tree depends on the image's geometry only, so image i's nine sums are the same bits whatever the batch
 // size and wherever the image sits in the batch.
 #include "kernels.h"
+#include "loss_common.h"
 
 namespace y4 {
 
 namespace {
-
-constexpr int LOSS_THREADS = 256;
-
-// Compacts the rows with w > 0 of one image's [mb] rows into LDS order (row order kept): -> position of this thread's row, or
-// -1; *total is the number of such rows.  One row per thread (mb <= LOSS_THREADS), called by every thread of the workgroup.
-__device__ inline int compact_valid(bool valid, int* s_wave, int* total) {
-    const int tid = threadIdx.x, wave = tid >> 6;
-    const unsigned long long bal = __ballot(valid);
-    if ((tid & 63) == 0) s_wave[wave] = __popcll(bal);
-    __syncthreads();
-    int base = 0;
-    for (int w = 0; w < wave; ++w) base += s_wave[w];
-    *total = s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
-    const unsigned long long below = bal & ((1ull << (tid & 63)) - 1ull);
-    return valid ? base + __popcll(below) : -1;
-}
 
 // One workgroup per image, one thread per box row.
 __global__ __launch_bounds__(LOSS_THREADS) void loss_assign_kernel(LossAssignK p) {
@@ -113,10 +98,6 @@ __global__ __launch_bounds__(LOSS_THREADS) void loss_assign_kernel(LossAssignK p
     for (int i = count * p.rw + tid; i < p.mb * p.rw; i += LOSS_THREADS) recs[i] = 0;
     if (tid == 0) p.counts[img] = any_bad ? -1 : count;
 }
-
-__device__ inline float sigmoidf(float x) { return 1.0f / (1.0f + expf(-x)); }
-// tf.nn.sigmoid_cross_entropy_with_logits, the stable form
-__device__ inline float bce_logits(float x, float z) { return fmaxf(x, 0.0f) - x * z + log1pf(expf(-fabsf(x))); }
 
 // grid (strips of one image, images); a strip is LOSS_THREADS consecutive (cell, anchor) lanes of ONE scale
 __global__ __launch_bounds__(LOSS_THREADS) void loss_kernel(LossK p) {

@@ -162,6 +162,9 @@ struct y4_ctx {
     // activation buffers share memory when their lifetimes do not overlap (y4_set_workspace_aliasing): a quarter of the
     // workspace, a hotter working set for the Infinity Cache; intermediate tensors are then not retained after a forward
     bool alias_bufs = false;
+    // y4_set_retain_head_inputs: the outputs of convs 92 / 100 / 108 -- the head convs' inputs -- are written to HBM (also where an
+    // LDS pair would keep them on chip) and live to the end of the forward: y4_head_grad reads them
+    bool retain_head_in = false;
 };
 
 namespace {
@@ -496,6 +499,9 @@ static void buffer_lifetimes(const y4_ctx& c, std::vector<int>& first, std::vect
         if (o.conv2 >= 0) touch(o.out2, i);
     }
     for (int k = 0; k < 3; ++k) last[c.heads[k].buf] = nops;          // the raw heads outlive the forward
+    if (c.retain_head_in)
+        for (const Op& o : c.ops)
+            if (o.out_f32) last[o.in.buf] = nops;                         // ... and so do their convs' inputs
 }
 
 void layout(y4_ctx& c) {
@@ -1187,6 +1193,128 @@ int y4_loss(y4_handle h, int n, const int32_t* records, const int32_t* counts, c
     k.input_area = (float)h->H * (float)h->W;          // input_size ** 2 of the reference (loss.py:158); H * W for a rectangle
     k.records = records; k.counts = counts; k.xywh = xywh; k.partials = scratch; k.out = out;
     return loss_launch(k, n, (hipStream_t)stream);
+}
+
+// ---- head fine-tuning (head_train.hip)
+
+int y4_set_retain_head_inputs(y4_handle h, int on) {
+    if (int r = check_handle(h)) return r;
+    Y4_REQUIRE(!h->act, Y4_ESTATE, "y4_set_retain_head_inputs: the workspace is already bound (call it before y4_workspace_bytes / y4_bind_workspace)");
+    h->retain_head_in = on != 0;
+    // an LDS pair whose tail is a head conv keeps the head's input in LDS: with retention it is stored as well
+    for (Chain& ch : h->chains)
+        if (ch.lds_pair && h->ops[ch.tail[0]].out_f32)
+            ch.store_x = h->retain_head_in || read_outside(*h, h->ops[ch.head].out.buf, ch.tail[0], ch.tail[0]);
+    layout(*h);
+    return Y4_OK;
+}
+
+// what the three gradient entry points share: the loss geometry and labels; -> Y4_OK
+static int grad_common(y4_handle h, GradK& k, const int32_t* records, const int32_t* counts, const float* xywh, int max_boxes,
+                       float iou_loss_thresh, const float* img_weight) {
+    loss_geometry(h, k.gh, k.gw, nullptr);
+    k.strips = loss_strips(k.gh, k.gw, k.strip_base);
+    for (int i = 0; i < 3; ++i) {
+        k.head[i] = (const float*)buf_ptr(h, h->heads[i]);
+        k.stride[i] = (float)h->cfg.strides[i];
+    }
+    memcpy(k.anchors, h->cfg.anchors, sizeof(k.anchors));
+    k.C = h->cfg.num_classes; k.hcs = h->hcs; k.mb = max_boxes; k.rw = 8 + (k.C + 31) / 32;
+    k.thresh = iou_loss_thresh;
+    k.input_area = (float)h->H * (float)h->W;
+    k.records = records; k.counts = counts; k.xywh = xywh; k.imgw = img_weight;
+    return Y4_OK;
+}
+
+// the op of head conv `i` (93 / 101 / 109)
+static const Op* head_op(y4_handle h, int i) {
+    for (const Op& o : h->ops)
+        if (o.out_f32 && o.out.buf == h->heads[i].buf) return &o;
+    return nullptr;
+}
+
+// float offsets of the three head records in the dw / master buffers and their total
+static size_t head_record_offsets(y4_handle h, size_t* off) {
+    size_t total = 0;
+    for (int i = 0; i < 3; ++i) {
+        const Layer& L = h->layers[head_op(h, i)->conv];
+        if (off) off[i] = total;
+        total += (size_t)L.d.cout * (1 + (size_t)L.d.cin);
+    }
+    return total;
+}
+
+int y4_loss_grad(y4_handle h, int n, const int32_t* records, const int32_t* counts, const float* xywh, int max_boxes,
+                 float iou_loss_thresh, const float* img_weight, float* out_s, float* out_m, float* out_l, void* stream) {
+    if (int r = check_ready(h, n)) return r;
+    Y4_REQUIRE(records && counts && xywh && img_weight && out_s && out_m && out_l, Y4_EINVAL, "y4_loss_grad: null argument");
+    Y4_REQUIRE(iou_loss_thresh >= 0.f, Y4_EINVAL, "y4_loss_grad: iou_loss_thresh %g", (double)iou_loss_thresh);
+    GradK k{};
+    grad_common(h, k, records, counts, xywh, max_boxes, iou_loss_thresh, img_weight);
+    k.dense[0] = out_s; k.dense[1] = out_m; k.dense[2] = out_l;
+    return loss_grad_launch(k, n, (hipStream_t)stream);
+}
+
+static void head_grad_geometry(y4_handle h, GradK& k) {
+    loss_geometry(h, k.gh, k.gw, nullptr);
+    for (int i = 0; i < 3; ++i) k.cin[i] = h->layers[head_op(h, i)->conv].d.cin;
+    head_grad_strips(k.gh, k.gw, k.pstrip_base, k.pstrips);
+}
+
+int y4_head_grad_scratch_floats(y4_handle h, int n, size_t* floats) {
+    if (int r = check_handle(h)) return r;
+    Y4_REQUIRE(n >= 1 && floats, Y4_EINVAL, "y4_head_grad_scratch_floats: bad argument");
+    GradK k{};
+    head_grad_geometry(h, k);
+    *floats = head_grad_scratch_floats(k.gh, k.gw, k.cin, n, nullptr);
+    return Y4_OK;
+}
+
+int y4_head_grad(y4_handle h, int n, const int32_t* records, const int32_t* counts, const float* xywh, int max_boxes,
+                 float iou_loss_thresh, const float* img_weight, float* scratch, size_t scratch_floats, float* dw, size_t dw_floats,
+                 int accumulate, void* stream) {
+    if (int r = check_ready(h, n)) return r;
+    Y4_REQUIRE(h->retain_head_in, Y4_ESTATE, "y4_head_grad: the head convs' inputs are not retained (y4_set_retain_head_inputs before "
+               "the workspace is bound)");
+    Y4_REQUIRE(records && counts && xywh && img_weight && scratch && dw, Y4_EINVAL, "y4_head_grad: null argument");
+    Y4_REQUIRE(iou_loss_thresh >= 0.f, Y4_EINVAL, "y4_head_grad: iou_loss_thresh %g", (double)iou_loss_thresh);
+    GradK k{};
+    grad_common(h, k, records, counts, xywh, max_boxes, iou_loss_thresh, img_weight);
+    head_grad_geometry(h, k);
+    const size_t need = head_grad_scratch_floats(k.gh, k.gw, k.cin, n, k.part_base);
+    Y4_REQUIRE(scratch_floats >= need, Y4_ENOMEM, "y4_head_grad: scratch %zu < %zu floats", scratch_floats, need);
+    const size_t total = head_record_offsets(h, k.dw_off);
+    Y4_REQUIRE(dw_floats >= total, Y4_ENOMEM, "y4_head_grad: dw %zu < %zu floats", dw_floats, total);
+    for (int i = 0; i < 3; ++i) {
+        const View& v = head_op(h, i)->in;
+        Y4_REQUIRE(v.coff == 0 && v.cstride == v.c, Y4_EINVAL, "y4_head_grad: head %d reads a channel slice", i);
+        k.x[i] = buf_ptr(h, v);
+    }
+    k.partials = scratch; k.dw = dw; k.accumulate = accumulate != 0;
+    return head_grad_launch(h->cfg.dtype, k, n, (hipStream_t)stream);
+}
+
+int y4_head_adam(y4_handle h, const float* dw, float* w, float* m, float* v, size_t n_floats, float lr, float beta1, float beta2,
+                 float epsilon, int t, void* stream) {
+    if (int r = check_handle(h)) return r;
+    Y4_REQUIRE(h->act && h->wts && h->weights_ready, Y4_ESTATE, "y4_head_adam: weights not packed (call y4_pack_weights first)");
+    Y4_REQUIRE(dw && w && m && v, Y4_EINVAL, "y4_head_adam: null argument");
+    Y4_REQUIRE(t >= 1, Y4_EINVAL, "y4_head_adam: step %d (the first step is 1)", t);
+    size_t off[3];
+    const size_t total = head_record_offsets(h, off);
+    Y4_REQUIRE(n_floats == total, Y4_EINVAL, "y4_head_adam: %zu floats, the three head records have %zu", n_floats, total);
+    hipStream_t s = (hipStream_t)stream;
+    const float lr_t = (float)((double)lr * sqrt(1.0 - pow((double)beta2, (double)t)) / (1.0 - pow((double)beta1, (double)t)));
+    if (int r = head_adam_launch(dw, w, m, v, total, lr_t, beta1, beta2, epsilon, s)) return r;
+    // the re-pack: what y4_pack_weights does with these three records (same kernels, same rounding)
+    for (int i = 0; i < 3; ++i) {
+        const Layer& L = h->layers[head_op(h, i)->conv];
+        const float* rec = w + off[i];
+        if (int r = fold_bn_launch(rec, (float*)(h->wts + L.scale_off), (float*)(h->wts + L.shift_off), L.d.cout, L.cout_pad, 0, s))
+            return r;
+        if (int r = pack_conv_weights(h->cfg.dtype, L.d.cout, L.d.cin, 1, rec + L.d.cout, h->wts + L.w_off, s)) return r;
+    }
+    return Y4_OK;
 }
 
 // forward + decode + NMS; when `ev` is given, ev[0] is recorded before the first op and ev[i+1] after op i

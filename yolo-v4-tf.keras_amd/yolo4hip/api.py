@@ -13,7 +13,8 @@ instead of the reference's stretch (Darknet's letter_box=1 geometry) with boxes 
 self-describing checkpoint of this framework (Keras' SavedModel / H5 needs TensorFlow); `eval_map` (models.py:182-507)
 is the VOC mAP tool over the exported text files (yolo4hip/evalmap.py).  `training_model.predict([X, y_s, y_m, y_l, true_xywh])`
 is the reference's yolo_loss FORWARD (models.py:54-65, loss.py) on the device and `evaluate(data_gen)` the validation loss over
-a `DataGenerator`; training itself (`fit`) is out of scope and raises.
+a `DataGenerator`; `fit(..., trainable='heads')` fine-tunes the three detection convs on a frozen backbone and neck, while
+training every layer (the reference's `fit`) is out of scope and raises.
 """
 import json
 import os
@@ -181,9 +182,88 @@ class Yolov4(object):
             self._tuned_first(lambda x: self.engine.predict(x, iou_threshold=0.413, score_threshold=0.3)), 'inference_model')
         self._thresholds = (0.413, 0.3)
 
-    # ---- out of scope (training).  The loss FORWARD is there (training_model.predict, evaluate): no gradients.
-    def fit(self, *a, **k):
-        raise NotImplementedError('training is out of scope of the MI355X inference path')
+    # ---- reference models.py:100-107.  Training all 110 convs is out of scope; what is here is the
+    # fine-tuning of the three detection convs on a frozen backbone and neck: in Keras terms every layer trainable = False
+    # except conv 93 / 101 / 109.
+    def fit(self, train_data_gen, epochs, val_data_gen=None, initial_epoch=0, callbacks=None, *, trainable=None,
+            learning_rate=1e-4):
+        """trainable='heads': Adam (the reference's compile, models.py:83; `learning_rate` replaces its 1e-4) on the weights and
+        biases of the three detection convs.  Per batch: `train_data_gen.boxes(i)` -> one upload -> forward in chunks of
+        max_batch -> labels assigned on the device -> y4_head_grad accumulated over the chunks (each image weighs 1 / batch
+        images) -> y4_head_adam; the batch's training loss is y4_loss on the same heads.  Per epoch a Keras-like line,
+        `train_data_gen.on_epoch_end()` and every callback's `on_epoch_end(epoch, logs)`.  -> an object whose `.history` is
+        {'loss': [...], 'val_loss': [...]} (val_loss only with `val_data_gen`).  A batch with a box off the grid or an unknown
+        class raises ValueError before any update.  trainable=None (the reference's meaning: every layer) is not implemented."""
+        if trainable != 'heads':
+            raise NotImplementedError("training every layer is out of scope of the MI355X path; fit(..., trainable='heads') "
+                                      "fine-tunes the three detection convs on a frozen backbone and neck")
+        from .engine import combine_loss
+        self._ensure_tuned()
+        if getattr(train_data_gen, 'max_boxes', self.max_boxes) != self.max_boxes:
+            raise ValueError(f"the generator's max_boxes {train_data_gen.max_boxes} != config['max_boxes'] {self.max_boxes}")
+        eng = self._train_engine()
+        torch = eng.torch
+        state = eng.head_state(self._flat)
+        dw = torch.empty((eng.head_floats(),), dtype=torch.float32, device=eng.device)
+        history = {'loss': []}
+        if val_data_gen is not None:
+            history['val_loss'] = []
+        for epoch in range(int(initial_epoch), int(epochs)):
+            total, images = 0.0, 0
+            for i in range(len(train_data_gen)):
+                X, boxes = train_data_gen.boxes(i)
+                boxes_dev = torch.from_numpy(eng._check_boxes(boxes)).to(eng.device)     # ValueError before any update
+                count = boxes_dev.shape[0]
+                weight = torch.full((count,), 1.0 / count, dtype=torch.float32, device=eng.device)
+                parts, i0 = [], 0
+                for chunk in eng._chunks(X):
+                    n = chunk.shape[0]
+                    if i0 + n > count:
+                        raise ValueError(f'labels for {count} images, the images are more')
+                    eng.forward_device(chunk)
+                    labels = eng.assign_device(boxes_dev[i0:i0 + n])
+                    eng.head_grad_device(n, records=labels, iou_loss_thresh=self.iou_loss_thresh, img_weight=weight[i0:i0 + n],
+                                         dw=dw, accumulate=i0 > 0)
+                    parts.append(eng.loss_device(n, records=labels, iou_loss_thresh=self.iou_loss_thresh))
+                    i0 += n
+                if i0 != count:
+                    raise ValueError(f'labels for {count} images, but {i0} images')
+                eng.head_adam_step(state, dw, lr=learning_rate)
+                total += float(combine_loss(torch.cat(parts).cpu().numpy())[0].sum())
+                images += count
+            if images == 0:
+                raise ValueError('fit: the generator is empty')
+            # the trained heads reach the host stream and the inference engine at the end of every epoch
+            eng.head_weights_to_flat(state, self._flat)
+            self.engine.load_weight_blob(self._flat)
+            logs = {'loss': total / images}
+            if val_data_gen is not None:
+                logs['val_loss'] = self.evaluate(val_data_gen)['loss']
+            for k, v in logs.items():
+                history[k].append(v)
+            print(f'Epoch {epoch + 1}/{int(epochs)} - ' + ' - '.join(f'{k}: {v:.4f}' for k, v in logs.items()))
+            if hasattr(train_data_gen, 'on_epoch_end'):
+                train_data_gen.on_epoch_end()
+            for cb in callbacks or []:
+                if hasattr(cb, 'on_epoch_end'):
+                    cb.on_epoch_end(epoch, logs)
+
+        class History:
+            pass
+        out = History()
+        out.history, out.epoch = history, list(range(int(initial_epoch), int(epochs)))
+        return out
+
+    def _train_engine(self):
+        """The engine `fit` runs on: created on the first `fit`, with the head convs' inputs retained (the inference engine keeps
+        its size for users who never train), the inference engine's schedule, and the current weights."""
+        eng = getattr(self, '_fit_engine', None)
+        if eng is None:
+            eng = self._fit_engine = Engine(self.num_classes, self.config, max_batch=self._max_batch, dtype=self._dtype,
+                                            device=self._device, alias_workspace=True, retain_head_inputs=True)
+        eng.load_weight_blob(self._flat)
+        self.engine.copy_schedule_to(eng)
+        return eng
 
     # ---- reference models.py:57-65: training_model's inputs [X, y_s, y_m, y_l, true_xywh] -> the yolo_loss Lambda's scalar
     def _loss_of_dense(self, inputs):

@@ -42,7 +42,8 @@ def _cfg_struct(config, num_classes, max_batch, dtype):
 
 
 class Engine:
-    def __init__(self, num_classes, config=None, max_batch=32, dtype="f32", device=None, alias_workspace=False):
+    def __init__(self, num_classes, config=None, max_batch=32, dtype="f32", device=None, alias_workspace=False,
+                 retain_head_inputs=False):
         import torch
         self.torch = torch
         self.lib = ext.load()
@@ -69,6 +70,11 @@ class Engine:
         self.alias_workspace = bool(alias_workspace)
         if self.alias_workspace:
             ext.check(self.lib.y4_set_workspace_aliasing(self.handle, 1))
+        # retain_head_inputs: the head convs' inputs stay in the workspace after a forward (y4_set_retain_head_inputs), which
+        # `head_grad_device` needs
+        self.retain_head_inputs = bool(retain_head_inputs)
+        if self.retain_head_inputs:
+            ext.check(self.lib.y4_set_retain_head_inputs(self.handle, 1))
         a, w = C.c_size_t(), C.c_size_t()
         ext.check(self.lib.y4_workspace_bytes(self.handle, C.byref(a), C.byref(w)))
         self.act_bytes, self.wts_bytes = a.value, w.value
@@ -482,7 +488,7 @@ class Engine:
         res = [np.concatenate(p, axis=0) for p in acc]
         return res if with_indices else res[:4]
 
-    # ---------------------------------------------------------------- validation loss (forward only)
+    # ---------------------------------------------------------------- validation loss
     def _loss_max_boxes(self):
         return int(self.config.get("max_boxes", 100))
 
@@ -588,6 +594,101 @@ class Engine:
         if i0 != count:
             raise ValueError(f"labels for {count} images, but {i0} images")
         return np.concatenate(parts, axis=0)
+
+    # ---------------------------------------------------------------- head fine-tuning (csrc/head_train.hip)
+    HEAD_CONVS = (93, 101, 109)
+
+    def head_records(self):
+        """[(float offset in the Darknet stream, floats)] of the records of convs 93 / 101 / 109: cout biases, then cout x cin
+        weights.  The gradient, master-weight and moment buffers hold these three records back to back."""
+        lt = self.layer_table()
+        return [(int(lt[i]["weight_offset"]), int(lt[i]["cout"] * (1 + lt[i]["cin"]))) for i in self.HEAD_CONVS]
+
+    def head_floats(self):
+        return sum(n for _, n in self.head_records())
+
+    def _labels(self, n, boxes_dev, records):
+        if (boxes_dev is None) == (records is None):
+            raise ValueError("give boxes_dev or records")
+        rec, cnt, xywh = self.assign_device(boxes_dev) if records is None else records
+        if rec.shape[0] != n or cnt.shape[0] != n or xywh.shape[0] != n:
+            raise ValueError(f"labels are for {rec.shape[0]} images, the batch has {n}")
+        return rec, cnt, xywh
+
+    def _img_weight(self, n, img_weight):
+        torch = self.torch
+        if img_weight is None:
+            return torch.full((n,), 1.0 / n, dtype=torch.float32, device=self.device)
+        if not isinstance(img_weight, torch.Tensor):
+            img_weight = torch.from_numpy(np.ascontiguousarray(img_weight, dtype=np.float32))
+        w = img_weight.to(self.device, dtype=torch.float32).contiguous()
+        if tuple(w.shape) != (n,):
+            raise ValueError(f"img_weight must have shape ({n},), got {tuple(w.shape)}")
+        return w
+
+    def loss_grad_device(self, n, boxes_dev=None, records=None, iou_loss_thresh=None, img_weight=None):
+        """y4_loss_grad: the DENSE gradient of sum_i img_weight[i] * loss_i (default 1 / n: the batch mean) w.r.t. the raw heads
+        in the workspace: three float32 cuda tensors [n, gh, gw, 3 (5 + C)].  For tests; training never builds these."""
+        torch = self.torch
+        rec, cnt, xywh = self._labels(n, boxes_dev, records)
+        w = self._img_weight(n, img_weight)
+        thr = float(self.config.get("iou_loss_thresh", 0.5) if iou_loss_thresh is None else iou_loss_thresh)
+        outs = [torch.empty((n, gh, gw, self.nout), dtype=torch.float32, device=self.device) for gh, gw in self.grids_hw]
+        with torch.cuda.device(self.device):
+            ext.check(self.lib.y4_loss_grad(self.handle, n, ext.ptr(rec), ext.ptr(cnt), ext.ptr(xywh), self._loss_max_boxes(), thr,
+                                            ext.ptr(w), ext.ptr(outs[0]), ext.ptr(outs[1]), ext.ptr(outs[2]), ext.stream_ptr()))
+        return outs
+
+    def head_grad_device(self, n, boxes_dev=None, records=None, iou_loss_thresh=None, img_weight=None, dw=None, accumulate=False):
+        """y4_head_grad after `forward_device` on n images (an engine with retain_head_inputs): the gradient of
+        sum_i img_weight[i] * loss_i w.r.t. the weights and biases of convs 93 / 101 / 109 -> float32 cuda tensor
+        [head_floats()] (`head_records` gives the layout), written into `dw` or, with accumulate=True, added to it."""
+        torch = self.torch
+        rec, cnt, xywh = self._labels(n, boxes_dev, records)
+        w = self._img_weight(n, img_weight)
+        thr = float(self.config.get("iou_loss_thresh", 0.5) if iou_loss_thresh is None else iou_loss_thresh)
+        total = self.head_floats()
+        if dw is None:
+            if accumulate:
+                raise ValueError("head_grad_device: accumulate needs the dw to add to")
+            dw = torch.empty((total,), dtype=torch.float32, device=self.device)
+        if dw.dtype != torch.float32 or dw.numel() != total or not dw.is_contiguous():
+            raise ValueError(f"dw must be a contiguous float32 tensor of {total} elements")
+        fl = C.c_size_t()
+        ext.check(self.lib.y4_head_grad_scratch_floats(self.handle, n, C.byref(fl)))
+        scratch = torch.empty((fl.value,), dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            ext.check(self.lib.y4_head_grad(self.handle, n, ext.ptr(rec), ext.ptr(cnt), ext.ptr(xywh), self._loss_max_boxes(), thr,
+                                            ext.ptr(w), ext.ptr(scratch), fl.value, ext.ptr(dw), total, 1 if accumulate else 0,
+                                            ext.stream_ptr()))
+        return dw
+
+    def head_state(self, flat):
+        """The optimiser state for `head_adam_step`: float32 master weights (the three head records of the host stream `flat`,
+        uploaded) and zero moments -> {'w', 'm', 'v', 't'}."""
+        torch = self.torch
+        flat = np.asarray(flat, dtype=np.float32)
+        w = np.concatenate([flat[o:o + n] for o, n in self.head_records()])
+        w = torch.from_numpy(np.ascontiguousarray(w)).to(self.device)
+        return {"w": w, "m": torch.zeros_like(w), "v": torch.zeros_like(w), "t": 0}
+
+    def head_adam_step(self, state, dw, lr=1e-4, beta1=0.9, beta2=0.999, epsilon=1e-7):
+        """y4_head_adam: one step of Keras' Adam on the master weights of `state` with the gradient `dw`, and the re-pack: the
+        next forward of this engine runs on the updated head convs."""
+        state["t"] += 1
+        with self.torch.cuda.device(self.device):
+            ext.check(self.lib.y4_head_adam(self.handle, ext.ptr(dw), ext.ptr(state["w"]), ext.ptr(state["m"]), ext.ptr(state["v"]),
+                                            state["w"].numel(), float(lr), float(beta1), float(beta2), float(epsilon),
+                                            int(state["t"]), ext.stream_ptr()))
+
+    def head_weights_to_flat(self, state, flat):
+        """Copy the master weights of `state` back into the host stream `flat` (in place)."""
+        w = state["w"].cpu().numpy()
+        pos = 0
+        for o, n in self.head_records():
+            flat[o:o + n] = w[pos:pos + n]
+            pos += n
+        return flat
 
     def predict_stream(self, batches, with_indices=False, in_flight=None, letterbox=False, pad_value=128):
         """Pipelined `inference_model.predict` over an iterable of uint8 batches ([n,h,w,3] numpy arrays or pinned torch
