@@ -205,7 +205,12 @@ int y4_loss(y4_handle h, int n, const int32_t* records_dev, const int32_t* count
 /* BEFORE y4_workspace_bytes / y4_bind_workspace, default off: the outputs of convs 92 / 100 / 108 (the head convs' inputs) are
  * written to the workspace and live to the end of the forward also under workspace aliasing; with chain fusion on, the LDS pair
  * conv 92 -> conv 93 -- which otherwise keeps conv 92's output on chip -- stores it as well.  Results are unchanged; off leaves
- * y4_workspace_bytes, y4_launch_counts and every result exactly as they are. */
+ * y4_workspace_bytes, y4_launch_counts and every result exactly as they are.
+ * on = 2 (the level y4_block_grad needs) additionally keeps the INPUTS of convs 92 / 100 / 108 -- the outputs of convs 91 / 99 / 107
+ * -- alive to the end of the forward under workspace aliasing; a run that would keep one of them on chip stores it as well (the
+ * launch count does not change; in this network each of them already has a reader outside every fused run, and the call returns
+ * Y4_ESTATE if a plan ever breaks that).  Results are again unchanged; levels 0 and 1 behave exactly as before, and every other
+ * non-zero value still means level 1. */
 int y4_set_retain_head_inputs(y4_handle h, int on);
 /* Parity / debugging entry, dense on purpose: the derivative above for the heads in the workspace, as three float32 tensors
  * [n, gh, gw, 3 * (5 + C)] (the layout of y4_get_heads).  Labels as y4_loss; img_weight_dev [n] float32. */
@@ -233,6 +238,52 @@ int y4_head_grad(y4_handle h, int n, const int32_t* records_dev, const int32_t* 
  * into the layers' shift, by the kernels of y4_pack_weights -- a handle that loads the updated stream afresh holds the same bytes. */
 int y4_head_adam(y4_handle h, const float* dw_dev, float* w_dev, float* m_dev, float* v_dev, size_t n_floats, float lr,
                  float beta1, float beta2, float epsilon, int t, void* stream);
+
+/* ---- Fine-tuning of the 3x3 convs in front of the heads: convs 92 / 100 / 108 (reference custom_layers.py yolov4_neck, the
+ * conv(x, 256 | 512 | 1024, 3) calls that feed the three detection convs; Conv + BatchNormalization + LeakyReLU(0.1)) -- in Keras
+ * terms the KERNELS of these three convs and the weights and biases of convs 93 / 101 / 109 trainable, every other layer
+ * trainable = False, including the three BatchNormalization layers, which run in inference mode (gamma, beta, moving mean and
+ * variance untouched), as Keras runs a frozen BN.  No other layer has a gradient here.
+ *
+ * Per scale, with U the conv's input (the output of conv 91 / 99 / 107), A its output (the head conv's input),
+ * s[c] = gamma[c] / sqrt(var[c] + 1e-3) (the scale y4_pack_weights folded), g the derivative of the objective of "Head fine-tuning"
+ * w.r.t. the raw head, and Wh the head conv's weights as the forward used them (in the handle's dtype):
+ *     dA[p, c]         = sum_o g[p, o] Wh[o, c]
+ *     dZ[p, c]         = dA[p, c] * (A[p, c] > 0 ? 1 : 0.1) * s[c]          (TensorFlow's LeakyReLU gradient: 0.1 at exactly 0)
+ *     dK[co,ci,kh,kw]  = sum over images, rows, columns of dZ[n,y,x,co] * U[n, y+kh-1, x+kw-1, ci]     ('same' zero padding)
+ * dA uses g's structure -- three confidence terms per cell in anchor order, then the cell's records in record order -- and never
+ * runs a full-width product over every cell; dZ is kept in scratch in the MFMA operand type (bf16 for a bf16 handle: one rounding
+ * to nearest even; float32 for a float32 handle).  dK is an implicit GEMM over K = pixels on the matrix pipes
+ * (v_mfma_f32_32x32x16_bf16; v_mfma_f32_32x32x2_f32, exact float32, for a float32 handle) with float32 accumulation: K is cut
+ * into (image, row strip) slices by the geometry alone, contiguous ranges of slices are summed in order into float32 partials in
+ * scratch and a finish kernel adds the partials in range order.  No floating-point atomics: the same call gives the same bits.
+ *
+ * The gradient, the float32 master copy and the Adam moments use ONE layout: the three kernels one after the other (conv 92, 100,
+ * 108), each cout * cin * 9 floats in the Darknet stream's (out, in, kh, kw) order, WITHOUT the four BatchNormalization vectors
+ * that precede them in the stream (they lie at y4_layer_info(...).weight_offset + 4 * cout).
+ * A float16 handle is refused (Y4_EINVAL): a 16-bit dZ in fp16 needs loss scaling. */
+
+/* bytes of scratch y4_block_grad needs for n images (dZ of the three scales, then the partials); 256-byte aligned.
+ * Width limit of the weight gradient (two grid rows and their halo in LDS): a grid row of the stride-8 scale of at most 105 cells
+ * on a float32 handle (an image 840 wide) and 200 cells on a bf16 handle (1600 wide); beyond it this call and y4_block_grad
+ * return Y4_EINVAL before anything is launched. */
+int y4_block_grad_scratch_bytes(y4_handle h, int n, size_t* bytes);
+/* The gradient above for the n images of the last y4_forward: their raw heads, the head convs' inputs AND the inputs of convs
+ * 92 / 100 / 108 are read from the workspace (Y4_ESTATE unless the retention level is 2: y4_set_retain_head_inputs(h, 2)).
+ * Labels, iou_loss_thresh and img_weight_dev as y4_head_grad.  Call it BEFORE y4_head_adam of the same step: both gradients use
+ * the head weights the forward used.  dk_dev (layout above, dk_floats >= the three kernels) is written, or with accumulate != 0
+ * added to (one more float32 add per element). */
+int y4_block_grad(y4_handle h, int n, const int32_t* records_dev, const int32_t* counts_dev, const float* xywh_dev, int max_boxes,
+                  float iou_loss_thresh, const float* img_weight_dev, void* scratch_dev, size_t scratch_bytes, float* dk_dev,
+                  size_t dk_floats, int accumulate, void* stream);
+/* One step of the Adam rule of y4_head_adam (same element rule, lr_t in double on the host; pass the same t for both calls of a
+ * step) on the caller's float32 master kernels k_dev and moments m_dev, v_dev (n_floats = the three kernels exactly), followed by
+ * the re-pack of the three layers: the new kernels go into the bound packed-weight workspace in the handle's dtype and canonical K
+ * order, and into the MFMA-fragment copy the halo2 tiles read where the layer has one, by the kernels of y4_pack_weights.  The
+ * BatchNormalization is frozen, so scale and shift stay as y4_pack_weights folded them: a handle that loads the updated stream
+ * afresh holds the same bytes over the whole weight workspace. */
+int y4_block_adam(y4_handle h, const float* dk_dev, float* k_dev, float* m_dev, float* v_dev, size_t n_floats, float lr,
+                  float beta1, float beta2, float epsilon, int t, void* stream);
 
 /* Replaces inference_model.predict(imgs) (reference models.py:69-73,113,159) = forward + decode + NMS. */
 int y4_predict(y4_handle h, const float* imgs_nhwc_dev, int n, float* boxes_dev, float* scores_dev,

@@ -182,4 +182,32 @@ int head_grad_launch(int dtype, const GradK& k, int n, hipStream_t stream);
 int head_adam_launch(const float* g, float* w, float* m, float* v, size_t count, float lr_t, float b1, float b2, float eps,
                      hipStream_t stream);
 
+// block_train.hip: the gradient of the 3x3 convs in front of the heads (92 / 100 / 108); labels and heads travel in a GradK
+struct BlockK {
+    const void* u[3];                // the 3x3 convs' inputs, dense NHWC [n, gh, gw, cin] in the handle's dtype
+    const void* a[3];                // their outputs (the head convs' inputs), dense NHWC [n, gh, gw, cout]
+    const void* wh[3];               // the head convs' packed weights [3 (5 + C) rows][cout]
+    const float* bn_scale[3];        // gamma / sqrt(var + eps) as fold_bn left it
+    int cin[3], cout[3];
+    int dstrip_base[3];              // 16-cell strips of one image: the first one of a scale
+    void* dz[3];                     // scratch: dZ [n, gh, gw, cout] in the handle's dtype
+    float* part[3];                  // scratch: wgrad partials [splits][9][cout][cin]
+    float* dk;                       // the three kernels (out, in, kh, kw), conv 92 / 100 / 108 at dk_off
+    size_t dk_off[3];
+    int accumulate;
+};
+struct WgradK {
+    const void* u;
+    const void* dz;
+    float* part;
+    int n, H, W, cin, cout;
+    int R, strips, slices, splits;   // rows of a K slice, slices per image, slices in all, contiguous slice ranges (= partials)
+    int Wp, upitch, uchan, dchan;    // LDS image: padded row length of dZ, row pitch of U, channel pitches (elements)
+};
+int block_dgrad_strips(const int* gh, const int* gw, int* base);
+size_t block_wgrad_geometry(int dtype, int n, int H, int W, int cin, int cout, WgradK& k);
+size_t block_grad_scratch_bytes(int dtype, int n, const int* gh, const int* gw, const int* cin, const int* cout, size_t* dz_off,
+                                size_t* part_off);
+int block_grad_launch(int dtype, const GradK& k, const BlockK& b, int n, hipStream_t stream);
+
 }  // namespace y4

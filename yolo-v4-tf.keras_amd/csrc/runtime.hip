@@ -165,6 +165,9 @@ struct y4_ctx {
     // y4_set_retain_head_inputs: the outputs of convs 92 / 100 / 108 -- the head convs' inputs -- are written to HBM (also where an
     // LDS pair would keep them on chip) and live to the end of the forward: y4_head_grad reads them
     bool retain_head_in = false;
+    // level 2 of the same switch: the inputs of convs 92 / 100 / 108 (the outputs of convs 91 / 99 / 107) live to the end of the
+    // forward too: y4_block_grad reads them
+    bool retain_block_in = false;
 };
 
 namespace {
@@ -502,6 +505,11 @@ static void buffer_lifetimes(const y4_ctx& c, std::vector<int>& first, std::vect
     if (c.retain_head_in)
         for (const Op& o : c.ops)
             if (o.out_f32) last[o.in.buf] = nops;                         // ... and so do their convs' inputs
+    if (c.retain_block_in)
+        for (const Op& o : c.ops)
+            if (o.out_f32)
+                for (const Op& q : c.ops)
+                    if (q.kind == OP_CONV && q.out.buf == o.in.buf) last[q.in.buf] = nops;      // ... and the inputs of the convs in front
 }
 
 void layout(y4_ctx& c) {
@@ -1197,10 +1205,34 @@ int y4_loss(y4_handle h, int n, const int32_t* records, const int32_t* counts, c
 
 // ---- head fine-tuning (head_train.hip)
 
+// the op of head conv `i` (93 / 101 / 109)
+static const Op* head_op(y4_handle h, int i) {
+    for (const Op& o : h->ops)
+        if (o.out_f32 && o.out.buf == h->heads[i].buf) return &o;
+    return nullptr;
+}
+// the op of the conv in front of it (92 / 100 / 108): the one that writes the head conv's input
+static const Op* block_op(y4_handle h, int i) {
+    const Op* ho = head_op(h, i);
+    if (!ho) return nullptr;
+    for (const Op& o : h->ops)
+        if (o.kind == OP_CONV && same_view(o.out, ho->in)) return &o;
+    return nullptr;
+}
+
 int y4_set_retain_head_inputs(y4_handle h, int on) {
     if (int r = check_handle(h)) return r;
     Y4_REQUIRE(!h->act, Y4_ESTATE, "y4_set_retain_head_inputs: the workspace is already bound (call it before y4_workspace_bytes / y4_bind_workspace)");
-    h->retain_head_in = on != 0;
+    // level 2 relies on the plan, not on a switch: a run keeps only its head's output on chip, its tail is a 1x1 conv, and the
+    // inputs of convs 92 / 100 / 108 are each the output of a 1x1 conv that is the tail of its run or has a reader outside it
+    if (on == 2)
+        for (const Chain& ch : h->chains)
+            for (int i = 0; i < 3; ++i)
+                if (const Op* b = block_op(h, i))
+                    Y4_REQUIRE(h->ops[ch.head].out.buf != b->in.buf || ch.store_x, Y4_ESTATE,
+                               "y4_set_retain_head_inputs: a fused run keeps the input of conv %d on chip", h->layers[b->conv].d.idx);
+    h->retain_head_in = on != 0;                                         // (every non-zero value but 2 is level 1, as before level 2 existed)
+    h->retain_block_in = on == 2;
     // an LDS pair whose tail is a head conv keeps the head's input in LDS: with retention it is stored as well
     for (Chain& ch : h->chains)
         if (ch.lds_pair && h->ops[ch.tail[0]].out_f32)
@@ -1224,13 +1256,6 @@ static int grad_common(y4_handle h, GradK& k, const int32_t* records, const int3
     k.input_area = (float)h->H * (float)h->W;
     k.records = records; k.counts = counts; k.xywh = xywh; k.imgw = img_weight;
     return Y4_OK;
-}
-
-// the op of head conv `i` (93 / 101 / 109)
-static const Op* head_op(y4_handle h, int i) {
-    for (const Op& o : h->ops)
-        if (o.out_f32 && o.out.buf == h->heads[i].buf) return &o;
-    return nullptr;
 }
 
 // float offsets of the three head records in the dw / master buffers and their total
@@ -1313,6 +1338,103 @@ int y4_head_adam(y4_handle h, const float* dw, float* w, float* m, float* v, siz
         if (int r = fold_bn_launch(rec, (float*)(h->wts + L.scale_off), (float*)(h->wts + L.shift_off), L.d.cout, L.cout_pad, 0, s))
             return r;
         if (int r = pack_conv_weights(h->cfg.dtype, L.d.cout, L.d.cin, 1, rec + L.d.cout, h->wts + L.w_off, s)) return r;
+    }
+    return Y4_OK;
+}
+
+// ---- fine-tuning of the 3x3 convs in front of the heads (block_train.hip)
+
+// float offsets of the three kernels (conv 92 / 100 / 108, cout * cin * 9 each) in the dk / master buffers and their total
+static size_t block_kernel_offsets(y4_handle h, size_t* off) {
+    size_t total = 0;
+    for (int i = 0; i < 3; ++i) {
+        const Layer& L = h->layers[block_op(h, i)->conv];
+        if (off) off[i] = total;
+        total += (size_t)L.d.cout * L.d.cin * 9;
+    }
+    return total;
+}
+
+static int block_check(y4_handle h, const char* who) {
+    Y4_REQUIRE(h->cfg.dtype != Y4_F16, Y4_EINVAL, "%s: an f16 handle is not supported (a 16-bit dZ in fp16 needs loss scaling); use f32 or bf16", who);
+    for (int i = 0; i < 3; ++i) {
+        const Op* b = block_op(h, i);
+        Y4_REQUIRE(b != nullptr, Y4_EINVAL, "%s: no conv in front of head %d", who, i);
+        const Layer& L = h->layers[b->conv];
+        Y4_REQUIRE(L.d.ksize == 3 && L.d.stride == 1 && L.d.act == Y4_ACT_LEAKY && L.d.has_bn && !b->has_res && !b->upsample && b->conv2 < 0 &&
+                   L.fused_with < 0 && L.extra_rows == 0, Y4_EINVAL, "%s: conv %d is not a plain 3x3 Conv + BN + LeakyReLU", who, L.d.idx);
+    }
+    return Y4_OK;
+}
+
+int y4_block_grad_scratch_bytes(y4_handle h, int n, size_t* bytes) {
+    if (int r = check_handle(h)) return r;
+    Y4_REQUIRE(n >= 1 && bytes, Y4_EINVAL, "y4_block_grad_scratch_bytes: bad argument");
+    if (int r = block_check(h, "y4_block_grad_scratch_bytes")) return r;
+    int gh[3], gw[3], cin[3], cout[3];
+    loss_geometry(h, gh, gw, nullptr);
+    for (int i = 0; i < 3; ++i) { const Layer& L = h->layers[block_op(h, i)->conv]; cin[i] = L.d.cin; cout[i] = L.d.cout; }
+    *bytes = block_grad_scratch_bytes(h->cfg.dtype, n, gh, gw, cin, cout, nullptr, nullptr);
+    Y4_REQUIRE(*bytes > 0, Y4_EINVAL, "y4_block_grad_scratch_bytes: a grid row of %d cells does not fit the weight gradient's LDS tile", gw[0]);
+    return Y4_OK;
+}
+
+int y4_block_grad(y4_handle h, int n, const int32_t* records, const int32_t* counts, const float* xywh, int max_boxes,
+                  float iou_loss_thresh, const float* img_weight, void* scratch, size_t scratch_bytes, float* dk, size_t dk_floats,
+                  int accumulate, void* stream) {
+    if (int r = check_ready(h, n)) return r;
+    if (int r = block_check(h, "y4_block_grad")) return r;
+    Y4_REQUIRE(h->retain_block_in, Y4_ESTATE, "y4_block_grad: the inputs of convs 92 / 100 / 108 are not retained (retention level 2: "
+               "y4_set_retain_head_inputs(h, 2) before the workspace is bound)");
+    Y4_REQUIRE(records && counts && xywh && img_weight && scratch && dk, Y4_EINVAL, "y4_block_grad: null argument");
+    Y4_REQUIRE(((uintptr_t)scratch & 255) == 0, Y4_EINVAL, "y4_block_grad: scratch must be 256-byte aligned");
+    Y4_REQUIRE(iou_loss_thresh >= 0.f, Y4_EINVAL, "y4_block_grad: iou_loss_thresh %g", (double)iou_loss_thresh);
+    GradK k{};
+    grad_common(h, k, records, counts, xywh, max_boxes, iou_loss_thresh, img_weight);
+    BlockK b{};
+    for (int i = 0; i < 3; ++i) {
+        const Op* ho = head_op(h, i);
+        const Op* bo = block_op(h, i);
+        const Layer& L = h->layers[bo->conv];
+        const Layer& LH = h->layers[ho->conv];
+        Y4_REQUIRE(ho->in.coff == 0 && ho->in.cstride == ho->in.c && bo->in.coff == 0 && bo->in.cstride == bo->in.c, Y4_EINVAL,
+                   "y4_block_grad: scale %d reads a channel slice", i);
+        b.u[i] = buf_ptr(h, bo->in); b.a[i] = buf_ptr(h, ho->in);
+        b.wh[i] = h->wts + LH.w_off; b.bn_scale[i] = (const float*)(h->wts + L.scale_off);
+        b.cin[i] = L.d.cin; b.cout[i] = L.d.cout;
+    }
+    block_dgrad_strips(k.gh, k.gw, b.dstrip_base);
+    size_t dz_off[3], part_off[3];
+    const size_t need = block_grad_scratch_bytes(h->cfg.dtype, n, k.gh, k.gw, b.cin, b.cout, dz_off, part_off);
+    Y4_REQUIRE(need > 0, Y4_EINVAL, "y4_block_grad: a grid row of %d cells does not fit the weight gradient's LDS tile", k.gw[0]);
+    Y4_REQUIRE(scratch_bytes >= need, Y4_ENOMEM, "y4_block_grad: scratch %zu < %zu bytes", scratch_bytes, need);
+    const size_t total = block_kernel_offsets(h, b.dk_off);
+    Y4_REQUIRE(dk_floats >= total, Y4_ENOMEM, "y4_block_grad: dk %zu < %zu floats", dk_floats, total);
+    for (int i = 0; i < 3; ++i) { b.dz[i] = (char*)scratch + dz_off[i]; b.part[i] = (float*)((char*)scratch + part_off[i]); }
+    b.dk = dk; b.accumulate = accumulate != 0;
+    return block_grad_launch(h->cfg.dtype, k, b, n, (hipStream_t)stream);
+}
+
+int y4_block_adam(y4_handle h, const float* dk, float* w, float* m, float* v, size_t n_floats, float lr, float beta1, float beta2,
+                  float epsilon, int t, void* stream) {
+    if (int r = check_handle(h)) return r;
+    Y4_REQUIRE(h->act && h->wts && h->weights_ready, Y4_ESTATE, "y4_block_adam: weights not packed (call y4_pack_weights first)");
+    if (int r = block_check(h, "y4_block_adam")) return r;
+    Y4_REQUIRE(dk && w && m && v, Y4_EINVAL, "y4_block_adam: null argument");
+    Y4_REQUIRE(t >= 1, Y4_EINVAL, "y4_block_adam: step %d (the first step is 1)", t);
+    size_t off[3];
+    const size_t total = block_kernel_offsets(h, off);
+    Y4_REQUIRE(n_floats == total, Y4_EINVAL, "y4_block_adam: %zu floats, the three kernels have %zu", n_floats, total);
+    hipStream_t s = (hipStream_t)stream;
+    const float lr_t = (float)((double)lr * sqrt(1.0 - pow((double)beta2, (double)t)) / (1.0 - pow((double)beta1, (double)t)));
+    if (int r = head_adam_launch(dk, w, m, v, total, lr_t, beta1, beta2, epsilon, s)) return r;
+    // the re-pack: what y4_pack_weights does with these three kernels (same kernels, same rounding), every packed copy.  The
+    // BatchNormalization is frozen, so the scale / shift fold_bn made of it at y4_pack_weights are already what a fresh load makes.
+    for (int i = 0; i < 3; ++i) {
+        const Layer& L = h->layers[block_op(h, i)->conv];
+        if (int r = pack_conv_weights(h->cfg.dtype, L.d.cout, L.d.cin, 3, w + off[i], h->wts + L.w_off, s)) return r;
+        if (L.has_frag)
+            if (int r = pack_conv_frag32(h->cfg.dtype, L.d.cout, L.d.cin, h->wts + L.w_off, h->wts + L.frag_off, s)) return r;
     }
     return Y4_OK;
 }

@@ -193,22 +193,40 @@ class Yolov4(object):
         images) -> y4_head_adam; the batch's training loss is y4_loss on the same heads.  Per epoch a Keras-like line,
         `train_data_gen.on_epoch_end()` and every callback's `on_epoch_end(epoch, logs)`.  -> an object whose `.history` is
         {'loss': [...], 'val_loss': [...]} (val_loss only with `val_data_gen`).  A batch with a box off the grid or an unknown
-        class raises ValueError before any update.  trainable=None (the reference's meaning: every layer) is not implemented."""
-        if trainable != 'heads':
+        class raises ValueError before any update.  trainable=None (the reference's meaning: every layer) is not implemented.
+
+        trainable='head_blocks' additionally trains the KERNELS of the 3x3 convs in front of the heads (92 / 100 / 108); their
+        BatchNormalization stays frozen and runs in inference mode, as Keras runs a frozen BN.  Per chunk y4_block_grad follows
+        y4_head_grad (both use the head weights the forward used), per batch both Adam steps run with the same t.  f32 and bf16.
+
+        A callback with a `schedule(epoch, lr)` method (yolo4hip.callbacks.CosineAnnealingScheduler; Keras'
+        LearningRateScheduler pattern) is asked at the start of every epoch; its result is that epoch's learning rate."""
+        if trainable not in ('heads', 'head_blocks'):
             raise NotImplementedError("training every layer is out of scope of the MI355X path; fit(..., trainable='heads') "
-                                      "fine-tunes the three detection convs on a frozen backbone and neck")
+                                      "fine-tunes the three detection convs on a frozen backbone and neck, "
+                                      "trainable='head_blocks' also the 3x3 convs in front of them")
+        blocks = trainable == 'head_blocks'
+        if blocks and self._dtype == 'f16':
+            raise NotImplementedError("fit(trainable='head_blocks') on an f16 model: a 16-bit gradient in fp16 needs loss scaling; "
+                                      "use dtype 'bf16' or 'f32'")
         from .engine import combine_loss
         self._ensure_tuned()
         if getattr(train_data_gen, 'max_boxes', self.max_boxes) != self.max_boxes:
             raise ValueError(f"the generator's max_boxes {train_data_gen.max_boxes} != config['max_boxes'] {self.max_boxes}")
-        eng = self._train_engine()
+        eng = self._train_engine(2 if blocks else 1)
         torch = eng.torch
         state = eng.head_state(self._flat)
         dw = torch.empty((eng.head_floats(),), dtype=torch.float32, device=eng.device)
+        if blocks:
+            bstate = eng.block_state(self._flat)
+            dk = torch.empty((eng.block_floats(),), dtype=torch.float32, device=eng.device)
         history = {'loss': []}
         if val_data_gen is not None:
             history['val_loss'] = []
         for epoch in range(int(initial_epoch), int(epochs)):
+            for cb in callbacks or []:
+                if hasattr(cb, 'schedule'):
+                    learning_rate = float(cb.schedule(epoch, learning_rate))
             total, images = 0.0, 0
             for i in range(len(train_data_gen)):
                 X, boxes = train_data_gen.boxes(i)
@@ -224,17 +242,24 @@ class Yolov4(object):
                     labels = eng.assign_device(boxes_dev[i0:i0 + n])
                     eng.head_grad_device(n, records=labels, iou_loss_thresh=self.iou_loss_thresh, img_weight=weight[i0:i0 + n],
                                          dw=dw, accumulate=i0 > 0)
+                    if blocks:
+                        eng.block_grad_device(n, records=labels, iou_loss_thresh=self.iou_loss_thresh,
+                                              img_weight=weight[i0:i0 + n], dk=dk, accumulate=i0 > 0)
                     parts.append(eng.loss_device(n, records=labels, iou_loss_thresh=self.iou_loss_thresh))
                     i0 += n
                 if i0 != count:
                     raise ValueError(f'labels for {count} images, but {i0} images')
                 eng.head_adam_step(state, dw, lr=learning_rate)
+                if blocks:
+                    eng.block_adam_step(bstate, dk, lr=learning_rate)
                 total += float(combine_loss(torch.cat(parts).cpu().numpy())[0].sum())
                 images += count
             if images == 0:
                 raise ValueError('fit: the generator is empty')
             # the trained heads reach the host stream and the inference engine at the end of every epoch
             eng.head_weights_to_flat(state, self._flat)
+            if blocks:
+                eng.block_weights_to_flat(bstate, self._flat)
             self.engine.load_weight_blob(self._flat)
             logs = {'loss': total / images}
             if val_data_gen is not None:
@@ -254,13 +279,17 @@ class Yolov4(object):
         out.history, out.epoch = history, list(range(int(initial_epoch), int(epochs)))
         return out
 
-    def _train_engine(self):
+    def _train_engine(self, level=1):
         """The engine `fit` runs on: created on the first `fit`, with the head convs' inputs retained (the inference engine keeps
-        its size for users who never train), the inference engine's schedule, and the current weights."""
-        eng = getattr(self, '_fit_engine', None)
+        its size for users who never train), the inference engine's schedule, and the current weights.  level 2
+        (trainable='head_blocks') is an engine of its own that also retains the inputs of convs 92 / 100 / 108, so that
+        trainable='heads' keeps the engine, the workspace and the speed it has."""
+        name = '_fit_engine' if level == 1 else '_fit_engine_blocks'
+        eng = getattr(self, name, None)
         if eng is None:
-            eng = self._fit_engine = Engine(self.num_classes, self.config, max_batch=self._max_batch, dtype=self._dtype,
-                                            device=self._device, alias_workspace=True, retain_head_inputs=True)
+            eng = Engine(self.num_classes, self.config, max_batch=self._max_batch, dtype=self._dtype,
+                         device=self._device, alias_workspace=True, retain_head_inputs=level)
+            setattr(self, name, eng)
         eng.load_weight_blob(self._flat)
         self.engine.copy_schedule_to(eng)
         return eng

@@ -71,10 +71,13 @@ class Engine:
         if self.alias_workspace:
             ext.check(self.lib.y4_set_workspace_aliasing(self.handle, 1))
         # retain_head_inputs: the head convs' inputs stay in the workspace after a forward (y4_set_retain_head_inputs), which
-        # `head_grad_device` needs
-        self.retain_head_inputs = bool(retain_head_inputs)
+        # `head_grad_device` needs; level 2 also keeps the inputs of convs 92 / 100 / 108, which `block_grad_device` needs
+        self.retain_level = int(retain_head_inputs)
+        if self.retain_level not in (0, 1, 2):
+            raise ValueError(f"retain_head_inputs must be False / True (0 / 1) or 2, got {retain_head_inputs!r}")
+        self.retain_head_inputs = self.retain_level > 0
         if self.retain_head_inputs:
-            ext.check(self.lib.y4_set_retain_head_inputs(self.handle, 1))
+            ext.check(self.lib.y4_set_retain_head_inputs(self.handle, self.retain_level))
         a, w = C.c_size_t(), C.c_size_t()
         ext.check(self.lib.y4_workspace_bytes(self.handle, C.byref(a), C.byref(w)))
         self.act_bytes, self.wts_bytes = a.value, w.value
@@ -686,6 +689,72 @@ class Engine:
         w = state["w"].cpu().numpy()
         pos = 0
         for o, n in self.head_records():
+            flat[o:o + n] = w[pos:pos + n]
+            pos += n
+        return flat
+
+    # ---------------------------------------------------------------- the 3x3 convs in front of the heads (csrc/block_train.hip)
+    BLOCK_CONVS = (92, 100, 108)
+
+    def block_records(self):
+        """[(float offset in the Darknet stream, floats)] of the KERNELS of convs 92 / 100 / 108: cout x cin x 3 x 3 weights in
+        (out, in, kh, kw) order, behind the layer's four BatchNormalization vectors.  The gradient, master-weight and moment
+        buffers hold these three kernels back to back."""
+        lt = self.layer_table()
+        return [(int(lt[i]["weight_offset"] + 4 * lt[i]["cout"]), int(lt[i]["cout"] * lt[i]["cin"] * 9)) for i in self.BLOCK_CONVS]
+
+    def block_floats(self):
+        return sum(n for _, n in self.block_records())
+
+    def block_grad_device(self, n, boxes_dev=None, records=None, iou_loss_thresh=None, img_weight=None, dk=None, accumulate=False):
+        """y4_block_grad after `forward_device` on n images (an engine with retain_head_inputs=2), BEFORE the step's
+        `head_adam_step`: the gradient of sum_i img_weight[i] * loss_i w.r.t. the kernels of convs 92 / 100 / 108 -> float32 cuda
+        tensor [block_floats()] (`block_records` gives the layout), written into `dk` or, with accumulate=True, added to it."""
+        torch = self.torch
+        rec, cnt, xywh = self._labels(n, boxes_dev, records)
+        w = self._img_weight(n, img_weight)
+        thr = float(self.config.get("iou_loss_thresh", 0.5) if iou_loss_thresh is None else iou_loss_thresh)
+        total = self.block_floats()
+        if dk is None:
+            if accumulate:
+                raise ValueError("block_grad_device: accumulate needs the dk to add to")
+            dk = torch.empty((total,), dtype=torch.float32, device=self.device)
+        if dk.dtype != torch.float32 or dk.numel() != total or not dk.is_contiguous():
+            raise ValueError(f"dk must be a contiguous float32 tensor of {total} elements")
+        nb = C.c_size_t()
+        ext.check(self.lib.y4_block_grad_scratch_bytes(self.handle, n, C.byref(nb)))
+        scratch = getattr(self, "_block_scratch", None)                  # kept: hundreds of MB at batch 32
+        if scratch is None or scratch.numel() < nb.value:
+            scratch = self._block_scratch = torch.empty((nb.value,), dtype=torch.uint8, device=self.device)
+        with torch.cuda.device(self.device):
+            ext.check(self.lib.y4_block_grad(self.handle, n, ext.ptr(rec), ext.ptr(cnt), ext.ptr(xywh), self._loss_max_boxes(), thr,
+                                             ext.ptr(w), ext.ptr(scratch), scratch.numel(), ext.ptr(dk), total, 1 if accumulate else 0,
+                                             ext.stream_ptr()))
+        return dk
+
+    def block_state(self, flat):
+        """The optimiser state for `block_adam_step`: float32 master kernels (the three kernels of the host stream `flat`,
+        uploaded) and zero moments -> {'w', 'm', 'v', 't'}."""
+        torch = self.torch
+        flat = np.asarray(flat, dtype=np.float32)
+        w = np.concatenate([flat[o:o + n] for o, n in self.block_records()])
+        w = torch.from_numpy(np.ascontiguousarray(w)).to(self.device)
+        return {"w": w, "m": torch.zeros_like(w), "v": torch.zeros_like(w), "t": 0}
+
+    def block_adam_step(self, state, dk, lr=1e-4, beta1=0.9, beta2=0.999, epsilon=1e-7):
+        """y4_block_adam: one step of Keras' Adam on the master kernels of `state` with the gradient `dk`, and the re-pack: the
+        next forward of this engine runs on the updated convs 92 / 100 / 108."""
+        state["t"] += 1
+        with self.torch.cuda.device(self.device):
+            ext.check(self.lib.y4_block_adam(self.handle, ext.ptr(dk), ext.ptr(state["w"]), ext.ptr(state["m"]), ext.ptr(state["v"]),
+                                             state["w"].numel(), float(lr), float(beta1), float(beta2), float(epsilon),
+                                             int(state["t"]), ext.stream_ptr()))
+
+    def block_weights_to_flat(self, state, flat):
+        """Copy the master kernels of `state` back into the host stream `flat` (in place); the BatchNormalization vectors stay."""
+        w = state["w"].cpu().numpy()
+        pos = 0
+        for o, n in self.block_records():
             flat[o:o + n] = w[pos:pos + n]
             pos += n
         return flat
