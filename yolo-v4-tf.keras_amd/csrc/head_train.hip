@@ -208,9 +208,9 @@ __global__ __launch_bounds__(LOSS_THREADS) void head_sparse_wgrad_kernel(GradK p
     if (tid == 0) dw[row] = p.accumulate ? dw[row] + bias : bias;
 }
 
-// ---- y4_head_adam: Keras' Adam (the reference compiles Adam(learning_rate=1e-4), models.py:83) with lr_t = lr sqrt(1 - b2^t) / (1 - b1^t)
-__global__ void head_adam_kernel(const float* __restrict__ g, float* __restrict__ w, float* __restrict__ m, float* __restrict__ v,
-                                 size_t count, float lr_t, float b1, float b2, float eps) {
+// ---- y4_head_adam / y4_block_adam: Keras' Adam (the reference compiles Adam(learning_rate=1e-4), models.py:83) with lr_t = lr sqrt(1 - b2^t) / (1 - b1^t)
+__global__ void adam_kernel(const float* __restrict__ g, float* __restrict__ w, float* __restrict__ m, float* __restrict__ v,
+                            size_t count, float lr_t, float b1, float b2, float eps) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= count) return;
     const float gi = g[i];
@@ -276,10 +276,8 @@ int head_grad_launch(int dtype, const GradK& k, int n, hipStream_t stream) {
     }
 }
 
-int head_adam_launch(const float* g, float* w, float* m, float* v, size_t count, float lr_t, float b1, float b2, float eps,
-                     hipStream_t stream) {
-    hipLaunchKernelGGL(head_adam_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, stream, g, w, m, v, count, lr_t, b1, b2,
-                       eps);
+int adam_launch(const float* g, float* w, float* m, float* v, size_t count, float lr_t, float b1, float b2, float eps, hipStream_t stream) {
+    hipLaunchKernelGGL(adam_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, stream, g, w, m, v, count, lr_t, b1, b2, eps);
     Y4_CHECK_HIP(hipGetLastError());
     return Y4_OK;
 }

@@ -137,7 +137,8 @@ struct LossAssignK {
     int gh[3], gw[3], lane_base[3];  // lane_base: first (cell, anchor) index of a scale among the image's 3 * cells lanes
     float anchors[18];
 };
-struct LossK {
+// what the loss forward and its gradients read: the raw heads in the workspace, the 256-lane strips, and one batch's labels
+struct LossIn {
     const float* head[3];
     int gh[3], gw[3], strip_base[3], strips;   // strips: 256-lane workgroups per image, strip_base: the first one of a scale
     float stride[3], anchors[18];
@@ -146,6 +147,9 @@ struct LossK {
     const int32_t* records;          // [n, mb, rw]
     const int32_t* counts;           // [n]
     const float* xywh;               // [n, mb, 4]
+    const float* imgw;               // [n] weight of each image's loss (1 / N: the batch mean); null for the forward
+};
+struct LossK : LossIn {
     float* partials;                 // [n, strips, 3]
     float* out;                      // [n, 3 scales, 3] box, confidence, class sums
 };
@@ -154,16 +158,7 @@ int loss_assign_launch(const LossAssignK& k, int n, hipStream_t stream);
 int loss_launch(const LossK& k, int n, hipStream_t stream);
 
 // head_train.hip: the gradient of yolo_loss w.r.t. the raw heads, the weight gradient of the three head convs, Adam
-struct GradK {
-    const float* head[3];
-    int gh[3], gw[3], strip_base[3], strips;   // 256-lane strips as LossK (the dense gradient)
-    float stride[3], anchors[18];
-    int C, hcs, mb, rw;
-    float thresh, input_area;
-    const int32_t* records;          // [n, mb, rw]
-    const int32_t* counts;           // [n]
-    const float* xywh;               // [n, mb, 4]
-    const float* imgw;               // [n] weight of each image's loss (1 / N: the batch mean)
+struct GradK : LossIn {
     float* dense[3];                 // y4_loss_grad: [n, gh, gw, 3 (5 + C)] per scale
     // y4_head_grad
     const void* x[3];                // the head convs' inputs, dense NHWC [n, gh, gw, cin] in the handle's dtype
@@ -179,8 +174,7 @@ int head_grad_strips(const int* gh, const int* gw, int* pstrip_base, int* pstrip
 size_t head_grad_scratch_floats(const int* gh, const int* gw, const int* cin, int n, size_t* part_base);
 int loss_grad_launch(const GradK& k, int n, hipStream_t stream);
 int head_grad_launch(int dtype, const GradK& k, int n, hipStream_t stream);
-int head_adam_launch(const float* g, float* w, float* m, float* v, size_t count, float lr_t, float b1, float b2, float eps,
-                     hipStream_t stream);
+int adam_launch(const float* g, float* w, float* m, float* v, size_t count, float lr_t, float b1, float b2, float eps, hipStream_t stream);
 
 // block_train.hip: the gradient of the 3x3 convs in front of the heads (92 / 100 / 108); labels and heads travel in a GradK
 struct BlockK {

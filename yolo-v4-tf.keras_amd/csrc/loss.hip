@@ -101,42 +101,18 @@ __global__ __launch_bounds__(LOSS_THREADS) void loss_assign_kernel(LossAssignK p
 
 // grid (strips of one image, images); a strip is LOSS_THREADS consecutive (cell, anchor) lanes of ONE scale
 __global__ __launch_bounds__(LOSS_THREADS) void loss_kernel(LossK p) {
-    __shared__ float s_x1[LOSS_THREADS], s_y1[LOSS_THREADS], s_x2[LOSS_THREADS], s_y2[LOSS_THREADS], s_area[LOSS_THREADS];
+    __shared__ TrueBoxes tb;
     __shared__ int s_resp[LOSS_THREADS];
-    __shared__ int s_wave[4];
     __shared__ float s_red[4][3];
     const int img = blockIdx.y, strip = blockIdx.x, tid = threadIdx.x;
     const int s = strip >= p.strip_base[2] ? 2 : (strip >= p.strip_base[1] ? 1 : 0);
     const int lane0 = (strip - p.strip_base[s]) * LOSS_THREADS;
     const int gh = p.gh[s], gw = p.gw[s];
     const int lanes = 3 * gh * gw;
-
-    // the image's true boxes with w > 0 as corners in LDS (a row with w <= 0 intersects nothing: its IoU is 0, the maximum's
-    // starting value)
-    float bx = 0.f, by = 0.f, bw = 0.f, bh = 0.f;
-    if (tid < p.mb) {
-        const float* b = p.xywh + ((size_t)img * p.mb + tid) * 4;
-        bx = b[0]; by = b[1]; bw = b[2]; bh = b[3];
-    }
-    int nb = 0;
-    const int pos = compact_valid(tid < p.mb && bw > 0.f, s_wave, &nb);
-    if (pos >= 0) {
-        s_x1[pos] = bx - bw * 0.5f; s_y1[pos] = by - bh * 0.5f;
-        s_x2[pos] = bx + bw * 0.5f; s_y2[pos] = by + bh * 0.5f;
-        s_area[pos] = bw * bh;
-    }
+    const int nb = load_true_boxes(p, img, tb);
     s_resp[tid] = -1;
     __syncthreads();
-    int count = p.counts[img];
-    count = count < 0 ? 0 : (count > p.mb ? p.mb : count);
-    const int32_t* recs = p.records + (size_t)img * p.mb * p.rw;
-    if (tid < count) {
-        const int32_t* r = recs + (size_t)tid * p.rw;
-        if (r[0] == s && r[1] >= 0 && r[1] < gh && r[2] >= 0 && r[2] < gw && r[3] >= 0 && r[3] < 3) {
-            const int k = (r[1] * gw + r[2]) * 3 + r[3] - lane0;
-            if (k >= 0 && k < LOSS_THREADS) s_resp[k] = tid;
-        }
-    }
+    map_records(p, img, s, lane0, LOSS_THREADS, s_resp);
     __syncthreads();
 
     float box_t = 0.f, conf_t = 0.f, cls_t = 0.f;
@@ -145,29 +121,17 @@ __global__ __launch_bounds__(LOSS_THREADS) void loss_kernel(LossK p) {
         const int cell = lane / 3, a = lane - cell * 3;
         const int row = cell / gw, col = cell - row * gw;
         const float* t = p.head[s] + ((size_t)img * gh * gw + cell) * p.hcs + a * (p.C + 5);
-        const float tx = t[0], ty = t[1], tw = t[2], th = t[3], tc = t[4];
-        // loss.py:195-212: no xyscale here, unlike the inference decode
-        const float px = (sigmoidf(tx) + (float)col) * p.stride[s];
-        const float py = (sigmoidf(ty) + (float)row) * p.stride[s];
-        const float pw = expf(tw) * p.anchors[(s * 3 + a) * 2], ph = expf(th) * p.anchors[(s * 3 + a) * 2 + 1];
-        const float area_p = pw * ph;
-        const float px1 = px - pw * 0.5f, py1 = py - ph * 0.5f, px2 = px + pw * 0.5f, py2 = py + ph * 0.5f;
-        float max_iou = 0.0f;
-        for (int j = 0; j < nb; ++j) {
-            const float iw = fmaxf(fminf(px2, s_x2[j]) - fmaxf(px1, s_x1[j]), 0.0f);
-            const float ih = fmaxf(fminf(py2, s_y2[j]) - fmaxf(py1, s_y1[j]), 0.0f);
-            const float inter = iw * ih;
-            const float uni = area_p + s_area[j] - inter;
-            max_iou = fmaxf(max_iou, inter / (uni + 1e-7f));
-        }
+        const float tc = t[4];
+        const PredBox pb = decode_lane(p, s, a, row, col, t);              // loss.py:195-212: no xyscale here, unlike the inference decode
+        const float px1 = pb.x1, py1 = pb.y1, px2 = pb.x2, py2 = pb.y2, area_p = pb.pw * pb.ph;
         const int ri = s_resp[tid];
         const float respond = ri >= 0 ? 1.0f : 0.0f;
-        const float bgd = (1.0f - respond) * (max_iou < p.thresh ? 1.0f : 0.0f);
+        const float bgd = (1.0f - respond) * (max_iou(tb, nb, pb) < p.thresh ? 1.0f : 0.0f);
         const float d = respond - sigmoidf(tc);
         const float bce = bce_logits(tc, respond);
         conf_t = (d * d) * (respond * bce + bgd * bce);
         if (ri >= 0) {
-            const int32_t* r = recs + (size_t)ri * p.rw;
+            const int32_t* r = p.records + ((size_t)img * p.mb + ri) * p.rw;
             const float lx = __int_as_float(r[4]), ly = __int_as_float(r[5]), lw = __int_as_float(r[6]), lh = __int_as_float(r[7]);
             const float area_l = lw * lh;
             const float lx1 = lx - lw * 0.5f, ly1 = ly - lh * 0.5f, lx2 = lx + lw * 0.5f, ly2 = ly + lh * 0.5f;

@@ -1,4 +1,5 @@
-// loss_common.h -- device helpers shared by loss.hip (the yolo_loss forward) and head_train.hip (its gradient).
+// loss_common.h -- what the yolo_loss forward (loss.hip) and its gradients (head_train.hip, block_train.hip) share on the device:
+// the image's true boxes in LDS, the record map of a strip, the decode of a lane and its largest IoU.
 #pragma once
 #include "kernels.h"
 
@@ -24,6 +25,72 @@ __device__ inline int compact_valid(bool valid, int* s_wave, int* total) {
 __device__ inline float sigmoidf(float x) { return 1.0f / (1.0f + expf(-x)); }
 // tf.nn.sigmoid_cross_entropy_with_logits, the stable form
 __device__ inline float bce_logits(float x, float z) { return fmaxf(x, 0.0f) - x * z + log1pf(expf(-fabsf(x))); }
+
+
+// The image's true boxes with w > 0 as corners in LDS -> their number (a row with w <= 0 intersects nothing: its IoU is 0, the
+// maximum's starting value).  Called by every thread.
+struct TrueBoxes {
+    float x1[LOSS_THREADS], y1[LOSS_THREADS], x2[LOSS_THREADS], y2[LOSS_THREADS], area[LOSS_THREADS];
+    int wave[4];
+};
+__device__ inline int load_true_boxes(const LossIn& p, int img, TrueBoxes& tb) {
+    const int tid = threadIdx.x;
+    float bx = 0.f, by = 0.f, bw = 0.f, bh = 0.f;
+    if (tid < p.mb) {
+        const float* b = p.xywh + ((size_t)img * p.mb + tid) * 4;
+        bx = b[0]; by = b[1]; bw = b[2]; bh = b[3];
+    }
+    int nb = 0;
+    const int pos = compact_valid(tid < p.mb && bw > 0.f, tb.wave, &nb);
+    if (pos >= 0) {
+        tb.x1[pos] = bx - bw * 0.5f; tb.y1[pos] = by - bh * 0.5f;
+        tb.x2[pos] = bx + bw * 0.5f; tb.y2[pos] = by + bh * 0.5f;
+        tb.area[pos] = bw * bh;
+    }
+    return nb;
+}
+
+// s_resp[k] = the record of lane lane0 + k of scale s (k < nlanes), or -1.  Followed by a __syncthreads of the caller.
+__device__ inline void map_records(const LossIn& p, int img, int s, int lane0, int nlanes, int* s_resp) {
+    const int tid = threadIdx.x;
+    const int gh = p.gh[s], gw = p.gw[s];
+    int count = p.counts[img];
+    count = count < 0 ? 0 : (count > p.mb ? p.mb : count);
+    if (tid < count) {
+        const int32_t* r = p.records + ((size_t)img * p.mb + tid) * p.rw;
+        if (r[0] == s && r[1] >= 0 && r[1] < gh && r[2] >= 0 && r[2] < gw && r[3] >= 0 && r[3] < 3) {
+            const int k = (r[1] * gw + r[2]) * 3 + r[3] - lane0;
+            if (k >= 0 && k < nlanes) s_resp[k] = tid;
+        }
+    }
+}
+
+// The decoded box of a lane, loss.py:206-207 (no xyscale)
+struct PredBox {
+    float sx, sy, pw, ph, x1, y1, x2, y2;
+};
+__device__ inline PredBox decode_lane(const LossIn& p, int s, int a, int row, int col, const float* t) {
+    PredBox b;
+    b.sx = sigmoidf(t[0]); b.sy = sigmoidf(t[1]);
+    const float px = (b.sx + (float)col) * p.stride[s], py = (b.sy + (float)row) * p.stride[s];
+    b.pw = expf(t[2]) * p.anchors[(s * 3 + a) * 2]; b.ph = expf(t[3]) * p.anchors[(s * 3 + a) * 2 + 1];
+    b.x1 = px - b.pw * 0.5f; b.y1 = py - b.ph * 0.5f; b.x2 = px + b.pw * 0.5f; b.y2 = py + b.ph * 0.5f;
+    return b;
+}
+
+// The largest IoU of a lane's decoded box with the image's true boxes, loss.py:166-170
+__device__ inline float max_iou(const TrueBoxes& tb, int nb, const PredBox& b) {
+    const float area_p = b.pw * b.ph;
+    float best = 0.0f;
+    for (int j = 0; j < nb; ++j) {
+        const float iw = fmaxf(fminf(b.x2, tb.x2[j]) - fmaxf(b.x1, tb.x1[j]), 0.0f);
+        const float ih = fmaxf(fminf(b.y2, tb.y2[j]) - fmaxf(b.y1, tb.y1[j]), 0.0f);
+        const float inter = iw * ih;
+        const float uni = area_p + tb.area[j] - inter;
+        best = fmaxf(best, inter / (uni + 1e-7f));
+    }
+    return best;
+}
 
 }  // namespace
 }  // namespace y4

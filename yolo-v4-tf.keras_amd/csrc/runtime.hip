@@ -1181,16 +1181,11 @@ int y4_loss_scratch_floats(y4_handle h, int n, size_t* floats) {
     return Y4_OK;
 }
 
-int y4_loss(y4_handle h, int n, const int32_t* records, const int32_t* counts, const float* xywh, int max_boxes,
-            float iou_loss_thresh, float* scratch, size_t scratch_floats, float* out, void* stream) {
-    if (int r = check_ready(h, n)) return r;
-    Y4_REQUIRE(records && counts && xywh && scratch && out, Y4_EINVAL, "y4_loss: null argument");
-    Y4_REQUIRE(iou_loss_thresh >= 0.f, Y4_EINVAL, "y4_loss: iou_loss_thresh %g", (double)iou_loss_thresh);
-    LossK k{};
+// what y4_loss and the three gradient entry points share: the heads, the loss geometry and one batch's labels
+static void loss_inputs(y4_handle h, LossIn& k, const int32_t* records, const int32_t* counts, const float* xywh, int max_boxes,
+                        float iou_loss_thresh, const float* img_weight) {
     loss_geometry(h, k.gh, k.gw, nullptr);
     k.strips = loss_strips(k.gh, k.gw, k.strip_base);
-    Y4_REQUIRE(scratch_floats >= (size_t)n * k.strips * 3, Y4_ENOMEM, "y4_loss: scratch %zu < %zu floats", scratch_floats,
-               (size_t)n * k.strips * 3);
     for (int i = 0; i < 3; ++i) {
         k.head[i] = (const float*)buf_ptr(h, h->heads[i]);
         k.stride[i] = (float)h->cfg.strides[i];
@@ -1199,7 +1194,19 @@ int y4_loss(y4_handle h, int n, const int32_t* records, const int32_t* counts, c
     k.C = h->cfg.num_classes; k.hcs = h->hcs; k.mb = max_boxes; k.rw = 8 + (k.C + 31) / 32;
     k.thresh = iou_loss_thresh;
     k.input_area = (float)h->H * (float)h->W;          // input_size ** 2 of the reference (loss.py:158); H * W for a rectangle
-    k.records = records; k.counts = counts; k.xywh = xywh; k.partials = scratch; k.out = out;
+    k.records = records; k.counts = counts; k.xywh = xywh; k.imgw = img_weight;
+}
+
+int y4_loss(y4_handle h, int n, const int32_t* records, const int32_t* counts, const float* xywh, int max_boxes,
+            float iou_loss_thresh, float* scratch, size_t scratch_floats, float* out, void* stream) {
+    if (int r = check_ready(h, n)) return r;
+    Y4_REQUIRE(records && counts && xywh && scratch && out, Y4_EINVAL, "y4_loss: null argument");
+    Y4_REQUIRE(iou_loss_thresh >= 0.f, Y4_EINVAL, "y4_loss: iou_loss_thresh %g", (double)iou_loss_thresh);
+    LossK k{};
+    loss_inputs(h, k, records, counts, xywh, max_boxes, iou_loss_thresh, nullptr);
+    Y4_REQUIRE(scratch_floats >= (size_t)n * k.strips * 3, Y4_ENOMEM, "y4_loss: scratch %zu < %zu floats", scratch_floats,
+               (size_t)n * k.strips * 3);
+    k.partials = scratch; k.out = out;
     return loss_launch(k, n, (hipStream_t)stream);
 }
 
@@ -1241,32 +1248,83 @@ int y4_set_retain_head_inputs(y4_handle h, int on) {
     return Y4_OK;
 }
 
-// what the three gradient entry points share: the loss geometry and labels; -> Y4_OK
-static int grad_common(y4_handle h, GradK& k, const int32_t* records, const int32_t* counts, const float* xywh, int max_boxes,
-                       float iou_loss_thresh, const float* img_weight) {
-    loss_geometry(h, k.gh, k.gw, nullptr);
-    k.strips = loss_strips(k.gh, k.gw, k.strip_base);
+// A trainable group: three convs, one per scale, whose float32 records lie back to back in the gradient, master-weight and
+// moment buffers.  A record is [cout biases, if the group trains them][cout x cin x ksize x ksize weights].  (The fragment-order
+// copy of a 3x3 conv's weights needs no column: Layer::has_frag says where one exists, and no 1x1 conv has one.)
+struct Group {
+    const Op* (*op)(y4_handle, int);   // the group's conv of scale i
+    int ksize;
+    bool bias;                         // the record opens with the biases, which reach the packed weights through fold_bn_launch
+    const char *noun, *unit, *grad;    // for messages
+};
+static const Group HEADS{head_op, 1, true, "three head records", "head", "dw"};
+static const Group BLOCKS{block_op, 3, false, "three kernels", "scale", "dk"};
+
+// float offsets of the group's three records and their total
+static size_t group_offsets(y4_handle h, const Group& g, size_t* off) {
+    size_t total = 0;
     for (int i = 0; i < 3; ++i) {
-        k.head[i] = (const float*)buf_ptr(h, h->heads[i]);
-        k.stride[i] = (float)h->cfg.strides[i];
+        const Layer& L = h->layers[g.op(h, i)->conv];
+        if (off) off[i] = total;
+        total += (size_t)L.d.cout * ((g.bias ? 1 : 0) + (size_t)L.d.cin * g.ksize * g.ksize);
     }
-    memcpy(k.anchors, h->cfg.anchors, sizeof(k.anchors));
-    k.C = h->cfg.num_classes; k.hcs = h->hcs; k.mb = max_boxes; k.rw = 8 + (k.C + 31) / 32;
-    k.thresh = iou_loss_thresh;
-    k.input_area = (float)h->H * (float)h->W;
-    k.records = records; k.counts = counts; k.xywh = xywh; k.imgw = img_weight;
+    return total;
+}
+
+// the channels of the group's three convs
+static void group_channels(y4_handle h, const Group& g, int* cin, int* cout) {
+    for (int i = 0; i < 3; ++i) {
+        const Layer& L = h->layers[g.op(h, i)->conv];
+        cin[i] = L.d.cin;
+        if (cout) cout[i] = L.d.cout;
+    }
+}
+
+// the shared front of y4_head_grad / y4_block_grad: the arguments, the labels into k, dense inputs, the size of dw -> offsets
+static int grad_front(y4_handle h, const Group& g, const char* who, GradK& k, const int32_t* records, const int32_t* counts,
+                      const float* xywh, int max_boxes, float iou_loss_thresh, const float* img_weight, const void* scratch,
+                      const float* dw, size_t dw_floats, size_t* off) {
+    Y4_REQUIRE(records && counts && xywh && img_weight && scratch && dw, Y4_EINVAL, "%s: null argument", who);
+    Y4_REQUIRE(iou_loss_thresh >= 0.f, Y4_EINVAL, "%s: iou_loss_thresh %g", who, (double)iou_loss_thresh);
+    loss_inputs(h, k, records, counts, xywh, max_boxes, iou_loss_thresh, img_weight);
+    for (int i = 0; i < 3; ++i)
+        for (const View& v : {head_op(h, i)->in, g.op(h, i)->in})
+            Y4_REQUIRE(v.coff == 0 && v.cstride == v.c, Y4_EINVAL, "%s: %s %d reads a channel slice", who, g.unit, i);
+    const size_t total = group_offsets(h, g, off);
+    Y4_REQUIRE(dw_floats >= total, Y4_ENOMEM, "%s: %s %zu < %zu floats", who, g.grad, dw_floats, total);
     return Y4_OK;
 }
 
-// float offsets of the three head records in the dw / master buffers and their total
-static size_t head_record_offsets(y4_handle h, size_t* off) {
-    size_t total = 0;
+// Adam on the group's master weights and the re-pack: what y4_pack_weights does with these three records (same kernels, same
+// rounding), every packed copy.  A group without biases leaves scale / shift alone: its BatchNormalization is frozen, so what
+// fold_bn made of it at y4_pack_weights is already what a fresh load makes.
+static int adam_step(y4_handle h, const Group& g, const char* who, const float* dw, float* w, float* m, float* v, size_t n_floats,
+                     float lr, float beta1, float beta2, float epsilon, int t, void* stream) {
+    Y4_REQUIRE(dw && w && m && v, Y4_EINVAL, "%s: null argument", who);
+    Y4_REQUIRE(t >= 1, Y4_EINVAL, "%s: step %d (the first step is 1)", who, t);
+    size_t off[3];
+    const size_t total = group_offsets(h, g, off);
+    Y4_REQUIRE(n_floats == total, Y4_EINVAL, "%s: %zu floats, the %s have %zu", who, n_floats, g.noun, total);
+    hipStream_t s = (hipStream_t)stream;
+    const float lr_t = (float)((double)lr * sqrt(1.0 - pow((double)beta2, (double)t)) / (1.0 - pow((double)beta1, (double)t)));
+    if (int r = adam_launch(dw, w, m, v, total, lr_t, beta1, beta2, epsilon, s)) return r;
     for (int i = 0; i < 3; ++i) {
-        const Layer& L = h->layers[head_op(h, i)->conv];
-        if (off) off[i] = total;
-        total += (size_t)L.d.cout * (1 + (size_t)L.d.cin);
+        const Layer& L = h->layers[g.op(h, i)->conv];
+        const float* rec = w + off[i];
+        if (g.bias)
+            if (int r = fold_bn_launch(rec, (float*)(h->wts + L.scale_off), (float*)(h->wts + L.shift_off), L.d.cout, L.cout_pad, 0, s))
+                return r;
+        if (int r = pack_conv_weights(h->cfg.dtype, L.d.cout, L.d.cin, g.ksize, rec + (g.bias ? L.d.cout : 0), h->wts + L.w_off, s)) return r;
+        if (L.has_frag)
+            if (int r = pack_conv_frag32(h->cfg.dtype, L.d.cout, L.d.cin, h->wts + L.w_off, h->wts + L.frag_off, s)) return r;
     }
-    return total;
+    return Y4_OK;
+}
+
+static int check_packed(y4_handle h, const char* who) {
+    if (int r = check_handle(h)) return r;
+    Y4_REQUIRE(h->act && h->wts && h->weights_ready, Y4_ESTATE, "%s: weights not packed (call y4_pack_weights first)", who);
+    return Y4_OK;
 }
 
 int y4_loss_grad(y4_handle h, int n, const int32_t* records, const int32_t* counts, const float* xywh, int max_boxes,
@@ -1275,23 +1333,18 @@ int y4_loss_grad(y4_handle h, int n, const int32_t* records, const int32_t* coun
     Y4_REQUIRE(records && counts && xywh && img_weight && out_s && out_m && out_l, Y4_EINVAL, "y4_loss_grad: null argument");
     Y4_REQUIRE(iou_loss_thresh >= 0.f, Y4_EINVAL, "y4_loss_grad: iou_loss_thresh %g", (double)iou_loss_thresh);
     GradK k{};
-    grad_common(h, k, records, counts, xywh, max_boxes, iou_loss_thresh, img_weight);
+    loss_inputs(h, k, records, counts, xywh, max_boxes, iou_loss_thresh, img_weight);
     k.dense[0] = out_s; k.dense[1] = out_m; k.dense[2] = out_l;
     return loss_grad_launch(k, n, (hipStream_t)stream);
-}
-
-static void head_grad_geometry(y4_handle h, GradK& k) {
-    loss_geometry(h, k.gh, k.gw, nullptr);
-    for (int i = 0; i < 3; ++i) k.cin[i] = h->layers[head_op(h, i)->conv].d.cin;
-    head_grad_strips(k.gh, k.gw, k.pstrip_base, k.pstrips);
 }
 
 int y4_head_grad_scratch_floats(y4_handle h, int n, size_t* floats) {
     if (int r = check_handle(h)) return r;
     Y4_REQUIRE(n >= 1 && floats, Y4_EINVAL, "y4_head_grad_scratch_floats: bad argument");
-    GradK k{};
-    head_grad_geometry(h, k);
-    *floats = head_grad_scratch_floats(k.gh, k.gw, k.cin, n, nullptr);
+    int gh[3], gw[3], cin[3];
+    loss_geometry(h, gh, gw, nullptr);
+    group_channels(h, HEADS, cin, nullptr);
+    *floats = head_grad_scratch_floats(gh, gw, cin, n, nullptr);
     return Y4_OK;
 }
 
@@ -1301,59 +1354,26 @@ int y4_head_grad(y4_handle h, int n, const int32_t* records, const int32_t* coun
     if (int r = check_ready(h, n)) return r;
     Y4_REQUIRE(h->retain_head_in, Y4_ESTATE, "y4_head_grad: the head convs' inputs are not retained (y4_set_retain_head_inputs before "
                "the workspace is bound)");
-    Y4_REQUIRE(records && counts && xywh && img_weight && scratch && dw, Y4_EINVAL, "y4_head_grad: null argument");
-    Y4_REQUIRE(iou_loss_thresh >= 0.f, Y4_EINVAL, "y4_head_grad: iou_loss_thresh %g", (double)iou_loss_thresh);
     GradK k{};
-    grad_common(h, k, records, counts, xywh, max_boxes, iou_loss_thresh, img_weight);
-    head_grad_geometry(h, k);
+    if (int r = grad_front(h, HEADS, "y4_head_grad", k, records, counts, xywh, max_boxes, iou_loss_thresh, img_weight, scratch, dw,
+                           dw_floats, k.dw_off))
+        return r;
+    group_channels(h, HEADS, k.cin, nullptr);
+    head_grad_strips(k.gh, k.gw, k.pstrip_base, k.pstrips);
     const size_t need = head_grad_scratch_floats(k.gh, k.gw, k.cin, n, k.part_base);
     Y4_REQUIRE(scratch_floats >= need, Y4_ENOMEM, "y4_head_grad: scratch %zu < %zu floats", scratch_floats, need);
-    const size_t total = head_record_offsets(h, k.dw_off);
-    Y4_REQUIRE(dw_floats >= total, Y4_ENOMEM, "y4_head_grad: dw %zu < %zu floats", dw_floats, total);
-    for (int i = 0; i < 3; ++i) {
-        const View& v = head_op(h, i)->in;
-        Y4_REQUIRE(v.coff == 0 && v.cstride == v.c, Y4_EINVAL, "y4_head_grad: head %d reads a channel slice", i);
-        k.x[i] = buf_ptr(h, v);
-    }
+    for (int i = 0; i < 3; ++i) k.x[i] = buf_ptr(h, head_op(h, i)->in);
     k.partials = scratch; k.dw = dw; k.accumulate = accumulate != 0;
     return head_grad_launch(h->cfg.dtype, k, n, (hipStream_t)stream);
 }
 
 int y4_head_adam(y4_handle h, const float* dw, float* w, float* m, float* v, size_t n_floats, float lr, float beta1, float beta2,
                  float epsilon, int t, void* stream) {
-    if (int r = check_handle(h)) return r;
-    Y4_REQUIRE(h->act && h->wts && h->weights_ready, Y4_ESTATE, "y4_head_adam: weights not packed (call y4_pack_weights first)");
-    Y4_REQUIRE(dw && w && m && v, Y4_EINVAL, "y4_head_adam: null argument");
-    Y4_REQUIRE(t >= 1, Y4_EINVAL, "y4_head_adam: step %d (the first step is 1)", t);
-    size_t off[3];
-    const size_t total = head_record_offsets(h, off);
-    Y4_REQUIRE(n_floats == total, Y4_EINVAL, "y4_head_adam: %zu floats, the three head records have %zu", n_floats, total);
-    hipStream_t s = (hipStream_t)stream;
-    const float lr_t = (float)((double)lr * sqrt(1.0 - pow((double)beta2, (double)t)) / (1.0 - pow((double)beta1, (double)t)));
-    if (int r = head_adam_launch(dw, w, m, v, total, lr_t, beta1, beta2, epsilon, s)) return r;
-    // the re-pack: what y4_pack_weights does with these three records (same kernels, same rounding)
-    for (int i = 0; i < 3; ++i) {
-        const Layer& L = h->layers[head_op(h, i)->conv];
-        const float* rec = w + off[i];
-        if (int r = fold_bn_launch(rec, (float*)(h->wts + L.scale_off), (float*)(h->wts + L.shift_off), L.d.cout, L.cout_pad, 0, s))
-            return r;
-        if (int r = pack_conv_weights(h->cfg.dtype, L.d.cout, L.d.cin, 1, rec + L.d.cout, h->wts + L.w_off, s)) return r;
-    }
-    return Y4_OK;
+    if (int r = check_packed(h, "y4_head_adam")) return r;
+    return adam_step(h, HEADS, "y4_head_adam", dw, w, m, v, n_floats, lr, beta1, beta2, epsilon, t, stream);
 }
 
 // ---- fine-tuning of the 3x3 convs in front of the heads (block_train.hip)
-
-// float offsets of the three kernels (conv 92 / 100 / 108, cout * cin * 9 each) in the dk / master buffers and their total
-static size_t block_kernel_offsets(y4_handle h, size_t* off) {
-    size_t total = 0;
-    for (int i = 0; i < 3; ++i) {
-        const Layer& L = h->layers[block_op(h, i)->conv];
-        if (off) off[i] = total;
-        total += (size_t)L.d.cout * L.d.cin * 9;
-    }
-    return total;
-}
 
 static int block_check(y4_handle h, const char* who) {
     Y4_REQUIRE(h->cfg.dtype != Y4_F16, Y4_EINVAL, "%s: an f16 handle is not supported (a 16-bit dZ in fp16 needs loss scaling); use f32 or bf16", who);
@@ -1373,7 +1393,7 @@ int y4_block_grad_scratch_bytes(y4_handle h, int n, size_t* bytes) {
     if (int r = block_check(h, "y4_block_grad_scratch_bytes")) return r;
     int gh[3], gw[3], cin[3], cout[3];
     loss_geometry(h, gh, gw, nullptr);
-    for (int i = 0; i < 3; ++i) { const Layer& L = h->layers[block_op(h, i)->conv]; cin[i] = L.d.cin; cout[i] = L.d.cout; }
+    group_channels(h, BLOCKS, cin, cout);
     *bytes = block_grad_scratch_bytes(h->cfg.dtype, n, gh, gw, cin, cout, nullptr, nullptr);
     Y4_REQUIRE(*bytes > 0, Y4_EINVAL, "y4_block_grad_scratch_bytes: a grid row of %d cells does not fit the weight gradient's LDS tile", gw[0]);
     return Y4_OK;
@@ -1386,57 +1406,34 @@ int y4_block_grad(y4_handle h, int n, const int32_t* records, const int32_t* cou
     if (int r = block_check(h, "y4_block_grad")) return r;
     Y4_REQUIRE(h->retain_block_in, Y4_ESTATE, "y4_block_grad: the inputs of convs 92 / 100 / 108 are not retained (retention level 2: "
                "y4_set_retain_head_inputs(h, 2) before the workspace is bound)");
-    Y4_REQUIRE(records && counts && xywh && img_weight && scratch && dk, Y4_EINVAL, "y4_block_grad: null argument");
-    Y4_REQUIRE(((uintptr_t)scratch & 255) == 0, Y4_EINVAL, "y4_block_grad: scratch must be 256-byte aligned");
-    Y4_REQUIRE(iou_loss_thresh >= 0.f, Y4_EINVAL, "y4_block_grad: iou_loss_thresh %g", (double)iou_loss_thresh);
     GradK k{};
-    grad_common(h, k, records, counts, xywh, max_boxes, iou_loss_thresh, img_weight);
     BlockK b{};
-    for (int i = 0; i < 3; ++i) {
-        const Op* ho = head_op(h, i);
-        const Op* bo = block_op(h, i);
-        const Layer& L = h->layers[bo->conv];
-        const Layer& LH = h->layers[ho->conv];
-        Y4_REQUIRE(ho->in.coff == 0 && ho->in.cstride == ho->in.c && bo->in.coff == 0 && bo->in.cstride == bo->in.c, Y4_EINVAL,
-                   "y4_block_grad: scale %d reads a channel slice", i);
-        b.u[i] = buf_ptr(h, bo->in); b.a[i] = buf_ptr(h, ho->in);
-        b.wh[i] = h->wts + LH.w_off; b.bn_scale[i] = (const float*)(h->wts + L.scale_off);
-        b.cin[i] = L.d.cin; b.cout[i] = L.d.cout;
-    }
+    if (int r = grad_front(h, BLOCKS, "y4_block_grad", k, records, counts, xywh, max_boxes, iou_loss_thresh, img_weight, scratch, dk,
+                           dk_floats, b.dk_off))
+        return r;
+    Y4_REQUIRE(((uintptr_t)scratch & 255) == 0, Y4_EINVAL, "y4_block_grad: scratch must be 256-byte aligned");
+    group_channels(h, BLOCKS, b.cin, b.cout);
     block_dgrad_strips(k.gh, k.gw, b.dstrip_base);
     size_t dz_off[3], part_off[3];
     const size_t need = block_grad_scratch_bytes(h->cfg.dtype, n, k.gh, k.gw, b.cin, b.cout, dz_off, part_off);
     Y4_REQUIRE(need > 0, Y4_EINVAL, "y4_block_grad: a grid row of %d cells does not fit the weight gradient's LDS tile", k.gw[0]);
     Y4_REQUIRE(scratch_bytes >= need, Y4_ENOMEM, "y4_block_grad: scratch %zu < %zu bytes", scratch_bytes, need);
-    const size_t total = block_kernel_offsets(h, b.dk_off);
-    Y4_REQUIRE(dk_floats >= total, Y4_ENOMEM, "y4_block_grad: dk %zu < %zu floats", dk_floats, total);
-    for (int i = 0; i < 3; ++i) { b.dz[i] = (char*)scratch + dz_off[i]; b.part[i] = (float*)((char*)scratch + part_off[i]); }
+    for (int i = 0; i < 3; ++i) {
+        const Op* ho = head_op(h, i);
+        const Op* bo = block_op(h, i);
+        b.u[i] = buf_ptr(h, bo->in); b.a[i] = buf_ptr(h, ho->in);
+        b.wh[i] = h->wts + h->layers[ho->conv].w_off; b.bn_scale[i] = (const float*)(h->wts + h->layers[bo->conv].scale_off);
+        b.dz[i] = (char*)scratch + dz_off[i]; b.part[i] = (float*)((char*)scratch + part_off[i]);
+    }
     b.dk = dk; b.accumulate = accumulate != 0;
     return block_grad_launch(h->cfg.dtype, k, b, n, (hipStream_t)stream);
 }
 
 int y4_block_adam(y4_handle h, const float* dk, float* w, float* m, float* v, size_t n_floats, float lr, float beta1, float beta2,
                   float epsilon, int t, void* stream) {
-    if (int r = check_handle(h)) return r;
-    Y4_REQUIRE(h->act && h->wts && h->weights_ready, Y4_ESTATE, "y4_block_adam: weights not packed (call y4_pack_weights first)");
+    if (int r = check_packed(h, "y4_block_adam")) return r;
     if (int r = block_check(h, "y4_block_adam")) return r;
-    Y4_REQUIRE(dk && w && m && v, Y4_EINVAL, "y4_block_adam: null argument");
-    Y4_REQUIRE(t >= 1, Y4_EINVAL, "y4_block_adam: step %d (the first step is 1)", t);
-    size_t off[3];
-    const size_t total = block_kernel_offsets(h, off);
-    Y4_REQUIRE(n_floats == total, Y4_EINVAL, "y4_block_adam: %zu floats, the three kernels have %zu", n_floats, total);
-    hipStream_t s = (hipStream_t)stream;
-    const float lr_t = (float)((double)lr * sqrt(1.0 - pow((double)beta2, (double)t)) / (1.0 - pow((double)beta1, (double)t)));
-    if (int r = head_adam_launch(dk, w, m, v, total, lr_t, beta1, beta2, epsilon, s)) return r;
-    // the re-pack: what y4_pack_weights does with these three kernels (same kernels, same rounding), every packed copy.  The
-    // BatchNormalization is frozen, so the scale / shift fold_bn made of it at y4_pack_weights are already what a fresh load makes.
-    for (int i = 0; i < 3; ++i) {
-        const Layer& L = h->layers[block_op(h, i)->conv];
-        if (int r = pack_conv_weights(h->cfg.dtype, L.d.cout, L.d.cin, 3, w + off[i], h->wts + L.w_off, s)) return r;
-        if (L.has_frag)
-            if (int r = pack_conv_frag32(h->cfg.dtype, L.d.cout, L.d.cin, h->wts + L.w_off, h->wts + L.frag_off, s)) return r;
-    }
-    return Y4_OK;
+    return adam_step(h, BLOCKS, "y4_block_adam", dk, w, m, v, n_floats, lr, beta1, beta2, epsilon, t, stream);
 }
 
 // forward + decode + NMS; when `ev` is given, ev[0] is recorded before the first op and ev[i+1] after op i

@@ -205,21 +205,18 @@ class Yolov4(object):
             raise NotImplementedError("training every layer is out of scope of the MI355X path; fit(..., trainable='heads') "
                                       "fine-tunes the three detection convs on a frozen backbone and neck, "
                                       "trainable='head_blocks' also the 3x3 convs in front of them")
-        blocks = trainable == 'head_blocks'
-        if blocks and self._dtype == 'f16':
+        groups = ('heads', 'blocks') if trainable == 'head_blocks' else ('heads',)
+        if 'blocks' in groups and self._dtype == 'f16':
             raise NotImplementedError("fit(trainable='head_blocks') on an f16 model: a 16-bit gradient in fp16 needs loss scaling; "
                                       "use dtype 'bf16' or 'f32'")
         from .engine import combine_loss
         self._ensure_tuned()
         if getattr(train_data_gen, 'max_boxes', self.max_boxes) != self.max_boxes:
             raise ValueError(f"the generator's max_boxes {train_data_gen.max_boxes} != config['max_boxes'] {self.max_boxes}")
-        eng = self._train_engine(2 if blocks else 1)
+        eng = self._train_engine(2 if 'blocks' in groups else 1)
         torch = eng.torch
-        state = eng.head_state(self._flat)
-        dw = torch.empty((eng.head_floats(),), dtype=torch.float32, device=eng.device)
-        if blocks:
-            bstate = eng.block_state(self._flat)
-            dk = torch.empty((eng.block_floats(),), dtype=torch.float32, device=eng.device)
+        state = {g: eng._group_state(g, self._flat) for g in groups}
+        grad = {g: torch.empty((eng._group_floats(g),), dtype=torch.float32, device=eng.device) for g in groups}
         history = {'loss': []}
         if val_data_gen is not None:
             history['val_loss'] = []
@@ -240,26 +237,23 @@ class Yolov4(object):
                         raise ValueError(f'labels for {count} images, the images are more')
                     eng.forward_device(chunk)
                     labels = eng.assign_device(boxes_dev[i0:i0 + n])
-                    eng.head_grad_device(n, records=labels, iou_loss_thresh=self.iou_loss_thresh, img_weight=weight[i0:i0 + n],
-                                         dw=dw, accumulate=i0 > 0)
-                    if blocks:
-                        eng.block_grad_device(n, records=labels, iou_loss_thresh=self.iou_loss_thresh,
-                                              img_weight=weight[i0:i0 + n], dk=dk, accumulate=i0 > 0)
+                    for g in groups:
+                        eng._group_grad_device(g, n, None, labels, self.iou_loss_thresh, weight[i0:i0 + n], grad[g], i0 > 0)
                     parts.append(eng.loss_device(n, records=labels, iou_loss_thresh=self.iou_loss_thresh))
                     i0 += n
                 if i0 != count:
                     raise ValueError(f'labels for {count} images, but {i0} images')
-                eng.head_adam_step(state, dw, lr=learning_rate)
-                if blocks:
-                    eng.block_adam_step(bstate, dk, lr=learning_rate)
+                # heads first, and every gradient of the batch before the first step: y4_block_grad must see the head weights
+                # the forward used.  The steps share their t.
+                for g in groups:
+                    eng._group_adam_step(g, state[g], grad[g], lr=learning_rate)
                 total += float(combine_loss(torch.cat(parts).cpu().numpy())[0].sum())
                 images += count
             if images == 0:
                 raise ValueError('fit: the generator is empty')
             # the trained heads reach the host stream and the inference engine at the end of every epoch
-            eng.head_weights_to_flat(state, self._flat)
-            if blocks:
-                eng.block_weights_to_flat(bstate, self._flat)
+            for g in groups:
+                eng._group_weights_to_flat(g, state[g], self._flat)
             self.engine.load_weight_blob(self._flat)
             logs = {'loss': total / images}
             if val_data_gen is not None:

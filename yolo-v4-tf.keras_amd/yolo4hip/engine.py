@@ -533,12 +533,8 @@ class Engine:
         = per image and scale the box, confidence and class sums (y4_loss).  Labels: `boxes_dev` [n, max_boxes, 5] (assigned
         on the device), or `records` = the (records, counts, xywh) triple of `assign_device` / `upload_records`."""
         torch = self.torch
-        if (boxes_dev is None) == (records is None):
-            raise ValueError("loss_device: give boxes_dev or records")
-        rec, cnt, xywh = self.assign_device(boxes_dev) if records is None else records
-        if rec.shape[0] != n or cnt.shape[0] != n or xywh.shape[0] != n:
-            raise ValueError(f"labels are for {rec.shape[0]} images, the batch has {n}")
-        thr = float(self.config.get("iou_loss_thresh", 0.5) if iou_loss_thresh is None else iou_loss_thresh)
+        rec, cnt, xywh = self._labels(n, boxes_dev, records)
+        thr = self._thr(iou_loss_thresh)
         fl = C.c_size_t()
         ext.check(self.lib.y4_loss_scratch_floats(self.handle, n, C.byref(fl)))
         scratch = torch.empty((fl.value,), dtype=torch.float32, device=self.device)
@@ -598,17 +594,19 @@ class Engine:
             raise ValueError(f"labels for {count} images, but {i0} images")
         return np.concatenate(parts, axis=0)
 
-    # ---------------------------------------------------------------- head fine-tuning (csrc/head_train.hip)
+    # ---------------------------------------------------------------- fine-tuning (csrc/head_train.hip, csrc/block_train.hip)
     HEAD_CONVS = (93, 101, 109)
-
-    def head_records(self):
-        """[(float offset in the Darknet stream, floats)] of the records of convs 93 / 101 / 109: cout biases, then cout x cin
-        weights.  The gradient, master-weight and moment buffers hold these three records back to back."""
-        lt = self.layer_table()
-        return [(int(lt[i]["weight_offset"]), int(lt[i]["cout"] * (1 + lt[i]["cin"]))) for i in self.HEAD_CONVS]
-
-    def head_floats(self):
-        return sum(n for _, n in self.head_records())
+    BLOCK_CONVS = (92, 100, 108)
+    # A trainable group, in the order a step runs them.  Its record in a conv's part of the Darknet stream: behind `skip`
+    # vectors of cout floats, cout * (bias + cin * ksize^2) floats.  C entry points y4_<name>_grad / _adam and the scratch
+    # query; `grad` is the gradient buffer's name in messages.  keep_scratch: heads take fresh float scratch per call, blocks
+    # keep one byte buffer on the engine (hundreds of MB at batch 32).
+    _GROUPS = {
+        "heads": dict(name="head", convs=HEAD_CONVS, skip=0, bias=1, ksize=1, grad="dw", query="y4_head_grad_scratch_floats",
+                      keep_scratch=False),
+        "blocks": dict(name="block", convs=BLOCK_CONVS, skip=4, bias=0, ksize=3, grad="dk", query="y4_block_grad_scratch_bytes",
+                       keep_scratch=True),
+    }
 
     def _labels(self, n, boxes_dev, records):
         if (boxes_dev is None) == (records is None):
@@ -617,6 +615,9 @@ class Engine:
         if rec.shape[0] != n or cnt.shape[0] != n or xywh.shape[0] != n:
             raise ValueError(f"labels are for {rec.shape[0]} images, the batch has {n}")
         return rec, cnt, xywh
+
+    def _thr(self, iou_loss_thresh):
+        return float(self.config.get("iou_loss_thresh", 0.5) if iou_loss_thresh is None else iou_loss_thresh)
 
     def _img_weight(self, n, img_weight):
         torch = self.torch
@@ -635,129 +636,131 @@ class Engine:
         torch = self.torch
         rec, cnt, xywh = self._labels(n, boxes_dev, records)
         w = self._img_weight(n, img_weight)
-        thr = float(self.config.get("iou_loss_thresh", 0.5) if iou_loss_thresh is None else iou_loss_thresh)
         outs = [torch.empty((n, gh, gw, self.nout), dtype=torch.float32, device=self.device) for gh, gw in self.grids_hw]
         with torch.cuda.device(self.device):
-            ext.check(self.lib.y4_loss_grad(self.handle, n, ext.ptr(rec), ext.ptr(cnt), ext.ptr(xywh), self._loss_max_boxes(), thr,
-                                            ext.ptr(w), ext.ptr(outs[0]), ext.ptr(outs[1]), ext.ptr(outs[2]), ext.stream_ptr()))
+            ext.check(self.lib.y4_loss_grad(self.handle, n, ext.ptr(rec), ext.ptr(cnt), ext.ptr(xywh), self._loss_max_boxes(),
+                                            self._thr(iou_loss_thresh), ext.ptr(w), ext.ptr(outs[0]), ext.ptr(outs[1]),
+                                            ext.ptr(outs[2]), ext.stream_ptr()))
         return outs
+
+    # ---- one implementation per verb; the public head_* / block_* methods below name the group
+    def _group_records(self, g):
+        g, lt = self._GROUPS[g], self.layer_table()
+        return [(int(lt[i]["weight_offset"] + g["skip"] * lt[i]["cout"]),
+                 int(lt[i]["cout"] * (g["bias"] + lt[i]["cin"] * g["ksize"] ** 2))) for i in g["convs"]]
+
+    def _group_floats(self, g):
+        return sum(n for _, n in self._group_records(g))
+
+    def _group_scratch(self, g, n):
+        torch, g = self.torch, self._GROUPS[g]
+        size = C.c_size_t()
+        ext.check(getattr(self.lib, g["query"])(self.handle, n, C.byref(size)))
+        if not g["keep_scratch"]:
+            return torch.empty((size.value,), dtype=torch.float32, device=self.device)
+        scratch = getattr(self, "_block_scratch", None)
+        if scratch is None or scratch.numel() < size.value:
+            scratch = self._block_scratch = torch.empty((size.value,), dtype=torch.uint8, device=self.device)
+        return scratch
+
+    def _group_grad_device(self, g, n, boxes_dev, records, iou_loss_thresh, img_weight, dw, accumulate):
+        torch = self.torch
+        name, grad, total = self._GROUPS[g]["name"], self._GROUPS[g]["grad"], self._group_floats(g)
+        rec, cnt, xywh = self._labels(n, boxes_dev, records)
+        w = self._img_weight(n, img_weight)
+        if dw is None:
+            if accumulate:
+                raise ValueError(f"{name}_grad_device: accumulate needs the {grad} to add to")
+            dw = torch.empty((total,), dtype=torch.float32, device=self.device)
+        if dw.dtype != torch.float32 or dw.numel() != total or not dw.is_contiguous():
+            raise ValueError(f"{grad} must be a contiguous float32 tensor of {total} elements")
+        scratch = self._group_scratch(g, n)
+        with torch.cuda.device(self.device):
+            ext.check(getattr(self.lib, f"y4_{name}_grad")(
+                self.handle, n, ext.ptr(rec), ext.ptr(cnt), ext.ptr(xywh), self._loss_max_boxes(), self._thr(iou_loss_thresh),
+                ext.ptr(w), ext.ptr(scratch), scratch.numel(), ext.ptr(dw), total, 1 if accumulate else 0, ext.stream_ptr()))
+        return dw
+
+    def _group_state(self, g, flat):
+        torch = self.torch
+        flat = np.asarray(flat, dtype=np.float32)
+        w = np.concatenate([flat[o:o + n] for o, n in self._group_records(g)])
+        w = torch.from_numpy(np.ascontiguousarray(w)).to(self.device)
+        return {"w": w, "m": torch.zeros_like(w), "v": torch.zeros_like(w), "t": 0}
+
+    def _group_adam_step(self, g, state, dw, lr=1e-4, beta1=0.9, beta2=0.999, epsilon=1e-7):
+        state["t"] += 1
+        with self.torch.cuda.device(self.device):
+            ext.check(getattr(self.lib, f"y4_{self._GROUPS[g]['name']}_adam")(
+                self.handle, ext.ptr(dw), ext.ptr(state["w"]), ext.ptr(state["m"]), ext.ptr(state["v"]), state["w"].numel(),
+                float(lr), float(beta1), float(beta2), float(epsilon), int(state["t"]), ext.stream_ptr()))
+
+    def _group_weights_to_flat(self, g, state, flat):
+        w = state["w"].cpu().numpy()
+        pos = 0
+        for o, n in self._group_records(g):
+            flat[o:o + n] = w[pos:pos + n]
+            pos += n
+        return flat
+
+    # ---- the three detection convs
+    def head_records(self):
+        """[(float offset in the Darknet stream, floats)] of the records of convs 93 / 101 / 109: cout biases, then cout x cin
+        weights.  The gradient, master-weight and moment buffers hold these three records back to back."""
+        return self._group_records("heads")
+
+    def head_floats(self):
+        return self._group_floats("heads")
 
     def head_grad_device(self, n, boxes_dev=None, records=None, iou_loss_thresh=None, img_weight=None, dw=None, accumulate=False):
         """y4_head_grad after `forward_device` on n images (an engine with retain_head_inputs): the gradient of
         sum_i img_weight[i] * loss_i w.r.t. the weights and biases of convs 93 / 101 / 109 -> float32 cuda tensor
         [head_floats()] (`head_records` gives the layout), written into `dw` or, with accumulate=True, added to it."""
-        torch = self.torch
-        rec, cnt, xywh = self._labels(n, boxes_dev, records)
-        w = self._img_weight(n, img_weight)
-        thr = float(self.config.get("iou_loss_thresh", 0.5) if iou_loss_thresh is None else iou_loss_thresh)
-        total = self.head_floats()
-        if dw is None:
-            if accumulate:
-                raise ValueError("head_grad_device: accumulate needs the dw to add to")
-            dw = torch.empty((total,), dtype=torch.float32, device=self.device)
-        if dw.dtype != torch.float32 or dw.numel() != total or not dw.is_contiguous():
-            raise ValueError(f"dw must be a contiguous float32 tensor of {total} elements")
-        fl = C.c_size_t()
-        ext.check(self.lib.y4_head_grad_scratch_floats(self.handle, n, C.byref(fl)))
-        scratch = torch.empty((fl.value,), dtype=torch.float32, device=self.device)
-        with torch.cuda.device(self.device):
-            ext.check(self.lib.y4_head_grad(self.handle, n, ext.ptr(rec), ext.ptr(cnt), ext.ptr(xywh), self._loss_max_boxes(), thr,
-                                            ext.ptr(w), ext.ptr(scratch), fl.value, ext.ptr(dw), total, 1 if accumulate else 0,
-                                            ext.stream_ptr()))
-        return dw
+        return self._group_grad_device("heads", n, boxes_dev, records, iou_loss_thresh, img_weight, dw, accumulate)
 
     def head_state(self, flat):
         """The optimiser state for `head_adam_step`: float32 master weights (the three head records of the host stream `flat`,
         uploaded) and zero moments -> {'w', 'm', 'v', 't'}."""
-        torch = self.torch
-        flat = np.asarray(flat, dtype=np.float32)
-        w = np.concatenate([flat[o:o + n] for o, n in self.head_records()])
-        w = torch.from_numpy(np.ascontiguousarray(w)).to(self.device)
-        return {"w": w, "m": torch.zeros_like(w), "v": torch.zeros_like(w), "t": 0}
+        return self._group_state("heads", flat)
 
     def head_adam_step(self, state, dw, lr=1e-4, beta1=0.9, beta2=0.999, epsilon=1e-7):
         """y4_head_adam: one step of Keras' Adam on the master weights of `state` with the gradient `dw`, and the re-pack: the
         next forward of this engine runs on the updated head convs."""
-        state["t"] += 1
-        with self.torch.cuda.device(self.device):
-            ext.check(self.lib.y4_head_adam(self.handle, ext.ptr(dw), ext.ptr(state["w"]), ext.ptr(state["m"]), ext.ptr(state["v"]),
-                                            state["w"].numel(), float(lr), float(beta1), float(beta2), float(epsilon),
-                                            int(state["t"]), ext.stream_ptr()))
+        self._group_adam_step("heads", state, dw, lr, beta1, beta2, epsilon)
 
     def head_weights_to_flat(self, state, flat):
         """Copy the master weights of `state` back into the host stream `flat` (in place)."""
-        w = state["w"].cpu().numpy()
-        pos = 0
-        for o, n in self.head_records():
-            flat[o:o + n] = w[pos:pos + n]
-            pos += n
-        return flat
+        return self._group_weights_to_flat("heads", state, flat)
 
-    # ---------------------------------------------------------------- the 3x3 convs in front of the heads (csrc/block_train.hip)
-    BLOCK_CONVS = (92, 100, 108)
-
+    # ---- the 3x3 convs in front of them
     def block_records(self):
         """[(float offset in the Darknet stream, floats)] of the KERNELS of convs 92 / 100 / 108: cout x cin x 3 x 3 weights in
         (out, in, kh, kw) order, behind the layer's four BatchNormalization vectors.  The gradient, master-weight and moment
         buffers hold these three kernels back to back."""
-        lt = self.layer_table()
-        return [(int(lt[i]["weight_offset"] + 4 * lt[i]["cout"]), int(lt[i]["cout"] * lt[i]["cin"] * 9)) for i in self.BLOCK_CONVS]
+        return self._group_records("blocks")
 
     def block_floats(self):
-        return sum(n for _, n in self.block_records())
+        return self._group_floats("blocks")
 
     def block_grad_device(self, n, boxes_dev=None, records=None, iou_loss_thresh=None, img_weight=None, dk=None, accumulate=False):
         """y4_block_grad after `forward_device` on n images (an engine with retain_head_inputs=2), BEFORE the step's
         `head_adam_step`: the gradient of sum_i img_weight[i] * loss_i w.r.t. the kernels of convs 92 / 100 / 108 -> float32 cuda
         tensor [block_floats()] (`block_records` gives the layout), written into `dk` or, with accumulate=True, added to it."""
-        torch = self.torch
-        rec, cnt, xywh = self._labels(n, boxes_dev, records)
-        w = self._img_weight(n, img_weight)
-        thr = float(self.config.get("iou_loss_thresh", 0.5) if iou_loss_thresh is None else iou_loss_thresh)
-        total = self.block_floats()
-        if dk is None:
-            if accumulate:
-                raise ValueError("block_grad_device: accumulate needs the dk to add to")
-            dk = torch.empty((total,), dtype=torch.float32, device=self.device)
-        if dk.dtype != torch.float32 or dk.numel() != total or not dk.is_contiguous():
-            raise ValueError(f"dk must be a contiguous float32 tensor of {total} elements")
-        nb = C.c_size_t()
-        ext.check(self.lib.y4_block_grad_scratch_bytes(self.handle, n, C.byref(nb)))
-        scratch = getattr(self, "_block_scratch", None)                  # kept: hundreds of MB at batch 32
-        if scratch is None or scratch.numel() < nb.value:
-            scratch = self._block_scratch = torch.empty((nb.value,), dtype=torch.uint8, device=self.device)
-        with torch.cuda.device(self.device):
-            ext.check(self.lib.y4_block_grad(self.handle, n, ext.ptr(rec), ext.ptr(cnt), ext.ptr(xywh), self._loss_max_boxes(), thr,
-                                             ext.ptr(w), ext.ptr(scratch), scratch.numel(), ext.ptr(dk), total, 1 if accumulate else 0,
-                                             ext.stream_ptr()))
-        return dk
+        return self._group_grad_device("blocks", n, boxes_dev, records, iou_loss_thresh, img_weight, dk, accumulate)
 
     def block_state(self, flat):
         """The optimiser state for `block_adam_step`: float32 master kernels (the three kernels of the host stream `flat`,
         uploaded) and zero moments -> {'w', 'm', 'v', 't'}."""
-        torch = self.torch
-        flat = np.asarray(flat, dtype=np.float32)
-        w = np.concatenate([flat[o:o + n] for o, n in self.block_records()])
-        w = torch.from_numpy(np.ascontiguousarray(w)).to(self.device)
-        return {"w": w, "m": torch.zeros_like(w), "v": torch.zeros_like(w), "t": 0}
+        return self._group_state("blocks", flat)
 
     def block_adam_step(self, state, dk, lr=1e-4, beta1=0.9, beta2=0.999, epsilon=1e-7):
         """y4_block_adam: one step of Keras' Adam on the master kernels of `state` with the gradient `dk`, and the re-pack: the
         next forward of this engine runs on the updated convs 92 / 100 / 108."""
-        state["t"] += 1
-        with self.torch.cuda.device(self.device):
-            ext.check(self.lib.y4_block_adam(self.handle, ext.ptr(dk), ext.ptr(state["w"]), ext.ptr(state["m"]), ext.ptr(state["v"]),
-                                             state["w"].numel(), float(lr), float(beta1), float(beta2), float(epsilon),
-                                             int(state["t"]), ext.stream_ptr()))
+        self._group_adam_step("blocks", state, dk, lr, beta1, beta2, epsilon)
 
     def block_weights_to_flat(self, state, flat):
         """Copy the master kernels of `state` back into the host stream `flat` (in place); the BatchNormalization vectors stay."""
-        w = state["w"].cpu().numpy()
-        pos = 0
-        for o, n in self.block_records():
-            flat[o:o + n] = w[pos:pos + n]
-            pos += n
-        return flat
+        return self._group_weights_to_flat("blocks", state, flat)
 
     def predict_stream(self, batches, with_indices=False, in_flight=None, letterbox=False, pad_value=128):
         """Pipelined `inference_model.predict` over an iterable of uint8 batches ([n,h,w,3] numpy arrays or pinned torch
