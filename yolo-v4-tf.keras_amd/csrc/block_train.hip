@@ -319,11 +319,6 @@ size_t block_grad_scratch_bytes(int dtype, int n, const int* gh, const int* gw, 
 
 template <int DT>
 static int block_grad_launch_t(const GradK& k, const BlockK& b, int n, hipStream_t stream) {
-    static PerDeviceOnce once;
-    if (const uint64_t bit = once.due()) {
-        Y4_CHECK_HIP(hipFuncSetAttribute((const void*)block_wgrad_kernel<DT>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        once.mark(bit);
-    }
     WgradK w[3]{};
     size_t lds[3];
     for (int s = 0; s < 3; ++s) {                                         // every check before the first launch
@@ -335,7 +330,7 @@ static int block_grad_launch_t(const GradK& k, const BlockK& b, int n, hipStream
     const size_t sp_bytes = (size_t)DG_PIX * 3 * (k.C + 5) * sizeof(float);
     hipLaunchKernelGGL(block_dgrad_kernel<DT>, dim3(nstrips, n), dim3(LOSS_THREADS), sp_bytes, stream, k, b);
     for (int s = 0; s < 3; ++s) {
-        hipLaunchKernelGGL(block_wgrad_kernel<DT>, dim3(w[s].cin / WG_TILE, w[s].cout / WG_TILE, w[s].splits), dim3(256), lds[s], stream, w[s]);
+        if (int r = launch_lds<block_wgrad_kernel<DT>>(160 * 1024, dim3(w[s].cin / WG_TILE, w[s].cout / WG_TILE, w[s].splits), dim3(256), lds[s], stream, w[s])) return r;
         const size_t total = (size_t)9 * w[s].cout * w[s].cin;
         hipLaunchKernelGGL(block_wgrad_finish_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, (const float*)b.part[s],
                            b.dk + b.dk_off[s], w[s].cout, w[s].cin, w[s].splits, b.accumulate);

@@ -44,6 +44,38 @@ struct PerDeviceOnce {
     void mark(uint64_t bit) { done.fetch_or(bit, std::memory_order_release); }
 };
 
+// One launch of kernel KERN with `lds` bytes of dynamic LDS: raises KERN's MaxDynamicSharedMemorySize to `lds_limit` the first time on
+// each device (0: the 48 KB default is enough, leave it alone), launches, reports a launch error.  The flag is a static of this
+// instantiation, i.e. one per kernel.
+template <auto KERN, class... Args>
+static int launch_lds(int lds_limit, dim3 grid, dim3 block, size_t lds, hipStream_t stream, const Args&... args) {
+    if (lds_limit > 0) {
+        static PerDeviceOnce once;
+        if (const uint64_t bit = once.due()) {
+            Y4_CHECK_HIP(hipFuncSetAttribute((const void*)KERN, hipFuncAttributeMaxDynamicSharedMemorySize, lds_limit));
+            once.mark(bit);
+        }
+    }
+    hipLaunchKernelGGL(KERN, grid, block, lds, stream, args...);
+    Y4_CHECK_HIP(hipGetLastError());
+    return Y4_OK;
+}
+
+// *n = compute units of the current device (asked once per device ordinal): what the persistent kernels size their grids by
+inline int cu_count(int* n) {
+    static std::atomic<int> n_cus[64];
+    int dev = 0;
+    Y4_CHECK_HIP(hipGetDevice(&dev));
+    int v = n_cus[dev & 63].load(std::memory_order_relaxed);
+    if (v == 0) {
+        Y4_CHECK_HIP(hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev));
+        if (v <= 0) v = 256;
+        n_cus[dev & 63].store(v, std::memory_order_relaxed);
+    }
+    *n = v;
+    return Y4_OK;
+}
+
 inline int elem_size(int dtype) { return dtype == Y4_F32 ? 4 : 2; }
 inline int64_t round_up(int64_t x, int64_t m) { return (x + m - 1) / m * m; }
 

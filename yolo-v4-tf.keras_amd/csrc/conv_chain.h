@@ -47,7 +47,7 @@ template <int CFG> struct ChainShape {
     static constexpr int LDS_BYTES = T0_BYTES + T1_BYTES;
 };
 
-// Tail weights (fragment order, pack_tail_kernel) -> LDS, issued at kernel start with buffer_load ... lds so the copies
+// Tail weights (fragment order: pack_frag16, conv_igemm.hip) -> LDS, issued at kernel start with buffer_load ... lds so the copies
 // fly under the head conv's K loop; the K loop's last iteration waits for vmcnt(0) and takes a workgroup barrier, after
 // which every wave may read them.
 template <int CFG, int NWAVES>

@@ -395,15 +395,7 @@ template <int DT, int BM, int BN, int WM, int WN, int KC, int OCC>
 static int launch_halo2_cfg(const ConvK& k, hipStream_t stream) {
     const size_t lds = halo2_lds_bytes(k.h_rows, k.h_pitch, KC);
     Y4_REQUIRE(lds <= (size_t)(160 * 1024 / OCC), Y4_EINVAL, "conv2d: halo2 tile needs %zu bytes of LDS", lds);
-    auto kern = conv_halo2_kernel<DT, BM, BN, WM, WN, KC, OCC>;
-    static PerDeviceOnce once;
-    if (const uint64_t bit = once.due()) {
-        Y4_CHECK_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 / OCC));
-        once.mark(bit);
-    }
-    hipLaunchKernelGGL(kern, dim3(k.grid_m * k.grid_n), dim3(256), lds, stream, k);
-    Y4_CHECK_HIP(hipGetLastError());
-    return Y4_OK;
+    return launch_lds<conv_halo2_kernel<DT, BM, BN, WM, WN, KC, OCC>>(160 * 1024 / OCC, dim3(k.grid_m * k.grid_n), dim3(256), lds, stream, k);
 }
 
 template <int DT>

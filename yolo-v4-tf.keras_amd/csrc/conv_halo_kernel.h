@@ -281,15 +281,7 @@ static int launch_halo_cfg(const ConvK& k, hipStream_t stream) {
         static_assert(!PAIR || (BN / 64) * BM * 128 + 2 * BN * 128 <= 160 * 1024, "LDS budget of the pair phase");
         lds = lds > lds_pair ? lds : lds_pair;
     }
-    auto kern = conv_halo_kernel<DT, BM, BN, WM, WN, PAIR>;
-    static PerDeviceOnce once;
-    if (const uint64_t bit = once.due()) {
-        Y4_CHECK_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        once.mark(bit);
-    }
-    hipLaunchKernelGGL(kern, dim3(k.grid_m * k.grid_n), dim3(64 * WM * WN), lds, stream, k);
-    Y4_CHECK_HIP(hipGetLastError());
-    return Y4_OK;
+    return launch_lds<conv_halo_kernel<DT, BM, BN, WM, WN, PAIR>>(160 * 1024, dim3(k.grid_m * k.grid_n), dim3(64 * WM * WN), lds, stream, k);
 }
 
 template <int DT>

@@ -11,31 +11,28 @@ int conv_launch_f16(int tile, const ConvK& k, hipStream_t s);
 int conv_launch_bf16_fused(int tile, const ConvK& k, hipStream_t s);
 int conv_launch_f16_fused(int tile, const ConvK& k, hipStream_t s);
 
+// the 16-bit-only kernel families have one translation unit per dtype: the dtype's launcher, or a refusal of float32
+template <class F, class... A>
+static int launch_16bit(int dtype, const char* who, F* bf16, F* f16, const A&... a) {
+    if (dtype == Y4_BF16) return bf16(a...);
+    if (dtype == Y4_F16) return f16(a...);
+    set_error("conv2d: %s 16-bit only", who);
+    return Y4_EINVAL;
+}
 int conv_p8_launch_bf16(int bm, int nst, const ConvK& k, hipStream_t s);
 int conv_p8_launch_f16(int bm, int nst, const ConvK& k, hipStream_t s);
-int conv_p8_launch(int dtype, int bm, int nst, const ConvK& k, hipStream_t s) {
-    if (dtype == Y4_BF16) return conv_p8_launch_bf16(bm, nst, k, s);
-    if (dtype == Y4_F16) return conv_p8_launch_f16(bm, nst, k, s);
-    set_error("conv2d: the phased kernel is 16-bit only");
-    return Y4_EINVAL;
-}
-
 int conv_halo_launch_bf16(int bm, int bn, const ConvK& k, hipStream_t s);
 int conv_halo_launch_f16(int bm, int bn, const ConvK& k, hipStream_t s);
-int conv_halo_launch(int dtype, int bm, int bn, const ConvK& k, hipStream_t s) {
-    if (dtype == Y4_BF16) return conv_halo_launch_bf16(bm, bn, k, s);
-    if (dtype == Y4_F16) return conv_halo_launch_f16(bm, bn, k, s);
-    set_error("conv2d: halo tiles are 16-bit only");
-    return Y4_EINVAL;
-}
-
 int conv_halo2_launch_bf16(int tile, const ConvK& k, hipStream_t s);
 int conv_halo2_launch_f16(int tile, const ConvK& k, hipStream_t s);
+int conv_p8_launch(int dtype, int bm, int nst, const ConvK& k, hipStream_t s) {
+    return launch_16bit(dtype, "the phased kernel is", conv_p8_launch_bf16, conv_p8_launch_f16, bm, nst, k, s);
+}
+int conv_halo_launch(int dtype, int bm, int bn, const ConvK& k, hipStream_t s) {
+    return launch_16bit(dtype, "halo tiles are", conv_halo_launch_bf16, conv_halo_launch_f16, bm, bn, k, s);
+}
 int conv_halo2_launch(int dtype, int tile, const ConvK& k, hipStream_t s) {
-    if (dtype == Y4_BF16) return conv_halo2_launch_bf16(tile, k, s);
-    if (dtype == Y4_F16) return conv_halo2_launch_f16(tile, k, s);
-    set_error("conv2d: halo2 tiles are 16-bit only");
-    return Y4_EINVAL;
+    return launch_16bit(dtype, "halo2 tiles are", conv_halo2_launch_bf16, conv_halo2_launch_f16, tile, k, s);
 }
 
 int conv_tile_count() { return kNumTiles; }
@@ -49,6 +46,13 @@ bool weight_touch_enabled() {
 static bool tile_ok(const TileCfg& tc, int dtype, int cin, int cout_pad) {
     const int bk = tc.bkb / elem_size(dtype);
     return cin % bk == 0 && cout_pad % tc.bn == 0;
+}
+
+// the band geometry of a halo / halo2 tile (conv_tiles.h) as the kernels read it; one workgroup row per band
+static void set_bands(ConvK& k, const HaloPlan& hp, int n) {
+    k.h_rows = hp.rows; k.h_bands = hp.bands; k.h_pitch = hp.pitch;
+    k.h_div_pitch = fastdiv_make((uint32_t)hp.pitch); k.h_div_bands = fastdiv_make((uint32_t)hp.bands);
+    k.grid_m = n * hp.bands;
 }
 
 // Heuristic tile choice (speed only; every valid tile gives the same result up to fp32 summation order
@@ -180,9 +184,7 @@ int conv2d_launch(const y4_conv_desc* d, const char* zero_page, hipStream_t stre
                        !d->out_f32 && !d->out2 && halo_plan(tc.bm, tc.bn, d->h, d->w, &hp),
                    Y4_EINVAL, "conv2d: tile %d (halo, %d x %d) does not fit this conv (3x3 stride 1, 16-bit, cin %% 64 == 0, %d x %d map)", tile,
                    tc.bm, tc.bn, d->h, d->w);
-        k.h_rows = hp.rows; k.h_bands = hp.bands; k.h_pitch = hp.pitch;
-        k.h_div_pitch = fastdiv_make((uint32_t)hp.pitch); k.h_div_bands = fastdiv_make((uint32_t)hp.bands);
-        k.grid_m = d->n * hp.bands;
+        set_bands(k, hp, d->n);
         k.h_xmap = wt_bytes > ((int64_t)3 << 20) ? 1 : 0;
         { static const int abl = [] { const char* e = getenv("HALO_ABL"); return e ? atoi(e) : 0; }(); k.h_abl = abl; }      // (read only by a -DHALO_ABLATIONS=1 build of the kernel)
     }
@@ -195,9 +197,7 @@ int conv2d_launch(const y4_conv_desc* d, const char* zero_page, hipStream_t stre
                    tc.bm, tc.bn, d->h, d->w);
         Y4_REQUIRE(d->wt_frag, Y4_EINVAL, "conv2d: tile %d (halo2) needs the fragment-ordered weights (y4_conv_desc.wt_frag, y4_pack_conv_frag32)", tile);
         k.wfrag = (const char*)d->wt_frag; k.wfrag_bytes = (unsigned)wt_bytes;
-        k.h_rows = hp.rows; k.h_bands = hp.bands; k.h_pitch = hp.pitch;
-        k.h_div_pitch = fastdiv_make((uint32_t)hp.pitch); k.h_div_bands = fastdiv_make((uint32_t)hp.bands);
-        k.grid_m = d->n * hp.bands;
+        set_bands(k, hp, d->n);
         // (the halo kernel's XCD <-> channel tile map for weights larger than an L2 is OFF here: these kernels look two taps ahead for their
         //  weights, and measured L2-cold -- as in a step -- the map costs 512 -> 1024 @19^2 88 -> 106 us and 256 -> 512 @38^2 95 -> 100;
         //  Y4_H2_XMAP=1 turns it on for experiments)
@@ -270,20 +270,57 @@ int pack_conv_weights(int dtype, int cout, int cin, int ksize, const float* oihw
     return Y4_OK;
 }
 
-// 1x1 conv weights (cout, cin, 1, 1) -> ready-made MFMA A fragments for conv_chain.h (natural K order, chunked
-// output-channel layout): out[((s*NREP2 + j2)*64 + lane)][e] = W[ch2][32*s + 8*(lane>>4) + e],
-// ch2 = ((j2>>1)*4 + (i>>2))*8 + (j2&1)*4 + (i&3), i = lane & 15, NREP2 = cout/16, s < cin/32.
+// Darknet (cout, cin, k, k) float32 -> ready-made A operands of v_mfma_f32_16x16x32 ("fragment order"), one KB per (k-step, 16-row
+// fragment): what the chain tails (conv_chain.h), csp_stage_kernel and resblock_kernel copy lane-linearly into LDS or registers.
+//     out[((s * NREP + j) * 64 + lane) * 8 + e] = W[ch][ci][tap],     NREP = cout / 16, i = lane & 15,
+//     ch = ((j >> 1) * 4 + (i >> 2)) * 8 + (j & 1) * 4 + (i & 3)      (the chunked output-channel layout of conv_common.h)
+//     ci = 32 * cb + 8 * (lane >> 4) + e
+// The k-steps s of 32 channels run in the canonical K order of common.h with KC = min(cin, 64): 64-channel chunk -> tap -> the
+// chunk's 32-channel halves, i.e. s = (chunk * k*k + tap) * (KC / 32) + half, cb = chunk * (KC / 32) + half.  (A 1x1 conv: cb = s.)
 template <int DT>
-__global__ void pack_tail_kernel(const float* __restrict__ w, typename Elem<DT>::type* __restrict__ out, int cout, int cin) {
-    const int total = cout * cin, nrep2 = cout / 16;
+__global__ void pack_frag16_kernel(const float* __restrict__ w, typename Elem<DT>::type* __restrict__ out, int cout, int cin, int kk) {
+    const int nrep = cout / 16, sps = (cin < K_CHUNK ? cin : K_CHUNK) / 32, total = cout * cin * kk;
     for (int idx = blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += gridDim.x * blockDim.x) {
-        const int e = idx & 7, lane = (idx >> 3) & 63;
-        const int r = idx >> 9;
-        const int j2 = r % nrep2, s = r / nrep2;
+        const int e = idx & 7, lane = (idx >> 3) & 63, r = idx >> 9;
+        const int j = r % nrep, s = r / nrep;
+        const int step = s / sps, half = s - step * sps, chunk = step / kk, tap = step - chunk * kk, cb = chunk * sps + half;
         const int i = lane & 15, g = lane >> 4;
-        const int ch2 = ((j2 >> 1) * 4 + (i >> 2)) * 8 + (j2 & 1) * 4 + (i & 3);
-        out[idx] = Elem<DT>::st(w[ch2 * cin + 32 * s + 8 * g + e]);
+        const int ch = ((j >> 1) * 4 + (i >> 2)) * 8 + (j & 1) * 4 + (i & 3);
+        const int ci = 32 * cb + 8 * g + e;
+        out[idx] = Elem<DT>::st(w[((int64_t)ch * cin + ci) * kk + tap]);
     }
+}
+
+int pack_frag16(int dtype, int cout, int cin, int ksize, const float* oihw, void* dst, hipStream_t stream) {
+    const int kk = ksize * ksize, kc = cin < K_CHUNK ? cin : K_CHUNK;
+    Y4_REQUIRE(cout > 0 && cout % 16 == 0 && cin > 0 && cin % 32 == 0 && cin % kc == 0 && (ksize == 1 || ksize == 3) && oihw && dst, Y4_EINVAL,
+               "pack_frag16: cout %d cin %d ksize %d", cout, cin, ksize);
+    const dim3 grid((cout * cin * kk + 255) / 256), block(256);
+    switch (dtype) {
+        case Y4_BF16: hipLaunchKernelGGL(pack_frag16_kernel<Y4_BF16>, grid, block, 0, stream, oihw, (uint16_t*)dst, cout, cin, kk); break;
+        case Y4_F16: hipLaunchKernelGGL(pack_frag16_kernel<Y4_F16>, grid, block, 0, stream, oihw, (_Float16*)dst, cout, cin, kk); break;
+        default: set_error("pack_frag16: 16-bit dtypes only (got %d)", dtype); return Y4_EINVAL;
+    }
+    Y4_CHECK_HIP(hipGetLastError());
+    return Y4_OK;
+}
+
+// src[0], src[1], ... (c <= 128 floats each: a conv's folded scale, its shift, the next conv's ...) -> consecutive slots of c floats:
+// the affine part of the stage and residual-block blobs
+struct AffineSrc { const float* p[4]; int n; };
+__global__ void copy_affine_kernel(const AffineSrc src, float* dst, int c) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < c)
+        for (int k = 0; k < src.n; ++k) dst[k * c + i] = src.p[k][i];
+}
+
+int copy_affine(int c, std::initializer_list<const float*> src, float* dst, hipStream_t stream) {
+    Y4_REQUIRE(c > 0 && c <= 128 && src.size() <= 4 && dst, Y4_EINVAL, "copy_affine: %d channels, %d tables", c, (int)src.size());
+    AffineSrc a{};
+    for (const float* p : src) a.p[a.n++] = p;
+    hipLaunchKernelGGL(copy_affine_kernel, dim3(1), dim3(128), 0, stream, a, dst, c);
+    Y4_CHECK_HIP(hipGetLastError());
+    return Y4_OK;
 }
 
 // packed 3x3 weights [cout_pad][cin/64][9][64] -> MFMA-fragment order of the halo2 tiles (conv_halo2_kernel.h):
@@ -320,14 +357,8 @@ int pack_conv_frag32(int dtype, int cout, int cin, const void* packed, void* fra
 int pack_tail_weights(int dtype, int cout, int cin, const float* oihw, void* packed, hipStream_t stream) {
     Y4_REQUIRE((cout == 32 || cout == 64 || cout == 128) && (cin == 64 || cin == 128) && oihw && packed, Y4_EINVAL,
                "pack_tail_weights: cout %d cin %d", cout, cin);
-    const int blocks = (cout * cin + 255) / 256;
-    switch (dtype) {
-        case Y4_BF16: hipLaunchKernelGGL(pack_tail_kernel<Y4_BF16>, dim3(blocks), dim3(256), 0, stream, oihw, (uint16_t*)packed, cout, cin); break;
-        case Y4_F16: hipLaunchKernelGGL(pack_tail_kernel<Y4_F16>, dim3(blocks), dim3(256), 0, stream, oihw, (_Float16*)packed, cout, cin); break;
-        default: set_error("pack_tail_weights: 16-bit dtypes only (got %d)", dtype); return Y4_EINVAL;
-    }
-    Y4_CHECK_HIP(hipGetLastError());
-    return Y4_OK;
+    Y4_REQUIRE(dtype == Y4_BF16 || dtype == Y4_F16, Y4_EINVAL, "pack_tail_weights: 16-bit dtypes only (got %d)", dtype);
+    return pack_frag16(dtype, cout, cin, 1, oihw, packed, stream);
 }
 
 }  // namespace y4

@@ -662,26 +662,14 @@ static int launch_cfg(const ConvK& k, hipStream_t stream) {
     constexpr int lds_pair = PAIR ? (BN / 64) * BM * 128 + 2 * BN * 128 : 0;     // tile panels + two weight stages of the tail
     constexpr int lds = lds_main > lds_pair ? lds_main : lds_pair;
     static_assert(lds <= 160 * 1024, "LDS budget");
-    auto kern = conv_igemm_kernel<DT, BM, BN, WM, WN, BKB, NST, CHAIN, PAIR>;
-    if (lds > 48 * 1024) {
-        static PerDeviceOnce once;
-        if (const uint64_t bit = once.due()) {
-            Y4_CHECK_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-            once.mark(bit);
-        }
+    constexpr int lds_limit = lds > 48 * 1024 ? lds : 0;
+    int grid = k.grid_m * k.grid_n;
+    if (k.ksplit > 1) {
+        Y4_REQUIRE(CHAIN == 0 && !PAIR && NST != 12 && NST != 32, Y4_EINVAL, "conv2d: this tile / fusion cannot run split-K");
+        const int nwg = k.grid_m * k.grid_n, per_xcd = (nwg >> 3) + ((nwg & 7) ? 1 : 0);
+        grid = 8 * per_xcd * k.ksplit;
     }
-    if constexpr (CHAIN == 0 && !PAIR && NST != 12 && NST != 32) {
-        if (k.ksplit > 1) {
-            const int nwg = k.grid_m * k.grid_n, per_xcd = (nwg >> 3) + ((nwg & 7) ? 1 : 0);
-            hipLaunchKernelGGL(kern, dim3(8 * per_xcd * k.ksplit), dim3(64 * WM * WN), lds, stream, k);
-            Y4_CHECK_HIP(hipGetLastError());
-            return Y4_OK;
-        }
-    }
-    Y4_REQUIRE(k.ksplit <= 1, Y4_EINVAL, "conv2d: this tile / fusion cannot run split-K");
-    hipLaunchKernelGGL(kern, dim3(k.grid_m * k.grid_n), dim3(64 * WM * WN), lds, stream, k);
-    Y4_CHECK_HIP(hipGetLastError());
-    return Y4_OK;
+    return launch_lds<conv_igemm_kernel<DT, BM, BN, WM, WN, BKB, NST, CHAIN, PAIR>>(lds_limit, dim3(grid), dim3(64 * WM * WN), lds, stream, k);
 }
 
 // the phased kernel (conv_p8_kernel.h) lives in its own translation units (conv_p8_<dt>.hip), the halo kernel

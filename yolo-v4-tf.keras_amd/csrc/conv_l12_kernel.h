@@ -234,15 +234,7 @@ __global__ __launch_bounds__(768, 1) void conv_l12_kernel(const ConvK p) {
 template <int DT>
 static int launch_l12(const ConvK& k, hipStream_t stream) {
     constexpr int lds = 2 * (192 + 256) * 128;
-    auto kern = conv_l12_kernel<DT>;
-    static PerDeviceOnce once;
-    if (const uint64_t bit = once.due()) {
-        Y4_CHECK_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        once.mark(bit);
-    }
-    hipLaunchKernelGGL(kern, dim3(k.grid_m * k.grid_n), dim3(768), lds, stream, k);
-    Y4_CHECK_HIP(hipGetLastError());
-    return Y4_OK;
+    return launch_lds<conv_l12_kernel<DT>>(lds, dim3(k.grid_m * k.grid_n), dim3(768), lds, stream, k);
 }
 
 }  // namespace y4

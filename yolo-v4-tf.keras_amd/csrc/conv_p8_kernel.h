@@ -393,15 +393,7 @@ template <int DT, int BM, int SCHED>
 static int launch_p8_cfg(const ConvK& k, hipStream_t stream) {
     constexpr int lds = 2 * (BM + 256) * 128 + TOUCH_LDS;
     static_assert(lds <= 160 * 1024, "LDS budget");
-    auto kern = conv_p8_kernel<DT, BM, SCHED>;
-    static PerDeviceOnce once;
-    if (const uint64_t bit = once.due()) {
-        Y4_CHECK_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        once.mark(bit);
-    }
-    hipLaunchKernelGGL(kern, dim3(k.grid_m * k.grid_n), dim3(512), lds, stream, k);
-    Y4_CHECK_HIP(hipGetLastError());
-    return Y4_OK;
+    return launch_lds<conv_p8_kernel<DT, BM, SCHED>>(lds, dim3(k.grid_m * k.grid_n), dim3(512), lds, stream, k);
 }
 
 // nst: the schedule code of conv_tiles.h (8: staggered wave groups, 9: software-pipelined)

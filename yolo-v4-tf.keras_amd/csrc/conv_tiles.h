@@ -113,16 +113,21 @@ inline bool tile_id_ok(int tile) {
 // image), bands per image, LDS pitch of a halo row -- and the LDS it needs with BN output channels per tile.
 inline bool halo_tile(int tile) { return tile >= 1 && tile <= kNumTiles && kTiles[tile - 1].nst == 20; }
 struct HaloPlan { int rows, bands, pitch; };
+// the bands of both halo families: whole image rows, at most bm pixels; false if a row does not fit or the tiles would be too empty
+inline bool band_split(int bm, int H, int W, int* rows, int* bands) {
+    if (W < 1 || H < 1 || W > bm) return false;
+    int r = bm / W;
+    if (r > H) r = H;
+    *bands = (H + r - 1) / r;
+    *rows = (H + *bands - 1) / *bands;                    // balanced: the last band is at most one row short per band
+    return (int64_t)H * W * 4 >= (int64_t)*bands * bm * 3;               // at least 3/4 of the MFMA tiles' rows are pixels
+}
 inline size_t halo_lds_bytes(int rows, int pitch, int bn) { return (size_t)2 * (rows + 2) * pitch * 128 + (size_t)2 * bn * 128 + 256; }
 inline bool halo_plan(int bm, int bn, int H, int W, HaloPlan* out) {
-    if (W < 1 || H < 1 || W > bm) return false;
-    int rows = bm / W;
-    if (rows > H) rows = H;
-    const int bands = (H + rows - 1) / rows;
-    rows = (H + bands - 1) / bands;                       // balanced: the last band is at most one row short per band
+    int rows, bands;
+    if (!band_split(bm, H, W, &rows, &bands)) return false;
     const int pitch = (W + 2 + 7) / 8 * 8;
     if (halo_lds_bytes(rows, pitch, bn) > 160 * 1024) return false;
-    if ((int64_t)H * W * 4 < (int64_t)bands * bm * 3) return false;      // less than 3/4 of the MFMA tiles' rows would be pixels
     *out = HaloPlan{rows, bands, pitch};
     return true;
 }
@@ -154,17 +159,11 @@ inline __host__ __device__ int halo2_rows_alloc(int rows, int pitch) { return ((
 inline size_t halo2_lds_bytes(int rows, int pitch, int kc) { return (size_t)2 * halo2_rows_alloc(rows, pitch) * 2 * kc + 1024 + 256; }
 inline bool halo2_plan(int tile, int H, int W, HaloPlan* out) {
     const Halo2Cfg* hc = halo2_cfg(tile);
-    if (!hc || W < 1 || H < 1) return false;
-    const int bm = kTiles[tile - 1].bm;
-    if (W > bm) return false;
-    int rows = bm / W;
-    if (rows > H) rows = H;
-    const int bands = (H + rows - 1) / rows;
-    rows = (H + bands - 1) / bands;
+    int rows, bands;
+    if (!hc || !band_split(kTiles[tile - 1].bm, H, W, &rows, &bands)) return false;
     const int pitch = W + 128 / hc->kc;
     if (halo2_lds_bytes(rows, pitch, hc->kc) > (size_t)(160 * 1024 / hc->occ)) return false;
     if (((size_t)halo2_rows_alloc(rows, pitch) * 2 * hc->kc / 1024 + 3) / 4 > (size_t)halo2_pmax(hc->kc, hc->occ)) return false;
-    if ((int64_t)H * W * 4 < (int64_t)bands * bm * 3) return false;
     *out = HaloPlan{rows, bands, pitch};
     return true;
 }

@@ -73,7 +73,7 @@ constexpr int CS_ACT = CS_ABL == 1 ? Y4_ACT_LEAKY : Y4_ACT_MISH;
 #define CS_SEG(K)
 #endif
 
-// ---- LDS map (bytes).  Weight fragments are "fragment ordered" (pack_frag_kernel): [(kstep*NREP + j)*64 + lane][8].
+// ---- LDS map (bytes).  Weight fragments are "fragment ordered" (pack_frag16, conv_igemm.hip):[(kstep*NREP + j)*64 + lane][8].
 constexpr int CS_W3 = 0;                        // 64 x 64      : 2 k-steps x 4 fragments x 1 KB
 constexpr int CS_W4 = CS_W3 + 8 * 1024;         // 32 x 64      : 2 x 2
 constexpr int CS_W2 = CS_W4 + 4 * 1024;         // 64 x 64
@@ -478,72 +478,31 @@ int csp_stage_launch(int dtype, const void* in, int n, int h, int w, int in_cstr
     k.in_bytes = (unsigned)in_bytes;
     k.N = n; k.H = h; k.W = w;
     k.tiles_x = w / CS_T; k.tiles_y = h / CS_T; k.tiles_per_img = k.tiles_x * k.tiles_y; k.ntiles = n * k.tiles_per_img;
-    static int n_cus[64] = {0};
-    int dev = 0;
-    Y4_CHECK_HIP(hipGetDevice(&dev));
-    if (n_cus[dev & 63] == 0) {
-        int v = 0;
-        Y4_CHECK_HIP(hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev));
-        n_cus[dev & 63] = v > 0 ? v : 256;
-    }
+    int cus = 0;
+    if (int r = cu_count(&cus)) return r;
     // one workgroup per CU (LDS); a multiple of 8 so that every XCD gets the same number of blocks
-    int grid = n_cus[dev & 63] & ~7;
+    int grid = cus & ~7;
     if (grid < 8) grid = 8;
     if (grid > ((k.ntiles + 7) & ~7)) grid = (k.ntiles + 7) & ~7;
-    auto launch = [&](auto kern) -> int {
-        static PerDeviceOnce once;
-        if (const uint64_t bit = once.due()) {
-            Y4_CHECK_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, CS_LDS));
-            once.mark(bit);
-        }
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * CS_WAVES), CS_LDS, stream, k);
-        Y4_CHECK_HIP(hipGetLastError());
-        return Y4_OK;
-    };
-    return dtype == Y4_BF16 ? launch(csp_stage_kernel<Y4_BF16>) : launch(csp_stage_kernel<Y4_F16>);
+    return dtype == Y4_BF16 ? launch_lds<csp_stage_kernel<Y4_BF16>>(CS_LDS, dim3(grid), dim3(64 * CS_WAVES), CS_LDS, stream, k)
+                            : launch_lds<csp_stage_kernel<Y4_F16>>(CS_LDS, dim3(grid), dim3(64 * CS_WAVES), CS_LDS, stream, k);
 }
 
 // ------------------------------------------------------------------------------------------------ weight packing
-// Darknet (cout, cin, k, k) float32 -> ready-made MFMA A fragments, natural K order, chunked output-channel layout:
-//   out[((s*NREP + j)*64 + lane)*8 + e] = W[ch][ci][tap],  ch = ((j>>1)*4 + (i>>2))*8 + (j&1)*4 + (i&3), i = lane & 15,
-//   k-step s = tap*(cin/32) + cb, ci = 32*cb + 8*(lane>>4) + e      (1x1: tap = 0; 3x3: tap = ky*3 + kx)
-template <int DT>
-__global__ void pack_frag_kernel(const float* __restrict__ w, typename Elem<DT>::type* __restrict__ out, int cout, int cin, int kk) {
-    const int nrep = cout / 16, cbs = cin / 32, total = cout * cin * kk;
-    for (int idx = blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += gridDim.x * blockDim.x) {
-        const int e = idx & 7, lane = (idx >> 3) & 63, r = idx >> 9;
-        const int j = r % nrep, s = r / nrep;
-        const int tap = s / cbs, cb = s - tap * cbs;
-        const int i = lane & 15, gg = lane >> 4;
-        const int ch = ((j >> 1) * 4 + (i >> 2)) * 8 + (j & 1) * 4 + (i & 3);
-        const int ci = 32 * cb + 8 * gg + e;
-        out[idx] = Elem<DT>::st(w[((int64_t)ch * cin + ci) * kk + tap]);
-    }
-}
-
-__global__ void csp_affine_kernel(const float* s0, const float* h0, float* dst, int cout) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < cout) { dst[i] = s0[i]; dst[cout + i] = h0[i]; }
-}
-
+// The weights are pack_frag16's fragments (conv_igemm.hip: the layout is described there), the affines (scale, shift) pairs.
 // `w[6]` = Darknet-order float32 kernels of convs 2..7 (device), `scale/shift[6]` their folded BN (device, fp32)
 int pack_csp_stage(int dtype, const float* const* w, const float* const* scale, const float* const* shift, void* blob,
                    hipStream_t stream) {
     Y4_REQUIRE(dtype == Y4_BF16 || dtype == Y4_F16, Y4_EINVAL, "pack_csp_stage: 16-bit dtypes only (got %d)", dtype);
-    struct Item { int conv, cout, cin, kk, woff, aoff; };
+    struct Item { int conv, cout, cin, ksize, woff, aoff; };
     static const Item items[6] = {{2, 64, 64, 1, CS_W2, CS_A2},  {3, 64, 64, 1, CS_W3, CS_A3}, {4, 32, 64, 1, CS_W4, CS_A4},
-                                  {5, 64, 32, 9, CS_W5, CS_A5},  {6, 64, 64, 1, CS_W6, CS_A6}, {7, 64, 128, 1, CS_W7, CS_A7}};
+                                  {5, 64, 32, 3, CS_W5, CS_A5},  {6, 64, 64, 1, CS_W6, CS_A6}, {7, 64, 128, 1, CS_W7, CS_A7}};
     for (int k = 0; k < 6; ++k) {
         const Item& it = items[k];
         Y4_REQUIRE(w[k] && scale[k] && shift[k], Y4_EINVAL, "pack_csp_stage: null pointer for conv %d", it.conv);
-        const int total = it.cout * it.cin * it.kk, blocks = (total + 255) / 256;
-        char* dst = (char*)blob + it.woff;
-        if (dtype == Y4_BF16) hipLaunchKernelGGL(pack_frag_kernel<Y4_BF16>, dim3(blocks), dim3(256), 0, stream, w[k], (uint16_t*)dst, it.cout, it.cin, it.kk);
-        else hipLaunchKernelGGL(pack_frag_kernel<Y4_F16>, dim3(blocks), dim3(256), 0, stream, w[k], (_Float16*)dst, it.cout, it.cin, it.kk);
-        hipLaunchKernelGGL(csp_affine_kernel, dim3(1), dim3(128), 0, stream, scale[k], shift[k],
-                           (float*)((char*)blob + CS_AFF) + it.aoff, it.cout);
+        if (int r = pack_frag16(dtype, it.cout, it.cin, it.ksize, w[k], (char*)blob + it.woff, stream)) return r;
+        if (int r = copy_affine(it.cout, {scale[k], shift[k]}, (float*)((char*)blob + CS_AFF) + it.aoff, stream)) return r;
     }
-    Y4_CHECK_HIP(hipGetLastError());
     return Y4_OK;
 }
 

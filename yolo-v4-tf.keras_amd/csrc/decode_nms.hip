@@ -725,14 +725,7 @@ int decode_launch(const DecodeK& k, hipStream_t stream, int clear_images) {
 int nms_launch(const NmsK& k, hipStream_t stream) {
     const size_t lds = nms_lds_bytes(k.max_total, k.C);
     Y4_REQUIRE(lds <= 160 * 1024 && k.max_total <= 1024, Y4_EINVAL, "nms: max_total %d needs %zu bytes of LDS", k.max_total, lds);
-    static PerDeviceOnce once;
-    if (const uint64_t bit = once.due()) {
-        Y4_CHECK_HIP(hipFuncSetAttribute((const void*)nms_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        once.mark(bit);
-    }
-    hipLaunchKernelGGL(nms_kernel, dim3(k.N), dim3(NMS_THREADS), lds, stream, k);
-    Y4_CHECK_HIP(hipGetLastError());
-    return Y4_OK;
+    return launch_lds<nms_kernel>(160 * 1024, dim3(k.N), dim3(NMS_THREADS), lds, stream, k);
 }
 
 }  // namespace y4

@@ -1,5 +1,7 @@
 // kernels.h -- launch-side interface between runtime.hip and the kernel files.
 #pragma once
+#include <initializer_list>
+
 #include "common.h"
 
 namespace y4 {
@@ -42,6 +44,11 @@ struct ConvObjDesc {
 int conv2d_launch(const y4_conv_desc* d, const char* zero_page, hipStream_t stream, const ConvChainDesc* chain = nullptr,
                   const ConvPairDesc* pair = nullptr, const ConvObjDesc* obj = nullptr);
 int pack_tail_weights(int dtype, int cout, int cin, const float* oihw, void* packed, hipStream_t stream);
+// (cout, cin, k, k) float32 -> 16-bit A fragments of the 16x16x32 MFMA in the canonical K order: THE fragment order of the chain
+// tails, the stage blob and the residual-block blobs (layout: at pack_frag16_kernel, conv_igemm.hip)
+int pack_frag16(int dtype, int cout, int cin, int ksize, const float* oihw, void* dst, hipStream_t stream);
+// up to four tables of c <= 128 floats (scale, shift, scale, shift) -> consecutive slots of c floats: a blob's affine part
+int copy_affine(int c, std::initializer_list<const float*> src, float* dst, hipStream_t stream);
 int conv_tile_count();
 bool weight_touch_enabled();          // conv_common.h: weight_touch (off with Y4_NO_WEIGHT_TOUCH=1, for A/B runs)
 int conv_pick_tile(int dtype, int M, int cin, int cout);

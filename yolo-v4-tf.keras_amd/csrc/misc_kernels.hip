@@ -364,17 +364,10 @@ static int spp_dispatch(void* buf, int n, int h, int w, int c, hipStream_t strea
     constexpr int EPC = Elem<DT>::EPC;
     constexpr int CPG = 2;
     const size_t lds = (size_t)h * w * CPG * 16 * 4;
-    if (c % (CPG * EPC) == 0 && lds <= 150 * 1024) {
-        static PerDeviceOnce once;
-        if (const uint64_t bit = once.due()) {
-            Y4_CHECK_HIP(hipFuncSetAttribute((const void*)spp_lds_kernel<DT, CPG>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-            once.mark(bit);
-        }
-        hipLaunchKernelGGL((spp_lds_kernel<DT, CPG>), dim3(n * (c / (CPG * EPC))), dim3(256), lds, stream, (T*)buf, n, h, w, c);
-    } else {
-        const int64_t total = (int64_t)n * h * w * (c / EPC);
-        hipLaunchKernelGGL(spp_kernel<DT>, dim3((int)((total + 255) / 256)), dim3(256), 0, stream, (T*)buf, n, h, w, c);
-    }
+    if (c % (CPG * EPC) == 0 && lds <= 150 * 1024)
+        return launch_lds<spp_lds_kernel<DT, CPG>>(150 * 1024, dim3(n * (c / (CPG * EPC))), dim3(256), lds, stream, (T*)buf, n, h, w, c);
+    const int64_t total = (int64_t)n * h * w * (c / EPC);
+    hipLaunchKernelGGL(spp_kernel<DT>, dim3((int)((total + 255) / 256)), dim3(256), 0, stream, (T*)buf, n, h, w, c);
     Y4_CHECK_HIP(hipGetLastError());
     return Y4_OK;
 }

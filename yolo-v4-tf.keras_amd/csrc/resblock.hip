@@ -452,14 +452,7 @@ static int resblock_run(const ResBlockK& k, int slots, hipStream_t stream) {
     if (grid > ((span + 7) & ~7)) grid = (span + 7) & ~7;
     if (grid < 8) grid = 8;
     constexpr int lds = RbGeom<C, TY>::LDS;
-    static PerDeviceOnce once;
-    if (const uint64_t bit = once.due()) {
-        Y4_CHECK_HIP(hipFuncSetAttribute((const void*)resblock_kernel<DT, C, TY>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        once.mark(bit);
-    }
-    hipLaunchKernelGGL((resblock_kernel<DT, C, TY>), dim3(grid), dim3(64 * RB_WAVES), lds, stream, k);
-    Y4_CHECK_HIP(hipGetLastError());
-    return Y4_OK;
+    return launch_lds<resblock_kernel<DT, C, TY>>(lds, dim3(grid), dim3(64 * RB_WAVES), lds, stream, k);
 }
 
 // Y4_RB_PARTS=0 runs every tile as a full 16x16 tile (A/B measurements; results are the same either way)
@@ -470,16 +463,10 @@ static bool rb_parts_enabled() {
 
 template <int DT, int C>
 static int resblock_dispatch(ResBlockK& k, hipStream_t stream) {
-    static int n_cus[64] = {0};
-    int dev = 0;
-    Y4_CHECK_HIP(hipGetDevice(&dev));
-    if (n_cus[dev & 63] == 0) {
-        int v = 0;
-        Y4_CHECK_HIP(hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev));
-        n_cus[dev & 63] = v > 0 ? v : 256;
-    }
+    int cus = 0;
+    if (int r = cu_count(&cus)) return r;
     // one workgroup per CU for C = 128 (LDS), two for C = 64 (79 KB each: their phases overlap)
-    const int slots = (n_cus[dev & 63] & ~7) * (C == 64 ? 2 : 1);
+    const int slots = (cus & ~7) * (C == 64 ? 2 : 1);
     // Round quantisation: 800 tiles on 256 slots are 3 full rounds and one round on 32 slots (4 tile times for 3.1 of work).  The
     // tiles of the partial last round run as half / quarter tiles (8 / 4 output rows: the halo'd 1x1 phase is repeated per part,
     // the 3x3 phase splits) when all their parts fit one round; a launch with fewer tiles than slots is split the same way.
@@ -525,44 +512,15 @@ int resblock_launch(int dtype, int c, const void* in, int n, int h, int w, int i
 }
 
 // ------------------------------------------------------------------------------------------------ weight packing
-// (cout, cin, k, k) float32 -> MFMA A fragments, natural K order, chunked output-channel layout (same as csp_stage.hip):
-//   out[((s*NREP + j)*64 + lane)*8 + e] = W[ch][ci][tap], ch = ((j>>1)*4 + (i>>2))*8 + (j&1)*4 + (i&3), i = lane & 15,
-//   k-step s = 2*(cb64*k*k + tap) + half (64-channel block cb64 -> tap -> half: common.h), ci = 32*(2*cb64 + half) + 8*(lane>>4) + e
-template <int DT>
-__global__ void rb_pack_frag_kernel(const float* __restrict__ w, typename Elem<DT>::type* __restrict__ out, int cout, int cin, int kk) {
-    const int nrep = cout / 16, cbs = cin / 32, total = cout * cin * kk;
-    for (int idx = blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += gridDim.x * blockDim.x) {
-        const int e = idx & 7, lane = (idx >> 3) & 63, r = idx >> 9;
-        const int j = r % nrep, s = r / nrep;
-        // canonical K order (common.h): 64-channel block -> tap -> the block's two 32-channel k-steps
-        const int step = s >> 1, cb64 = step / kk, tap = step - cb64 * kk, cb = cb64 * 2 + (s & 1);
-        const int i = lane & 15, gg = lane >> 4;
-        const int ch = ((j >> 1) * 4 + (i >> 2)) * 8 + (j & 1) * 4 + (i & 3);
-        const int ci = 32 * cb + 8 * gg + e;
-        out[idx] = Elem<DT>::st(w[((int64_t)ch * cin + ci) * kk + tap]);
-    }
-}
-__global__ void rb_affine_kernel(const float* s1, const float* h1, const float* s3, const float* h3, float* dst, int c) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < c) { dst[i] = s1[i]; dst[c + i] = h1[i]; dst[2 * c + i] = s3[i]; dst[3 * c + i] = h3[i]; }
-}
-
 // w1 / w3: Darknet-order float32 kernels of the block's 1x1 and 3x3 convs (device); scale / shift: their folded BN
 int pack_resblock(int dtype, int c, const float* w1, const float* scale1, const float* shift1, const float* w3, const float* scale3,
                   const float* shift3, void* blob, hipStream_t stream) {
     Y4_REQUIRE(resblock_supported(dtype, c) && w1 && w3 && scale1 && shift1 && scale3 && shift3 && blob, Y4_EINVAL, "pack_resblock: bad argument");
     const int w1_bytes = c * c * 2, aff_pad = (4 * c * 4 + 1023) / 1024 * 1024;
-    char* b = (char*)blob;                           // [affine | W1 fragments | W3 fragments]
-    if (dtype == Y4_BF16) {
-        hipLaunchKernelGGL(rb_pack_frag_kernel<Y4_BF16>, dim3((c * c + 255) / 256), dim3(256), 0, stream, w1, (uint16_t*)(b + aff_pad), c, c, 1);
-        hipLaunchKernelGGL(rb_pack_frag_kernel<Y4_BF16>, dim3((9 * c * c + 255) / 256), dim3(256), 0, stream, w3, (uint16_t*)(b + aff_pad + w1_bytes), c, c, 9);
-    } else {
-        hipLaunchKernelGGL(rb_pack_frag_kernel<Y4_F16>, dim3((c * c + 255) / 256), dim3(256), 0, stream, w1, (_Float16*)(b + aff_pad), c, c, 1);
-        hipLaunchKernelGGL(rb_pack_frag_kernel<Y4_F16>, dim3((9 * c * c + 255) / 256), dim3(256), 0, stream, w3, (_Float16*)(b + aff_pad + w1_bytes), c, c, 9);
-    }
-    hipLaunchKernelGGL(rb_affine_kernel, dim3(1), dim3(128), 0, stream, scale1, shift1, scale3, shift3, (float*)b, c);
-    Y4_CHECK_HIP(hipGetLastError());
-    return Y4_OK;
+    char* b = (char*)blob;                           // [affine | W1 fragments | W3 fragments]: pack_frag16's layout (conv_igemm.hip)
+    if (int r = pack_frag16(dtype, c, c, 1, w1, b + aff_pad, stream)) return r;
+    if (int r = pack_frag16(dtype, c, c, 3, w3, b + aff_pad + w1_bytes, stream)) return r;
+    return copy_affine(c, {scale1, shift1, scale3, shift3}, (float*)b, stream);
 }
 
 }  // namespace y4

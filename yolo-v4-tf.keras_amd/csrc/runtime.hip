@@ -647,6 +647,15 @@ OpExec resolve_op(y4_handle h, int oi, bool allow_chain) {
     return {chain->lds_pair ? EX_LDS_PAIR : chain->alt_of >= 0 ? EX_ALT_CHAIN : EX_CHAIN, nullptr, chain};
 }
 
+// A layer's packed weights and folded BN in the wts workspace.  A fused CSP pair shares one packed matrix: the partner's rows (and
+// its scale / shift) follow the first conv's, at row `fused_row` of layer `fused_with`.
+struct LayerW { char* w; float* scale; float* shift; };
+static LayerW layer_w(y4_handle h, const Layer& L) {
+    const Layer& D = L.fused_with >= 0 ? h->layers[L.fused_with] : L;
+    const size_t row_bytes = (size_t)L.d.ksize * L.d.ksize * L.d.cin * h->es;
+    return {h->wts + D.w_off + (size_t)L.fused_row * row_bytes, (float*)(h->wts + D.scale_off) + L.fused_row, (float*)(h->wts + D.shift_off) + L.fused_row};
+}
+
 // The kernels address their input through a raw buffer descriptor (2 GiB range, conv_igemm.hip): a batch whose input view is
 // larger runs as consecutive image chunks (images are independent), `launch(first image, count)` each.  `reach`: what a 3x3
 // conv's biased tap offsets add to the range (conv2d_launch's own check).  `fmt, args...` word the error; the bytes of one image
@@ -675,17 +684,16 @@ int run_op(y4_handle h, int oi, const void* imgs, int n, hipStream_t s, int img0
     case EX_STEM_DOWN: {
         const Op& o1 = h->ops[1];
         const Layer &L = h->layers[0], &L1 = h->layers[1];
+        const LayerW p = layer_w(h, L), p1 = layer_w(h, L1);
         return stem_down_launch(h->cfg.dtype, img_at(h, imgs, img0), h->img_u8 ? 1 : 0, n, h->H,      // (square only: y4_set_stem_fusion)
-                                h->wts + L.w_off, (const float*)(h->wts + L.scale_off), (const float*)(h->wts + L.shift_off), L.d.act,
-                                h->wts + L1.w_off, (const float*)(h->wts + L1.scale_off), (const float*)(h->wts + L1.shift_off), L1.d.act,
+                                p.w, p.scale, p.shift, L.d.act, p1.w, p1.scale, p1.shift, L1.d.act,
                                 buf_ptr(h, o1.out, img0), o1.out.cstride, o1.out.coff, s);
     }
     case EX_STEM: {
         const Layer& L = h->layers[0];
-        return stem_conv_launch(h->cfg.dtype, img_at(h, imgs, img0), h->img_u8 ? 1 : 0, n, h->H, h->W,
-                                (const float*)(h->wts + L.w_off), (const float*)(h->wts + L.scale_off),
-                                (const float*)(h->wts + L.shift_off), L.d.cout, L.d.act, buf_ptr(h, op.out, img0), op.out.cstride,
-                                op.out.coff, s);
+        const LayerW p = layer_w(h, L);
+        return stem_conv_launch(h->cfg.dtype, img_at(h, imgs, img0), h->img_u8 ? 1 : 0, n, h->H, h->W, (const float*)p.w, p.scale, p.shift,
+                                L.d.cout, L.d.act, buf_ptr(h, op.out, img0), op.out.cstride, op.out.coff, s);
     }
     case EX_RESBLOCK: {
         const Op& last = h->ops[ex.res->tail];
@@ -710,6 +718,7 @@ int run_op(y4_handle h, int oi, const void* imgs, int n, hipStream_t s, int img0
     }
     // the conv family: one conv2d_launch, carrying the run's tails when op heads one
     const Layer& L = h->layers[op.conv];
+    const LayerW lw = layer_w(h, L);
     const Chain* chain = ex.chain;
     auto launch = [&](int i0, int cnt) -> int {
         y4_conv_desc d{};
@@ -719,8 +728,7 @@ int run_op(y4_handle h, int oi, const void* imgs, int n, hipStream_t s, int img0
         d.upsample = op.upsample ? 1 : 0; d.out_f32 = op.out_f32 ? 1 : 0;
         d.in_cstride = op.in.cstride; d.in_coff = op.in.coff;
         d.out_cstride = op.out.cstride; d.out_coff = op.out.coff;
-        d.in = buf_ptr(h, op.in, i0); d.wt = h->wts + L.w_off;
-        d.scale = (const float*)(h->wts + L.scale_off); d.shift = (const float*)(h->wts + L.shift_off);
+        d.in = buf_ptr(h, op.in, i0); d.wt = lw.w; d.scale = lw.scale; d.shift = lw.shift;
         d.wt_frag = L.has_frag ? h->wts + L.frag_off : nullptr;
         d.out = buf_ptr(h, op.out, i0);
         if (op.has_res) { d.res = buf_ptr(h, op.res, i0); d.res_cstride = op.res.cstride; d.res_coff = op.res.coff; }
@@ -750,10 +758,9 @@ int run_op(y4_handle h, int oi, const void* imgs, int n, hipStream_t s, int img0
         if (ex.kind == EX_LDS_PAIR) {
             const Op& to = h->ops[chain->tail[0]];
             const Layer& TL = h->layers[to.conv];
+            const LayerW tw = layer_w(h, TL);
             ConvPairDesc pd{};
-            pd.w = h->wts + TL.w_off;
-            pd.scale = (const float*)(h->wts + TL.scale_off);
-            pd.shift = (const float*)(h->wts + TL.shift_off);
+            pd.w = tw.w; pd.scale = tw.scale; pd.shift = tw.shift;
             pd.act = TL.d.act; pd.cout = TL.d.cout; pd.out_f32 = to.out_f32 ? 1 : 0; pd.store_x = chain->store_x ? 1 : 0;
             pd.fin = buf_ptr(h, to.out, i0); pd.fin_cstride = to.out.cstride; pd.fin_coff = to.out.coff;
             if (to.conv2 >= 0) {          // the tail is a fused CSP pair: both convs' rows, split over two views
@@ -768,9 +775,8 @@ int run_op(y4_handle h, int oi, const void* imgs, int n, hipStream_t s, int img0
             const Layer& TL = h->layers[to.conv];
             ConvChainDesc cd{};
             cd.ntail = 2; cd.concat_only = 1; cd.store_x = 0;
-            cd.tail[1].w = h->wts + TL.tail_off;
-            cd.tail[1].scale = (const float*)(h->wts + TL.scale_off);
-            cd.tail[1].shift = (const float*)(h->wts + TL.shift_off);
+            const LayerW tw = layer_w(h, TL);
+            cd.tail[1].w = h->wts + TL.tail_off; cd.tail[1].scale = tw.scale; cd.tail[1].shift = tw.shift;
             cd.tail[1].cout = TL.d.cout;
             cd.tail[1].src2 = buf_ptr(h, to.in, i0);
             cd.tail[1].src2_cstride = to.in.cstride;
@@ -785,9 +791,8 @@ int run_op(y4_handle h, int oi, const void* imgs, int n, hipStream_t s, int img0
             for (int t = 0; t < 2 && chain->tail[t] >= 0; ++t) {
                 const Op& to = h->ops[chain->tail[t]];
                 const Layer& TL = h->layers[to.conv];
-                cd.tail[t].w = h->wts + TL.tail_off;
-                cd.tail[t].scale = (const float*)(h->wts + TL.scale_off);
-                cd.tail[t].shift = (const float*)(h->wts + TL.shift_off);
+                const LayerW tw = layer_w(h, TL);
+                cd.tail[t].w = h->wts + TL.tail_off; cd.tail[t].scale = tw.scale; cd.tail[t].shift = tw.shift;
                 cd.tail[t].cout = TL.d.cout;
                 if (t == 1) {                       // the concat partner: channels [64, 128) of the buffer the first tail writes into
                     cd.tail[t].src2 = buf_ptr(h, to.in, i0);
@@ -985,21 +990,16 @@ int y4_pack_weights(y4_handle h, const float* blob, size_t n_floats, void* strea
     for (const Layer& L : h->layers) {
         const float* rec = blob + L.d.weight_offset;
         const float* w = rec + (L.d.has_bn ? 4 : 1) * (int64_t)L.d.cout;
-        // a fused CSP pair shares one packed matrix: the partner's rows (and scale/shift) follow the first conv's
-        const Layer& D = L.fused_with >= 0 ? h->layers[L.fused_with] : L;
-        const size_t row_bytes = (size_t)L.d.ksize * L.d.ksize * L.d.cin * h->es;
-        char* wdst = h->wts + D.w_off + (size_t)L.fused_row * row_bytes;
-        if (int r = fold_bn_launch(rec, (float*)(h->wts + D.scale_off) + L.fused_row, (float*)(h->wts + D.shift_off) + L.fused_row,
-                                   L.d.cout, L.cout_pad, L.d.has_bn, s))
-            return r;
+        const LayerW p = layer_w(h, L);                    // (a fused CSP pair's partner: its rows of the first conv's matrix)
+        if (int r = fold_bn_launch(rec, p.scale, p.shift, L.d.cout, L.cout_pad, L.d.has_bn, s)) return r;
         if (L.d.idx == 0) {
-            if (int r = pack_stem_weights(w, (float*)(h->wts + L.w_off), L.d.cout, s)) return r;
+            if (int r = pack_stem_weights(w, (float*)p.w, L.d.cout, s)) return r;
         } else {
-            if (int r = pack_conv_weights(h->cfg.dtype, L.d.cout, L.d.cin, L.d.ksize, w, wdst, s)) return r;
+            if (int r = pack_conv_weights(h->cfg.dtype, L.d.cout, L.d.cin, L.d.ksize, w, p.w, s)) return r;
             if (L.has_tail)
                 if (int r = pack_tail_weights(h->cfg.dtype, L.d.cout, L.d.cin, w, h->wts + L.tail_off, s)) return r;
             if (L.has_frag)
-                if (int r = pack_conv_frag32(h->cfg.dtype, L.d.cout, L.d.cin, wdst, h->wts + L.frag_off, s)) return r;
+                if (int r = pack_conv_frag32(h->cfg.dtype, L.d.cout, L.d.cin, p.w, h->wts + L.frag_off, s)) return r;
         }
     }
     if (h->stage_first >= 0) {
@@ -1010,19 +1010,17 @@ int y4_pack_weights(y4_handle h, const float* blob, size_t n_floats, void* strea
         const float *w[6], *sc[6], *sh[6];
         for (int k = 0; k < 6; ++k) {
             const Layer& L = h->layers[convs[k]];
-            const Layer& D = L.fused_with >= 0 ? h->layers[L.fused_with] : L;
+            const LayerW p = layer_w(h, L);
             w[k] = blob + L.d.weight_offset + 4 * (int64_t)L.d.cout;
-            sc[k] = (const float*)(h->wts + D.scale_off) + L.fused_row;
-            sh[k] = (const float*)(h->wts + D.shift_off) + L.fused_row;
+            sc[k] = p.scale; sh[k] = p.shift;
         }
         if (int r = pack_csp_stage(h->cfg.dtype, w, sc, sh, h->wts + h->stage_blob_off, s)) return r;
     }
     for (const ResRun& r : h->resruns) {
         const Layer &L1 = h->layers[h->ops[r.head].conv], &L3 = h->layers[h->ops[r.tail].conv];
-        if (int rc = pack_resblock(h->cfg.dtype, r.c, blob + L1.d.weight_offset + 4 * (int64_t)L1.d.cout,
-                                   (const float*)(h->wts + L1.scale_off), (const float*)(h->wts + L1.shift_off),
-                                   blob + L3.d.weight_offset + 4 * (int64_t)L3.d.cout, (const float*)(h->wts + L3.scale_off),
-                                   (const float*)(h->wts + L3.shift_off), h->wts + r.blob_off, s))
+        const LayerW p1 = layer_w(h, L1), p3 = layer_w(h, L3);
+        if (int rc = pack_resblock(h->cfg.dtype, r.c, blob + L1.d.weight_offset + 4 * (int64_t)L1.d.cout, p1.scale, p1.shift,
+                                   blob + L3.d.weight_offset + 4 * (int64_t)L3.d.cout, p3.scale, p3.shift, h->wts + r.blob_off, s))
             return rc;
     }
     h->weights_ready = true;

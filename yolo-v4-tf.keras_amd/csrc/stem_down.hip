@@ -459,36 +459,20 @@ static int stem_down_dispatch(const StemDownK& k, hipStream_t stream) {
     const int mfw = (k.S / 32 + SD_WM - 1) / SD_WM;         // ceil((Wo/16) / SD_WM)
     const size_t lds = stem_down_lds_bytes(k.S);
     // persistent: one workgroup per CU (LDS), each a contiguous band of the N * S/2 output rows
-    static int n_cus[64] = {0};
-    int dev = 0;
-    Y4_CHECK_HIP(hipGetDevice(&dev));
-    if (n_cus[dev & 63] == 0) {
-        int v = 0;
-        Y4_CHECK_HIP(hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev));
-        n_cus[dev & 63] = v > 0 ? v : 256;
-    }
+    int cus = 0;
+    if (int r = cu_count(&cus)) return r;
     const int rows = k.N * (k.S / 2);
-    const int blocks = rows < n_cus[dev & 63] ? rows : n_cus[dev & 63];
-#define Y4_SD_CASE(M)                                                                                        \
-    case M: {                                                                                                \
-        static PerDeviceOnce once;                                                                           \
-        if (const uint64_t bit = once.due()) {                                                               \
-            Y4_CHECK_HIP(hipFuncSetAttribute((const void*)stem_down_kernel<DT, M, IMG>,                     \
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));       \
-            once.mark(bit);                                                                                  \
-        }                                                                                                    \
-        hipLaunchKernelGGL((stem_down_kernel<DT, M, IMG>), dim3(blocks), dim3(64 * SD_WAVES), lds, stream, k);         \
-        break;                                                                                               \
-    }
+    const dim3 grid(rows < cus ? rows : cus), block(64 * SD_WAVES);
+#define Y4_SD_CASE(M) case M: return launch_lds<stem_down_kernel<DT, M, IMG>>(160 * 1024, grid, block, lds, stream, k);
     switch (mfw) {
         Y4_SD_CASE(1) Y4_SD_CASE(2) Y4_SD_CASE(3)
 #if SD_W8
         Y4_SD_CASE(4) Y4_SD_CASE(5)
 #endif
-        default: set_error("stem_down: image side %d not supported", k.S); return Y4_EINVAL;
     }
-    Y4_CHECK_HIP(hipGetLastError());
-    return Y4_OK;
+#undef Y4_SD_CASE
+    set_error("stem_down: image side %d not supported", k.S);
+    return Y4_EINVAL;
 }
 
 int stem_down_launch(int dtype, const void* imgs, int img_u8, int n, int S, const void* stem_wk, const float* s0_scale,
