@@ -477,6 +477,30 @@ typedef struct y4_image_desc {
  * and sizes inside the source buffer, h, w, out_h, out_w >= 1, the rectangle inside the canvas). */
 int y4_resize_u8_ragged(const uint8_t* src_dev, const y4_image_desc* desc_dev, int n, uint8_t* out_dev, int H, int W,
                         int pad_value, void* stream);
+/* One image of a ragged batch for y4_augment_u8_ragged: the fields of y4_image_desc, then the augmentation of this image --
+ * flip (0 / 1: mirror left-right) and the HSV factors (hue is added, sat and val multiply; 0, 1, 1 change nothing). */
+typedef struct y4_augment_desc {
+    int64_t offset;
+    int32_t h, w, out_h, out_w, pad_top, pad_left;   /* as y4_image_desc */
+    int32_t flip;                                    /* 0 / 1 */
+    float   hue, sat, val;
+} y4_augment_desc;                                   /* 48 bytes */
+/* y4_resize_u8_ragged with the training-time augmentation of Yolov4.fit, still one launch: image i -> slot i of the uint8
+ * [n,H,W,3] batch y4_forward_u8 takes.
+ *   flip      canvas column x is sourced from canvas column x' = W - 1 - x (x' = x without flip);
+ *   geometry  with yy = y - pad_top, xx = x' - pad_left: inside [0,out_h) x [0,out_w) the pixel is cv2.resize's uint8
+ *             INTER_LINEAR resize of the source to out_w x out_h at (yy, xx) -- the arithmetic of y4_resize_u8_ragged --,
+ *             otherwise `pad_value` in all three channels, without the colour transform.  The rectangle may lie partly or wholly
+ *             outside the canvas (pad_top / pad_left negative, out_h > H, out_w > W); only its visible part is computed;
+ *   colour    on resized pixels only, in float32, skipped when hue == 0 && sat == 1 && val == 1 (the bytes are then exactly the
+ *             resize's): RGB / 255 -> HSV by the colorsys.rgb_to_hsv rule (hue in [0,1); S = 0 and H = 0 at max == 0 or
+ *             max == min), H <- H + hue - floor(H + hue), S <- clamp(S * sat, 0, 1), V <- clamp(V * val, 0, 1), back by the
+ *             colorsys.hsv_to_rgb rule, byte = clamp(floor(255 c + 0.5), 0, 255).
+ * The arguments are checked on the host as in y4_resize_u8_ragged (NULL pointers, n in 1..65535, H, W > 0, pad_value in 0..255,
+ * an output of 2^31 bytes or more: Y4_EINVAL before any launch).  The descriptors live on the device and are NOT checked: the
+ * caller owns the table's correctness (offsets and sizes inside the source buffer, h, w, out_h, out_w >= 1, finite factors). */
+int y4_augment_u8_ragged(const uint8_t* src_dev, const y4_augment_desc* desc_dev, int n, uint8_t* out_dev, int H, int W,
+                         int pad_value, void* stream);
 /* SPP (custom_layers.py:130-134): x = buf[..., 3c:4c] -> buf[..., 0:c]=maxpool13, [c:2c]=maxpool9,
  * [2c:3c]=maxpool5 (stride 1, 'same'), buf is [n,side,side,4c] */
 int y4_spp(int dtype, void* buf_dev, int n, int side, int c, void* stream);

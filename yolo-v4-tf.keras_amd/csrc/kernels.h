@@ -70,6 +70,10 @@ int view_to_f32_launch(int dtype, const void* src, float* dst, int64_t pixels, i
 int f32_to_view_launch(const float* src, float* dst, int64_t pixels, int cstride, int c, hipStream_t stream);
 int fold_bn_launch(const float* rec, float* scale, float* shift, int cout, int cout_pad, int has_bn, hipStream_t stream);
 
+// augment.hip
+int augment_u8_ragged_launch(const uint8_t* src, const y4_augment_desc* desc, int n, uint8_t* out, int H, int W, int pad,
+                             hipStream_t stream);
+
 // stem_down.hip: convs 0+1 fused (16-bit dtypes), c0 stays in LDS
 bool stem_down_supported(int dtype, int S);
 int stem_down_launch(int dtype, const void* imgs, int img_u8, int n, int S, const void* stem_wk, const float* s0_scale,

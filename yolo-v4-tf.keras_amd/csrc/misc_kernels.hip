@@ -3,6 +3,7 @@
 //   SPP max-pools + concat (reference custom_layers.py:130-134)
 //   view -> dense float32 copies (what Keras returns from yolo_model.predict, reference models.py:514)
 #include "kernels.h"
+#include "resize_common.h"
 #include "stem_common.h"
 
 namespace y4 {
@@ -387,22 +388,8 @@ int spp_launch(int dtype, void* buf, int n, int h, int w, int c, hipStream_t str
 
 // ------------------------------------------------------------------------------ image pre-processing
 // Yolov4.preprocess_img (reference models.py:95-98): cv2.resize(img, (W,H)) [INTER_LINEAR, plain stretch] then
-// img / 255.  uint8 RGB [h,w,3] on device -> float32 [H,W,3] in [0,1].  Restates OpenCV's uint8 fixed-point
-// bilinear scheme (half-pixel centres, 11-bit coefficients, two rounding shifts) exactly like the host version
-// yolo4hip/prepost.py: resize_bilinear, so both paths give identical floats.
-__device__ __forceinline__ void lin_coeff(int d, int dst, int src, int& s0, int& s1, int& a0, int& a1) {
-    const double scale = (double)src / (double)dst;
-    double f = ((double)d + 0.5) * scale - 0.5;
-    int s = (int)floor(f);
-    float fr = (float)(f - (double)s);
-    if (s < 0) { fr = 0.f; s = 0; }
-    if (s >= src - 1) { fr = 0.f; s = src - 1; }
-    s0 = s;
-    s1 = s + 1 < src ? s + 1 : src - 1;
-    a1 = (int)rintf(fr * 2048.0f);
-    a0 = (int)rintf((1.0f - fr) * 2048.0f);
-}
-
+// img / 255.  uint8 RGB [h,w,3] on device -> float32 [H,W,3] in [0,1], with the fixed-point bilinear scheme of resize_common.h
+// (lin_coeff, resize_px_u8), so the host version yolo4hip/prepost.py: resize_bilinear gives identical floats.
 __global__ void preprocess_u8_kernel(const uint8_t* __restrict__ img, int h, int w, float* __restrict__ out, int H, int W) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= H * W) return;
@@ -423,26 +410,6 @@ __global__ void preprocess_u8_kernel(const uint8_t* __restrict__ img, int h, int
             v = v < 0 ? 0 : (v > 255 ? 255 : v);
         }
         out[i * 3 + c] = (float)((double)v / 255.0);
-    }
-}
-
-// One output pixel (row y, column x) of cv2.resize's uint8 INTER_LINEAR resize of `src` [h,w,3] to dw x dh, all three channels:
-// the arithmetic every uint8 resize kernel here shares (prepost.py: resize_bilinear is its host restatement).
-__device__ __forceinline__ void resize_px_u8(const uint8_t* __restrict__ src, int h, int w, int dh, int dw, int y, int x, int v[3]) {
-    int x0, x1, ax0, ax1, y0, y1, ay0, ay1;
-    lin_coeff(x, dw, w, x0, x1, ax0, ax1);
-    lin_coeff(y, dh, h, y0, y1, ay0, ay1);
-    const bool same = (h == dh && w == dw);
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        if (same) {
-            v[c] = src[(y * w + x) * 3 + c];
-        } else {
-            const int top = src[(y0 * w + x0) * 3 + c] * ax0 + src[(y0 * w + x1) * 3 + c] * ax1;   // x2048
-            const int bot = src[(y1 * w + x0) * 3 + c] * ax0 + src[(y1 * w + x1) * 3 + c] * ax1;
-            const int r = (((ay0 * (top >> 4)) >> 16) + ((ay1 * (bot >> 4)) >> 16) + 2) >> 2;
-            v[c] = r < 0 ? 0 : (r > 255 ? 255 : r);
-        }
     }
 }
 
@@ -494,26 +461,12 @@ __global__ __launch_bounds__(256) void resize_u8_ragged_kernel(const uint8_t* __
 #pragma unroll
         for (int c = 0; c < 3; ++c) px[k * 3 + c] = (uint8_t)v[c];
     }
-    uint8_t* o = out + ((int64_t)b * hw + p0) * 3;
-    if constexpr (PX == 4) {
-        uint32_t* o32 = (uint32_t*)o;
-#pragma unroll
-        for (int j = 0; j < 3; ++j)
-            o32[j] = (uint32_t)px[4 * j] | ((uint32_t)px[4 * j + 1] << 8) | ((uint32_t)px[4 * j + 2] << 16) | ((uint32_t)px[4 * j + 3] << 24);
-    } else {
-#pragma unroll
-        for (int c = 0; c < 3; ++c) o[c] = px[c];
-    }
+    store_px_u8<PX>(out + ((int64_t)b * hw + p0) * 3, px);
 }
 
 int resize_u8_ragged_launch(const uint8_t* src, const y4_image_desc* desc, int n, uint8_t* out, int H, int W, int pad,
                             hipStream_t stream) {
-    Y4_REQUIRE(src && desc && out, Y4_EINVAL, "resize_u8_ragged: null pointer");
-    Y4_REQUIRE(n > 0 && n <= 65535, Y4_EINVAL, "resize_u8_ragged: n = %d (1..65535)", n);
-    Y4_REQUIRE(H > 0 && W > 0, Y4_EINVAL, "resize_u8_ragged: canvas %d x %d", H, W);
-    Y4_REQUIRE(pad >= 0 && pad <= 255, Y4_EINVAL, "resize_u8_ragged: pad_value %d (0..255)", pad);
-    Y4_REQUIRE((int64_t)n * H * W * 3 < (1ll << 31), Y4_EINVAL, "resize_u8_ragged: output of %lld bytes (< 2^31)",
-               (long long)n * H * W * 3);
+    if (int rc = ragged_args_check("resize_u8_ragged", src, desc, out, n, H, W, pad)) return rc;
     const int hw = H * W;
     if (hw % 4 == 0 && ((uintptr_t)out & 3) == 0)
         hipLaunchKernelGGL(resize_u8_ragged_kernel<4>, dim3((hw / 4 + 255) / 256, n), dim3(256), 0, stream, src, desc, out, H, W, pad);

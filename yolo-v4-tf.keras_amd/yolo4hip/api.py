@@ -13,7 +13,8 @@ instead of the reference's stretch (Darknet's letter_box=1 geometry) with boxes 
 self-describing checkpoint of this framework (Keras' SavedModel / H5 needs TensorFlow); `eval_map` (models.py:182-507)
 is the VOC mAP tool over the exported text files (yolo4hip/evalmap.py).  `training_model.predict([X, y_s, y_m, y_l, true_xywh])`
 is the reference's yolo_loss FORWARD (models.py:54-65, loss.py) on the device and `evaluate(data_gen)` the validation loss over
-a `DataGenerator`; `fit(..., trainable='heads')` fine-tunes the three detection convs on a frozen backbone and neck, while
+a `DataGenerator`; `fit(..., trainable='heads')` fine-tunes the three detection convs on a frozen backbone and neck (with a
+`DataGenerator(..., augment=AugmentConfig())` under scale, shift, flip and HSV augmentation applied on the device), while
 training every layer (the reference's `fit`) is out of scope and raises.
 """
 import json
@@ -199,6 +200,13 @@ class Yolov4(object):
         BatchNormalization stays frozen and runs in inference mode, as Keras runs a frozen BN.  Per chunk y4_block_grad follows
         y4_head_grad (both use the head weights the forward used), per batch both Adam steps run with the same t.  f32 and bf16.
 
+        Augmentation: a `train_data_gen` whose `augment` is an `AugmentConfig` (DataGenerator(..., augment=, seed=)) is read
+        through `raw(i)`: the raw uint8 images cross PCIe once, `Engine.augment_u8_batch` resizes, shifts, flips and colour-shifts
+        them in one launch into the uint8 batch the forward takes, and the boxes arrive already transformed.  With
+        AugmentConfig.identity() that path gives the bits of the host path.  `val_data_gen` and `evaluate` never take the device
+        path: handed an augmenting generator they call `boxes(i)`, which augments on the host and draws from the generator's own
+        random stream -- validate on a generator without `augment`.
+
         A callback with a `schedule(epoch, lr)` method (yolo4hip.callbacks.CosineAnnealingScheduler; Keras'
         LearningRateScheduler pattern) is asked at the start of every epoch; its result is that epoch's learning rate."""
         if trainable not in ('heads', 'head_blocks'):
@@ -217,6 +225,7 @@ class Yolov4(object):
         torch = eng.torch
         state = {g: eng._group_state(g, self._flat) for g in groups}
         grad = {g: torch.empty((eng._group_floats(g),), dtype=torch.float32, device=eng.device) for g in groups}
+        augment = getattr(train_data_gen, 'augment', None)
         history = {'loss': []}
         if val_data_gen is not None:
             history['val_loss'] = []
@@ -226,8 +235,13 @@ class Yolov4(object):
                     learning_rate = float(cb.schedule(epoch, learning_rate))
             total, images = 0.0, 0
             for i in range(len(train_data_gen)):
-                X, boxes = train_data_gen.boxes(i)
+                if augment is not None:
+                    raws, params, boxes = train_data_gen.raw(i)
+                else:
+                    X, boxes = train_data_gen.boxes(i)
                 boxes_dev = torch.from_numpy(eng._check_boxes(boxes)).to(eng.device)     # ValueError before any update
+                if augment is not None:
+                    X = eng.augment_u8_batch(raws, params, pad_value=augment.pad_value)
                 count = boxes_dev.shape[0]
                 weight = torch.full((count,), 1.0 / count, dtype=torch.float32, device=eng.device)
                 parts, i0 = [], 0

@@ -190,9 +190,17 @@ class DataGenerator:
     """The reference's Keras `Sequence` (utils.py:121-212) without Keras: `len(gen)` batches, `gen[i]` ->
     ([X, y_s, y_m, y_l, y_true_boxes_xywh], zeros(batch)).  img_size, batch_size (x num_gpu) and anchors come from `config`
     (default: the package's `yolo_config`); images are read and stretched through `prepost`.  `boxes(i)` gives batch i as
-    (X, [n, max_boxes, 5] boxes) -- what `Yolov4.evaluate` uploads instead of the dense labels."""
+    (X, [n, max_boxes, 5] boxes) -- what `Yolov4.evaluate` uploads instead of the dense labels.
 
-    def __init__(self, annotation_lines, class_name_path, folder_path, max_boxes=100, shuffle=True, config=None):
+    augment=None (default): the reference's plain stretch, every epoch the same pixels.  augment=AugmentConfig(...)
+    (yolo4hip.augment) with seed=: every batch draws one parameter row per image from the generator's own
+    `numpy.random.default_rng(seed)`; `raw(i)` gives (uint8 images, parameters, transformed boxes) for the device path of
+    `Yolov4.fit` (`Engine.augment_u8_batch`), `boxes(i)` and `gen[i]` the same batch through `augment.augment_host` -- either
+    way one draw per image in batch order, so a seed gives the same parameters on both paths.  The box shuffle and the epoch
+    shuffle stay on the global `np.random`, as without augmentation."""
+
+    def __init__(self, annotation_lines, class_name_path, folder_path, max_boxes=100, shuffle=True, config=None, augment=None,
+                 seed=None):
         config = yolo_config if config is None else config
         self.annotation_lines = annotation_lines
         self.class_name_path = class_name_path
@@ -205,6 +213,8 @@ class DataGenerator:
         self.indexes = np.arange(len(self.annotation_lines))
         self.folder_path = folder_path
         self.max_boxes = max_boxes
+        self.augment = augment
+        self.rng = np.random.default_rng(seed)              # augmentation parameters only
         self.on_epoch_end()
 
     def __len__(self):
@@ -217,7 +227,30 @@ class DataGenerator:
     def __iter__(self):
         return (self[i] for i in range(len(self)))
 
+    def raw(self, index):
+        """Batch `index` of an augmenting generator -> (list of uint8 RGB images as read, parameter rows
+        (augment.PARAM_DTYPE) [n], boxes float32 [n, max_boxes, 5] already on the augmented canvas)."""
+        from . import augment as A
+        if self.augment is None:
+            raise ValueError("DataGenerator.raw: this generator does not augment (augment=None)")
+        idxs = self.indexes[index * self.batch_size:(index + 1) * self.batch_size]
+        read = [self._read(self.annotation_lines[j]) for j in idxs]
+        imgs = [img for img, _ in read]
+        hw = self.target_img_size[:2]
+        params = A.draw_params(self.rng, [img.shape[:2] for img in imgs], hw, self.augment)
+        y_bbox = np.zeros((len(idxs), self.max_boxes, 5), dtype=np.float32)
+        for i, (img, boxes) in enumerate(read):
+            y_bbox[i] = A.transform_boxes(boxes, img.shape[:2], params[i], hw, self.max_boxes)
+        return imgs, params, y_bbox
+
     def boxes(self, index):
+        if self.augment is not None:
+            from .augment import augment_host
+            imgs, params, y_bbox = self.raw(index)
+            X = np.empty((len(imgs), *self.target_img_size), dtype=np.float32)
+            for i, img in enumerate(imgs):
+                X[i] = augment_host(img, params[i], self.target_img_size[:2], self.augment.pad_value) / 255.
+            return X, y_bbox
         idxs = self.indexes[index * self.batch_size:(index + 1) * self.batch_size]
         X = np.empty((len(idxs), *self.target_img_size), dtype=np.float32)
         y_bbox = np.empty((len(idxs), self.max_boxes, 5), dtype=np.float32)
@@ -230,18 +263,25 @@ class DataGenerator:
         y_tensor, y_xywh = preprocess_true_boxes(y_bbox, self.target_img_size[:2], self.anchors, self.num_classes)
         return [X, *y_tensor, y_xywh], np.zeros(len(X))
 
-    def get_data(self, annotation_line):
-        """One annotation line "path x1,y1,x2,y2,cls ..." -> (image [H, W, 3] in [0, 1], boxes [max_boxes, 5] scaled to it)."""
+    def _read(self, annotation_line):
+        """One annotation line "path x1,y1,x2,y2,cls ..." -> (uint8 RGB image as read, its boxes float32 [k, 5] in the image's
+        own pixels, shuffled (global np.random) and cut to max_boxes)."""
         fields = annotation_line.split()
         img = prepost.imread_rgb(os.path.join(self.folder_path, fields[0]))
-        ih, iw = img.shape[:2]
-        h, w = self.target_img_size[:2]
         boxes = np.array([[float(v) for v in f.split(',')] for f in fields[1:]], dtype=np.float32)
-        image_data = prepost.resize_bilinear(img, (w, h)) / 255.
-        box_data = np.zeros((self.max_boxes, 5))
         if len(boxes) > 0:
             np.random.shuffle(boxes)
             boxes = boxes[:self.max_boxes]
+        return img, boxes
+
+    def get_data(self, annotation_line):
+        """One annotation line "path x1,y1,x2,y2,cls ..." -> (image [H, W, 3] in [0, 1], boxes [max_boxes, 5] scaled to it)."""
+        img, boxes = self._read(annotation_line)
+        ih, iw = img.shape[:2]
+        h, w = self.target_img_size[:2]
+        image_data = prepost.resize_bilinear(img, (w, h)) / 255.
+        box_data = np.zeros((self.max_boxes, 5))
+        if len(boxes) > 0:
             boxes[:, [0, 2]] = boxes[:, [0, 2]] * (w / iw)
             boxes[:, [1, 3]] = boxes[:, [1, 3]] * (h / ih)
             box_data[:len(boxes)] = boxes

@@ -261,34 +261,78 @@ class Engine:
         for stretch, prepost.box_map for letterbox).  Asynchronous on the current stream."""
         torch = self.torch
         from . import prepost
-        if isinstance(raw_imgs, np.ndarray) and raw_imgs.ndim == 3:
-            raw_imgs = [raw_imgs]
-        raw_imgs = list(raw_imgs)
+        raw_imgs, pad_value = self._check_ragged(raw_imgs, pad_value, "preprocess_u8_batch")
         n = len(raw_imgs)
-        if n == 0:
-            raise ValueError("preprocess_u8_batch: no images")
-        pad_value = int(pad_value)
-        if not 0 <= pad_value <= 255:
-            raise ValueError(f"pad_value must be a uint8 level 0..255, got {pad_value}")
         H, W = self.img_hw
-        for a in raw_imgs:
-            if getattr(a, "dtype", None) != np.uint8 or a.ndim != 3 or a.shape[2] != 3 or a.shape[0] < 1 or a.shape[1] < 1:
-                raise ValueError(f"expected uint8 [h,w,3] images, got {getattr(a, 'dtype', type(a))} {getattr(a, 'shape', '')}")
-        # staging layout: descriptors [n] (32 B each) | box map float32 [n,4] | the images, packed; descriptor offsets count from
-        # the first image byte
-        desc_bytes, map_bytes = n * C.sizeof(ext.y4_image_desc), n * 16
-        head = desc_bytes + map_bytes
         desc = (ext.y4_image_desc * n)()
         maps = np.empty((n, 4), np.float32)
-        off = 0
         for i, a in enumerate(raw_imgs):
             h, w = a.shape[:2]
             rect = prepost.letterbox_rect(h, w, H, W) if letterbox else (H, W, 0, 0)
             d = desc[i]
-            d.offset, d.h, d.w = off, h, w
             d.out_h, d.out_w, d.pad_top, d.pad_left = rect
             maps[i] = prepost.box_map(h, w, H, W, rect)
-            off += h * w * 3
+        dev, desc_bytes, head = self._upload_ragged(raw_imgs, desc, maps)
+        with torch.cuda.device(self.device):
+            out = torch.empty((n, H, W, 3), dtype=torch.uint8, device=self.device)
+            ext.check(self.lib.y4_resize_u8_ragged(C.c_void_p(dev.data_ptr() + head), ext.ptr(dev), n, ext.ptr(out), H, W,
+                                                   pad_value, ext.stream_ptr()))
+        return out, dev[desc_bytes:head].view(torch.float32).view(n, 4)
+
+    def augment_u8_batch(self, raw_imgs, params, pad_value=128):
+        """The training input of `Yolov4.fit` on the device: uint8 RGB images [h,w,3] of any mix of sizes and one parameter row
+        per image (yolo4hip.augment.PARAM_DTYPE: `draw_params`) -> the augmented uint8 cuda batch [n,H,W,3] for
+        `forward_device`, through one pinned staging buffer, one copy and one launch (`y4_augment_u8_ragged`): resize into a
+        rectangle that may stick out of the canvas, left-right flip and the HSV transform; `augment.augment_host` is the same
+        function on the host.  Asynchronous on the current stream."""
+        torch = self.torch
+        raw_imgs, pad_value = self._check_ragged(raw_imgs, pad_value, "augment_u8_batch")
+        n = len(raw_imgs)
+        if len(params) != n:
+            raise ValueError(f"augment_u8_batch: {n} images, {len(params)} parameter rows")
+        desc = (ext.y4_augment_desc * n)()
+        for d, p in zip(desc, params):
+            d.out_h, d.out_w, d.pad_top, d.pad_left = int(p["out_h"]), int(p["out_w"]), int(p["pad_top"]), int(p["pad_left"])
+            d.flip, d.hue, d.sat, d.val = int(p["flip"]), float(p["hue"]), float(p["sat"]), float(p["val"])
+            if d.out_h < 1 or d.out_w < 1 or not np.isfinite([d.hue, d.sat, d.val]).all():
+                raise ValueError(f"augment_u8_batch: rectangle {d.out_h} x {d.out_w}, factors {d.hue}, {d.sat}, {d.val}")
+        dev, _, head = self._upload_ragged(raw_imgs, desc)
+        H, W = self.img_hw
+        with torch.cuda.device(self.device):
+            out = torch.empty((n, H, W, 3), dtype=torch.uint8, device=self.device)
+            ext.check(self.lib.y4_augment_u8_ragged(C.c_void_p(dev.data_ptr() + head), ext.ptr(dev), n, ext.ptr(out), H, W,
+                                                    pad_value, ext.stream_ptr()))
+        return out
+
+    @staticmethod
+    def _check_ragged(raw_imgs, pad_value, who):
+        """One image or a list of them -> (list of uint8 [h,w,3] arrays, pad_value as an int), or ValueError."""
+        if isinstance(raw_imgs, np.ndarray) and raw_imgs.ndim == 3:
+            raw_imgs = [raw_imgs]
+        raw_imgs = list(raw_imgs)
+        if len(raw_imgs) == 0:
+            raise ValueError(f"{who}: no images")
+        pad_value = int(pad_value)
+        if not 0 <= pad_value <= 255:
+            raise ValueError(f"pad_value must be a uint8 level 0..255, got {pad_value}")
+        for a in raw_imgs:
+            if getattr(a, "dtype", None) != np.uint8 or a.ndim != 3 or a.shape[2] != 3 or a.shape[0] < 1 or a.shape[1] < 1:
+                raise ValueError(f"expected uint8 [h,w,3] images, got {getattr(a, 'dtype', type(a))} {getattr(a, 'shape', '')}")
+        return raw_imgs, pad_value
+
+    def _upload_ragged(self, raw_imgs, desc, extra=None):
+        """The one upload of a ragged batch (`preprocess_u8_batch`, `augment_u8_batch`): fills offset, h, w of every row of
+        `desc` (a ctypes array of y4_image_desc or y4_augment_desc), packs descriptors | `extra` (a numpy array, or None) | the
+        images into the pinned staging buffer (kept across calls) and copies it to a fresh device block in one copy.
+        -> (device block, descriptor bytes, bytes before the first image); descriptor offsets count from the first image byte."""
+        torch = self.torch
+        n = len(raw_imgs)
+        desc_bytes = C.sizeof(desc)
+        head = desc_bytes + (extra.nbytes if extra is not None else 0)
+        off = 0
+        for d, a in zip(desc, raw_imgs):
+            d.offset, d.h, d.w = off, a.shape[0], a.shape[1]
+            off += a.shape[0] * a.shape[1] * 3
         total = head + off
         pin = getattr(self, "_batch_pin", None)
         if pin is None or pin.numel() < total:
@@ -301,7 +345,8 @@ class Engine:
             self._batch_pin_free.synchronize()              # the previous call's upload has left the buffer
         buf = self._batch_pin_np
         buf[:desc_bytes] = np.frombuffer(desc, dtype=np.uint8)
-        buf[desc_bytes:head] = maps.view(np.uint8).reshape(-1)
+        if extra is not None:
+            buf[desc_bytes:head] = extra.view(np.uint8).reshape(-1)
 
         def pack(i):
             a, o = raw_imgs[i], head + desc[i].offset
@@ -318,14 +363,11 @@ class Engine:
             for i in range(n):
                 pack(i)
         with torch.cuda.device(self.device):
-            # a fresh device block per call (torch's caching allocator): the returned box map is a view of it and stays valid
+            # a fresh device block per call (torch's caching allocator): views of it (the box map) stay valid
             dev = torch.empty(total, dtype=torch.uint8, device=self.device)
             dev.copy_(pin[:total], non_blocking=True)
             self._batch_pin_free.record()
-            out = torch.empty((n, H, W, 3), dtype=torch.uint8, device=self.device)
-            ext.check(self.lib.y4_resize_u8_ragged(C.c_void_p(dev.data_ptr() + head), ext.ptr(dev), n, ext.ptr(out), H, W,
-                                                   pad_value, ext.stream_ptr()))
-        return out, dev[desc_bytes:head].view(torch.float32).view(n, 4)
+        return dev, desc_bytes, head
 
     def resize_u8_ragged(self, src_dev, desc_dev, n, out, pad_value=128):
         """y4_resize_u8_ragged on device buffers: `desc_dev` holds n y4_image_desc rows (offsets into `src_dev`), `out` is a

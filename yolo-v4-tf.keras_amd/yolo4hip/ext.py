@@ -53,6 +53,10 @@ class y4_image_desc(C.Structure):
                 ("pad_top", C.c_int32), ("pad_left", C.c_int32)]
 
 
+class y4_augment_desc(C.Structure):
+    _fields_ = y4_image_desc._fields_ + [("flip", C.c_int32), ("hue", C.c_float), ("sat", C.c_float), ("val", C.c_float)]
+
+
 # every symbol include/yolo4hip.h declares: name -> (restype, argtypes)
 _VP, _I, _F = C.c_void_p, C.c_int, C.c_float
 SYMBOLS = {
@@ -123,6 +127,7 @@ SYMBOLS = {
     "y4_preprocess_u8": (_I, [_VP, _I, _I, _VP, _I, _I, _VP]),
     "y4_resize_u8": (_I, [_VP, _I, _I, _I, _VP, _I, _I, _VP]),
     "y4_resize_u8_ragged": (_I, [_VP, _VP, _I, _VP, _I, _I, _I, _VP]),
+    "y4_augment_u8_ragged": (_I, [_VP, _VP, _I, _VP, _I, _I, _I, _VP]),
     "y4_spp": (_I, [_I, _VP, _I, _I, _I, _VP]),
     "y4_spp_hw": (_I, [_I, _VP, _I, _I, _I, _I, _VP]),
 }
