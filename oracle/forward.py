@@ -42,7 +42,12 @@ def _round_storage(t, storage):
 
 
 class _Net:
-    def __init__(self, weights, dtype, collect=None, storage=None, trunk=None):
+    def __init__(self, weights, dtype, collect=None, storage=None, trunk=None, pre=None, rewrite=None):
+        # pre (a dict): filled with the pre-activation (after BN / bias, before the activation) of every conv in `collect`.
+        # rewrite(idx, cw, raw) -> cw: called with every BN conv's raw output before its BN is applied; what it returns is used
+        # from there on (tests/helpers.widen_activations calibrates BN rows in one pass with it).  Test diagnostics, not reference behaviour.
+        self.pre = pre
+        self.rewrite = rewrite
         self.weights = weights
         self.dtype = dtype
         self.i = 0
@@ -74,6 +79,8 @@ class _Net:
             y = F.conv2d(x, w, None, stride=2, padding=0)
         else:
             y = F.conv2d(x, w, None, stride=1, padding=kernel_size // 2)
+        if batch_norm and self.rewrite is not None:
+            cw = self.rewrite(idx, cw, y)
         if batch_norm:
             beta, gamma, mean, var = (torch.from_numpy(np.ascontiguousarray(r)).to(self.dtype) for r in cw.bn)
             scale = gamma * torch.rsqrt(var + BN_EPS)
@@ -81,6 +88,8 @@ class _Net:
             y = y * scale.view(1, -1, 1, 1) + shift.view(1, -1, 1, 1)
         else:
             y = y + torch.from_numpy(np.ascontiguousarray(cw.bias)).to(self.dtype).view(1, -1, 1, 1)
+        if self.pre is not None and idx in self.collect:
+            self.pre[idx] = y.permute(0, 2, 3, 1).contiguous().numpy()
         if activation == "mish":
             y = y * torch.tanh(F.softplus(y))     # :6-7
         elif activation == "leaky":
@@ -199,17 +208,18 @@ class _Net:
         return [conv_sbbox, conv_mbbox, conv_lbbox]
 
 
-def yolo_model_forward(imgs_nhwc, weights, num_classes, dtype=torch.float32, collect=None, threads=None, storage=None, trunk=None):
+def yolo_model_forward(imgs_nhwc, weights, num_classes, dtype=torch.float32, collect=None, threads=None, storage=None, trunk=None,
+                       pre=None, rewrite=None):
     """`yolo_model.predict(imgs)` (`models.py:50-52`): NHWC float images in [0,1] -> list of 3 NHWC
     arrays [N,H/8,W/8,3(C+5)], [N,H/16,..], [N,H/32,..] (raw logits).  With `collect=[conv idx...]`
     also returns {idx: NHWC array of that conv's post-activation output}.  `storage` ('bf16' | 'f16'): emulate the 16-bit
-    storage pipeline (see _Net) -- a diagnostic, not a reference behaviour."""
+    storage pipeline (see _Net) -- a diagnostic, not a reference behaviour.  `pre`, `rewrite`: see _Net."""
     if threads:
         torch.set_num_threads(int(threads))
     x = torch.from_numpy(np.ascontiguousarray(imgs_nhwc)).to(dtype)      # Keras casts to float32
     x = _round_storage(x, storage)                      # the stem's MFMA operand is 16-bit
     x = x.permute(0, 3, 1, 2).contiguous(memory_format=torch.channels_last)
-    net = _Net(weights, dtype, collect, storage, trunk)
+    net = _Net(weights, dtype, collect, storage, trunk, pre, rewrite)
     with torch.no_grad():
         outs = net.yolov4_neck(x, num_classes)
     assert net.i == len(weights) == 110, net.i

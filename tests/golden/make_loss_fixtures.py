@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Loss fixtures written by the REFERENCE'S OWN PYTHON (runs only where /root/reference exists; nothing of it is copied).
 
-  python tests/golden/make_loss_fixtures.py          writes tests/golden/loss_416_bccd.npz and loss_160_coco.npz
+  python tests/golden/make_loss_fixtures.py          writes tests/golden/loss_<case>.npz for every case of tests/loss_cases.py
   python tests/golden/make_loss_fixtures.py --seeds  prints, per case, the first seed that passes check_case
 
 The reference's `loss.py` and `utils.py` are imported UNMODIFIED.  `tensorflow` is a module of eager torch-CPU float32

@@ -3,10 +3,10 @@
 imported unmodified through make_loss_fixtures.import_reference, under the same eager torch-CPU stand-in for `tensorflow`;
 nothing of it is copied).
 
-  python tests/golden/make_lossgrad_fixtures.py          writes tests/golden/lossgrad_416_bccd_g.npz and lossgrad_160_coco_g.npz
+  python tests/golden/make_lossgrad_fixtures.py          writes tests/golden/lossgrad_<case>.npz for every case of tests/lossgrad_cases.py
   python tests/golden/make_lossgrad_fixtures.py --seeds  prints, per case, the first seed that passes every assertion
 
-For the two cases of tests/lossgrad_cases.py (those of loss_cases.py hold exact ties, see there): `yolo_loss([heads..., labels..., true_xywh])` with the three heads as leaves, then
+For the cases of tests/lossgrad_cases.py (those of loss_cases.py hold exact ties, see there): `yolo_loss([heads..., labels..., true_xywh])` with the three heads as leaves, then
 `.backward()`, once in float32 and once in float64.  Stored per scale s: the confidence columns dense (`conf32_s`, `conf64_s`:
 [n, gh, gw, 3]), every other non-zero as flat index + value (`idx_s`, `val32_s`, `val64_s` over the union of both runs'
 non-zeros), `d_ref` [3] = max |g32 - g64| / max |g64| per scale -- how far the reference's own float32 gradient lies from

@@ -138,6 +138,41 @@ def randomize_bn(ws, seed):
     return out
 
 
+def widen_activations(ws, seed, sigma=12.0):
+    """A copy of a synthetic weight set (3 x (5 + C) head channels) whose activations leave the range of order 1: the BN gamma and
+    beta of every BN conv -- the backbone's convs 0..37 and the neck's alike -- are rescaled and shifted so that the conv's
+    pre-activation has standard deviation `sigma` about a per-channel centre drawn from U(-4, 4), with the sign of gamma flipped
+    on three channels in ten: 2 Phi(-20 / 12) = 9.6 % of the pre-activations lie beyond +-20, the largest of a layer near 6 sigma.
+    The scale is set layer by layer in ONE pass of the oracle over two 96 x 96 synthetic images (the layer's pooled standard
+    deviation, each channel's mean), so a layer sees the widened output of the layers before it -- what a constant factor per layer
+    cannot do without compounding.  The three convs in front of the heads (92, 100, 108) are brought back to N(1, 1), so that the
+    raw heads stay of the order the synthetic net was built for.  Kernels are untouched; mean and var rows stay 0 and 1."""
+    from oracle.forward import yolo_model_forward
+    from yolo4hip import weights as W
+    from yolo4hip.weights import BN_EPS, ConvWeights
+    out = list(ws)
+    ncls = ws[93].bias.shape[0] // 3 - 5
+
+    def rewrite(idx, cw, raw):
+        rng = np.random.default_rng([seed, 0xA1DE, idx])
+        r = raw.numpy().astype(np.float64)                                   # [n, cout, h, w]
+        cout = r.shape[1]
+        m = r.mean(axis=(0, 2, 3))
+        s = max(float(np.sqrt(((r - m[None, :, None, None]) ** 2).mean())), 1e-6)
+        if idx in (92, 100, 108):
+            g, centre = np.full(cout, 1.0 / s), np.ones(cout)
+        else:
+            g = np.where(rng.random(cout) < 0.3, -1.0, 1.0) * sigma / s
+            centre = rng.uniform(-4.0, 4.0, cout)
+        _, _, mean, var = cw.bn.astype(np.float64)
+        gamma = g * np.sqrt(var + BN_EPS)                                    # scale = gamma / sqrt(var + eps) = g
+        beta = centre - (m - mean) * g                                       # shift = beta - mean * scale = centre - m g
+        out[idx] = ConvWeights(w=cw.w, bn=np.stack([beta, gamma, mean, var]).astype(np.float32))
+        return out[idx]
+    yolo_model_forward(W.synth_images(2, 96, seed), out, ncls, rewrite=rewrite)
+    return out
+
+
 def detection_agreement(kept, classes, scores, boxes, valid, ri, rc, rs, rb, rv):
     """Per-image agreement of two NMS results matched by (box index, class): fraction of the reference's
     detections also present, max |score delta| and max |box delta| over the matched ones."""

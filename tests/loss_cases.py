@@ -15,6 +15,9 @@ IOU_LOSS_THRESH = 0.5
 CASES = {
     "416_bccd": dict(hw=(416, 416), ncls=3, n=4, seed=1),
     "160_coco": dict(hw=(160, 160), ncls=80, n=4, seed=2),
+    # heads far outside the range a freshly initialised detector produces (make_heads(wide=True)): saturating confidence and class
+    # logits, xy at the cell borders, boxes from a fraction of a pixel to thousands of pixels
+    "160_wide": dict(hw=(160, 160), ncls=3, n=4, seed=1, wide=True),
 }
 
 
@@ -51,8 +54,48 @@ def make_boxes(hw, ncls, n, seed, max_boxes=MAX_BOXES):
     return boxes
 
 
-def make_heads(hw, ncls, n, seed, records):
+def _make_heads_wide(hw, ncls, n, seed, records):
+    """The heads of a net whose logits left the range of order 1: confidence and class logits uniform over +-40 on every lane, the
+    responsible ones included (so both the right and the wrong sign occur there, saturated), xy logits over +-20 and wh logits over
+    +-8 -- around the label's value on the lanes that predict a labelled box, half of which stay near their label as in make_heads
+    (the ignore region and a box term that is not all saturation)."""
+    rng = np.random.default_rng(seed + 1000)
+    heads = []
+    for s, stride in enumerate(STRIDES):
+        gh, gw = hw[0] // stride, hw[1] // stride
+        t = np.empty((n, gh, gw, 3, 5 + ncls))
+        t[..., 0:2] = rng.uniform(-20.0, 20.0, size=t[..., 0:2].shape)
+        t[..., 2:4] = rng.uniform(-8.0, 8.0, size=t[..., 2:4].shape)
+        t[..., 4:] = rng.uniform(-40.0, 40.0, size=t[..., 4:].shape)
+        heads.append(t)
+    for b, rec in enumerate(records):
+        for r in rec:
+            s, row, col, a = (int(v) for v in r[0:4])
+            x, y, w, h = r[4:8].view(np.float32).astype(np.float64)
+            if w <= 0 or h <= 0:
+                continue
+            u = rng.uniform(size=3)
+            picks = [a] if u[0] < 0.75 else []
+            if u[1] < 0.5:
+                picks.append((a + 1) % 3)
+            for q in picks:
+                t = heads[s][b, row, col, q]
+                off = np.clip(np.array([x / STRIDES[s] - col, y / STRIDES[s] - row]), 0.05, 0.95)
+                near = u[2] < 0.5
+                t[0:2] = np.log(off / (1 - off)) + rng.normal(0.0, 0.3, size=2) if near else rng.uniform(-20.0, 20.0, size=2)
+                t[2:4] = np.log(np.array([w, h]) / ANCHORS[3 * s + q]) + (rng.normal(0.0, 0.15, size=2) if near else rng.uniform(-8.0, 8.0, size=2))
+    out = []
+    for t in heads:
+        t[..., 0:2] = np.clip(t[..., 0:2], -20.0, 20.0)
+        t[..., 4:] = np.clip(t[..., 4:], -40.0, 40.0)
+        out.append(_snap(t).reshape(t.shape[:3] + (3 * (5 + ncls),)))
+    return out
+
+
+def make_heads(hw, ncls, n, seed, records, wide=False):
     """Three float32 heads [n, gh, gw, 3 (5 + C)]; `records` (per image, yolo4hip.data format) say where the labels are."""
+    if wide:
+        return _make_heads_wide(hw, ncls, n, seed, records)
     rng = np.random.default_rng(seed + 1000)
     heads = []
     for s, stride in enumerate(STRIDES):
@@ -94,6 +137,6 @@ def make_case(name):
     c = CASES[name]
     boxes = make_boxes(c["hw"], c["ncls"], c["n"], c["seed"])
     records, _ = records_from_boxes(boxes, c["hw"], ANCHORS, c["ncls"])
-    heads = make_heads(c["hw"], c["ncls"], c["n"], c["seed"], records)
+    heads = make_heads(c["hw"], c["ncls"], c["n"], c["seed"], records, c.get("wide", False))
     sha = hashlib.sha256(b"".join(np.ascontiguousarray(a).tobytes() for a in [boxes] + heads)).hexdigest()
     return dict(hw=c["hw"], ncls=c["ncls"], n=c["n"], boxes=boxes, heads=heads, sha=sha)

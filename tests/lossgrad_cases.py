@@ -14,6 +14,7 @@ import loss_cases as LC
 CASES = {
     "416_bccd_g": dict(hw=(416, 416), ncls=3, n=4, seed=2),
     "160_coco_g": dict(hw=(160, 160), ncls=80, n=4, seed=6),
+    "160_wide_g": dict(hw=(160, 160), ncls=3, n=4, seed=1, wide=True),         # loss_cases._make_heads_wide
 }
 
 
@@ -31,6 +32,6 @@ def make_case(name):
     c = CASES[name]
     boxes = make_boxes(c["hw"], c["ncls"], c["n"], c["seed"])
     records, _ = records_from_boxes(boxes, c["hw"], LC.ANCHORS, c["ncls"])
-    heads = LC.make_heads(c["hw"], c["ncls"], c["n"], c["seed"], records)
+    heads = LC.make_heads(c["hw"], c["ncls"], c["n"], c["seed"], records, c.get("wide", False))
     sha = hashlib.sha256(b"".join(np.ascontiguousarray(a).tobytes() for a in [boxes] + heads)).hexdigest()
     return dict(hw=c["hw"], ncls=c["ncls"], n=c["n"], boxes=boxes, heads=heads, sha=sha)

@@ -160,8 +160,8 @@ def test_training_model_predict_end_to_end(hw, dtype, seed):
     box_front = m.engine.loss(imgs, boxes=boxes)
     assert np.array_equal(dense.view(np.int32), box_front.view(np.int32))     # the dense front and the box front: same bits
     # no reference run exists for these heads: d_ref is the reference's own error where it was measured, the larger of the
-    # two fixture sets per (scale, term)
-    d_ref = np.maximum(*(load_fixture(name)[1]["d_ref"] for name in CASE_NAMES))
+    # two fixture sets with heads of order 1 per (scale, term)
+    d_ref = np.maximum(*(load_fixture(name)[1]["d_ref"] for name in ("160_coco", "416_bccd")))
     _within_budget(f"e2e_{hw[0]}x{hw[1]}_{dtype}", dense, oracle, d_ref)
     assert abs(float(loss) - LO.total(oracle)) <= 5e-6 * LO.total(oracle)
     assert np.float32(combine_loss(dense)[0].mean()) == loss
