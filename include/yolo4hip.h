@@ -317,7 +317,8 @@ int y4_get_tiles(y4_handle h, int32_t* tiles, int cap);
  * force); a plain -t (older files) leaves the own tile as it is, so y4_set_tiles(y4_get_tiles()) restores a handle exactly. */
 int y4_set_tiles(y4_handle h, const int32_t* tiles, int count);
 /* Every scheduling choice of `src` -> `dst`, a second handle created from the same configuration (the sibling that runs a second
- * batch in flight): tiles, each run's state, stage-kernel and residual-block verdicts, the fusion switches, sub-batching.
+ * batch in flight): the `Schedule` (csrc/runtime.hip) -- tiles, each run's state, stage-kernel and residual-block verdicts, the
+ * fusion switches, sub-batching, the halo2 permission.
  * (No reference counterpart: TensorFlow's executor schedules the reference's graph; models.py:113,159.) */
 int y4_copy_schedule(y4_handle src, y4_handle dst);
 

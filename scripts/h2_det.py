@@ -20,7 +20,8 @@ saved = json.load(open(sched))
 swap = dict((int(x.split(":")[0]), int(x.split(":")[1])) for x in a.swap.split(",") if x)
 saved["tiles"] = [swap.get(t, t) for t in saved["tiles"]]
 eng.apply_schedule(saved)
-print("halo2 ids in use:", sorted(set(t for t in saved["tiles"] if 55 <= t <= 62)))
+from yolo4hip import schedule
+print("halo2 ids in use:", sorted(set(t for e in saved["tiles"] for t in schedule.decode(e) if schedule.uses_halo2(eng.lib, [t]))))
 fl, u8 = _inputs(eng, size, n)
 side = torch.cuda.Stream(device=eng.device)
 junk = torch.randn(2048, 2048, device=eng.device)

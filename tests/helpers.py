@@ -36,7 +36,7 @@ def run_conv_gpu(x, cw, k, stride, act, dtype, residual=None, upsample=False, ou
     in_pad/out_pad = (channels before, channels after) of extra garbage around the view, to exercise
     channel-slice reads/stores.  Returns float32 NHWC output (the slice only) and the full out buffer."""
     import torch
-    from yolo4hip import ext
+    from yolo4hip import ext, schedule
     lib = ext.load()
     dev = "cuda:0"
     td = torch_dtype(dtype)
@@ -69,10 +69,8 @@ def run_conv_gpu(x, cw, k, stride, act, dtype, residual=None, upsample=False, ou
     d.in_ = xin.data_ptr(); d.wt = packed.data_ptr(); d.scale = sc.data_ptr(); d.shift = sh.data_ptr()
     d.out = out.data_ptr(); d.tile = tile
     frag = None
-    if k == 3 and dtype != "f32" and cin % 64 == 0 and 1 <= tile % 100 <= lib.y4_conv_tile_count():
-        cfg = (C.c_int32 * 6)()
-        ext.check(lib.y4_conv_tile_desc(tile % 100, cfg))
-        if cfg[5] == 21:                 # a halo2 tile: the weights once more in MFMA-fragment order
+    if k == 3 and dtype != "f32" and cin % 64 == 0 and 1 <= schedule.base(tile) <= lib.y4_conv_tile_count():
+        if schedule.uses_halo2(lib, [tile]):     # the weights once more in MFMA-fragment order
             frag = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
             ext.check(lib.y4_pack_conv_frag32(did, cout, cin, ext.ptr(packed), ext.ptr(frag), ext.stream_ptr()))
             d.wt_frag = frag.data_ptr()
@@ -217,7 +215,7 @@ def tap_snapshot(eng, n):
     if not hasattr(eng, "_lt"):
         eng._lt = eng.layer_table()
     snap = {}
-    if not getattr(eng, "alias_workspace", False):
+    if not eng.alias_workspace:
         for i, lt in enumerate(eng._lt):
             side = lt["out_side"] * (2 if i in (78, 85) else 1)
             out = torch.empty((n, side, side, lt["cout"]), dtype=torch.float32, device=eng.device)

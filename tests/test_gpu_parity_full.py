@@ -102,7 +102,7 @@ def test_headline_config_vs_oracle(dtype):
     bench.py times -- against oracle.forward (fp32) on 4 images of the batch (indices 0, 9, 18, 31).  bf16 is what BASELINE names;
     fp16 is the same kernels at the same MFMA rate with three more mantissa bits (measured side by side)."""
     import torch
-    from yolo4hip import weights as W
+    from yolo4hip import schedule, weights as W
     from yolo4hip.plan import build_plan
     size, ncls, n = 608, 80, 32
     ws = W.synth_weights(build_plan(size, ncls), seed=0)
@@ -131,7 +131,7 @@ def test_headline_config_vs_oracle(dtype):
     # ... and the schedule that SHIPS for this shape (what the default bench.py and the facade run): since round 6 it holds halo2 tile
     # ids (conv_halo2_kernel.h: k-steps of 16, another fixed fp32 summation order) -- the same budget against the same oracle
     sched = eng.shipped_schedule()
-    assert sched is not None and sched.get("halo2") == any(55 <= t <= 62 for t in sched["tiles"])
+    assert sched is not None and sched.get("halo2") == schedule.uses_halo2(eng.lib, sched["tiles"])
     eng.set_res_fusion(True)
     eng.apply_schedule(sched)
     outs = [o.cpu().numpy() for o in eng.predict_device(dev)]
@@ -293,7 +293,7 @@ def test_shipped_schedule_keeps_the_bits_at_the_headline_shape():
         the same 16-bit pipeline have from each other (the `kernels` figure of test_16bit_error_is_the_storage_floor: of the
         size of the storage floor itself) -- its distance to the ORACLE is held by test_headline_config_vs_oracle."""
     import torch
-    from yolo4hip import weights as W
+    from yolo4hip import schedule, weights as W
     from yolo4hip.config import make_config
     from yolo4hip.engine import Engine
     from yolo4hip.plan import build_plan
@@ -306,8 +306,8 @@ def test_shipped_schedule_keeps_the_bits_at_the_headline_shape():
     plain = [o.cpu().numpy() for o in eng.predict_device(imgs)]
     plain_heads = [h.cpu().numpy() for h in eng.heads_device(n)]
     eng.set_stem_fusion(True); eng.set_chain_fusion(True); eng.set_stage_fusion(True); eng.set_res_fusion(True)
-    is_h2 = lambda t: 55 <= t <= 62
-    assert bool(sched.get("halo2")) == any(is_h2(t) for t in sched["tiles"])
+    is_h2 = lambda t: schedule.uses_halo2(eng.lib, [t])
+    assert bool(sched.get("halo2")) == schedule.uses_halo2(eng.lib, sched["tiles"])
     no_h2 = dict(sched)
     no_h2["tiles"] = [51 if is_h2(t) else t for t in sched["tiles"]]          # the 16x16x32 halo tile every one of these layers also fits
     eng.apply_schedule(no_h2)

@@ -132,7 +132,7 @@ def test_every_shipped_schedule_is_accepted_by_the_library():
     import itertools
     import glob
     import json
-    from yolo4hip import ext
+    from yolo4hip import ext, schedule
     from yolo4hip.config import make_config
     from yolo4hip.engine import _cfg_struct
     lib = ext.load()
@@ -155,8 +155,7 @@ def test_every_shipped_schedule_is_accepted_by_the_library():
             assert lib.y4_set_res_fusion(h, 1) > 0
         if s.get("splitk"):                                # latency schedules: split-K ids (base + 100 e) on plain launches only
             assert s["batch"] <= 2 and any(t >= 100 for t in s["tiles"]) and all(t < 400 for t in s["tiles"])
-        else:
-            assert all(abs(t) % 1000 < 100 for t in s["tiles"])
+        assert schedule.uses_splitk(s["tiles"]) == bool(s.get("splitk"))          # (both halves of every entry)
         tiles = (C.c_int32 * len(s["tiles"]))(*s["tiles"])
         assert len(s["tiles"]) == lib.y4_num_layers(h) == 110
         ext.check(lib.y4_set_tiles(h, tiles, len(s["tiles"])))
@@ -175,7 +174,7 @@ def test_every_shipped_schedule_is_accepted_by_the_library():
         # a run head's own tile survives the round trip: give conv 15 (the alternative run's head) one, with the run in force
         if back[15] < 0:
             probe = list(back)
-            probe[15] = -((-back[15]) % 1000 + 1000 * 7)
+            probe[15] = schedule.encode(schedule.decode(back[15])[0], 7)
             arr = (C.c_int32 * 110)(*probe)
             ext.check(lib.y4_set_tiles(h, arr, 110))
             ext.check(lib.y4_get_tiles(h, back2, 110))
@@ -186,8 +185,8 @@ def test_every_shipped_schedule_is_accepted_by_the_library():
             assert list(back3) == probe
             ext.check(lib.y4_set_tiles(h, tiles, len(s["tiles"])))       # a plain -t (older files) leaves the own tile: still 7
             ext.check(lib.y4_get_tiles(h, back2, 110))
-            own = (-s["tiles"][15]) // 1000 or 7
-            assert back2[15] == -((-s["tiles"][15]) % 1000 + 1000 * own)
+            run, own = schedule.decode(s["tiles"][15])
+            assert back2[15] == schedule.encode(run, own or 7)
         assert lib.y4_copy_schedule(h, h) < 0
         lib.y4_destroy(h2)
         if not f32:

@@ -42,7 +42,6 @@ struct Op {
     int conv = -1;
     View in, out, res;
     bool has_res = false, upsample = false, out_f32 = false;
-    int tile = 0;          // 0 = heuristic; set by y4_autotune
     int conv2 = -1;        // fused CSP pair: second conv index (main-in), its output view and the channel split
     View out2;
     int split = 0;
@@ -66,10 +65,8 @@ struct Layer {
 // then one or two 1x1 convs; the second reads Concatenate([first tail's output, route]).
 struct Chain {
     int head, tail[2];      // op indices (tail[1] = -1 for a 2-conv chain)
-    bool store_x;           // the head's output has other consumers and is still written
+    bool store_x;           // the head's output has other consumers and is still written (y4_ctx::stores_x adds retention)
     bool lds_pair = false;  // the tail runs from the head's tile kept in LDS (128/256 channels), not from registers
-    bool enabled = true;    // y4_autotune turns a run off when its separate kernels measure faster
-    int tile = 0;           // the head's tile when it runs chained (0 = heuristic); Op::tile stays the unfused choice
     // "Alternative" run (conv_chain.h CFG 4): the 64 -> 64 tail of run `alt_of` as a HEAD chained straight to that run's conv
     // over the concat (tail[0] here).  In force only while run `alt_of` cannot exist because its own head executes inside
     // a residual-block kernel.
@@ -82,6 +79,41 @@ struct ResRun {
     int c;                  // channels (64 | 128): the tuner decides per channel group
     size_t blob_off = 0;    // fragment-ordered weights + affine in the wts workspace
 };
+
+// Every scheduling choice of a handle: which kernel runs each op.  The plan (Op, Chain, ResRun) is fixed once y4_create_hw
+// returns; the setters and the autotuner write only this, and y4_copy_schedule copies it whole.
+struct Schedule {
+    struct Run {
+        bool enabled = true;          // y4_autotune turns a run off when its separate kernels measure faster
+        int tile = 0;                 // the head's tile when it runs chained (0 = heuristic); tile[head] stays the unfused choice
+    };
+    std::vector<int> tile;            // per op: 0 = heuristic
+    std::vector<Run> run;             // per Chain
+    bool fuse_stem = false;           // convs 0+1 as one kernel (stem_down.hip): op 0 launches it into op 1's output view, op 1 is a no-op
+    bool fuse_chains = false;         // the runs as one kernel each
+    // the stage kernel and the residual-block kernels (group 0 = C 128, 1 = C 64): `_on` = requested, `_enabled` = the tuner's verdict
+    bool stage_on = false, stage_enabled = true;
+    bool res_on = false, res_enabled[2] = {true, true};
+    // sub-batching: ops [0, sub_last_op] run over `sub_images` images at a time (keeps the large early
+    // activations of one sub-batch resident in the 256 MiB Infinity Cache between producer and consumer)
+    int sub_images = 0, sub_last_op = -1;
+    // y4_autotune may pick halo2 tile ids (conv_halo2_kernel.h: v_mfma_32x32x16, another fp32 summation order than the 16x16x32 tiles)
+    bool allow_halo2 = false;
+};
+// Would two handles run the same kernels for the same tiles (y4_autotune_pair)?  The switches and sub-batching, not the tiles
+// and verdicts the tuner writes.  A new switch goes into the struct and, if a pair must agree on it, here.
+static bool same_switches(const Schedule& a, const Schedule& b) {
+    return a.fuse_stem == b.fuse_stem && a.fuse_chains == b.fuse_chains && a.stage_on == b.stage_on && a.res_on == b.res_on &&
+           a.sub_images == b.sub_images && a.sub_last_op == b.sub_last_op;
+}
+
+// One entry of y4_set_tiles / y4_get_tiles.  A plain conv's entry is its tile id.  The head of a run carries two choices in one
+// entry, so that a get -> set round trip loses neither: -(run tile + 1000 * stand-alone tile) while the run executes as one
+// kernel (0: with the heuristic tile; plain -t leaves the stand-alone tile as it is), its stand-alone tile (> 0) while it runs
+// as separate kernels.  Either tile may be a split-K id, base + 100 e (conv_tiles.h).
+struct TileEntry { int run, own; bool chained; };      // chained: entry <= 0
+static TileEntry decode_entry(int v) { return v < 0 ? TileEntry{(-v) % 1000, (-v) / 1000, true} : TileEntry{0, v, v == 0}; }
+static int encode_entry(int run, int own) { return -(run + 1000 * own); }
 
 }  // namespace y4
 
@@ -99,6 +131,33 @@ struct y4_ctx {
     std::vector<Buffer> bufs;
     std::vector<Op> ops;
     View heads[3];
+    std::vector<Chain> chains;        // 3x3+Add -> 1x1 (-> 1x1 over the concat) runs found in the plan
+    // the first CSP stage (convs 2..7) as one spatially tiled kernel (csp_stage.hip): ops [stage_first, stage_last];
+    // stage_first < 0 when the plan / dtype does not allow it
+    int stage_first = -1, stage_last = -1;
+    size_t stage_blob_off = 0;
+    std::vector<ResRun> resruns;      // residual blocks of the 128- and 64-channel stages as one kernel each
+    // ---- the plan above is fixed once y4_create_hw returns; this is what the setters and the tuner change
+    Schedule sched;
+    // a tuner permission and tuner scratch, not choices: y4_copy_schedule does not carry them
+    bool allow_splitk = false;        // y4_autotune may pick split-K tile ids (conv_tiles.h); their counters + partial sums live at splitk_off
+    int force_chain = -1;             // the tuner times this alternative run while the residual-block kernels are switched off
+    bool stage_active() const { return stage_first >= 0 && sched.stage_on && sched.stage_enabled; }
+    const ResRun* res_of(int oi, bool* is_head) const {
+        if (!sched.res_on) return nullptr;
+        for (const ResRun& r : resruns)
+            if ((r.head == oi || r.tail == oi) && sched.res_enabled[r.c == 128 ? 0 : 1]) { if (is_head) *is_head = r.head == oi; return &r; }
+        return nullptr;
+    }
+    bool heads_res(int oi) const { bool is_head = false; return res_of(oi, &is_head) && is_head; }
+    // does this run execute as one kernel under the current settings?
+    bool chain_active(const Chain& ch) const {
+        const int ci = (int)(&ch - chains.data());
+        if (!sched.fuse_chains || !sched.run[ci].enabled) return false;
+        if (ch.alt_of >= 0) return ci == force_chain || res_of(chains[ch.alt_of].head, nullptr) != nullptr;
+        if (force_chain >= 0 && chains[force_chain].alt_of == ci) return false;
+        return res_of(ch.head, nullptr) == nullptr;
+    }
     // workspace layout
     size_t act_bytes = 0, wts_bytes = 0;
     size_t zero_off = 0, dbox_off = 0, keys_off = 0, counts_off = 0, status_off = 0, scratch_off = 0, splitk_off = 0, obj_off = 0;
@@ -106,10 +165,6 @@ struct y4_ctx {
     // -- written by the head conv's own launch, so they ARE the stored logits; y4_set_heads writes heads only and voids them
     int obj_n[3] = {-1, -1, -1};
     int cells_per_img = 0, cell_base[3] = {0, 0, 0};
-    // latency schedules: y4_autotune may pick split-K tile ids (conv_tiles.h); their counters + partial sums live at splitk_off
-    bool allow_splitk = false;
-    // y4_autotune may pick halo2 tile ids (conv_halo2_kernel.h: v_mfma_32x32x16, another fp32 summation order than the 16x16x32 tiles)
-    bool allow_halo2 = false;
     // decode's per-image candidate counters are zero (nms_kernel resets them); false: the next decode clears them itself
     bool counts_clean = false;
     int counts_n = 0;
@@ -123,40 +178,7 @@ struct y4_ctx {
     std::vector<int> t_slot_op;       // op index credited with each event interval of a step
     std::vector<char> t_rec;          // per launch: record an event after it?
     bool t_coarse = false;            // events only where the op kind changes (stem | conv run | spp | conv run | decode | nms)
-    // sub-batching: ops [0, sub_last_op] run over `sub_images` images at a time (keeps the large early
-    // activations of one sub-batch resident in the 256 MiB Infinity Cache between producer and consumer)
-    int sub_images = 0, sub_last_op = -1;
-    // convs 0+1 as one kernel (stem_down.hip): op 0 launches it into op 1's output view, op 1 becomes a no-op
-    bool fuse_stem = false;
-    // 3x3+Add -> 1x1 (-> 1x1 over the concat) runs found in the plan, executed as one kernel each when fuse_chains
-    std::vector<Chain> chains;
-    bool fuse_chains = false;
     bool t_recorded_this_call = false;
-    // the first CSP stage (convs 2..7) as one spatially tiled kernel (csp_stage.hip): ops [stage_first, stage_last];
-    // stage_first < 0 when the plan / dtype does not allow it.  `stage_on` = requested, `stage_enabled` = the tuner's verdict
-    int stage_first = -1, stage_last = -1;
-    size_t stage_blob_off = 0;
-    bool stage_on = false, stage_enabled = true;
-    bool stage_active() const { return stage_first >= 0 && stage_on && stage_enabled; }
-    // residual blocks of the 128- and 64-channel stages as one kernel each; group 0 = C 128, group 1 = C 64
-    std::vector<ResRun> resruns;
-    bool res_on = false, res_enabled[2] = {true, true};
-    const ResRun* res_of(int oi, bool* is_head) const {
-        if (!res_on) return nullptr;
-        for (const ResRun& r : resruns)
-            if ((r.head == oi || r.tail == oi) && res_enabled[r.c == 128 ? 0 : 1]) { if (is_head) *is_head = r.head == oi; return &r; }
-        return nullptr;
-    }
-    // does this run execute as one kernel under the current settings?  (force_chain: the tuner times an alternative run while
-    // the residual-block kernels are switched off)
-    int force_chain = -1;
-    bool chain_active(const Chain& ch) const {
-        if (!fuse_chains || !ch.enabled) return false;
-        const int ci = (int)(&ch - chains.data());
-        if (ch.alt_of >= 0) return ci == force_chain || res_of(chains[ch.alt_of].head, nullptr) != nullptr;
-        if (force_chain >= 0 && chains[force_chain].alt_of == ci) return false;
-        return res_of(ch.head, nullptr) == nullptr;
-    }
     // images of the current call are uint8 frames at network size (y4_forward_u8 / y4_predict_u8): the stem divides by 255
     bool img_u8 = false;
     // activation buffers share memory when their lifetimes do not overlap (y4_set_workspace_aliasing): a quarter of the
@@ -168,6 +190,8 @@ struct y4_ctx {
     // level 2 of the same switch: the inputs of convs 92 / 100 / 108 (the outputs of convs 91 / 99 / 107) live to the end of the
     // forward too: y4_block_grad reads them
     bool retain_block_in = false;
+    // is the head's output of this run written to HBM?  (an LDS pair in front of a head conv: also when that conv's input is retained)
+    bool stores_x(const Chain& ch) const { return ch.store_x || (ch.lds_pair && retain_head_in && ops[ch.tail[0]].out_f32); }
 };
 
 namespace {
@@ -585,6 +609,18 @@ int check_handle(y4_handle h) {
     Y4_REQUIRE(h != nullptr, Y4_EINVAL, "null handle");
     return Y4_OK;
 }
+// the preface of a setter: the events of an open timing session were laid out for the schedule it began with
+int check_settable(y4_handle h, const char* who) {
+    if (int r = check_handle(h)) return r;
+    Y4_REQUIRE(h->t_max_steps == 0, Y4_ESTATE, "%s: a timing session is open", who);
+    return Y4_OK;
+}
+// were the two handles created from the same configuration (the same plan, buffers of the same size)?
+bool same_plan(const y4_ctx* a, const y4_ctx* b) {
+    return a->ops.size() == b->ops.size() && a->chains.size() == b->chains.size() && a->resruns.size() == b->resruns.size() &&
+           a->cfg.dtype == b->cfg.dtype && a->H == b->H && a->W == b->W && a->cfg.num_classes == b->cfg.num_classes &&
+           a->cfg.max_batch == b->cfg.max_batch;
+}
 int check_ready(y4_handle h, int n) {
     if (int r = check_handle(h)) return r;
     Y4_REQUIRE(h->act && h->wts, Y4_ESTATE, "workspace not bound (call y4_bind_workspace first)");
@@ -611,11 +647,12 @@ struct Launch {
 void build_schedule(y4_handle h, int n, std::vector<Launch>& out) {
     out.clear();
     const int nops = (int)h->ops.size();
+    const Schedule& sc = h->sched;
     int first_full = 0;
-    if (h->sub_images > 0 && h->sub_last_op >= 0 && n > h->sub_images) {
-        for (int img0 = 0; img0 < n; img0 += h->sub_images)
-            for (int i = 0; i <= h->sub_last_op; ++i) out.push_back({i, img0, n - img0 < h->sub_images ? n - img0 : h->sub_images});
-        first_full = h->sub_last_op + 1;
+    if (sc.sub_images > 0 && sc.sub_last_op >= 0 && n > sc.sub_images) {
+        for (int img0 = 0; img0 < n; img0 += sc.sub_images)
+            for (int i = 0; i <= sc.sub_last_op; ++i) out.push_back({i, img0, n - img0 < sc.sub_images ? n - img0 : sc.sub_images});
+        first_full = sc.sub_last_op + 1;
     }
     for (int i = first_full; i < nops; ++i) out.push_back({i, 0, n});
 }
@@ -631,11 +668,10 @@ struct OpExec {
 OpExec resolve_op(y4_handle h, int oi, bool allow_chain) {
     const Op& op = h->ops[oi];
     if (op.kind == OP_SPP) return {EX_SPP};
-    if (op.kind == OP_STEM) return {h->fuse_stem ? EX_STEM_DOWN : EX_STEM};
-    if (h->fuse_stem && op.conv == 1) return {EX_SKIP};                   // ran inside stem_down
+    if (op.kind == OP_STEM) return {h->sched.fuse_stem ? EX_STEM_DOWN : EX_STEM};
+    if (h->sched.fuse_stem && op.conv == 1) return {EX_SKIP};                   // ran inside stem_down
     if (!allow_chain) return {EX_PLAIN};
-    bool is_head = false;
-    if (const ResRun* rr = h->res_of(oi, &is_head)) return is_head ? OpExec{EX_RESBLOCK, rr} : OpExec{EX_SKIP};
+    if (const ResRun* rr = h->res_of(oi, nullptr)) return h->heads_res(oi) ? OpExec{EX_RESBLOCK, rr} : OpExec{EX_SKIP};
     if (h->stage_active() && oi >= h->stage_first && oi <= h->stage_last) return {oi == h->stage_first ? EX_STAGE : EX_SKIP};
     const Chain* chain = nullptr;
     for (const Chain& ch : h->chains) {
@@ -733,7 +769,7 @@ int run_op(y4_handle h, int oi, const void* imgs, int n, hipStream_t s, int img0
         d.out = buf_ptr(h, op.out, i0);
         if (op.has_res) { d.res = buf_ptr(h, op.res, i0); d.res_cstride = op.res.cstride; d.res_coff = op.res.coff; }
         if (op.conv2 >= 0) { d.out2 = buf_ptr(h, op.out2, i0); d.out2_cstride = op.out2.cstride; d.out2_coff = op.out2.coff; d.split = op.split; }
-        d.tile = chain ? chain->tile : op.tile;
+        d.tile = chain ? h->sched.run[chain - h->chains.data()].tile : h->sched.tile[oi];
         d.splitk_ws = h->act + h->splitk_off; d.splitk_ws_bytes = SPLITK_WS_BYTES;
         // a float32 head (as a plain launch or as the tail of an LDS pair) also fills its cells' slots of the objectness array
         ConvObjDesc od{};
@@ -761,7 +797,7 @@ int run_op(y4_handle h, int oi, const void* imgs, int n, hipStream_t s, int img0
             const LayerW tw = layer_w(h, TL);
             ConvPairDesc pd{};
             pd.w = tw.w; pd.scale = tw.scale; pd.shift = tw.shift;
-            pd.act = TL.d.act; pd.cout = TL.d.cout; pd.out_f32 = to.out_f32 ? 1 : 0; pd.store_x = chain->store_x ? 1 : 0;
+            pd.act = TL.d.act; pd.cout = TL.d.cout; pd.out_f32 = to.out_f32 ? 1 : 0; pd.store_x = h->stores_x(*chain) ? 1 : 0;
             pd.fin = buf_ptr(h, to.out, i0); pd.fin_cstride = to.out.cstride; pd.fin_coff = to.out.coff;
             if (to.conv2 >= 0) {          // the tail is a fused CSP pair: both convs' rows, split over two views
                 pd.cout = 2 * TL.d.cout; pd.split = to.split;
@@ -786,7 +822,7 @@ int run_op(y4_handle h, int oi, const void* imgs, int n, hipStream_t s, int img0
         }
         if (ex.kind == EX_CHAIN) {
             ConvChainDesc cd{};
-            cd.store_x = chain->store_x ? 1 : 0;
+            cd.store_x = h->stores_x(*chain) ? 1 : 0;
             const Op* last = &op;
             for (int t = 0; t < 2 && chain->tail[t] >= 0; ++t) {
                 const Op& to = h->ops[chain->tail[t]];
@@ -898,6 +934,8 @@ int y4_create_hw(const y4_config* cfg, int32_t img_h, int32_t img_w, y4_handle* 
     find_chains(*c);
     find_stage(*c);
     find_resruns(*c);
+    c->sched.tile.assign(c->ops.size(), 0);
+    c->sched.run.assign(c->chains.size(), Schedule::Run{});
     layout(*c);
     *out = c;
     return Y4_OK;
@@ -944,7 +982,7 @@ int y4_model_info(y4_handle h, int64_t* flops_per_image, int32_t* num_boxes, int
 int y4_set_workspace_aliasing(y4_handle h, int on) {
     if (int r = check_handle(h)) return r;
     Y4_REQUIRE(!h->act, Y4_ESTATE, "y4_set_workspace_aliasing: the workspace is already bound (call it before y4_workspace_bytes / y4_bind_workspace)");
-    Y4_REQUIRE(!(on && h->sub_images > 0), Y4_ESTATE, "y4_set_workspace_aliasing: not together with sub-batching");
+    Y4_REQUIRE(!(on && h->sched.sub_images > 0), Y4_ESTATE, "y4_set_workspace_aliasing: not together with sub-batching");
     h->alias_bufs = on != 0;
     layout(*h);
     return Y4_OK;
@@ -1057,18 +1095,13 @@ int y4_forward_until(y4_handle h, const float* imgs, int n, int last_conv, void*
     for (int i = 0; i < (int)h->ops.size(); ++i)
         if (h->ops[i].kind != OP_SPP && (h->ops[i].conv == last_conv || h->ops[i].conv2 == last_conv)) last_op = i;
     Y4_REQUIRE(last_op >= 0, Y4_EINVAL, "y4_forward_until: no conv %d", last_conv);
-    if (h->fuse_chains)
-        for (const Chain& ch : h->chains)
-            Y4_REQUIRE(!(h->chain_active(ch) && ch.head <= last_op && (ch.tail[0] > last_op || ch.tail[1] > last_op)), Y4_EINVAL,
-                       "y4_forward_until: conv %d sits inside a fused run that continues behind it", last_conv);
-    {
-        bool is_head = false;
-        Y4_REQUIRE(!(h->res_of(last_op, &is_head) && is_head), Y4_EINVAL,
-                   "y4_forward_until: conv %d heads a residual-block kernel that continues behind it", last_conv);
-    }
+    for (const Chain& ch : h->chains)
+        Y4_REQUIRE(!(h->chain_active(ch) && ch.head <= last_op && (ch.tail[0] > last_op || ch.tail[1] > last_op)), Y4_EINVAL,
+                   "y4_forward_until: conv %d sits inside a fused run that continues behind it", last_conv);
+    Y4_REQUIRE(!h->heads_res(last_op), Y4_EINVAL, "y4_forward_until: conv %d heads a residual-block kernel that continues behind it", last_conv);
     Y4_REQUIRE(!(h->stage_active() && last_op >= h->stage_first && last_op < h->stage_last), Y4_EINVAL,
                "y4_forward_until: conv %d sits inside the stage kernel", last_conv);
-    Y4_REQUIRE(!(h->fuse_stem && last_op == 0), Y4_EINVAL, "y4_forward_until: conv 0 runs fused with conv 1");
+    Y4_REQUIRE(!(h->sched.fuse_stem && last_op == 0), Y4_EINVAL, "y4_forward_until: conv 0 runs fused with conv 1");
     h->img_u8 = false;
     std::vector<Launch> sched;
     build_schedule(h, n, sched);
@@ -1113,15 +1146,11 @@ int y4_get_conv_output(y4_handle h, int conv_idx, int n, float* out, size_t out_
     Y4_REQUIRE(!h->alias_bufs, Y4_ESTATE, "intermediate tensors are not retained with workspace aliasing on");
     for (const Op& op : h->ops) {
         if (op.kind == OP_SPP || (op.conv != conv_idx && op.conv2 != conv_idx)) continue;
-        Y4_REQUIRE(!(h->fuse_stem && conv_idx == 0), Y4_ESTATE, "conv 0 is not materialised while stem fusion is on");
-        {
-            const int oi = (int)(&op - h->ops.data());
-            Y4_REQUIRE(!(h->stage_active() && oi >= h->stage_first && oi < h->stage_last), Y4_ESTATE,
-                       "conv %d is not materialised while the stage fusion is on", conv_idx);
-            bool is_head = false;
-            Y4_REQUIRE(!(h->res_of(oi, &is_head) && is_head), Y4_ESTATE,
-                       "conv %d is not materialised while the residual-block fusion is on", conv_idx);
-        }
+        Y4_REQUIRE(!(h->sched.fuse_stem && conv_idx == 0), Y4_ESTATE, "conv 0 is not materialised while stem fusion is on");
+        const int oi = (int)(&op - h->ops.data());
+        Y4_REQUIRE(!(h->stage_active() && oi >= h->stage_first && oi < h->stage_last), Y4_ESTATE,
+                   "conv %d is not materialised while the stage fusion is on", conv_idx);
+        Y4_REQUIRE(!h->heads_res(oi), Y4_ESTATE, "conv %d is not materialised while the residual-block fusion is on", conv_idx);
         const View& v = op.conv == conv_idx ? op.out : op.out2;
         const int64_t px = (int64_t)n * v.h * v.w;   // for an upsampling conv: the upsampled tensor
         Y4_REQUIRE((int64_t)out_floats >= px * v.c, Y4_EINVAL, "output buffer too small: %zu < %lld", out_floats,
@@ -1234,14 +1263,10 @@ int y4_set_retain_head_inputs(y4_handle h, int on) {
         for (const Chain& ch : h->chains)
             for (int i = 0; i < 3; ++i)
                 if (const Op* b = block_op(h, i))
-                    Y4_REQUIRE(h->ops[ch.head].out.buf != b->in.buf || ch.store_x, Y4_ESTATE,
+                    Y4_REQUIRE(h->ops[ch.head].out.buf != b->in.buf || h->stores_x(ch), Y4_ESTATE,
                                "y4_set_retain_head_inputs: a fused run keeps the input of conv %d on chip", h->layers[b->conv].d.idx);
     h->retain_head_in = on != 0;                                         // (every non-zero value but 2 is level 1, as before level 2 existed)
-    h->retain_block_in = on == 2;
-    // an LDS pair whose tail is a head conv keeps the head's input in LDS: with retention it is stored as well
-    for (Chain& ch : h->chains)
-        if (ch.lds_pair && h->ops[ch.tail[0]].out_f32)
-            ch.store_x = h->retain_head_in || read_outside(*h, h->ops[ch.head].out.buf, ch.tail[0], ch.tail[0]);
+    h->retain_block_in = on == 2;                                        // (y4_ctx::stores_x: the LDS pairs in front of the heads follow)
     layout(*h);
     return Y4_OK;
 }
@@ -1518,9 +1543,8 @@ static int autotune_impl(y4_handle h, y4_handle h2, int n, int reps, hipStream_t
     if (h2)
         if (int r = check_ready(h2, n)) return r;
     Y4_REQUIRE(reps >= 1 && reps <= 100, Y4_EINVAL, "y4_autotune: reps %d", reps);
-    Y4_REQUIRE(!h2 || (h2 != h && h2->ops.size() == h->ops.size() && h2->chains.size() == h->chains.size() &&
-                       h2->cfg.dtype == h->cfg.dtype && h2->H == h->H && h2->W == h->W && s2 != s),
-               Y4_EINVAL, "y4_autotune_pair: the second handle must be a sibling of the first (same plan) on another stream");
+    Y4_REQUIRE(!h2 || (h2 != h && same_plan(h, h2) && s2 != s), Y4_EINVAL,
+               "y4_autotune_pair: the second handle must be a sibling of the first (same plan) on another stream");
     hipEvent_t e0, e1, e2;
     Y4_CHECK_HIP(hipEventCreate(&e0));
     Y4_CHECK_HIP(hipEventCreate(&e1));
@@ -1605,29 +1629,27 @@ static int autotune_impl(y4_handle h, y4_handle h2, int n, int reps, hipStream_t
         return Y4_OK;
     };
     // every choice is made on both handles: the sibling ends up with the same schedule
-    auto on_both = [&](const auto& set) {
-        for (y4_handle x : {h, h2})
-            if (x) set(x);
+    auto choose = [&](const auto& write) {
+        write(h->sched);
+        if (h2) write(h2->sched);
     };
-    auto set_tile = [&](int oi, int tile) { on_both([&](y4_handle x) { x->ops[oi].tile = tile; }); };
-    auto set_chain = [&](int ci, int tile, bool on) { on_both([&](y4_handle x) { x->chains[ci].tile = tile; x->chains[ci].enabled = on; }); };
-    auto set_stage = [&](bool on) { on_both([&](y4_handle x) { x->stage_enabled = on; }); };
-    auto set_res = [&](int grp, bool on) { on_both([&](y4_handle x) { x->res_enabled[grp] = on; }); };
-    auto images_of = [&](int oi) { return (h->sub_images > 0 && oi <= h->sub_last_op && n > h->sub_images) ? h->sub_images : n; };
-    set_stage(false);                  // passes 1 and 2 tune the stage's convs as separate kernels; pass 3 decides
-    set_res(0, false); set_res(1, false);               // likewise the residual-block kernels: pass 4
+    auto force_chain = [&](int ci) { h->force_chain = ci; if (h2) h2->force_chain = ci; };
+    const Schedule& sc = h->sched;
+    auto images_of = [&](int oi) { return (sc.sub_images > 0 && oi <= sc.sub_last_op && n > sc.sub_images) ? sc.sub_images : n; };
+    // passes 1 and 2 tune the stage's convs as separate kernels, pass 3 decides; likewise the residual-block kernels: pass 4
+    choose([](Schedule& x) { x.stage_enabled = x.res_enabled[0] = x.res_enabled[1] = false; });
     // pass 1: every conv as its own kernel
     two = h2 && (pair_passes & 1);
     for (int oi = 0; oi < (int)h->ops.size() && rc == Y4_OK; ++oi) {
-        Op& op = h->ops[oi];
-        if (op.kind != OP_CONV || (h->fuse_stem && op.conv == 1)) continue;
+        const Op& op = h->ops[oi];
+        if (op.kind != OP_CONV || (sc.fuse_stem && op.conv == 1)) continue;
         float best = 1e30f;
         int best_tile = 0;
         for (int tile = 1; tile <= ntiles; ++tile) {
             // the 32x32x16-MFMA tiles sum in another order than all the others: offering them here would make the outputs
             // depend on the tuner's choice.  They are measured slower anyway (LABNOTES.md section 4.1) and stay explicit-only.
-            if (tuner_skips_tile(tile) && !(h->allow_halo2 && halo2_tile(tile))) continue;
-            set_tile(oi, tile);
+            if (tuner_skips_tile(tile) && !(sc.allow_halo2 && halo2_tile(tile))) continue;
+            choose([&](Schedule& x) { x.tile[oi] = tile; });
             const float ms = time_op(oi, images_of(oi), false);
             if (ms == -2.f) { rc = Y4_EHIP; break; }
             if (ms >= 0.f && ms < best) { best = ms; best_tile = tile; }
@@ -1638,31 +1660,31 @@ static int autotune_impl(y4_handle h, y4_handle h2, int n, int reps, hipStream_t
             for (int tile = 1; tile <= ntiles && rc == Y4_OK; ++tile) {
                 if (tuner_skips_tile(tile) || !splitk_tile(tile)) continue;
                 for (int e = 1; e <= SPLITK_MAX_E; ++e) {
-                    set_tile(oi, tile + 100 * e);
+                    choose([&](Schedule& x) { x.tile[oi] = tile + 100 * e; });
                     const float ms = time_op(oi, images_of(oi), false);
                     if (ms == -2.f) { rc = Y4_EHIP; break; }
                     if (ms < 0.f) break;                       // a wider split of this tile will not fit either
                     if (ms < best) { best = ms; best_tile = tile + 100 * e; }
                 }
             }
-        set_tile(oi, best_tile);
+        choose([&](Schedule& x) { x.tile[oi] = best_tile; });
     }
     // pass 2: each chain as one kernel against its separate kernels
     two = h2 && (pair_passes & 2);
-    for (int ci = 0; h->fuse_chains && ci < (int)h->chains.size() && rc == Y4_OK; ++ci) {
+    for (int ci = 0; sc.fuse_chains && ci < (int)h->chains.size() && rc == Y4_OK; ++ci) {
         const Chain& ch = h->chains[ci];
         // an alternative run is timed as if its parent's head sat in a residual-block kernel (those are off until pass 4)
-        on_both([&](y4_handle x) { x->force_chain = ch.alt_of >= 0 ? ci : -1; });
+        force_chain(ch.alt_of >= 0 ? ci : -1);
         float best = 1e30f;
         int best_tile = 0;
         for (int tile = 1; tile <= ntiles; ++tile) {
-            set_chain(ci, tile, true);
+            choose([&](Schedule& x) { x.run[ci] = {true, tile}; });
             const float ms = time_op(ch.head, images_of(ch.head), true);
             if (ms == -2.f) { rc = Y4_EHIP; break; }
             if (ms >= 0.f && ms < best) { best = ms; best_tile = tile; }
         }
-        set_chain(ci, best_tile, best_tile > 0);
-        if (!ch.enabled || rc != Y4_OK) continue;
+        choose([&](Schedule& x) { x.run[ci] = {best_tile > 0, best_tile}; });
+        if (!sc.run[ci].enabled || rc != Y4_OK) continue;
         bool wins = false;
         rc = head_to_head([&](bool fused) -> int {
             if (fused) return run_both(ch.head, images_of(ch.head), true);
@@ -1671,25 +1693,25 @@ static int autotune_impl(y4_handle h, y4_handle h2, int n, int reps, hipStream_t
                     if (int r = run_both(oi, images_of(oi), false)) return r;
             return Y4_OK;
         }, &wins);
-        if (rc == Y4_OK) set_chain(ci, ch.tile, wins);     // (on a failure the run stays as its tile probe left it)
+        if (rc == Y4_OK) choose([&](Schedule& x) { x.run[ci].enabled = wins; });     // (on a failure the run stays as its tile probe left it)
     }
-    on_both([](y4_handle x) { x->force_chain = -1; });
+    force_chain(-1);
     // pass 3: the stage kernel (convs 2..7 in one launch) head to head against the same ops as tuned above
     two = h2 && (pair_passes & 4);
-    if (rc == Y4_OK && h->stage_first >= 0 && h->stage_on) {
+    if (rc == Y4_OK && h->stage_first >= 0 && sc.stage_on) {
         const int ne = images_of(h->stage_first);
         bool wins = false;
         rc = head_to_head([&](bool fused) -> int {
-            set_stage(fused);
+            choose([&](Schedule& x) { x.stage_enabled = fused; });
             for (int oi = h->stage_first; oi <= h->stage_last; ++oi)
                 if (int r = run_both(oi, ne, true)) return r;
             return Y4_OK;
         }, &wins);
-        set_stage(rc == Y4_OK && wins);
+        choose([&](Schedule& x) { x.stage_enabled = rc == Y4_OK && wins; });
     }
     // pass 4: per channel group, the residual blocks as one kernel each against the same op range as tuned above
     two = h2 && (pair_passes & 8);
-    for (int grp = 0; grp < 2 && rc == Y4_OK && h->res_on; ++grp) {
+    for (int grp = 0; grp < 2 && rc == Y4_OK && sc.res_on; ++grp) {
         int lo = -1, hi = -1;
         for (const ResRun& r : h->resruns)
             if ((r.c == 128 ? 0 : 1) == grp) { if (lo < 0) lo = r.head; hi = r.tail; }
@@ -1700,12 +1722,12 @@ static int autotune_impl(y4_handle h, y4_handle h2, int n, int reps, hipStream_t
         const int ne = images_of(lo);
         bool wins = false;
         rc = head_to_head([&](bool fused) -> int {
-            set_res(grp, fused);
+            choose([&](Schedule& x) { x.res_enabled[grp] = fused; });
             for (int oi = lo; oi <= hi; ++oi)
                 if (int r = run_both(oi, ne, true)) return r;
             return Y4_OK;
         }, &wins);
-        set_res(grp, rc == Y4_OK && wins);
+        choose([&](Schedule& x) { x.res_enabled[grp] = rc == Y4_OK && wins; });
     }
     (void)hipEventDestroy(e0);
     (void)hipEventDestroy(e1);
@@ -1720,10 +1742,7 @@ int y4_autotune_pair(y4_handle h, y4_handle h2, int n, int reps, void* stream, v
     if (int r = check_handle(h2)) return r;
     Y4_REQUIRE(pair_passes >= 0 && pair_passes <= 15, Y4_EINVAL, "y4_autotune_pair: pair_passes %d (bits 0..3)", pair_passes);
     if (int r = check_handle(h)) return r;
-    // the sibling is tuned with the primary's choices: they only apply to it if it runs the same kernels
-    Y4_REQUIRE(h2->fuse_stem == h->fuse_stem && h2->fuse_chains == h->fuse_chains && h2->stage_on == h->stage_on &&
-               h2->res_on == h->res_on && h2->sub_images == h->sub_images && h2->sub_last_op == h->sub_last_op &&
-               h2->alias_bufs == h->alias_bufs, Y4_ESTATE,
+    Y4_REQUIRE(same_switches(h->sched, h2->sched) && h2->alias_bufs == h->alias_bufs, Y4_ESTATE,
                "y4_autotune_pair: the two handles differ in their fusion switches, sub-batching or workspace aliasing "
                "(y4_copy_schedule(h, h2) makes them equal)");
     return autotune_impl(h, h2, n, reps, (hipStream_t)stream, (hipStream_t)stream2, pair_passes);
@@ -1732,46 +1751,39 @@ int y4_autotune_pair(y4_handle h, y4_handle h2, int n, int reps, void* stream, v
 int y4_set_tiles(y4_handle h, const int32_t* tiles, int count) {
     if (int r = check_handle(h)) return r;
     Y4_REQUIRE(tiles && count == (int)h->layers.size(), Y4_EINVAL, "y4_set_tiles: expected %d entries", (int)h->layers.size());
+    Schedule& sc = h->sched;
     for (int oi = 0; oi < (int)h->ops.size(); ++oi) {
-        Op& op = h->ops[oi];
+        const Op& op = h->ops[oi];
         if (op.kind != OP_CONV) continue;
         const int v = tiles[op.conv];
-        Chain* head_of = nullptr;
-        for (Chain& ch : h->chains)
-            if (ch.head == oi) head_of = &ch;
-        // a run's head carries two choices in one entry: -(run tile + 1000 * stand-alone tile); plain -t leaves the stand-alone one
-        const int run_tile = v < 0 ? (-v) % 1000 : 0, own_tile = v < 0 ? (-v) / 1000 : v;
-        Y4_REQUIRE(tile_id_ok(own_tile) && run_tile <= conv_tile_count() && (v >= 0 || (head_of && h->fuse_chains)), Y4_EINVAL,
+        int head_of = -1;
+        for (int ci = 0; ci < (int)h->chains.size(); ++ci)
+            if (h->chains[ci].head == oi) head_of = ci;
+        const bool is_head = head_of >= 0 && sc.fuse_chains;
+        const TileEntry e = decode_entry(v);
+        Y4_REQUIRE(tile_id_ok(e.own) && e.run <= conv_tile_count() && (v >= 0 || is_head), Y4_EINVAL,
                    "y4_set_tiles: tile id %d for conv %d", v, op.conv);
-        if (head_of && h->fuse_chains) {      // < 0: chained with tile run_tile; > 0: separate kernels; 0: chained, heuristic tile
-            head_of->enabled = v <= 0;
-            head_of->tile = run_tile;
-            if (v > 0 || own_tile > 0) op.tile = own_tile;
-        } else {
-            op.tile = v;
-        }
+        if (is_head) sc.run[head_of] = {e.chained, e.run};       // (a plain -t leaves the stand-alone tile below as it is)
+        if (!is_head || v > 0 || e.own > 0) sc.tile[oi] = e.own;
     }
     return Y4_OK;
 }
 
 int y4_set_subbatch(y4_handle h, int images, int last_conv) {
-    if (int r = check_handle(h)) return r;
-    Y4_REQUIRE(h->t_max_steps == 0, Y4_ESTATE, "y4_set_subbatch: a timing session is open");
+    if (int r = check_settable(h, "y4_set_subbatch")) return r;
     Y4_REQUIRE(images <= 0 || !h->alias_bufs, Y4_ESTATE, "y4_set_subbatch: not together with workspace aliasing (a sub-batch's "
                "early tensors would share memory with another sub-batch's later ones)");
-    if (images <= 0) { h->sub_images = 0; h->sub_last_op = -1; return Y4_OK; }
+    if (images <= 0) { h->sched.sub_images = 0; h->sched.sub_last_op = -1; return Y4_OK; }
     int last_op = -1;
     for (int i = 0; i < (int)h->ops.size(); ++i)
         if (h->ops[i].kind != OP_SPP && (h->ops[i].conv == last_conv || h->ops[i].conv2 == last_conv)) last_op = i;
     Y4_REQUIRE(last_op >= 0, Y4_EINVAL, "y4_set_subbatch: no conv %d", last_conv);
-    h->sub_images = images;
-    h->sub_last_op = last_op;
+    h->sched.sub_images = images; h->sched.sub_last_op = last_op;
     return Y4_OK;
 }
 
 int y4_set_stem_fusion(y4_handle h, int on) {
-    if (int r = check_handle(h)) return r;
-    Y4_REQUIRE(h->t_max_steps == 0, Y4_ESTATE, "y4_set_stem_fusion: a timing session is open");
+    if (int r = check_settable(h, "y4_set_stem_fusion")) return r;
     if (on) {
         const bool shape_ok = h->ops.size() > 1 && h->ops[0].kind == OP_STEM && h->ops[1].kind == OP_CONV &&
                               h->ops[1].conv == 1 && h->ops[1].conv2 < 0 && !h->ops[1].has_res &&
@@ -1783,42 +1795,39 @@ int y4_set_stem_fusion(y4_handle h, int on) {
         Y4_REQUIRE(shape_ok && stem_down_supported(h->cfg.dtype, h->H), Y4_EINVAL,
                    "y4_set_stem_fusion: needs a 16-bit dtype and img_size <= 640 (dtype %d, img_size %d)", h->cfg.dtype, h->H);
     }
-    h->fuse_stem = on != 0;
+    h->sched.fuse_stem = on != 0;
     return Y4_OK;
 }
 
 int y4_set_chain_fusion(y4_handle h, int on) {
-    if (int r = check_handle(h)) return r;
-    Y4_REQUIRE(h->t_max_steps == 0, Y4_ESTATE, "y4_set_chain_fusion: a timing session is open");
+    if (int r = check_settable(h, "y4_set_chain_fusion")) return r;
     Y4_REQUIRE(!on || h->cfg.dtype != Y4_F32, Y4_EINVAL, "y4_set_chain_fusion: 16-bit dtypes only");
-    h->fuse_chains = on != 0;
-    for (Chain& ch : h->chains) { ch.enabled = true; ch.tile = 0; }
+    h->sched.fuse_chains = on != 0;
+    h->sched.run.assign(h->chains.size(), Schedule::Run{});
     return on ? (int)h->chains.size() : Y4_OK;
 }
 
 int y4_set_stage_fusion(y4_handle h, int on) {
-    if (int r = check_handle(h)) return r;
-    Y4_REQUIRE(h->t_max_steps == 0, Y4_ESTATE, "y4_set_stage_fusion: a timing session is open");
+    if (int r = check_settable(h, "y4_set_stage_fusion")) return r;
     Y4_REQUIRE(!on || h->stage_first >= 0, Y4_EINVAL, "y4_set_stage_fusion: needs a 16-bit dtype (dtype %d)", h->cfg.dtype);
-    h->stage_on = on != 0;
-    h->stage_enabled = true;
+    h->sched.stage_on = on != 0;
+    h->sched.stage_enabled = true;
     return h->stage_active() ? 1 : 0;
 }
 
 int y4_set_res_fusion(y4_handle h, int on) {
-    if (int r = check_handle(h)) return r;
-    Y4_REQUIRE(h->t_max_steps == 0, Y4_ESTATE, "y4_set_res_fusion: a timing session is open");
+    if (int r = check_settable(h, "y4_set_res_fusion")) return r;
     Y4_REQUIRE(!on || h->cfg.dtype != Y4_F32, Y4_EINVAL, "y4_set_res_fusion: 16-bit dtypes only");
-    h->res_on = on != 0;
-    h->res_enabled[0] = h->res_enabled[1] = true;
+    h->sched.res_on = on != 0;
+    h->sched.res_enabled[0] = h->sched.res_enabled[1] = true;
     return on ? (int)h->resruns.size() : Y4_OK;
 }
 
 int y4_get_res_fusion(y4_handle h) {
     if (int r = check_handle(h)) return r;
-    if (!h->res_on) return 0;
+    if (!h->sched.res_on) return 0;
     int mask = 0;
-    for (const ResRun& r : h->resruns) mask |= h->res_enabled[r.c == 128 ? 0 : 1] ? (r.c == 128 ? 1 : 2) : 0;
+    for (const ResRun& r : h->resruns) mask |= h->sched.res_enabled[r.c == 128 ? 0 : 1] ? (r.c == 128 ? 1 : 2) : 0;
     return mask;
 }
 
@@ -1826,10 +1835,10 @@ int y4_set_res_fusion_mask(y4_handle h, int mask) {
     if (int r = check_handle(h)) return r;
     Y4_REQUIRE(h->cfg.dtype != Y4_F32 || mask == 0, Y4_EINVAL, "y4_set_res_fusion_mask: 16-bit dtypes only");
     Y4_REQUIRE(mask >= 0 && mask <= 3, Y4_EINVAL, "y4_set_res_fusion_mask: mask %d (bit 0: 128-channel blocks, bit 1: 64-channel blocks)", mask);
-    Y4_REQUIRE(h->t_max_steps == 0, Y4_ESTATE, "y4_set_res_fusion_mask: a timing session is open");
-    h->res_on = mask != 0;
-    h->res_enabled[0] = (mask & 1) != 0;
-    h->res_enabled[1] = (mask & 2) != 0;
+    if (int r = check_settable(h, "y4_set_res_fusion_mask")) return r;
+    h->sched.res_on = mask != 0;
+    h->sched.res_enabled[0] = (mask & 1) != 0;
+    h->sched.res_enabled[1] = (mask & 2) != 0;
     return Y4_OK;
 }
 
@@ -1842,7 +1851,7 @@ int y4_set_splitk(y4_handle h, int on) {
 int y4_set_halo2(y4_handle h, int on) {
     if (int r = check_handle(h)) return r;
     Y4_REQUIRE(!on || h->cfg.dtype != Y4_F32, Y4_EINVAL, "y4_set_halo2: 16-bit dtypes only");
-    h->allow_halo2 = on != 0;
+    h->sched.allow_halo2 = on != 0;
     return Y4_OK;
 }
 
@@ -1855,41 +1864,30 @@ int y4_get_tiles(y4_handle h, int32_t* tiles, int cap) {
     if (int r = check_handle(h)) return r;
     Y4_REQUIRE(tiles && cap >= (int)h->layers.size(), Y4_EINVAL, "y4_get_tiles: need room for %d layers", (int)h->layers.size());
     for (int i = 0; i < (int)h->layers.size(); ++i) tiles[i] = 0;
-    for (const Op& op : h->ops)
-        if (op.kind == OP_CONV) {
-            tiles[op.conv] = op.tile;
-            if (op.conv2 >= 0) tiles[op.conv2] = op.tile;
-        }
-    if (h->fuse_chains)                       // a chained run reports its head as -(run tile + 1000 * the conv's stand-alone tile), so
-        for (const Chain& ch : h->chains)     // that a get -> set round trip loses neither (see y4_set_tiles)
-            if (ch.enabled) tiles[h->ops[ch.head].conv] = -(ch.tile + 1000 * h->ops[ch.head].tile);
+    const Schedule& sc = h->sched;
+    for (int oi = 0; oi < (int)h->ops.size(); ++oi) {
+        const Op& op = h->ops[oi];
+        if (op.kind != OP_CONV) continue;
+        tiles[op.conv] = sc.tile[oi];
+        if (op.conv2 >= 0) tiles[op.conv2] = sc.tile[oi];
+    }
+    for (int ci = 0; sc.fuse_chains && ci < (int)h->chains.size(); ++ci) {      // a chained run's head: both tiles (TileEntry)
+        const int head = h->chains[ci].head;
+        if (sc.run[ci].enabled) tiles[h->ops[head].conv] = encode_entry(sc.run[ci].tile, sc.tile[head]);
+    }
     return Y4_OK;
 }
 
-// Every scheduling choice of `src` -> `dst` (a sibling built from the same configuration): the per-op tiles, every run's
-// enabled / tile state INCLUDING the stand-alone tile of a conv that currently heads a run (y4_get_tiles reports such a conv as
-// -run_tile and cannot carry both), the stage-kernel and residual-block verdicts, the fusion switches and sub-batching.
+// Every scheduling choice of `src` -> `dst` (a sibling built from the same configuration): the whole Schedule.
 int y4_copy_schedule(y4_handle src, y4_handle dst) {
     if (int r = check_handle(src)) return r;
     if (int r = check_handle(dst)) return r;
     Y4_REQUIRE(src != dst, Y4_EINVAL, "y4_copy_schedule: source and destination are the same handle");
     Y4_REQUIRE(dst->t_max_steps == 0, Y4_ESTATE, "y4_copy_schedule: a timing session is open on the destination");
-    Y4_REQUIRE(src->ops.size() == dst->ops.size() && src->chains.size() == dst->chains.size() &&
-               src->resruns.size() == dst->resruns.size() && src->cfg.dtype == dst->cfg.dtype && src->H == dst->H && src->W == dst->W &&
-               src->cfg.num_classes == dst->cfg.num_classes && src->cfg.max_batch == dst->cfg.max_batch, Y4_EINVAL,
-               "y4_copy_schedule: the handles were not created from the same configuration");
-    Y4_REQUIRE(src->sub_images <= 0 || !dst->alias_bufs, Y4_ESTATE,
+    Y4_REQUIRE(same_plan(src, dst), Y4_EINVAL, "y4_copy_schedule: the handles were not created from the same configuration");
+    Y4_REQUIRE(src->sched.sub_images <= 0 || !dst->alias_bufs, Y4_ESTATE,
                "y4_copy_schedule: the source runs sub-batches, the destination's workspace is aliased");
-    for (size_t i = 0; i < src->ops.size(); ++i) dst->ops[i].tile = src->ops[i].tile;
-    for (size_t i = 0; i < src->chains.size(); ++i) {
-        dst->chains[i].enabled = src->chains[i].enabled;
-        dst->chains[i].tile = src->chains[i].tile;
-    }
-    dst->fuse_stem = src->fuse_stem; dst->fuse_chains = src->fuse_chains;
-    dst->stage_on = src->stage_on; dst->stage_enabled = src->stage_enabled;
-    dst->res_on = src->res_on; dst->res_enabled[0] = src->res_enabled[0]; dst->res_enabled[1] = src->res_enabled[1];
-    dst->sub_images = src->sub_images; dst->sub_last_op = src->sub_last_op;
-    dst->allow_halo2 = src->allow_halo2;
+    dst->sched = src->sched;
     return Y4_OK;
 }
 

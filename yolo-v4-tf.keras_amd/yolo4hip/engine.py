@@ -9,7 +9,7 @@ import os
 
 import numpy as np
 
-from . import ext
+from . import ext, schedule
 from .config import yolo_config
 
 
@@ -44,6 +44,11 @@ def _cfg_struct(config, num_classes, max_batch, dtype):
 class Engine:
     def __init__(self, num_classes, config=None, max_batch=32, dtype="f32", device=None, alias_workspace=False,
                  retain_head_inputs=False):
+        self._build(num_classes, config, max_batch, dtype, device, alias_workspace, retain_head_inputs, None)
+
+    def _build(self, num_classes, config, max_batch, dtype, device, alias_workspace, retain_head_inputs, parent):
+        """What `__init__` and `sibling` share: the handle, its workspaces and every attribute.  `parent` is None for an engine
+        with weights of its own, or the engine whose packed weights and schedule this one takes over."""
         import torch
         self.torch = torch
         self.lib = ext.load()
@@ -71,28 +76,35 @@ class Engine:
         if self.alias_workspace:
             ext.check(self.lib.y4_set_workspace_aliasing(self.handle, 1))
         # retain_head_inputs: the head convs' inputs stay in the workspace after a forward (y4_set_retain_head_inputs), which
-        # `head_grad_device` needs; level 2 also keeps the inputs of convs 92 / 100 / 108, which `block_grad_device` needs
+        # `head_grad_device` needs; level 2 also keeps the inputs of convs 92 / 100 / 108, which `block_grad_device` needs.
+        # A sibling computes batches for inference: it records its parent's level, its own handle retains nothing.
         self.retain_level = int(retain_head_inputs)
         if self.retain_level not in (0, 1, 2):
             raise ValueError(f"retain_head_inputs must be False / True (0 / 1) or 2, got {retain_head_inputs!r}")
         self.retain_head_inputs = self.retain_level > 0
-        if self.retain_head_inputs:
+        if self.retain_head_inputs and parent is None:
             ext.check(self.lib.y4_set_retain_head_inputs(self.handle, self.retain_level))
-        a, w = C.c_size_t(), C.c_size_t()
-        ext.check(self.lib.y4_workspace_bytes(self.handle, C.byref(a), C.byref(w)))
-        self.act_bytes, self.wts_bytes = a.value, w.value
+        if parent is None:
+            a, w = C.c_size_t(), C.c_size_t()
+            ext.check(self.lib.y4_workspace_bytes(self.handle, C.byref(a), C.byref(w)))
+            self.act_bytes, self.wts_bytes = a.value, w.value
+        else:
+            self.act_bytes, self.wts_bytes = parent.act_bytes, parent.wts_bytes
         with torch.cuda.device(self.device):
             self.act = torch.empty(self.act_bytes, dtype=torch.uint8, device=self.device)
-            self.wts = torch.zeros(self.wts_bytes, dtype=torch.uint8, device=self.device)
+            # a sibling's is the SAME tensor: packed weights are never written after packing
+            self.wts = torch.zeros(self.wts_bytes, dtype=torch.uint8, device=self.device) if parent is None else parent.wts
             ext.check(self.lib.y4_bind_workspace(self.handle, ext.ptr(self.act), self.act_bytes, ext.ptr(self.wts),
                                                  self.wts_bytes))
         self.grids_hw = [(self.img_hw[0] // s, self.img_hw[1] // s) for s in self.config["strides"]]
         self.grids = [g[0] for g in self.grids_hw] if self.img_hw[0] == self.img_hw[1] else list(self.grids_hw)
         self.nout = 3 * (self.num_classes + 5)
         self.T = self.cfg.max_total
-        self.halo2 = False
-        import os
-        if self.dtype != "f32" and os.environ.get("YOLO4HIP_HALO2", "0") == "1":
+        self.stem_fusion = self.halo2 = False
+        if parent is not None:
+            self.adopt_packed()
+            parent.copy_schedule_to(self)
+        elif self.dtype != "f32" and os.environ.get("YOLO4HIP_HALO2", "0") == "1":
             self.set_halo2(True)          # (experiments: `autotune` may pick the halo2 tiles; shipped schedules that hold them need no switch)
 
     def sibling(self):
@@ -100,35 +112,19 @@ class Engine:
         workspace, with the same scheduling choices (fusions, tuned tiles).  Two independent batches can then be in flight
         on two HIP streams (`InFlight`): one batch's partial last rounds, its 32-workgroup NMS and its small 19^2 layers
         overlap the other batch's kernels.  Results are those of this engine, bit for bit."""
-        torch = self.torch
         e = Engine.__new__(Engine)
-        e.torch, e.lib, e.config, e.device = torch, self.lib, dict(self.config), self.device
-        e.num_classes, e.max_batch, e.cfg, e.dtype, e.img_size = self.num_classes, self.max_batch, self.cfg, self.dtype, self.img_size
-        e.img_hw = self.img_hw
-        e.handle = C.c_void_p()
-        ext.check(self.lib.y4_create_hw(C.byref(e.cfg), e.img_hw[0], e.img_hw[1], C.byref(e.handle)))
-        e.alias_workspace = getattr(self, "alias_workspace", False)
-        if e.alias_workspace:
-            ext.check(self.lib.y4_set_workspace_aliasing(e.handle, 1))
-        e.flops_per_image, e.num_boxes = self.flops_per_image, self.num_boxes
-        e.head_cstride, e.weight_floats = self.head_cstride, self.weight_floats
-        e.act_bytes, e.wts_bytes = self.act_bytes, self.wts_bytes
-        with torch.cuda.device(self.device):
-            e.act = torch.empty(e.act_bytes, dtype=torch.uint8, device=self.device)
-            e.wts = self.wts                                   # the SAME tensor: packed weights are never written after packing
-            ext.check(self.lib.y4_bind_workspace(e.handle, ext.ptr(e.act), e.act_bytes, ext.ptr(e.wts), e.wts_bytes))
-        e.grids, e.grids_hw, e.nout, e.T = list(self.grids), list(self.grids_hw), self.nout, self.T
-        e.adopt_packed()
-        self.copy_schedule_to(e)
+        e._build(self.num_classes, self.config, self.max_batch, self.dtype, self.device, self.alias_workspace, self.retain_level, self)
         return e
+
+    # what the Python side remembers of the handle's schedule (`stem_fusion`: tests/test_gpu_api.py; `halo2`: the YOLO4HIP_HALO2 switch)
+    _SCHEDULE_SHADOWS = ("stem_fusion", "halo2")
 
     def copy_schedule_to(self, e):
         """Give engine `e` (a sibling) this engine's scheduling choices: sub-batching, fusions, every run's state, tuned tiles
-        (y4_copy_schedule mirrors the handle itself; a get_tiles -> set_tiles hop could not carry a run head's two tiles)."""
+        (y4_copy_schedule copies the handle's Schedule; a get_tiles -> set_tiles hop would not carry the switches)."""
         ext.check(self.lib.y4_copy_schedule(self.handle, e.handle))
-        e._subbatch = getattr(self, "_subbatch", None)
-        e.stem_fusion = bool(getattr(self, "stem_fusion", False))
-        e.chain_fusion = bool(getattr(self, "chain_fusion", False))
+        for name in self._SCHEDULE_SHADOWS:
+            setattr(e, name, getattr(self, name))
 
     def close(self):
         for e in getattr(self, "_stream_siblings", []):
@@ -991,11 +987,10 @@ class Engine:
         (`yolo4hip/schedules/<side>_<classes>_<batch>_<dtype>.json`; the headline shape's file IS `profiles/r03/tiles.json`,
         the set the committed PMC passes profiled).  A schedule WITHOUT split-K or halo2 ids (`"splitk": false`, `"halo2": false`) is a
         pure scheduling choice: every such choice gives the same bits.  The batch-1 files carry split-K ids (`"splitk": true`), the
-        batch-32 / 64 16-bit files since round 6 halo2 ids (`"halo2": true`: tile ids 55-62, conv_halo2_kernel.h, v_mfma_32x32x16):
+        batch-32 / 64 16-bit files since round 6 halo2 ids (`"halo2": true`: family 21, `schedule.uses_halo2`; conv_halo2_kernel.h, v_mfma_32x32x16):
         those sum the K loop in another, fixed fp32 order -- the same on every machine because the file is the same -- and are held
         to the oracle instead (tests/test_gpu_forward.py::test_splitk_latency_schedule_vs_oracle, tests/test_gpu_parity_full.py)."""
         import json
-        import os
         path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "schedules",
                             f"{self.shape_key}_{self.num_classes}_{self.max_batch}_{self.dtype}.json")
         try:
@@ -1011,7 +1006,6 @@ class Engine:
     def schedule_cache_path(self):
         """Where a schedule tuned on first use is kept: $YOLO4HIP_CACHE (default ~/.cache/yolo4hip) / schedules /
         <side>_<classes>_<batch>_<dtype>_<gfx arch>_<library version>.json (<H>x<W>_... for a rectangular engine)."""
-        import os
         root = os.environ.get("YOLO4HIP_CACHE") or os.path.join(os.path.expanduser("~"), ".cache", "yolo4hip")
         arch = self.torch.cuda.get_device_properties(self.device).gcnArchName.split(":")[0]
         ver = self.lib.y4_version().decode().replace(" ", "_").replace("/", "_")
@@ -1062,7 +1056,6 @@ class Engine:
         return src, path
 
     def say_schedule(self):
-        import os
         src, path = self.schedule_source
         what = {"shipped": "shipped with the package", "cached": "tuned earlier on this machine", "tuned": "tuned now (first use of this shape)",
                 "shared": "rank 0's, received by broadcast", "heuristic": "NONE: built-in tile heuristic, fusion kernels off"}[src]
@@ -1083,7 +1076,6 @@ class Engine:
     def _resolve_schedule(self, tune):
         """(source, path, schedule dict or None) of `ensure_schedule`'s steps (1)-(3) on THIS rank; the schedule is applied."""
         import json
-        import os
         saved = self.shipped_schedule()
         if saved is not None and len(saved.get("tiles", [])) == 110:
             self._use_schedule(saved)
@@ -1109,14 +1101,9 @@ class Engine:
         from . import weights as W
         imgs = torch.from_numpy(W.synth_images(self.max_batch, self.img_hw, seed=0)).to(self.device)
         self.predict_device(imgs)                      # real activations in the workspace
-        tiles = self.autotune(self.max_batch, reps=3)
+        self.autotune(self.max_batch, reps=3)
         self.set_splitk(False)
-        saved = {"size": self.img_size if isinstance(self.img_size, int) else list(self.img_size), "classes": self.num_classes, "batch": self.max_batch, "dtype": self.dtype,
-                 "tiles": tiles, "stage_fusion": bool(self.stage_fusion_active()) if self.dtype != "f32" else False,
-                 "res_fusion_mask": int(self.res_fusion_mask()) if self.dtype != "f32" else 0, "in_flight": 1,
-                 "splitk": any(abs(t) % 1000 >= 100 or abs(t) // 1000 >= 100 for t in tiles),
-                 "halo2": bool(getattr(self, "halo2", False)) and any(55 <= abs(t) % 100 <= 62 for t in tiles),
-                 "tuned_on": torch.cuda.get_device_properties(self.device).gcnArchName}
+        saved = dict(schedule.describe(self), tuned_on=torch.cuda.get_device_properties(self.device).gcnArchName)
         try:
             os.makedirs(os.path.dirname(path), exist_ok=True)
             tmp = path + f".{os.getpid()}.tmp"
@@ -1145,7 +1132,6 @@ class Engine:
         sums in another fp32 order than the unsplit loop, so the tuned schedule then is part of the numerical result; off by
         default, and the schedules that ship for batch 1 say so (`"splitk": true`)."""
         ext.check(self.lib.y4_set_splitk(self.handle, int(bool(on))))
-        self.splitk = bool(on)
 
     def set_halo2(self, on=True):
         """Let `autotune` also offer the halo2 tiles (conv_halo2_kernel.h: one wave per SIMD, v_mfma_32x32x16, weights in registers)
@@ -1158,7 +1144,6 @@ class Engine:
         """Run convs 0..last_conv over `images` images at a time (Infinity-Cache residency of the big early
         activations); 0 turns it off.  Results are unchanged."""
         ext.check(self.lib.y4_set_subbatch(self.handle, int(images), int(last_conv)))
-        self._subbatch = (int(images), int(last_conv)) if images > 0 else None
 
     def set_stem_fusion(self, on=True):
         """Convs 0+1 as one kernel with conv 0's output kept in LDS (16-bit dtypes, square img_size <= 640).  Results are
@@ -1174,7 +1159,6 @@ class Engine:
         r = self.lib.y4_set_chain_fusion(self.handle, int(bool(on)))
         if r < 0:
             ext.check(r)
-        self.chain_fusion = bool(on)
         return r
 
     def set_stage_fusion(self, on=True):
@@ -1227,9 +1211,13 @@ class Engine:
         with self.torch.cuda.device(self.device):
             ext.check(self.lib.y4_timing_end(self.handle, ms, names, cap, C.byref(nops), C.byref(steps),
                                              ext.stream_ptr()))
+        return self._op_times(names, ms, nops.value), steps.value
+
+    @staticmethod
+    def _op_times(names, ms, n):
+        """[(op name, ms)] from the 16-byte name slots and the times y4_timing_end / y4_profile fill in."""
         raw = names.raw
-        ops = [(raw[16 * i:16 * i + 16].split(b"\0")[0].decode(), float(ms[i])) for i in range(nops.value)]
-        return ops, steps.value
+        return [(raw[16 * i:16 * i + 16].split(b"\0")[0].decode(), float(ms[i])) for i in range(n)]
 
     def profile(self, imgs_dev):
         n = imgs_dev.shape[0]
@@ -1240,8 +1228,7 @@ class Engine:
         with self.torch.cuda.device(self.device):
             ext.check(self.lib.y4_profile(self.handle, ext.ptr(imgs_dev), n, ms, names, cap, C.byref(nops),
                                           ext.stream_ptr()))
-        raw = names.raw
-        return [(raw[16 * i:16 * i + 16].split(b"\0")[0].decode(), float(ms[i])) for i in range(nops.value)]
+        return self._op_times(names, ms, nops.value)
 
 
 LOSS_WEIGHTS = (3.54, 64.3, 1.0)      # reference loss.py:136-138: box (GIoU), confidence, class
