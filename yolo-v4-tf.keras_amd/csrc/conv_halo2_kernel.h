@@ -213,11 +213,7 @@ __global__ __launch_bounds__(256, OCC) void conv_halo2_kernel(const ConvK p) {
         //  256-register K loop does not have: the optimiser then spills them and drains the whole load queue (vmcnt(0)) at every reload.
         //  With 512 registers they ARE hoisted, which is worth 10 % of the loop: 33.5 against 36.8 cycles per MFMA)
         int rr = r0[i];
-#if defined(H2_DBG) && H2_DBG == 3
-        asm volatile("" : "+v"(rr));
-#else
         if constexpr (OCC == 2) asm volatile("" : "+v"(rr));
-#endif
         const int r = rr + ky * P + kx;                   // (brow % 16 == 0: the swizzle does not see the buffer)
         const int e = ((r >> SH) - yq[i] - ky) ^ fh;
         return smem_u + (unsigned)((r + brow) * RB + ((e & (CPR - 1)) << 4));
@@ -274,9 +270,6 @@ __global__ __launch_bounds__(256, OCC) void conv_halo2_kernel(const ConvK p) {
                 for (int q = sg - (AHEAD - 1); q < sg; ++q) y += NB + piece(q);
                 return y;
             }();
-#if defined(H2_DBG) && H2_DBG == 4
-            asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-#endif
             h2_wait_vm_n<younger>();
 #pragma unroll
             for (int j = 0; j < NB; ++j) h2_landed(wf[sg % RING][j]);
@@ -352,11 +345,6 @@ __global__ __launch_bounds__(256, OCC) void conv_halo2_kernel(const ConvK p) {
     for (int x = 0; x < XS; ++x)
 #pragma unroll
         for (int i = 0; i < MB; ++i) h2_landed(xf[x][i]);
-#if defined(H2_DBG) && H2_DBG == 1
-    asm volatile("s_nop 15\n\ts_nop 15\n\ts_nop 15\n\ts_nop 15\n\ts_nop 15\n\ts_nop 15\n\ts_nop 15\n\ts_nop 15" ::: "memory");
-#elif defined(H2_DBG) && H2_DBG == 2
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-#endif
     if constexpr (OCC == 2) __builtin_amdgcn_s_setprio(0);
     __builtin_amdgcn_sched_barrier(0);
     H2_STAMP(12);
