@@ -502,6 +502,23 @@ typedef struct y4_augment_desc {
  * caller owns the table's correctness (offsets and sizes inside the source buffer, h, w, out_h, out_w >= 1, finite factors). */
 int y4_augment_u8_ragged(const uint8_t* src_dev, const y4_augment_desc* desc_dev, int n, uint8_t* out_dev, int H, int W,
                          int pad_value, void* stream);
+/* The cut of one mosaic canvas: rows [0, cut_y) x columns [0, cut_x) are tile 0's window, the three other rectangles the cut
+ * divides the canvas into those of tiles 1 (top right), 2 (bottom left), 3 (bottom right). */
+typedef struct y4_mosaic_cut { int32_t cut_y, cut_x; } y4_mosaic_cut;   /* 8 bytes */
+/* Mosaic: four images around a cut on each canvas, one launch for the batch.  Canvas i has the four rows
+ * tiles_dev[4 i + q], q = 0..3, and the cut cuts_dev[i]; its pixel (y, x) is pixel (y, x) of y4_augment_u8_ragged's rule
+ * under row q = 2 (y >= cut_y) + (x >= cut_x), applied on the WHOLE H x W canvas: the flip mirrors about the canvas
+ * (x' = W - 1 - x), pixels outside the row's rectangle are `pad_value`, colour is applied to resized pixels only and skipped
+ * at (0, 1, 1) -- byte for byte the y4_augment_u8_ragged canvas of that row inside the row's window.  A canvas with the cut
+ * (H, W) is row 4 i alone.  Rows may share a source (the same offset, h, w), within a canvas and across canvases.  The image
+ * of a row whose window is empty (cut_y or cut_x at 0 or at H / W) is never read; the row itself only has to be readable.
+ * The arguments are checked on the host as in y4_augment_u8_ragged, and cuts_dev against NULL (Y4_EINVAL before any launch).
+ * The rows and cuts live on the device and are NOT checked: the caller owns their correctness -- every row with a non-empty
+ * window as y4_augment_u8_ragged asks (offsets and sizes inside the source buffer, h, w, out_h, out_w >= 1, finite
+ * factors), and 0 <= cut_y <= H, 0 <= cut_x <= W. */
+int y4_mosaic_u8_ragged(const uint8_t* src_dev, const y4_augment_desc* tiles_dev /* [n][4] */,
+                        const y4_mosaic_cut* cuts_dev /* [n] */, int n, uint8_t* out_dev, int H, int W, int pad_value,
+                        void* stream);
 /* SPP (custom_layers.py:130-134): x = buf[..., 3c:4c] -> buf[..., 0:c]=maxpool13, [c:2c]=maxpool9,
  * [2c:3c]=maxpool5 (stride 1, 'same'), buf is [n,side,side,4c] */
 int y4_spp(int dtype, void* buf_dev, int n, int side, int c, void* stream);

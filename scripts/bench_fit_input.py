@@ -5,6 +5,11 @@ launch) with the identity config and with the default AugmentConfig, and the aug
 on the same descriptor table.  Default: 608^2, batch 32, bf16 engine, 32 in-memory photos of mixed sizes.  Writes
 profiles/fit/bench_fit_input.json.
 
+The mosaic row: y4_mosaic_u8_ragged beside y4_augment_u8_ragged on the SAME canvases (the default config's rows, every cut at
+(H, W): one tile per canvas) and on drawn mosaic canvases (AugmentConfig(mosaic=1): four tiles each), `Engine.mosaic_u8_batch`
+beside `Engine.augment_u8_batch` from the host images, and the host time of `DataGenerator.raw_mosaic` beside `raw` on 64
+JPEG files of those sizes in a temporary folder (decoding included: a mosaic batch reads its partners too).
+
   python scripts/bench_fit_input.py [--size 608] [--batch 32] [--dtype bf16] [--reps 20] [--out PATH]
 
 Timing: the three paths are wall clock from the host images to a synchronised device batch, measured in turn (host, identity,
@@ -15,6 +20,7 @@ import ctypes as C
 import json
 import os
 import sys
+import tempfile
 import time
 
 import numpy as np
@@ -36,7 +42,7 @@ def main():
     a = ap.parse_args()
     import torch
     from yolo4hip import ext, prepost
-    from yolo4hip.augment import AugmentConfig, draw_params
+    from yolo4hip.augment import AugmentConfig, draw_mosaic_params, draw_params
     from yolo4hip.config import make_config
     from yolo4hip.engine import Engine
     H = W = a.size
@@ -63,8 +69,15 @@ def main():
     def device_path(cfg):
         return eng.augment_u8_batch(photos, draw_params(draws, sizes, (H, W), cfg), pad_value=cfg.pad_value)
 
+    mosaic_cfg = AugmentConfig(mosaic=1.0)
+
+    def mosaic_path():
+        tile_src, params4, cuts = draw_mosaic_params(draws, n, n, (H, W), mosaic_cfg)
+        tile_src[:, 0] = np.arange(n)
+        return eng.mosaic_u8_batch(photos, tile_src, params4, cuts, pad_value=mosaic_cfg.pad_value)
+
     paths = {"host_resize_float32_upload": host_path, "device_identity_config": lambda: device_path(ident),
-             "device_default_config": lambda: device_path(full)}
+             "device_default_config": lambda: device_path(full), "device_mosaic": mosaic_path}
     wall = {k: [] for k in paths}
     for r in range(a.reps + 2):
         for k, fn in paths.items():
@@ -93,12 +106,41 @@ def main():
     p_flip = p_ident.copy()
     p_flip["flip"] = 1
     lib = eng.lib
+    offsets = np.concatenate([[0], np.cumsum([p.size for p in photos])])
+
+    def mosaic_table(tile_src, params4, cuts):
+        desc = (ext.y4_augment_desc * (4 * n))()
+        for d, k, p in zip(desc, tile_src.reshape(-1), params4.reshape(-1)):
+            d.offset, d.h, d.w = int(offsets[k]), photos[k].shape[0], photos[k].shape[1]
+            d.out_h, d.out_w, d.pad_top, d.pad_left = int(p["out_h"]), int(p["out_w"]), int(p["pad_top"]), int(p["pad_left"])
+            d.flip, d.hue, d.sat, d.val = int(p["flip"]), float(p["hue"]), float(p["sat"]), float(p["val"])
+        return (torch.from_numpy(np.frombuffer(desc, dtype=np.uint8).copy()).to(eng.device),
+                torch.from_numpy(np.ascontiguousarray(cuts, dtype=np.int32)).to(eng.device))
+
+    def mosaic_fn(cuts_dev):
+        return lambda s, d, n_, o, H_, W_, pad, st: lib.y4_mosaic_u8_ragged(s, d, ext.ptr(cuts_dev), n_, o, H_, W_, pad, st)
+    own = np.repeat(np.arange(n)[:, None], 4, axis=1)
+    single_desc, single_cuts = mosaic_table(own, np.repeat(p_full[:, None], 4, axis=1), np.tile([H, W], (n, 1)))
+    m_src, m_params, m_cuts = draw_mosaic_params(np.random.default_rng(1), n, n, (H, W), mosaic_cfg)
+    m_src[:, 0] = np.arange(n)
+    four_desc, four_cuts = mosaic_table(m_src, m_params, m_cuts)
     launches = {
         "resize_u8_ragged_stretch": (lib.y4_resize_u8_ragged, table(ext.y4_image_desc, p_ident)),
         "augment_identity": (lib.y4_augment_u8_ragged, table(ext.y4_augment_desc, p_ident)),
         "augment_flip_only": (lib.y4_augment_u8_ragged, table(ext.y4_augment_desc, p_flip)),
         "augment_default_config": (lib.y4_augment_u8_ragged, table(ext.y4_augment_desc, p_full)),
+        "mosaic_same_canvases_as_augment_default_config": (mosaic_fn(single_cuts), single_desc),
+        "mosaic_four_tiles_default_config": (mosaic_fn(four_cuts), four_desc),
     }
+    # the single-tile mosaic table must give the canvases of the augment launch it is timed beside
+    ext.check(lib.y4_augment_u8_ragged(ext.ptr(src), ext.ptr(launches["augment_default_config"][1]), n, ext.ptr(out), H, W, 128,
+                                       ext.stream_ptr()))
+    want = out.clone()
+    ext.check(launches["mosaic_same_canvases_as_augment_default_config"][0](ext.ptr(src), ext.ptr(single_desc), n, ext.ptr(out), H, W,
+                                                                           128, ext.stream_ptr()))
+    torch.cuda.synchronize()
+    if not torch.equal(out, want):
+        raise SystemExit("y4_mosaic_u8_ragged with cuts (H, W) differs from y4_augment_u8_ragged on the same rows")
     kern = {k: [] for k in launches}
     for r in range(a.reps + 5):
         for k, (fn, desc_dev) in launches.items():
@@ -110,6 +152,35 @@ def main():
             if r >= 5:
                 kern[k].append(e0.elapsed_time(e1))
 
+    # ---- the generator's host side: raw(i) against raw_mosaic(i), files decoded from a temporary folder
+    from PIL import Image
+    from yolo4hip.data import DataGenerator
+    gen_ms = {"raw": [], "raw_mosaic": []}
+    with tempfile.TemporaryDirectory() as folder:
+        lines = []
+        for i in range(2 * n):
+            photo = photos[i % n]
+            h, w = photo.shape[:2]
+            Image.fromarray(photo).save(os.path.join(folder, f"im{i}.jpg"), quality=90)
+            objs = [f"{x},{y},{x + w // 4},{y + h // 4},{c % 80}" for c, (x, y) in
+                    enumerate(zip(rng.integers(0, w // 2, 8), rng.integers(0, h // 2, 8)))]
+            lines.append(f"im{i}.jpg " + " ".join(objs) + "\n")
+        names = os.path.join(folder, "classes.txt")
+        with open(names, "w") as fh:
+            fh.write("".join(f"c{c}\n" for c in range(80)))
+        cfg = make_config(a.size, batch_size=n)
+        gens = {"raw": DataGenerator(lines, names, folder, shuffle=False, config=cfg, augment=full, seed=5),
+                "raw_mosaic": DataGenerator(lines, names, folder, shuffle=False, config=cfg, augment=mosaic_cfg, seed=5)}
+        distinct = []
+        for r in range(min(a.reps, 5) + 1):
+            for k, g in gens.items():
+                t0 = time.perf_counter()
+                got = getattr(g, k)(r % 2)
+                if r >= 1:
+                    gen_ms[k].append((time.perf_counter() - t0) * 1e3)
+                    if k == "raw_mosaic":
+                        distinct.append(len(got[0]))
+
     def stats(ms):
         return [float(np.median(ms)), float(np.min(ms)), float(np.max(ms))]
     moved = int(src.numel()) + n * H * W * 3                       # every source byte once + every canvas byte once
@@ -120,6 +191,10 @@ def main():
            "kernel_ms_median_min_max": kern_stats,
            "kernel_GBps_source_plus_canvas_bytes": {k: moved / (v[0] * 1e-3) / 1e9 for k, v in kern_stats.items()},
            "augment_identity_over_resize_ragged": kern_stats["augment_identity"][0] / kern_stats["resize_u8_ragged_stretch"][0],
+           "mosaic_over_augment_same_canvases": kern_stats["mosaic_same_canvases_as_augment_default_config"][0]
+           / kern_stats["augment_default_config"][0],
+           "generator_host_ms_median_min_max": {k: stats(v) for k, v in gen_ms.items()},
+           "generator_dataset_files": 2 * n, "raw_mosaic_distinct_images_per_batch": distinct,
            "reps": a.reps}
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
     with open(a.out, "w") as fh:

@@ -1,4 +1,5 @@
-// augment.hip -- the training input of Yolov4.fit in one launch (y4_augment_u8_ragged): the ragged resize of misc_kernels.hip
+// augment.hip -- the training input of Yolov4.fit in one launch (y4_augment_u8_ragged, and y4_mosaic_u8_ragged: four such
+// images around a cut on one canvas): the ragged resize of misc_kernels.hip
 // (resize_u8_ragged_kernel) with a rectangle that may stick out of the canvas, a mirrored column index and an HSV colour
 // transform.  All randomness is drawn on the host (yolo4hip/augment.py: draw_params); the kernel is a pure function of its
 // descriptor table.  yolo4hip/augment.py: augment_host is its NumPy restatement, tests/augment_oracle.py the float64 one.
@@ -86,6 +87,59 @@ int augment_u8_ragged_launch(const uint8_t* src, const y4_augment_desc* desc, in
         hipLaunchKernelGGL(augment_u8_ragged_kernel<4>, dim3((hw / 4 + 255) / 256, n), dim3(256), 0, stream, src, desc, out, H, W, pad);
     else
         hipLaunchKernelGGL(augment_u8_ragged_kernel<1>, dim3((hw + 255) / 256, n), dim3(256), 0, stream, src, desc, out, H, W, pad);
+    Y4_CHECK_HIP(hipGetLastError());
+    return Y4_OK;
+}
+
+// y4_mosaic_u8_ragged: four tiles around a cut on one canvas, in the shape of the kernel above.  Canvas pixel (y, x) belongs to
+// tile q = 2 (y >= cut_y) + (x >= cut_x) and is pixel (y, x) of the SINGLE-image rule under that tile's row on the whole
+// H x W canvas: the same resize_px_u8 / hsv_px_u8 / store_px_u8 calls, so its bytes are those of augment_u8_ragged_kernel on
+// that row.  A canvas's four rows and its cut reach LDS once per workgroup (50 dwords, one per thread) and are read from
+// there per pixel; a thread's PX pixels may lie on both sides of cut_x, so the tile is chosen per pixel.  A tile whose window
+// is empty is never chosen: its image is never dereferenced.
+template <int PX>
+__global__ __launch_bounds__(256) void mosaic_u8_ragged_kernel(const uint8_t* __restrict__ src, const y4_augment_desc* __restrict__ tiles,
+                                                               const y4_mosaic_cut* __restrict__ cuts, uint8_t* __restrict__ out,
+                                                               int H, int W, int pad) {
+    constexpr int TILE_WORDS = 4 * sizeof(y4_augment_desc) / 4, CUT_WORDS = sizeof(y4_mosaic_cut) / 4;
+    __shared__ __attribute__((aligned(16))) uint32_t table[TILE_WORDS + CUT_WORDS];
+    const int b = blockIdx.y;
+    if (threadIdx.x < TILE_WORDS) table[threadIdx.x] = ((const uint32_t*)(tiles + 4 * (int64_t)b))[threadIdx.x];
+    else if (threadIdx.x < TILE_WORDS + CUT_WORDS) table[threadIdx.x] = ((const uint32_t*)(cuts + b))[threadIdx.x - TILE_WORDS];
+    __syncthreads();
+    const int hw = H * W;                                  // < 2^31 (checked on the host)
+    const int p0 = (blockIdx.x * 256 + threadIdx.x) * PX;
+    if (p0 >= hw) return;
+    const y4_augment_desc* row = (const y4_augment_desc*)table;
+    const int cut_y = (int)table[TILE_WORDS], cut_x = (int)table[TILE_WORDS + 1];
+    uint8_t px[PX * 3];
+#pragma unroll
+    for (int k = 0; k < PX; ++k) {
+        const int p = p0 + k;
+        const int y = p / W, x = p - y * W;
+        const y4_augment_desc d = row[2 * (y >= cut_y) + (x >= cut_x)];
+        const bool colour = !(d.hue == 0.f && d.sat == 1.f && d.val == 1.f);
+        const int yy = y - d.pad_top, xx = (d.flip ? W - 1 - x : x) - d.pad_left;
+        int v[3] = {pad, pad, pad};
+        if (yy >= 0 && yy < d.out_h && xx >= 0 && xx < d.out_w) {
+            resize_px_u8(src + d.offset, d.h, d.w, d.out_h, d.out_w, yy, xx, v);
+            if (colour) hsv_px_u8(v, d.hue, d.sat, d.val);
+        }
+#pragma unroll
+        for (int c = 0; c < 3; ++c) px[k * 3 + c] = (uint8_t)v[c];
+    }
+    store_px_u8<PX>(out + ((int64_t)b * hw + p0) * 3, px);
+}
+
+int mosaic_u8_ragged_launch(const uint8_t* src, const y4_augment_desc* tiles, const y4_mosaic_cut* cuts, int n, uint8_t* out, int H,
+                            int W, int pad, hipStream_t stream) {
+    Y4_REQUIRE(cuts, Y4_EINVAL, "mosaic_u8_ragged: null pointer");
+    if (int rc = ragged_args_check("mosaic_u8_ragged", src, tiles, out, n, H, W, pad)) return rc;
+    const int hw = H * W;
+    if (hw % 4 == 0 && ((uintptr_t)out & 3) == 0)
+        hipLaunchKernelGGL(mosaic_u8_ragged_kernel<4>, dim3((hw / 4 + 255) / 256, n), dim3(256), 0, stream, src, tiles, cuts, out, H, W, pad);
+    else
+        hipLaunchKernelGGL(mosaic_u8_ragged_kernel<1>, dim3((hw + 255) / 256, n), dim3(256), 0, stream, src, tiles, cuts, out, H, W, pad);
     Y4_CHECK_HIP(hipGetLastError());
     return Y4_OK;
 }

@@ -73,6 +73,8 @@ int fold_bn_launch(const float* rec, float* scale, float* shift, int cout, int c
 // augment.hip
 int augment_u8_ragged_launch(const uint8_t* src, const y4_augment_desc* desc, int n, uint8_t* out, int H, int W, int pad,
                              hipStream_t stream);
+int mosaic_u8_ragged_launch(const uint8_t* src, const y4_augment_desc* tiles, const y4_mosaic_cut* cuts, int n, uint8_t* out, int H,
+                            int W, int pad, hipStream_t stream);
 
 // stem_down.hip: convs 0+1 fused (16-bit dtypes), c0 stays in LDS
 bool stem_down_supported(int dtype, int S);

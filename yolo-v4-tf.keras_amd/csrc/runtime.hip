@@ -2038,6 +2038,11 @@ int y4_augment_u8_ragged(const uint8_t* src_dev, const y4_augment_desc* desc_dev
     return augment_u8_ragged_launch(src_dev, desc_dev, n, out_dev, H, W, pad_value, (hipStream_t)stream);
 }
 
+int y4_mosaic_u8_ragged(const uint8_t* src_dev, const y4_augment_desc* tiles_dev, const y4_mosaic_cut* cuts_dev, int n,
+                        uint8_t* out_dev, int H, int W, int pad_value, void* stream) {
+    return mosaic_u8_ragged_launch(src_dev, tiles_dev, cuts_dev, n, out_dev, H, W, pad_value, (hipStream_t)stream);
+}
+
 int y4_preprocess_u8(const uint8_t* img_dev, int h, int w, float* out_dev, int out_h, int out_w, void* stream) {
     return preprocess_u8_launch(img_dev, h, w, out_dev, out_h, out_w, (hipStream_t)stream);
 }

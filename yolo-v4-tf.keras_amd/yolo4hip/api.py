@@ -207,6 +207,11 @@ class Yolov4(object):
         path: handed an augmenting generator they call `boxes(i)`, which augments on the host and draws from the generator's own
         random stream -- validate on a generator without `augment`.
 
+        Mosaic: with `augment.mosaic > 0` the batch is read through `raw_mosaic(i)` instead: every canvas is, with that
+        probability, four images around a random cut.  The distinct photos of the batch cross PCIe once, and
+        `Engine.mosaic_u8_batch` writes all canvases in one launch; the merged boxes arrive from the host.  Everything after
+        the uint8 batch -- chunks, labels, gradients, Adam -- is the same.
+
         A callback with a `schedule(epoch, lr)` method (yolo4hip.callbacks.CosineAnnealingScheduler; Keras'
         LearningRateScheduler pattern) is asked at the start of every epoch; its result is that epoch's learning rate."""
         if trainable not in ('heads', 'head_blocks'):
@@ -226,6 +231,7 @@ class Yolov4(object):
         state = {g: eng._group_state(g, self._flat) for g in groups}
         grad = {g: torch.empty((eng._group_floats(g),), dtype=torch.float32, device=eng.device) for g in groups}
         augment = getattr(train_data_gen, 'augment', None)
+        mosaic = augment is not None and getattr(augment, 'mosaic', 0) > 0
         history = {'loss': []}
         if val_data_gen is not None:
             history['val_loss'] = []
@@ -235,12 +241,16 @@ class Yolov4(object):
                     learning_rate = float(cb.schedule(epoch, learning_rate))
             total, images = 0.0, 0
             for i in range(len(train_data_gen)):
-                if augment is not None:
+                if mosaic:
+                    raws, tile_src, params, cuts, boxes = train_data_gen.raw_mosaic(i)
+                elif augment is not None:
                     raws, params, boxes = train_data_gen.raw(i)
                 else:
                     X, boxes = train_data_gen.boxes(i)
                 boxes_dev = torch.from_numpy(eng._check_boxes(boxes)).to(eng.device)     # ValueError before any update
-                if augment is not None:
+                if mosaic:
+                    X = eng.mosaic_u8_batch(raws, tile_src, params, cuts, pad_value=augment.pad_value)
+                elif augment is not None:
                     X = eng.augment_u8_batch(raws, params, pad_value=augment.pad_value)
                 count = boxes_dev.shape[0]
                 weight = torch.full((count,), 1.0 / count, dtype=torch.float32, device=eng.device)

@@ -15,6 +15,12 @@ Image rule (canvas H x W, parameters out_h, out_w, pad_top, pad_left, flip, hue,
   * colour, on resized pixels only, in float32, skipped when (hue, sat, val) == (0, 1, 1): RGB / 255 -> HSV as
     `colorsys.rgb_to_hsv`, H <- H + hue - floor(H + hue), S <- clamp(S sat, 0, 1), V <- clamp(V val, 0, 1), back as
     `colorsys.hsv_to_rgb`, byte = clamp(floor(255 c + 0.5), 0, 255).
+
+Mosaic (AugmentConfig.mosaic > 0) is defined by composition: a canvas has a cut (cut_y, cut_x) and four
+tiles q = 0..3 (top-left, top-right, bottom-left, bottom-right), each one parameter row of the rule above; canvas pixel (y, x)
+is pixel (y, x) of the single-image augmentation of tile q = 2 (y >= cut_y) + (x >= cut_x) on the whole canvas.
+`draw_mosaic_params` draws the rows, `mosaic_host` is np.where over four `augment_host` canvases, `mosaic_boxes` merges the
+boxes, and `y4_mosaic_u8_ragged` (`Engine.mosaic_u8_batch`) writes the batch in one launch.
 """
 from dataclasses import dataclass
 
@@ -32,7 +38,9 @@ class AugmentConfig:
     """jitter j: the aspect ratio is multiplied by r = U(1-j, 1+j) / U(1-j, 1+j); scale (lo, hi): the rectangle's long side is
     U(lo, hi) of the canvas side; flip: mirror left-right with probability 1/2; hue h: U(-h, h) is added to the hue (a turn is
     1); sat / val s: the factor is U(1, s) or its reciprocal, each with probability 1/2; pad_value: the uint8 level of the
-    canvas outside the rectangle.  AugmentConfig.identity() changes nothing: the plain stretch of `DataGenerator.get_data`."""
+    canvas outside the rectangle.  mosaic: the probability that a canvas is a mosaic of four images (`draw_mosaic_params`), in
+    [0, 1]; mosaic_center (lo, hi): the cut of a mosaic is U(lo, hi) of the canvas side, 0 <= lo <= hi <= 1.
+    AugmentConfig.identity() changes nothing: the plain stretch of `DataGenerator.get_data`."""
     jitter: float = 0.3
     scale: tuple = (0.25, 2.0)
     flip: bool = True
@@ -40,6 +48,8 @@ class AugmentConfig:
     sat: float = 1.5
     val: float = 1.5
     pad_value: int = 128
+    mosaic: float = 0.0
+    mosaic_center: tuple = (0.2, 0.8)
 
     def __post_init__(self):
         lo, hi = (float(v) for v in self.scale)
@@ -47,6 +57,10 @@ class AugmentConfig:
             raise ValueError(f"AugmentConfig: jitter in [0,1), 0 < scale[0] <= scale[1], hue in [0,1], sat >= 1, val >= 1; got {self}")
         if not 0 <= int(self.pad_value) <= 255:
             raise ValueError(f"pad_value must be a uint8 level 0..255, got {self.pad_value}")
+        if not 0.0 <= float(self.mosaic) <= 1.0:
+            raise ValueError(f"mosaic is a probability in [0,1], got {self.mosaic}")
+        if len(self.mosaic_center) != 2 or not 0.0 <= float(self.mosaic_center[0]) <= float(self.mosaic_center[1]) <= 1.0:
+            raise ValueError(f"mosaic_center (lo, hi): 0 <= lo <= hi <= 1, got {self.mosaic_center}")
 
     @classmethod
     def identity(cls, pad_value=128):
@@ -68,26 +82,80 @@ def draw_params(rng, sizes_hw, canvas_hw, cfg):
     Ranges: out_h in [max(1, rint(lo H (1-j)/(1+j))), rint(hi H)], out_w likewise with W; pad_left between 0 and W - out_w
     (either sign), pad_top likewise; |hue| <= cfg.hue; sat in [1/cfg.sat, cfg.sat], val in [1/cfg.val, cfg.val]."""
     H, W = int(canvas_hw[0]), int(canvas_hw[1])
-    j, (lo, hi) = float(cfg.jitter), cfg.scale
     out = np.zeros(len(sizes_hw), dtype=PARAM_DTYPE)
     for p in out:
-        ja, jb = rng.uniform(1.0 - j, 1.0 + j), rng.uniform(1.0 - j, 1.0 + j)
-        r = ja / jb
-        s = rng.uniform(lo, hi)
-        if r < 1.0:
-            nh, nw = np.rint(s * H), np.rint(s * W * r)
-        else:
-            nw, nh = np.rint(s * W), np.rint(s * H / r)
-        nh, nw = max(1, int(nh)), max(1, int(nw))
-        u, v, f = rng.uniform(), rng.uniform(), rng.uniform()
-        p["out_h"], p["out_w"] = nh, nw
-        p["pad_left"], p["pad_top"] = int(np.floor(u * (W - nw))), int(np.floor(v * (H - nh)))
-        p["flip"] = int(bool(cfg.flip) and f < 0.5)
-        p["hue"] = rng.uniform(-cfg.hue, cfg.hue) + 0.0          # (+ 0.0: U(-0, 0) may be -0.0)
-        for name, top in (("sat", cfg.sat), ("val", cfg.val)):
-            m, coin = rng.uniform(1.0, top), rng.uniform()
-            p[name] = m if coin < 0.5 else 1.0 / m
+        _draw_row(rng, p, H, W, cfg)
     return out
+
+
+def _draw_row(rng, p, H, W, cfg, window=None):
+    """One row of `draw_params` into `p`: its draws in its order.  window=None: the position on the whole canvas, as
+    `draw_params` states it.  window=(y0, y1, x0, x1) (a mosaic tile): the same u, u' place the VISIBLE rectangle in the window --
+    left edge L = x0 + floor(u (x1 - x0 - out_w)), top edge likewise -- and pad_left is L without flip, W - L - out_w with
+    flip: the rule mirrors about the whole canvas, which puts a rectangle stored at pad_left on the columns
+    [W - pad_left - out_w, W - pad_left)."""
+    j, (lo, hi) = float(cfg.jitter), cfg.scale
+    ja, jb = rng.uniform(1.0 - j, 1.0 + j), rng.uniform(1.0 - j, 1.0 + j)
+    r = ja / jb
+    s = rng.uniform(lo, hi)
+    if r < 1.0:
+        nh, nw = np.rint(s * H), np.rint(s * W * r)
+    else:
+        nw, nh = np.rint(s * W), np.rint(s * H / r)
+    nh, nw = max(1, int(nh)), max(1, int(nw))
+    u, v, f = rng.uniform(), rng.uniform(), rng.uniform()
+    p["out_h"], p["out_w"] = nh, nw
+    p["flip"] = int(bool(cfg.flip) and f < 0.5)
+    if window is None:
+        p["pad_left"], p["pad_top"] = int(np.floor(u * (W - nw))), int(np.floor(v * (H - nh)))
+    else:
+        y0, y1, x0, x1 = window
+        left = x0 + int(np.floor(u * (x1 - x0 - nw)))
+        p["pad_left"], p["pad_top"] = (W - left - nw if p["flip"] else left), y0 + int(np.floor(v * (y1 - y0 - nh)))
+    p["hue"] = rng.uniform(-cfg.hue, cfg.hue) + 0.0          # (+ 0.0: U(-0, 0) may be -0.0)
+    for name, top in (("sat", cfg.sat), ("val", cfg.val)):
+        m, coin = rng.uniform(1.0, top), rng.uniform()
+        p[name] = m if coin < 0.5 else 1.0 / m
+
+
+def tile_windows(cut, canvas_hw):
+    """The four windows (y0, y1, x0, x1) of a mosaic canvas, tile order 0..3: top-left, top-right, bottom-left, bottom-right."""
+    H, W = int(canvas_hw[0]), int(canvas_hw[1])
+    cy, cx = int(cut[0]), int(cut[1])
+    return [(0, cy, 0, cx), (0, cy, cx, W), (cy, H, 0, cx), (cy, H, cx, W)]
+
+
+def draw_mosaic_params(rng, n, dataset_len, canvas_hw, cfg):
+    """The draws of n canvases under cfg.mosaic -> (tile_src int64 [n,4]: indices into a dataset of `dataset_len` images, -1
+    where the caller puts the canvas's own image -- column 0 always, every column of a single canvas;
+    params PARAM_DTYPE [n,4]; cuts int32 [n,2] as (cut_y, cut_x)).  Per canvas, in this order, from `rng`:
+      c ~ U[0,1): a mosaic when c < cfg.mosaic, else a single image;
+      mosaic: ux, uy ~ U(cfg.mosaic_center): cut_x = rint(ux W), cut_y = rint(uy H);  three partners
+              rng.integers(dataset_len) for tiles 1, 2, 3 (with replacement; the own image may come again);  then four rows in
+              tile order, each the draws of a `draw_params` row: the size by the jitter and scale rule relative to the CANVAS
+              (the object sizes keep the distribution of the single-image path), the position inside the tile's WINDOW by the
+              shift rule (`_draw_row`: a rectangle larger than the window covers it and sticks out, a smaller one lies
+              inside it on pad), flip, hue, sat, val as there;
+      single: the cut is (H, W), row 0 one `draw_params` row on the whole canvas, rows 1..3 copies of it (their windows are
+              empty).
+    A mosaic canvas consumes 1 + 2 + 3 + 4 x 11 draws, a single one 1 + 11."""
+    H, W = int(canvas_hw[0]), int(canvas_hw[1])
+    lo, hi = (float(v) for v in cfg.mosaic_center)
+    src = np.full((int(n), 4), -1, dtype=np.int64)
+    params = np.zeros((int(n), 4), dtype=PARAM_DTYPE)
+    cuts = np.zeros((int(n), 2), dtype=np.int32)
+    for i in range(int(n)):
+        if rng.uniform() < cfg.mosaic:
+            ux, uy = rng.uniform(lo, hi), rng.uniform(lo, hi)
+            cuts[i] = int(np.rint(uy * H)), int(np.rint(ux * W))
+            src[i, 1:] = [int(rng.integers(dataset_len)) for _ in range(3)]
+            for q, window in enumerate(tile_windows(cuts[i], (H, W))):
+                _draw_row(rng, params[i, q], H, W, cfg, window)
+        else:
+            cuts[i] = H, W
+            _draw_row(rng, params[i, 0], H, W, cfg)
+            params[i, 1:] = params[i, 0]
+    return src, params, cuts
 
 
 def transform_boxes(raw_boxes, size_hw, param, canvas_hw, max_boxes):
@@ -157,3 +225,36 @@ def augment_host(img, param, canvas_hw, pad_value=128):
         rect = prepost.resize_bilinear(np.asarray(img, dtype=np.uint8), (out_w, out_h))[y0 - top:y1 - top, x0 - left:x1 - left]
         canvas[y0:y1, x0:x1] = hsv_shift_u8(rect, param["hue"], param["sat"], param["val"])
     return canvas[:, ::-1].copy() if param["flip"] else canvas
+
+
+def mosaic_boxes(tile_boxes, tile_sizes, params4, cut, canvas_hw, max_boxes):
+    """The boxes of one mosaic canvas: per tile q (raw boxes tile_boxes[q] of an image of tile_sizes[q] = (h, w), row
+    params4[q]) `transform_boxes` on the whole canvas, clipped to the tile's window, rows whose width or height is then <= 1
+    dropped; the tiles concatenated in the order 0..3, the first `max_boxes` kept, zero padded -> float32 [max_boxes,5].  A
+    tile whose window is empty contributes nothing."""
+    out = np.zeros((int(max_boxes), 5), dtype=np.float32)
+    kept = []
+    for q, (y0, y1, x0, x1) in enumerate(tile_windows(cut, canvas_hw)):
+        if y0 >= y1 or x0 >= x1:
+            continue
+        b = transform_boxes(tile_boxes[q], tile_sizes[q], params4[q], canvas_hw, max_boxes)
+        b = b[b[:, 2] - b[:, 0] > 0]                               # its compacted prefix
+        b[:, [0, 2]] = np.clip(b[:, [0, 2]], x0, x1)
+        b[:, [1, 3]] = np.clip(b[:, [1, 3]], y0, y1)
+        kept.append(b[(b[:, 2] - b[:, 0] > 1.0) & (b[:, 3] - b[:, 1] > 1.0)])
+    if kept:
+        rows = np.concatenate(kept)[:int(max_boxes)]
+        out[:len(rows)] = rows
+    return out
+
+
+def mosaic_host(imgs4, params4, cut, canvas_hw, pad_value=128):
+    """Four uint8 images, their four rows and the cut -> the mosaic canvas uint8 [H,W,3]: the NumPy restatement of
+    y4_mosaic_u8_ragged for one canvas -- np.where over the four `augment_host` canvases, of which only those with a
+    non-empty window are computed (the image of an empty window is not touched)."""
+    H, W = int(canvas_hw[0]), int(canvas_hw[1])
+    canvas = np.empty((H, W, 3), dtype=np.uint8)
+    for q, (y0, y1, x0, x1) in enumerate(tile_windows(cut, canvas_hw)):
+        if y0 < y1 and x0 < x1:
+            canvas[y0:y1, x0:x1] = augment_host(imgs4[q], params4[q], canvas_hw, pad_value)[y0:y1, x0:x1]
+    return canvas

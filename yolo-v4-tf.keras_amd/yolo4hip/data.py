@@ -197,7 +197,13 @@ class DataGenerator:
     `numpy.random.default_rng(seed)`; `raw(i)` gives (uint8 images, parameters, transformed boxes) for the device path of
     `Yolov4.fit` (`Engine.augment_u8_batch`), `boxes(i)` and `gen[i]` the same batch through `augment.augment_host` -- either
     way one draw per image in batch order, so a seed gives the same parameters on both paths.  The box shuffle and the epoch
-    shuffle stay on the global `np.random`, as without augmentation."""
+    shuffle stay on the global `np.random`, as without augmentation.
+
+    Mosaic: with `augment.mosaic > 0` every canvas is, with that probability, four images around a random cut
+    (`augment.draw_mosaic_params`): its own image top-left and three partners drawn from the whole dataset.  `raw_mosaic(i)`
+    gives (distinct uint8 images, tile_src [n,4] into them, parameters [n,4], cuts [n,2], merged boxes) for
+    `Engine.mosaic_u8_batch`; `boxes(i)` and `gen[i]` build the same batch through `augment.mosaic_host`, with the same draws.
+    `raw(i)` refuses such a generator: one parameter row per image cannot describe its batch."""
 
     def __init__(self, annotation_lines, class_name_path, folder_path, max_boxes=100, shuffle=True, config=None, augment=None,
                  seed=None):
@@ -233,6 +239,8 @@ class DataGenerator:
         from . import augment as A
         if self.augment is None:
             raise ValueError("DataGenerator.raw: this generator does not augment (augment=None)")
+        if self.augment.mosaic > 0:
+            raise ValueError("DataGenerator.raw: this generator draws mosaic canvases (augment.mosaic > 0), use raw_mosaic")
         idxs = self.indexes[index * self.batch_size:(index + 1) * self.batch_size]
         read = [self._read(self.annotation_lines[j]) for j in idxs]
         imgs = [img for img, _ in read]
@@ -243,7 +251,46 @@ class DataGenerator:
             y_bbox[i] = A.transform_boxes(boxes, img.shape[:2], params[i], hw, self.max_boxes)
         return imgs, params, y_bbox
 
+    def raw_mosaic(self, index):
+        """Batch `index` of a mosaic generator (augment.mosaic > 0) -> (images: the DISTINCT uint8 RGB photos of the batch,
+        each read once -- the batch's own images in batch order, then the partners in the order tiles first name them;
+        tile_src int64 [n,4]: per canvas and tile the index into `images`; parameter rows (augment.PARAM_DTYPE) [n,4];
+        cuts int32 [n,2] as (cut_y, cut_x); boxes float32 [n, max_boxes, 5] on the mosaic canvas, `augment.mosaic_boxes`).
+        A single canvas (cut (H, W)) carries its own image and row 0 in all four tiles."""
+        from . import augment as A
+        if self.augment is None or not self.augment.mosaic > 0:
+            raise ValueError("DataGenerator.raw_mosaic: this generator draws no mosaic canvases (augment.mosaic > 0)")
+        idxs = self.indexes[index * self.batch_size:(index + 1) * self.batch_size]
+        hw = self.target_img_size[:2]
+        slot, read = {}, []                                 # annotation line -> slot in `read`
+        for j in idxs:
+            slot[int(j)] = len(read)
+            read.append(self._read(self.annotation_lines[j]))
+        data_src, params, cuts = A.draw_mosaic_params(self.rng, len(idxs), len(self.annotation_lines), hw, self.augment)
+        tile_src = np.empty((len(idxs), 4), dtype=np.int64)
+        for i, j in enumerate(idxs):
+            for q in range(4):
+                k = int(j) if data_src[i, q] < 0 else int(data_src[i, q])
+                if k not in slot:
+                    slot[k] = len(read)
+                    read.append(self._read(self.annotation_lines[k]))
+                tile_src[i, q] = slot[k]
+        y_bbox = np.zeros((len(idxs), self.max_boxes, 5), dtype=np.float32)
+        for i in range(len(idxs)):
+            tiles = [read[k] for k in tile_src[i]]
+            y_bbox[i] = A.mosaic_boxes([b for _, b in tiles], [img.shape[:2] for img, _ in tiles], params[i], cuts[i], hw,
+                                       self.max_boxes)
+        return [img for img, _ in read], tile_src, params, cuts, y_bbox
+
     def boxes(self, index):
+        if self.augment is not None and self.augment.mosaic > 0:
+            from .augment import mosaic_host
+            imgs, tile_src, params, cuts, y_bbox = self.raw_mosaic(index)
+            X = np.empty((len(tile_src), *self.target_img_size), dtype=np.float32)
+            for i in range(len(tile_src)):
+                X[i] = mosaic_host([imgs[k] for k in tile_src[i]], params[i], cuts[i], self.target_img_size[:2],
+                                   self.augment.pad_value) / 255.
+            return X, y_bbox
         if self.augment is not None:
             from .augment import augment_host
             imgs, params, y_bbox = self.raw(index)

@@ -300,6 +300,40 @@ class Engine:
                                                     pad_value, ext.stream_ptr()))
         return out
 
+    def mosaic_u8_batch(self, images, tile_src, params, cuts, pad_value=128):
+        """Mosaic canvases on the device (`DataGenerator.raw_mosaic`): `images` the DISTINCT uint8 RGB photos [h,w,3] of the
+        batch, tile_src int [n,4] the image of every tile, params (yolo4hip.augment.PARAM_DTYPE) [n,4] its row, cuts int
+        [n,2] the (cut_y, cut_x) of every canvas -> the uint8 cuda batch [n,H,W,3].  Every image is packed and uploaded once,
+        however many tiles use it: the 4 n descriptors carry shared offsets, and they, the cuts and the images cross in the
+        one staging buffer and the one copy of `augment_u8_batch`; one launch (`y4_mosaic_u8_ragged`) follows.
+        `augment.mosaic_host` is the same function on the host.  What the kernel does not check is checked here (ValueError):
+        0 <= cut <= (H, W), tile_src inside `images`, out_h, out_w >= 1, finite factors.  Asynchronous on the current stream."""
+        torch = self.torch
+        images, pad_value = self._check_ragged(images, pad_value, "mosaic_u8_batch")
+        H, W = self.img_hw
+        tile_src, cuts = np.asarray(tile_src), np.ascontiguousarray(cuts, dtype=np.int32)
+        n = len(cuts)
+        if n < 1 or tile_src.shape != (n, 4) or np.shape(params) != (n, 4) or cuts.shape != (n, 2):
+            raise ValueError(f"mosaic_u8_batch: tile_src {tile_src.shape}, params {np.shape(params)}, cuts {cuts.shape}: "
+                             f"[n,4], [n,4], [n,2]")
+        if tile_src.dtype.kind not in "iu" or tile_src.min() < 0 or tile_src.max() >= len(images):
+            raise ValueError(f"mosaic_u8_batch: tile_src must index the {len(images)} images")
+        if (cuts < 0).any() or (cuts[:, 0] > H).any() or (cuts[:, 1] > W).any():
+            raise ValueError(f"mosaic_u8_batch: cuts (cut_y, cut_x) must lie in [0, {H}] x [0, {W}]")
+        desc = (ext.y4_augment_desc * (4 * n))()
+        for d, p in zip(desc, np.asarray(params).reshape(-1)):
+            d.out_h, d.out_w, d.pad_top, d.pad_left = int(p["out_h"]), int(p["out_w"]), int(p["pad_top"]), int(p["pad_left"])
+            d.flip, d.hue, d.sat, d.val = int(p["flip"]), float(p["hue"]), float(p["sat"]), float(p["val"])
+            if d.out_h < 1 or d.out_w < 1 or not np.isfinite([d.hue, d.sat, d.val]).all():
+                raise ValueError(f"mosaic_u8_batch: rectangle {d.out_h} x {d.out_w}, factors {d.hue}, {d.sat}, {d.val}")
+        dev, desc_bytes, head = self._upload_ragged(images, desc, cuts, rows=tile_src.reshape(-1))
+        with torch.cuda.device(self.device):
+            out = torch.empty((n, H, W, 3), dtype=torch.uint8, device=self.device)
+            ext.check(self.lib.y4_mosaic_u8_ragged(C.c_void_p(dev.data_ptr() + head), ext.ptr(dev),
+                                                   C.c_void_p(dev.data_ptr() + desc_bytes), n, ext.ptr(out), H, W, pad_value,
+                                                   ext.stream_ptr()))
+        return out
+
     @staticmethod
     def _check_ragged(raw_imgs, pad_value, who):
         """One image or a list of them -> (list of uint8 [h,w,3] arrays, pad_value as an int), or ValueError."""
@@ -316,19 +350,22 @@ class Engine:
                 raise ValueError(f"expected uint8 [h,w,3] images, got {getattr(a, 'dtype', type(a))} {getattr(a, 'shape', '')}")
         return raw_imgs, pad_value
 
-    def _upload_ragged(self, raw_imgs, desc, extra=None):
-        """The one upload of a ragged batch (`preprocess_u8_batch`, `augment_u8_batch`): fills offset, h, w of every row of
-        `desc` (a ctypes array of y4_image_desc or y4_augment_desc), packs descriptors | `extra` (a numpy array, or None) | the
-        images into the pinned staging buffer (kept across calls) and copies it to a fresh device block in one copy.
+    def _upload_ragged(self, raw_imgs, desc, extra=None, rows=None):
+        """The one upload of a ragged batch (`preprocess_u8_batch`, `augment_u8_batch`, `mosaic_u8_batch`): fills offset, h, w of
+        every row of `desc` (a ctypes array of y4_image_desc or y4_augment_desc; row k describes image k, or image rows[k]
+        where `rows` is given: rows may share an image), packs descriptors | `extra` (a numpy array, or None) | the images into
+        the pinned staging buffer (kept across calls) and copies it to a fresh device block in one copy.
         -> (device block, descriptor bytes, bytes before the first image); descriptor offsets count from the first image byte."""
         torch = self.torch
         n = len(raw_imgs)
         desc_bytes = C.sizeof(desc)
         head = desc_bytes + (extra.nbytes if extra is not None else 0)
-        off = 0
-        for d, a in zip(desc, raw_imgs):
-            d.offset, d.h, d.w = off, a.shape[0], a.shape[1]
+        offs, off = [], 0
+        for a in raw_imgs:
+            offs.append(off)
             off += a.shape[0] * a.shape[1] * 3
+        for d, k in zip(desc, range(n) if rows is None else rows):
+            d.offset, d.h, d.w = offs[k], raw_imgs[k].shape[0], raw_imgs[k].shape[1]
         total = head + off
         pin = getattr(self, "_batch_pin", None)
         if pin is None or pin.numel() < total:
@@ -345,7 +382,7 @@ class Engine:
             buf[desc_bytes:head] = extra.view(np.uint8).reshape(-1)
 
         def pack(i):
-            a, o = raw_imgs[i], head + desc[i].offset
+            a, o = raw_imgs[i], head + offs[i]
             np.copyto(buf[o:o + a.size].reshape(a.shape), a)   # (any strides: BGR views included; releases the GIL)
 
         if off >= (8 << 20) and n > 1:

@@ -57,6 +57,10 @@ class y4_augment_desc(C.Structure):
     _fields_ = y4_image_desc._fields_ + [("flip", C.c_int32), ("hue", C.c_float), ("sat", C.c_float), ("val", C.c_float)]
 
 
+class y4_mosaic_cut(C.Structure):
+    _fields_ = [("cut_y", C.c_int32), ("cut_x", C.c_int32)]
+
+
 # every symbol include/yolo4hip.h declares: name -> (restype, argtypes)
 _VP, _I, _F = C.c_void_p, C.c_int, C.c_float
 SYMBOLS = {
@@ -128,6 +132,7 @@ SYMBOLS = {
     "y4_resize_u8": (_I, [_VP, _I, _I, _I, _VP, _I, _I, _VP]),
     "y4_resize_u8_ragged": (_I, [_VP, _VP, _I, _VP, _I, _I, _I, _VP]),
     "y4_augment_u8_ragged": (_I, [_VP, _VP, _I, _VP, _I, _I, _I, _VP]),
+    "y4_mosaic_u8_ragged": (_I, [_VP, _VP, _VP, _I, _VP, _I, _I, _I, _VP]),
     "y4_spp": (_I, [_I, _VP, _I, _I, _I, _VP]),
     "y4_spp_hw": (_I, [_I, _VP, _I, _I, _I, _I, _VP]),
 }
