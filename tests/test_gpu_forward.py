@@ -493,6 +493,44 @@ def test_res_fusion_is_bit_identical(dtype, size, n):
     eng.close()
 
 
+_BUILTIN_TAPS = {}
+
+
+def _all_taps(eng, n):
+    return [eng.conv_output(i, n) for i in range(110)] + [h.cpu().numpy() for h in eng.heads_device(n)]
+
+
+# schedule codes of csrc/conv_tiles.h (y4_conv_tile_desc(...)[5]) per family
+SAME_ORDER_FAMILIES = {"ring3to7": (3, 4, 5, 6, 7), "code8": (8,), "code9": (9,), "code10": (10,), "staggered": (12,), "halo": (20,)}
+
+
+@pytest.mark.parametrize("family,dtype", [("ring3to7", "f32")] + [(f, d) for f in SAME_ORDER_FAMILIES for d in ("bf16", "f16")])
+def test_forced_same_order_tile_family_is_bit_identical_at_every_layer(family, dtype):
+    """The tile families that walk the K axis in the canonical order -- the rings of 3..7 LDS stages, the phased kernels (codes 8, 9,
+    10), the staggered schedule, the halo tiles -- forced onto every conv of the plan that accepts them (a refusal is Y4_EINVAL from
+    the next forward), with the plan's own views: CSP pair stores, residual operands, concat slices, the 2x stores of convs 78 / 85,
+    the float32 heads.  All 110 stored tensors and the three heads equal those of the built-in schedule bit for bit.  96 x 96 is the
+    smallest square input at which a halo band fits a map; float32 has the ring tiles only."""
+    import torch
+    import layer_local as LL
+    size, n = 96, 2
+    cfg, plan, ws, imgs, eng = _setup(size, 3, n, dtype, seed=0)
+    dev = torch.from_numpy(imgs).to(eng.device)
+    if dtype not in _BUILTIN_TAPS:
+        eng.forward_device(dev)
+        _BUILTIN_TAPS[dtype] = _all_taps(eng, n)
+    forced = LL.force_family(eng, dev, LL.tiles_of(eng.lib, SAME_ORDER_FAMILIES[family]))
+    eng.forward_device(dev)
+    got = _all_taps(eng, n)
+    eng.close()
+    accepted = {i: t for i, t in enumerate(forced) if t}
+    print(f"{family} {dtype}: forced on {len(accepted)} convs: {accepted}")
+    assert accepted, f"no conv accepted a {family} tile"
+    for i, (a, b) in enumerate(zip(got, _BUILTIN_TAPS[dtype])):
+        assert np.array_equal(a, b), f"{'conv %d' % i if i < 110 else 'head %d' % (i - 110)} differs from the built-in schedule with {family} " \
+                                     f"tiles {accepted}: {int((a != b).sum())} elements, max |delta| {np.abs(a - b).max():.3e}"
+
+
 def test_stem_fusion_rejected_where_unsupported():
     import yolo4hip.ext as ext
     cfg, plan, ws, imgs, eng = _setup(160, 3, 1, "f32")

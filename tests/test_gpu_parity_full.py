@@ -330,3 +330,90 @@ def test_shipped_schedule_keeps_the_bits_at_the_headline_shape():
             assert float(d.mean()) > 0, "the halo2 ids changed nothing: is the schedule applied?"
         _record("halo2_vs_16x16x32_schedule_608_80_32_bf16", {"mean_abs_head_delta": [float(np.abs(a - b).mean()) for a, b in zip(first, plain_heads)]})
     eng.close()
+
+
+# ---- every layer of the forward against float64 on the device's own inputs (tests/layer_local.py: the bound, its derivation and
+# what the CPU proof of the checker covers, tests/test_layer_local_cpu.py)
+LAYER_LOCAL_SHAPES = {"96x96n2": ((96, 96), 2), "96x160n1": ((96, 160), 1)}
+_LL_INPUTS = {}
+
+
+def _layer_local_inputs(shape, wset="synth"):
+    from helpers import widen_activations
+    from yolo4hip import weights as W
+    from yolo4hip.plan import build_plan
+    hw, n = LAYER_LOCAL_SHAPES[shape]
+    ncls = 3
+    if (shape, "synth") not in _LL_INPUTS:
+        plan = build_plan(hw, ncls)
+        _LL_INPUTS[(shape, "synth")] = (plan, W.synth_weights(plan, seed=0), W.synth_images(n, hw, seed=0))
+    if (shape, wset) not in _LL_INPUTS:
+        plan, ws, imgs = _LL_INPUTS[(shape, "synth")]
+        _LL_INPUTS[(shape, wset)] = (plan, widen_activations(ws, seed=0), imgs)
+    return (ncls, hw, n) + _LL_INPUTS[(shape, wset)]
+
+
+def _layer_local_run(dtype, shape, wset, case, force=None):
+    """One forward of an unfused, non-aliased engine (every conv materialised) with the built-in schedule, or with `force(eng)` ->
+    candidate tile ids put on every conv that accepts one; all 110 stored tensors through layer_local.check_forward."""
+    import torch
+    import layer_local as LL
+    from yolo4hip import weights as W
+    from yolo4hip.config import make_config
+    from yolo4hip.engine import Engine
+    ncls, hw, n, plan, ws, imgs = _layer_local_inputs(shape, wset)
+    eng = Engine(ncls, make_config(hw), max_batch=n, dtype=dtype)
+    eng.load_weight_blob(W.flatten(ws))
+    dev_imgs = torch.from_numpy(imgs).to(eng.device)
+    forced = None
+    if force is not None:
+        forced = LL.force_family(eng, dev_imgs, force(eng))
+    eng.forward_device(dev_imgs)
+    dev = LL.device_tensors(eng, n, plan)
+    eng.close()
+    report, failures = LL.check_forward(imgs, ws, ncls, dtype, dev)
+    print(LL.one_line(case, report))
+    payload = {"layers": LL.summary(report)}
+    if forced is not None:
+        payload["forced"] = {str(i): t for i, t in enumerate(forced) if t}
+        print(f"{case}: forced on {len(payload['forced'])} convs: {payload['forced']}")
+    LL.record("measured", case, payload)
+    assert len(report) == 110 and not failures, "\n".join(failures)
+    return forced
+
+
+@pytest.mark.parametrize("dtype,shape,wset", [(d, s, "synth") for d in ("f32", "bf16", "f16") for s in LAYER_LOCAL_SHAPES] +
+                         [("bf16", "96x96n2", "wide")])
+def test_every_layer_vs_float64_on_the_devices_own_inputs(dtype, shape, wset):
+    """Teacher forcing: each of the 110 convs (residual Adds, CSP views, SPP, concats and the 2x stores with them) in float64 on the
+    tensors the device itself stored for its inputs; the device's tensor within one storage rounding plus float32 accumulation of the
+    exact value at every element, and its mean error within 1.25 x that of a float32 evaluation rounded once (layer_local.py).  At
+    96 x 96 (n = 2) and 96 x 160 every layer has ragged pixel tiles and the deep maps are 3 x 3 and 3 x 5: mostly padding.  `wide`:
+    helpers.widen_activations, pre-activations beyond +-20 at every layer."""
+    _layer_local_run(dtype, shape, wset, f"builtin_{dtype}_{shape}_{wset}")
+
+
+def _splitk_ids(e):
+    # the 64 x 64 ring tiles with 128- and 64-byte K rows (conv_tiles.h ids 10, 11), K loop split 2^e ways
+    return lambda eng: (eng.set_splitk(True), [10 + 100 * e, 11 + 100 * e])[1]
+
+
+def _family_ids(code):
+    def ids(eng):
+        import layer_local as LL
+        return LL.tiles_of(eng.lib, (code,))
+    return ids
+
+
+@pytest.mark.parametrize("family,dtype,force", [
+    ("splitk2", "f32", _splitk_ids(1)), ("splitk2", "bf16", _splitk_ids(1)), ("splitk8", "f32", _splitk_ids(3)), ("splitk8", "bf16", _splitk_ids(3)),
+    ("mfma32x32x16", "bf16", _family_ids(32)), ("mfma32x32x16", "f16", _family_ids(32)),
+    ("halo2", "bf16", _family_ids(21)), ("halo2", "f16", _family_ids(21))])
+def test_every_layer_vs_float64_with_a_forced_tile_family(family, dtype, force):
+    """The tile families that sum the K axis in ANOTHER float32 order than the built-in schedule -- split-K (2- and 8-way), the
+    32x32x16 MFMA tiles, the halo2 tiles -- forced onto every conv that accepts them, through the same checker: its accumulation term
+    holds for any order.  96 x 96 is the smallest square input at which a halo2 band fits a map (12 x 12 = 3/4 of 192 pixels); the
+    other families take a conv by its channel counts alone, and run here on the same, smallest shape the suite builds engines for.
+    A family that no conv accepts fails; the accepted convs are printed and recorded."""
+    forced = _layer_local_run(dtype, "96x96n2", "synth", f"{family}_{dtype}_96x96n2", force)
+    assert any(forced), f"no conv accepted a {family} tile"
