@@ -89,9 +89,6 @@ __device__ unsigned long long h2_trace_blocks[4096][4];        // per workgroup 
 #ifndef H2_NOP
 #define H2_NOP -1               // >= 0: an `s_nop H2_NOP` behind every MFMA of the K loop (experiments only; see there)
 #endif
-#ifndef H2_LOOP_PRIO
-#define H2_LOOP_PRIO 2
-#endif
 #ifndef HALO2_ABLATIONS
 // 1 (kernel experiments only): the HALO_ABL environment variable then switches parts of the K loop off at run time -- bit 1 the
 // weight loads, 2 the halo pieces, 4 the fragment reads, 8 the barrier -- for TIMING; results are wrong.  Not in the regular build.
@@ -255,7 +252,7 @@ __global__ __launch_bounds__(256, OCC) void conv_halo2_kernel(const ConvK p) {
     const int nsteps = nchunks * 36;
     // Two workgroups per CU = two waves per SIMD: the one in its K loop must win the issue arbitration against the one in its
     // prologue / epilogue (plain age order lets an older wave's Mish epilogue starve the younger wave's MFMA stream of VALU slots)
-    if constexpr (OCC == 2) __builtin_amdgcn_s_setprio(H2_LOOP_PRIO);
+    if constexpr (OCC == 2) __builtin_amdgcn_s_setprio(2);
     for (int c = 0; c < nchunks; ++c) {
         h2_static_for<0, 36>([&](auto sgc) __attribute__((always_inline)) {
             constexpr int sg = decltype(sgc)::value;

@@ -191,13 +191,8 @@ __global__ __launch_bounds__(512, 1) void conv_p8_kernel(const ConvK p) {
     };
     set_tap();
     // the cursor's K-tile -> LDS stage st: pixel part r, the four weight parts; `advance` moves the cursor to the next K-tile
-#ifdef Y4_ABL_NOLOAD        // timing-only ablation builds (scripts/build_variant.sh; wrong results)
-    auto issue_a = [&](int r, int st) {};
-    auto issue_b = [&](int j, int st) {};
-#else
     auto issue_a = [&](int r, int st) { buffer_load16_lds(rs_in, smem + st * STAGE + wave_lds + r * PART, a_vo[r], c0b); };
     auto issue_b = [&](int j, int st) { buffer_load16_lds(rs_wt, smem + st * STAGE + wave_lds + A_TILE + j * PART, b_vo[j], ktb); };
-#endif
     auto advance = [&]() {
         ktb += BKB;
         c_in += BKB;
@@ -283,25 +278,17 @@ __global__ __launch_bounds__(512, 1) void conv_p8_kernel(const ConvK p) {
 #pragma unroll
                             for (int j = 0; j < NREP; ++j) {
                                 const int i = kk * 8 + h * 4 + j;      // MFMA slot of this phase
-#ifndef Y4_ABL_NOMFMA
                                 Mma<DT>::run(acc[2 * ph + h][j], wf[kk][j], xf[kk][h]);
-#else
-                                asm volatile("" : "+v"(acc[2 * ph + h][j]) : "v"(wf[kk][j]), "v"(xf[kk][h]));
-#endif
                                 __builtin_amdgcn_sched_barrier(0);
                                 // the side instruction(s) of the slot
                                 if (i == 0) slot_a(ph, st);
                                 if (ph == 1 && i >= 1 && i <= 4) issue_b(i - 1, st);
-#ifndef Y4_ABL_NOREAD
                                 if (j == NREP - 1) xf[kk][h] = *(const u32x4*)(na + h * 16 * BKB + xo[kk]);    // its last user has issued
                                 if (last && h == 1) wf[kk][j] = *(const u32x4*)(nb + j * 16 * BKB + xo[kk]);
-#endif
                                 __builtin_amdgcn_sched_barrier(0);
                             }
                     s9_wait_phase<NP, ph>();
-#ifndef Y4_ABL_NOBAR
                     p8_barrier();
-#endif
                 };
                 phase(std::integral_constant<int, 0>{});
                 phase(std::integral_constant<int, 1>{});

@@ -23,55 +23,23 @@
 // 352 Mish channels per pixel (LABNOTES.md section 4.1b).
 #include "conv_chain.h"
 
-// experiment switches (scripts/build_variant.sh): CS_ABL 1 = LeakyReLU instead of Mish (VALU ablation), 2 = no output
-// stores, 3 = the input tile is loaded once only; CS_VMCNT = stores that may stay in flight across the tile boundary
-#ifndef CS_ABL
-#define CS_ABL 0
-#endif
-#ifndef CS_PRIO
-// 1: "leapfrog" priorities -- a wave lowers its s_setprio level as it moves through the segments of a barrier interval, so the wave
-// of a SIMD that is BEHIND outranks its partner (the hardware's own tie-break is age: the older wave of a SIMD runs unimpeded and
-// the younger one gets the leftover VALU / transcendental slots, then finishes alone at a single wave's issue rate).
-// 2: waves 4..7 at priority 1 throughout (the mirror image of the default).
-#define CS_PRIO 1
-#endif
-#ifndef CS_LX
-#define CS_LX 1     // 1: the halo tile's per-lane offsets and border flags are computed once per workgroup, not once per tile
-#endif
-#ifndef CS_EXTRA
-#define CS_EXTRA 1  // 1: the five halo-ring fragments on waves 0..3 (wave 0 takes two) instead of waves 0..4
-#endif
-#ifndef CS_VMCNT
-// 0: the tile boundary drains everything.  4 would let the previous tile's 4 output stores stay in flight (measured: 583 ->
-// 578 us), but it relies on stores and LDS-DMA loads retiring in issue order RELATIVE TO EACH OTHER on one vmcnt counter,
-// which gfx9-family hardware does not promise (LLVM treats mixed pending loads / stores as out of order): not worth 1 %.
-#define CS_VMCNT 0
-#endif
+#include "phase_trace.h"
 
 namespace y4 {
 
 #ifdef CS_TRACE
-// In-kernel phase trace (kernel experiments only; scripts/stage_trace.py): workgroup CS_TR_WG records s_memtime per wave at
+// In-kernel phase trace (kernel experiments only; scripts/phase_trace.py csp_stage): workgroup CS_TR_WG records s_memtime per wave at
 // fixed points of its tiles CS_TR_T0 .. +3 into cs_trace_buf[tile][wave][point]; y4_cs_trace_read() copies it out.
 __device__ unsigned long long cs_trace_buf[4 * 8 * 16];
 #define CS_TR_WG 8
 #define CS_TR_T0 3
-#define CS_POINT(P)                                                                                         \
-    do {                                                                                                    \
-        __builtin_amdgcn_sched_barrier(0);                                                                  \
-        if (tr_on) asm volatile("s_memtime %0" : "=s"(tr_t[P]));                                            \
-        __builtin_amdgcn_sched_barrier(0);                                                                  \
-    } while (0)
-#else
-#define CS_POINT(P)
 #endif
 
-constexpr int CS_ACT = CS_ABL == 1 ? Y4_ACT_LEAKY : Y4_ACT_MISH;
-#if CS_PRIO == 1
+// "Leapfrog" priorities: a wave lowers its s_setprio level as it moves through the segments of a barrier interval, so the wave of a
+// SIMD that is BEHIND outranks its partner (the hardware's own tie-break is age: the older wave of a SIMD runs unimpeded and the
+// younger one gets the leftover VALU / transcendental slots, then finishes alone at a single wave's issue rate).  Rejected: waves
+// 4..7 at priority 1 throughout, the mirror image (LABNOTES.md section 4.1b, round 4).
 #define CS_SEG(K) do { __builtin_amdgcn_sched_barrier(0); __builtin_amdgcn_s_setprio(K); __builtin_amdgcn_sched_barrier(0); } while (0)
-#else
-#define CS_SEG(K)
-#endif
 
 // ---- LDS map (bytes).  Weight fragments are "fragment ordered" (pack_frag16, conv_igemm.hip):[(kstep*NREP + j)*64 + lane][8].
 constexpr int CS_W3 = 0;                        // 64 x 64      : 2 k-steps x 4 fragments x 1 KB
@@ -131,7 +99,7 @@ __device__ __forceinline__ void cs_act_pack(const f32x4 (&acc)[NREP], const floa
     float v[NREP * 4];
 #pragma unroll
     for (int j = 0; j < NREP; ++j)
-        bn_act4<true, CS_ACT>(acc[j], sc + j * 4, sh + j * 4, v + j * 4);
+        bn_act4<true, Y4_ACT_MISH>(acc[j], sc + j * 4, sh + j * 4, v + j * 4);
 #pragma unroll
     for (int c = 0; c < NREP / 2; ++c) Elem<DT>::store_chunk(&out[c], v + c * 8);
 }
@@ -163,8 +131,9 @@ __global__ __launch_bounds__(64 * CS_WAVES, 1) void csp_stage_kernel(const CspSt
     const __amdgpu_buffer_rsrc_t rs_in = make_rsrc(p.in, p.in_bytes);
     // halo'd tile of x -> X1: one wave-wide piece = 8 rows x 128 B; LDS-DMA writes lane-linearly, so the XOR swizzle of
     // the 16-byte chunk index is applied to the SOURCE address
-#if CS_LX
-    // per piece k of this wave (u = wave + 8k): byte offset of the lane's 16 bytes relative to halo pixel (0, 0) of the tile, with
+    // The per-lane offsets and border flags are computed once per workgroup, not once per tile (30 VALU + integer divisions per
+    // piece and tile: LABNOTES.md section 4.1b, round 4).
+    // Per piece k of this wave (u = wave + 8k): byte offset of the lane's 16 bytes relative to halo pixel (0, 0) of the tile, with
     // the lane's border flags in the four low bits (always zero in an offset): 1 = halo row 0, 2 = halo row 17, 4 = halo column 0,
     // 8 = halo column 17.  Rows past the 324 halo pixels get every flag and are always out of range.
     constexpr int CS_NPIECE = (CS_HROWS / 8 + CS_WAVES - 1) / CS_WAVES;
@@ -189,26 +158,11 @@ __global__ __launch_bounds__(64 * CS_WAVES, 1) void csp_stage_kernel(const CspSt
             buffer_load16_lds(rs_in, X1 + __builtin_amdgcn_readfirstlane(u * 1024), off, 0);
         }
     };
-#else
-    auto load_x = [&](int tile) {
-        const int n = tile / p.tiles_per_img, rem = tile - n * p.tiles_per_img;
-        const int ty = rem / p.tiles_x, tx = rem - ty * p.tiles_x;
-        const int y0 = ty * CS_T - 1, x0 = tx * CS_T - 1;
-        for (int u = wave; u < CS_HROWS / 8; u += CS_WAVES) {
-            const int hp = u * 8 + (lane >> 3);
-            const int hy = hp / CS_H, hx = hp - hy * CS_H;
-            const int gy = y0 + hy, gx = x0 + hx;
-            const bool ok = hp < CS_H * CS_H && (unsigned)gy < (unsigned)p.H && (unsigned)gx < (unsigned)p.W;
-            const int off = (((n * p.H + gy) * p.W + gx) * p.in_cstride + p.in_coff + (((lane & 7) ^ (hp & 7)) * 8)) * 2;
-            buffer_load16_lds(rs_in, X1 + __builtin_amdgcn_readfirstlane(u * 1024), ok ? off : (int)0x80000000, 0);
-        }
-    };
-#endif
     if (t < t_hi) load_x(t);
 
     // ---- per-wave fragment geometry (tile independent)
     // main fragments: inner rows iy = 2*wave + i -> halo'd row iy + 1, halo'd columns 1..16
-    // extra fragment (waves 0..4): the halo ring -- row 0, row 17, and the two halo columns as 36 pixels in 3 fragments
+    // extra fragments (waves 0..3): the halo ring -- row 0, row 17, and the two halo columns as 36 pixels in 3 fragments
     int xr_main[2];
 #pragma unroll
     for (int i = 0; i < 2; ++i) xr_main[i] = (2 * wave + i + 1) * CS_H + 1 + q;
@@ -220,16 +174,10 @@ __global__ __launch_bounds__(64 * CS_WAVES, 1) void csp_stage_kernel(const CspSt
             hy = pp >> 1; hx = (pp & 1) * (CS_H - 1);
         }
     };
-#if CS_EXTRA
-    // the older half of the workgroup (waves 0..3: they win every VALU arbitration on their SIMD) takes all five; wave 0 takes two
+    // the older half of the workgroup (waves 0..3: they win every VALU arbitration on their SIMD) takes all five, wave 0 takes two
+    // -- not one each on waves 0..4: the younger wave of a SIMD is its critical path (LABNOTES.md section 4.1b, round 4)
     const int n_extra = wave == 0 ? 2 : wave < 4 ? 1 : 0;
-#else
-    const int n_extra = wave < 5 ? 1 : 0;
-#endif
 
-#if CS_PRIO == 2
-    if (wave >= 4) __builtin_amdgcn_s_setprio(1);
-#endif
     bool first_tile = true;
 #ifdef CS_TRACE
     int tr_i = 0;
@@ -241,13 +189,15 @@ __global__ __launch_bounds__(64 * CS_WAVES, 1) void csp_stage_kernel(const CspSt
 #ifdef CS_TRACE
         const bool tr_on = blockIdx.x == CS_TR_WG && tr_i >= CS_TR_T0 && tr_i < CS_TR_T0 + 4;
 #endif
-        CS_POINT(0);                       // arrives at the tile barrier
+        PHASE_POINT(0);                       // arrives at the tile barrier
         // X1 (and, the first time, the weights) have landed for every wave; every wave is done with the previous tile's
-        // T4.  The previous tile's 4 output stores of this wave may still be in flight (they were issued after the DMA).
+        // T4.  The tile boundary drains everything, the previous tile's 4 output stores of this wave included: leaving them in
+        // flight would rely on stores and LDS-DMA loads retiring in issue order relative to each other (LABNOTES.md section 4.1b).
+        // (two branches with the same wait: collapsing them changes the device listing -- profiles/isa/README.md)
         if (first_tile) wait_vmcnt_then_barrier<0>();
-        else wait_vmcnt_then_barrier<CS_VMCNT>();
+        else wait_vmcnt_then_barrier<0>();
         first_tile = false;
-        CS_POINT(1);                       // tile landed, barrier passed
+        PHASE_POINT(1);                       // tile landed, barrier passed
         CS_SEG(3);
 
         // ================= phase A: conv3 -> conv4 -> T4 on the halo'd tile; conv2 on the inner rows
@@ -277,7 +227,7 @@ __global__ __launch_bounds__(64 * CS_WAVES, 1) void csp_stage_kernel(const CspSt
                         Mma<DT>::run(a2[i][j], w2[j], xf[i]);
                     }
             }
-            CS_POINT(2);                   // conv3 + conv2 MFMAs of the main fragments issued
+            PHASE_POINT(2);                   // conv3 + conv2 MFMAs of the main fragments issued
 #pragma unroll
             for (int i = 0; i < 2; ++i) cs_act_pack<DT, 4>(a3[i], sc3, sh3, R3[i]);
             {
@@ -286,7 +236,7 @@ __global__ __launch_bounds__(64 * CS_WAVES, 1) void csp_stage_kernel(const CspSt
 #pragma unroll
                 for (int i = 0; i < 2; ++i) cs_act_pack<DT, 4>(a2[i], sc2, sh2, C2[i]);
             }
-            CS_POINT(3);                   // their Mish
+            PHASE_POINT(3);                   // their Mish
             CS_SEG(2);
             // conv4 (64 -> 32) from registers, masked to zero outside the image, -> T4
             auto conv4_to_t4 = [&](const u32x4* x3, int xr, int hy, int hx) {
@@ -308,7 +258,7 @@ __global__ __launch_bounds__(64 * CS_WAVES, 1) void csp_stage_kernel(const CspSt
             // conv3 -> conv4 of the halo-ring fragment(s)
             for (int ex = 0; ex < n_extra; ++ex) {
                 int ex_hy, ex_hx;
-                ring_geom(CS_EXTRA && ex == 1 ? 4 : wave, ex_hy, ex_hx);
+                ring_geom(ex == 1 ? 4 : wave, ex_hy, ex_hx);
                 const int xr_extra = ex_hy * CS_H + ex_hx;
                 u32x4 X3e[2];
                 f32x4 a3e[4];
@@ -325,18 +275,18 @@ __global__ __launch_bounds__(64 * CS_WAVES, 1) void csp_stage_kernel(const CspSt
                 cs_act_pack<DT, 4>(a3e, sc3, sh3, X3e);
                 conv4_to_t4(X3e, xr_extra, ex_hy, ex_hx);
             }
-            CS_POINT(4);                   // halo-ring conv3 -> conv4
+            PHASE_POINT(4);                   // halo-ring conv3 -> conv4
             CS_SEG(1);
 #pragma unroll
             for (int i = 0; i < 2; ++i) conv4_to_t4(R3[i], xr_main[i], 2 * wave + i + 1, 1 + q);
         }
-        CS_POINT(5);                       // conv4 + Mish + T4 writes
+        PHASE_POINT(5);                       // conv4 + Mish + T4 writes
         // T4 complete for every wave; X1 is free: start the next tile's DMA under phases C..E
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-        CS_POINT(6);                       // mid barrier passed
+        PHASE_POINT(6);                       // mid barrier passed
         CS_SEG(3);
-        if (CS_ABL != 3 && t + nb_x < t_hi) load_x(t + nb_x);
-        CS_POINT(7);                       // next tile's DMA issued
+        if (t + nb_x < t_hi) load_x(t + nb_x);
+        PHASE_POINT(7);                       // next tile's DMA issued
 
         // ================= phase C: conv5 (3x3 over T4) + Add -> conv6 -> conv7 over [conv6 | route] -> HBM
         {
@@ -360,7 +310,7 @@ __global__ __launch_bounds__(64 * CS_WAVES, 1) void csp_stage_kernel(const CspSt
 #pragma unroll
                     for (int j = 0; j < 4; ++j) Mma<DT>::run(a5[i][j], w5[j], xf[i]);
             }
-            CS_POINT(8);                   // conv5 MFMAs issued
+            PHASE_POINT(8);                   // conv5 MFMAs issued
             u32x4 X5[2][2];
             {
                 float sc5[16], sh5[16];
@@ -370,7 +320,7 @@ __global__ __launch_bounds__(64 * CS_WAVES, 1) void csp_stage_kernel(const CspSt
                     float v[16];
 #pragma unroll
                     for (int j = 0; j < 4; ++j)
-                        bn_act4<true, CS_ACT>(a5[i][j], sc5 + j * 4, sh5 + j * 4, v + j * 4);
+                        bn_act4<true, Y4_ACT_MISH>(a5[i][j], sc5 + j * 4, sh5 + j * 4, v + j * 4);
 #pragma unroll
                     for (int c = 0; c < 2; ++c) {                  // residual Add (custom_layers.py:44), after the activation
                         float rv[8];
@@ -382,7 +332,7 @@ __global__ __launch_bounds__(64 * CS_WAVES, 1) void csp_stage_kernel(const CspSt
                     for (int c = 0; c < 2; ++c) E::store_chunk(&X5[i][c], v + c * 8);
                 }
             }
-            CS_POINT(9);                   // conv5 Mish + Add
+            PHASE_POINT(9);                   // conv5 Mish + Add
             CS_SEG(2);
             // conv6: 64 -> 64 from registers
             u32x4 Y6[2][2];
@@ -406,7 +356,7 @@ __global__ __launch_bounds__(64 * CS_WAVES, 1) void csp_stage_kernel(const CspSt
 #pragma unroll
                 for (int i = 0; i < 2; ++i) cs_act_pack<DT, 4>(a6[i], sc6, sh6, Y6[i]);
             }
-            CS_POINT(10);                  // conv6 + Mish
+            PHASE_POINT(10);                  // conv6 + Mish
             CS_SEG(1);
             // conv7: Concatenate([conv6, route]) (128) -> 64, then out
             {
@@ -424,7 +374,7 @@ __global__ __launch_bounds__(64 * CS_WAVES, 1) void csp_stage_kernel(const CspSt
 #pragma unroll
                         for (int j = 0; j < 4; ++j) Mma<DT>::run(a7[i][j], w7[j], s < 2 ? Y6[i][s] : C2[i][s - 2]);
                 }
-                CS_POINT(11);              // conv7 MFMAs issued
+                PHASE_POINT(11);              // conv7 MFMAs issued
                 float sc7[16], sh7[16];
                 cs_affine<2>(aff + CS_A7, 64, g, sc7, sh7);
 #pragma unroll
@@ -434,12 +384,11 @@ __global__ __launch_bounds__(64 * CS_WAVES, 1) void csp_stage_kernel(const CspSt
                     const int64_t pix = ((int64_t)n * p.H + ty * CS_T + 2 * wave + i) * p.W + tx * CS_T + q;
                     T* op = (T*)p.out + pix * p.out_cstride + p.out_coff;
 #pragma unroll
-                    for (int c = 0; c < 2; ++c)
-                        if (CS_ABL != 2 || Z[c][0] == 0x12345678u) *(u32x4*)(op + chunk_channel(0, c, g)) = Z[c];
+                    for (int c = 0; c < 2; ++c) *(u32x4*)(op + chunk_channel(0, c, g)) = Z[c];
                 }
             }
         }
-        CS_POINT(12);                      // conv7 Mish + stores issued
+        PHASE_POINT(12);                      // conv7 Mish + stores issued
 #ifdef CS_TRACE
         if (tr_on && lane == 0) {
 #pragma unroll
@@ -450,13 +399,7 @@ __global__ __launch_bounds__(64 * CS_WAVES, 1) void csp_stage_kernel(const CspSt
     }
 }
 
-#ifdef CS_TRACE
-}  // namespace y4
-extern "C" int y4_cs_trace_read(unsigned long long* dst) {
-    return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(y4::cs_trace_buf), sizeof(unsigned long long) * 4 * 8 * 16);
-}
-namespace y4 {
-#endif
+PHASE_TRACE_READER(y4_cs_trace_read, cs_trace_buf)
 
 // ------------------------------------------------------------------------------------------------ launch
 bool csp_stage_supported(int dtype, int h, int w) {

@@ -18,51 +18,18 @@
 
 #include "conv_chain.h"
 
-// experiment switches (scripts/build_variant.sh), a bit mask: 1 no 1x1 phase, 2 LeakyReLU instead of Mish, 4 the 3x3 weights
-// are not streamed, 8 the x tile is loaded once, 16 no output stores, 32 no fragment reads in the 3x3 loop, 64 no barriers
-// in the 3x3 loop (racy: timing only)
-#ifndef RB_ABL
-#define RB_ABL 0
-#endif
-#ifndef RB_RES_LDS
-// 1 (2: also C = 64, where it spills at the 128-register cap): the residual is read from the x tile in LDS (a barrier in front of the
-// 1x1 phase, which overwrites the tile in place) instead of a second time from memory.  Same bytes; measured NEUTRAL (r4): the loop's
-// tail gets 1.4 k cycles shorter per tile, but the next tile's x pieces then block their issuers for 5.4 - 9.8 k cycles instead of
-// 2.5 - 4.8 k -- the residual's loads had been evicting the previous epilogue's dirty output lines from L2 under the loop, which the x
-// fills now have to wait for (write-through stores, RB_ST_AUX=17, bring the 2.9 - 5.8 k back; tile 46.3 k cycles against 45.9 k).
-#define RB_RES_LDS 0
-#endif
-#ifndef RB_ST_AUX
-// cache policy bits of the output stores (1 sc0, 2 nt, 16 sc1); 0: write-back.  nt: tile 49.4 k cycles, write-through 46.3 k (see above)
-#define RB_ST_AUX 0
-#endif
-#ifndef RB_LATE
-// 1: the residual's loads are issued four stream steps before the end of the 3x3 loop instead of in front of it (they are needed in
-// the epilogue only), and stream step 3 -- whose ring slot is free from the start -- with steps 0..2 at the tile hand-over instead of
-// behind the mid barrier.  In-kernel trace: the stretch between the mid barrier and the loop was 1.9 k cycles for the older wave of a
-// SIMD and 4.1 k for the younger one (its loads queue behind the partner's), on the tile's critical path.  Bit-identical.
-#define RB_LATE 1
-#endif
+#include "phase_trace.h"
 
 namespace y4 {
 
 #ifdef RB_TRACE
-// In-kernel phase trace (kernel experiments only; scripts/res_trace.py): workgroup RB_TR_WG of the FULL-tile launch records s_memtime
-// per wave at fixed points of its tiles RB_TR_T0 .. +2 into rb_trace_buf[tile][wave][point]; y4_rb_trace_read() copies it out.
+// In-kernel phase trace (kernel experiments only; scripts/phase_trace.py resblock): workgroup RB_TR_WG of the FULL-tile launch records
+// s_memtime per wave at fixed points of its tiles RB_TR_T0 .. +2 into rb_trace_buf[tile][wave][point]; y4_rb_trace_read() copies it out.
 __device__ unsigned long long rb_trace_buf[3 * 8 * 16];
 #define RB_TR_WG 8
 #define RB_TR_T0 1
-#define RB_POINT(P)                                                                                         \
-    do {                                                                                                    \
-        __builtin_amdgcn_sched_barrier(0);                                                                  \
-        if (tr_on) asm volatile("s_memtime %0" : "=s"(tr_t[P]));                                            \
-        __builtin_amdgcn_sched_barrier(0);                                                                  \
-    } while (0)
-#else
-#define RB_POINT(P)
 #endif
 
-constexpr int RB_ACT = (RB_ABL & 2) ? Y4_ACT_LEAKY : Y4_ACT_MISH;
 constexpr int RB_T = 16, RB_H = RB_T + 2, RB_WAVES = 8;
 
 // TY = output rows of a workgroup's tile: 16 (the full 16x16 tile), or 8 / 4 -- a HALF / QUARTER tile (the same 16 columns): the
@@ -186,15 +153,14 @@ __global__ __launch_bounds__(64 * RB_WAVES, C == 64 ? 4 : 2) void resblock_kerne
             const int u = wave + k * RB_WAVES;
             if (u < G::XT_PIECES) {                                         // (wave-uniform; false for some waves' last piece only)
                 const bool ok = ch < CPR && hy < G::HR && (unsigned)(y0 + hy) < (unsigned)p.H && (unsigned)(x0 + hx) < (unsigned)p.W;
-                const int off_x = (RB_ABL & 128) ? (off & ~63) + (lane & 3) * 16 : off;      // (timing experiment: 64-byte aligned quads, wrong data)
-                buffer_load16_lds(rs_in, XT + __builtin_amdgcn_readfirstlane(u * 1024), ok ? off_x : (int)0x80000000, 0);
+                buffer_load16_lds(rs_in, XT + __builtin_amdgcn_readfirstlane(u * 1024), ok ? off : (int)0x80000000, 0);
             }
             ch += DCH; hx += DHX; hy += DHY; off += d_off;
             if (ch >= SPR) { ch -= SPR; hx += 1; off += c_ch; }
             if (hx >= RB_H) { hx -= RB_H; hy += 1; off += c_hx; }
         }
     };
-    if (t < t_hi) { load_x(t); stage_w(0); stage_w(1); stage_w(2); if (RB_LATE) stage_w(3); }
+    if (t < t_hi) { load_x(t); stage_w(0); stage_w(1); stage_w(2); stage_w(3); }
 
 #ifdef RB_TRACE
     int tr_i = 0;
@@ -206,21 +172,13 @@ __global__ __launch_bounds__(64 * RB_WAVES, C == 64 ? 4 : 2) void resblock_kerne
 #ifdef RB_TRACE
         const bool tr_on = TY == RB_T && C == RB_TRACE && blockIdx.x == RB_TR_WG && tr_i >= RB_TR_T0 && tr_i < RB_TR_T0 + 3;
 #endif
-        RB_POINT(0);                           // arrives at the tile barrier
-        wait_vmcnt_then_barrier<0>();          // x tile and stream steps 0..2 landed; all waves left the previous tile
-        RB_POINT(1);                           // barrier passed
+        PHASE_POINT(0);                           // arrives at the tile barrier
+        wait_vmcnt_then_barrier<0>();          // x tile and stream steps 0..3 landed; all waves left the previous tile
+        PHASE_POINT(1);                           // barrier passed
 
-        u32x4 res[MREP][2];                    // residual = x at this lane's output pixels / channels
-        constexpr bool RES_LDS = RB_RES_LDS && (C == 128 || RB_RES_LDS > 1);       // (C = 64: at the 128-register cap it would spill)
-        if (RES_LDS) {
-#pragma unroll
-            for (int i = 0; i < MREP; ++i)
-#pragma unroll
-                for (int c = 0; c < 2; ++c)
-                    res[i][c] = *(const u32x4*)(XT + ((wm * MREP + i + 1) * RB_H + q + 1) * ROWB + chunk_channel(wn * 64, c, g) * 2);
-            // every wave has its residual before any wave's 1x1 phase overwrites the tile
-            asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-        }
+        // residual = x at this lane's output pixels / channels: read a second time from memory under the 3x3 loop, not from the x tile
+        // in LDS in front of the 1x1 phase (same bytes, one more barrier; measured neutral: LABNOTES.md section 4.1c)
+        u32x4 res[MREP][2];
 
         // ================= phase A: t = Mish(BN(conv1x1(x))) on the halo'd tile, IN PLACE; zero outside the image.
         // 21 pixel fragments (18 rows + 3 fragments holding the two halo columns); a wave takes fragments wave, wave+8,
@@ -270,8 +228,8 @@ __global__ __launch_bounds__(64 * RB_WAVES, C == 64 ? 4 : 2) void resblock_kerne
 #pragma unroll
                 for (int k = 0; k < NFR; ++k) {
                     float v[8];
-                    bn_act4<true, RB_ACT>(acc[k][2 * c], sc, sh, v);
-                    bn_act4<true, RB_ACT>(acc[k][2 * c + 1], sc + 4, sh + 4, v + 4);
+                    bn_act4<true, Y4_ACT_MISH>(acc[k][2 * c], sc, sh, v);
+                    bn_act4<true, Y4_ACT_MISH>(acc[k][2 * c + 1], sc + 4, sh + 4, v + 4);
                     u32x4 pk;
                     E::store_chunk(&pk, v);
                     if (!inside[k]) pk = u32x4{0u, 0u, 0u, 0u};
@@ -279,14 +237,13 @@ __global__ __launch_bounds__(64 * RB_WAVES, C == 64 ? 4 : 2) void resblock_kerne
                 }
             }
         };
-        if (!(RB_ABL & 1)) {                   // NFA fragments over 8 waves: fragments wave, wave + 8, wave + 16 (wave-uniform counts)
-            if (wave + 2 * RB_WAVES < G::NFA) phase_a(std::integral_constant<int, 3>{});
-            else if (wave + RB_WAVES < G::NFA) phase_a(std::integral_constant<int, 2>{});
-            else if (wave < G::NFA) phase_a(std::integral_constant<int, 1>{});
-        }
-        RB_POINT(2);                           // 1x1 phase done (MFMAs, Mish, in-place stores issued)
+        // NFA fragments over 8 waves: fragments wave, wave + 8, wave + 16 (wave-uniform counts)
+        if (wave + 2 * RB_WAVES < G::NFA) phase_a(std::integral_constant<int, 3>{});
+        else if (wave + RB_WAVES < G::NFA) phase_a(std::integral_constant<int, 2>{});
+        else if (wave < G::NFA) phase_a(std::integral_constant<int, 1>{});
+        PHASE_POINT(2);                           // 1x1 phase done (MFMAs, Mish, in-place stores issued)
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-        RB_POINT(3);                           // mid barrier passed
+        PHASE_POINT(3);                           // mid barrier passed
 
         // ================= phase C: y = x + Mish(BN(conv3x3(t))): 9 taps x C/64 stream steps, weights through the ring.
         // Software pipelined at MFMA k-step (32-channel) granularity: the fragments of half-step h+1 are read from LDS
@@ -310,22 +267,23 @@ __global__ __launch_bounds__(64 * RB_WAVES, C == 64 ? 4 : 2) void resblock_kerne
                     for (int c = 0; c < 2; ++c) res[i][c] = buffer_load16(rs_in, o + chunk_channel(wn * 64, c, g) * 2);
                 }
             };
-            if (!RB_LATE && !RES_LDS) load_res();
-            // RB_LATE: the 2 MREP residual loads go out at the top of stream step S0 and stay in flight beside the stream's own loads:
-            // a wave's loads retire in order, so the counted waits of steps S0 .. S0 + 2 allow that many more outstanding
-            constexpr int S0 = G::NSTEPS - 4, RES_LOADS = RES_LDS ? 0 : 2 * MREP;
+            // The residual is needed in the epilogue only: its 2 MREP loads go out at the top of stream step S0, four steps before the
+            // end of the loop instead of in front of it, and stay in flight beside the stream's own loads: a wave's loads retire in
+            // order, so the counted waits of steps S0 .. S0 + 2 allow that many more outstanding.  Likewise stream step 3, whose ring
+            // slot is free from the start, is issued with steps 0..2 at the tile hand-over instead of behind the mid barrier (that
+            // stretch was on the tile's critical path: LABNOTES.md section 4.1c, "Late round 4").
+            constexpr int S0 = G::NSTEPS - 4, RES_LOADS = 2 * MREP;
             f32x4 acc[MREP][4];
 #pragma unroll
             for (int i = 0; i < MREP; ++i)
 #pragma unroll
                 for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-            // stream steps up to P+3 (4 slots: slot 3 is unused so far, slots < P held the 1x1 weights)
+            // stream steps 4 .. P+3 (their slots < P held the 1x1 weights)
 #pragma unroll
-            for (int st = RB_LATE ? 4 : 3; st <= G::P + 3; ++st) stage_w(st);
+            for (int st = 4; st <= G::P + 3; ++st) stage_w(st);
             const char* const xbase = XT + ((wm * MREP) * RB_H + q) * ROWB + g * 16;       // fragment 0, tap (0, 0), chunk g
             u32x4 xf[2][MREP], wf[2][4];
             auto read_frags = [&](int buf, int st, int kk) {              // all arguments are compile-time after unrolling
-                if ((RB_ABL & 32) && st > G::P) return;
                 const int ks = st - G::P;
                 const int cb = ks / 9, tap = ks - cb * 9;                  // tap `tap` of 64-channel block `cb`: the canonical K order (common.h)
                 const int ky = tap / 3, kx = tap - ky * 3;
@@ -344,13 +302,13 @@ __global__ __launch_bounds__(64 * RB_WAVES, C == 64 ? 4 : 2) void resblock_kerne
                     for (int j = 0; j < 4; ++j)
                         Mma<DT>::run(acc[i][j], wf[buf][j], xf[buf][i]);
             };
-            RB_POINT(4);                           // residual loads + stream steps issued
+            PHASE_POINT(4);                           // residual loads + stream steps issued
             read_frags(0, G::P, 0);                                        // step P landed at the top of the tile
 #pragma unroll
             for (int st = G::P; st < G::NSTEPS; ++st) {
-                if (st == G::P + 3 * G::P) RB_POINT(5);                    // a third of the stream done
-                if (st == G::P + 6 * G::P) RB_POINT(6);                    // two thirds
-                if (RB_LATE && !RES_LDS && st == S0) load_res();
+                if (st == G::P + 3 * G::P) PHASE_POINT(5);                    // a third of the stream done
+                if (st == G::P + 6 * G::P) PHASE_POINT(6);                    // two thirds
+                if (st == S0) load_res();
                 // sched_barrier: hipcc otherwise re-serialises the pipeline into "read one fragment, wait for it, 4 MFMAs"
                 // (fewer live registers, but every wait exposes the LDS latency); pinned, the 8-12 reads of the next
                 // half-step are all in flight while the 4*MREP MFMAs of this one issue
@@ -366,33 +324,30 @@ __global__ __launch_bounds__(64 * RB_WAVES, C == 64 ? 4 : 2) void resblock_kerne
                     constexpr int LAST = G::NSTEPS - 1;
                     const int younger = (st + 3 < LAST ? st + 3 : LAST) - (st + 1);
                     // (st is a compile-time constant after unrolling: one of the variants survives)
-                    const int extra = RB_LATE && st >= S0 && st <= S0 + 2 ? RES_LOADS : 0;
+                    const int extra = st >= S0 && st <= S0 + 2 ? RES_LOADS : 0;
                     static_assert(S0 > G::P && 2 * G::PPW + RES_LOADS < 64, "window of the residual's loads");
-                    if (RB_ABL & 64) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // (timing experiment: no barrier)
-                    else wait_vmcnt_lgkm_then_barrier_n<2 * G::PPW + RES_LOADS>(younger == 0 ? 0 : (younger >= 2 ? 2 : 1) * G::PPW + extra);
-                    if (!(RB_ABL & 4) && st + 4 < G::NSTEPS) stage_w(st + 4);
+                    wait_vmcnt_lgkm_then_barrier_n<2 * G::PPW + RES_LOADS>(younger == 0 ? 0 : (younger >= 2 ? 2 : 1) * G::PPW + extra);
+                    if (st + 4 < G::NSTEPS) stage_w(st + 4);
                     read_frags(0, st + 1, 0);
                     __builtin_amdgcn_sched_barrier(0);
                 }
                 mma(1);
                 __builtin_amdgcn_sched_barrier(0);
             }
-            RB_POINT(7);                           // all taps done
+            PHASE_POINT(7);                           // all taps done
             // every wave is done with the tile and the ring: bring in the next tile under this tile's epilogue
             asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-            RB_POINT(8);                           // end barrier passed
-            if constexpr (RB_LATE && !RES_LDS) {
+            PHASE_POINT(8);                           // end barrier passed
             // The residual has landed (the loop's last counted wait was vmcnt(0)), but the compiler does not know: its own wait in
             // front of the first use would sit behind the next tile's loads issued below and, counted conservatively, hold the
             // epilogue until most of THOSE have landed too.  Using the registers here puts that wait where it costs nothing.
 #pragma unroll
-                for (int i = 0; i < MREP; ++i)
+            for (int i = 0; i < MREP; ++i)
 #pragma unroll
-                    for (int c = 0; c < 2; ++c) asm volatile("" : "+v"(res[i][c]));
-            }
+                for (int c = 0; c < 2; ++c) asm volatile("" : "+v"(res[i][c]));
             const bool more = t + nb_x < t_hi;
-            if (more) { if (!(RB_ABL & 8)) load_x(t + nb_x); stage_w(0); stage_w(1); stage_w(2); if (RB_LATE) stage_w(3); }
-            RB_POINT(9);                           // next tile's loads issued
+            if (more) { load_x(t + nb_x); stage_w(0); stage_w(1); stage_w(2); stage_w(3); }
+            PHASE_POINT(9);                           // next tile's loads issued
             float sc3[16], sh3[16];
 #pragma unroll
             for (int c = 0; c < 2; ++c)
@@ -407,7 +362,7 @@ __global__ __launch_bounds__(64 * RB_WAVES, C == 64 ? 4 : 2) void resblock_kerne
             for (int i = 0; i < MREP; ++i) {
                 float v[16];
 #pragma unroll
-                for (int j = 0; j < 4; ++j) bn_act4<true, RB_ACT>(acc[i][j], sc3 + j * 4, sh3 + j * 4, v + j * 4);
+                for (int j = 0; j < 4; ++j) bn_act4<true, Y4_ACT_MISH>(acc[i][j], sc3 + j * 4, sh3 + j * 4, v + j * 4);
                 const int o = pix[i] < 0 ? (int)0x80000000 : (pix[i] * p.out_cstride + p.out_coff) * 2;
 #pragma unroll
                 for (int c = 0; c < 2; ++c) {
@@ -417,11 +372,12 @@ __global__ __launch_bounds__(64 * RB_WAVES, C == 64 ? 4 : 2) void resblock_kerne
                     for (int e = 0; e < 8; ++e) v[c * 8 + e] += rv[e];      // residual Add (custom_layers.py:44), after the activation
                     u32x4 pk;
                     E::store_chunk(&pk, v + c * 8);
-                    if (!(RB_ABL & 16) || pk[0] == 0x12345678u) buffer_store16<RB_ST_AUX>(rs_out, pk, o + chunk_channel(wn * 64, c, g) * 2);
+                    // write-back stores; nt / write-through cache policy bits were slower or neutral (LABNOTES.md section 4.1c)
+                    buffer_store16<0>(rs_out, pk, o + chunk_channel(wn * 64, c, g) * 2);
                 }
             }
         }
-        RB_POINT(10);                          // epilogue done, stores issued
+        PHASE_POINT(10);                          // epilogue done, stores issued
 #ifdef RB_TRACE
         if (tr_on && lane == 0) {
 #pragma unroll
@@ -432,13 +388,7 @@ __global__ __launch_bounds__(64 * RB_WAVES, C == 64 ? 4 : 2) void resblock_kerne
     }
 }
 
-#ifdef RB_TRACE
-}  // namespace y4
-extern "C" int y4_rb_trace_read(unsigned long long* dst) {
-    return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(y4::rb_trace_buf), sizeof(unsigned long long) * 3 * 8 * 16);
-}
-namespace y4 {
-#endif
+PHASE_TRACE_READER(y4_rb_trace_read, rb_trace_buf)
 
 // ------------------------------------------------------------------------------------------------ launch
 bool resblock_supported(int dtype, int c) { return dtype != Y4_F32 && (c == 128 || c == 64); }

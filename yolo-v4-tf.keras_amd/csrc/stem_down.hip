@@ -15,6 +15,7 @@
 // even and odd columns into planes turns the stride-2 tap walk into unit-stride slot reads (conflict-free with the
 // usual XOR swizzle), and slot 0 of the odd plane is the zero column left of the image.
 #include "conv_common.h"
+#include "phase_trace.h"
 #include "stem_common.h"
 
 namespace y4 {
@@ -33,58 +34,30 @@ struct StemDownK {
     unsigned w1_bytes;
 };
 
-#ifndef SD_W8
-// Experiment switch, measured SLOWER and off: 1 = EIGHT waves (4 pixel rows x 2 channel halves) with conv 1's weights in REGISTERS
-// (72 per wave; a 512-thread workgroup may use 256) instead of sixteen waves that re-read their 18 weight fragments from LDS for
-// every output row -- the conv phase is bound by its LDS reads (720 ds_read_b128 per row = 5.8 k of its ~7 k cycles, in-kernel
-// trace), and this halves them.  Result (same box, 608^2 batch 32): 321 us against 289-291; 416^2 batch 64 fp16: 317 against 257.
-// With two waves per SIMD the stem phase takes 7-8 k cycles instead of 2.3-4.5 k: a wave issues one VALU instruction per ~9
-// cycles at most, so two waves cannot fill the vector pipe through their own stalls, and the conv phase (5.4-6.7 k) gains nothing
-// because the MFMAs of ten waves' worth of fragments now queue behind two waves' issue.  Bit-identical either way.
-#define SD_W8 0
-#endif
-constexpr int SD_WAVES = SD_W8 ? 8 : 16, SD_WM = SD_W8 ? 4 : 8, SD_WN = 2;      // the block is alone on its CU (LDS), so it
-                                                                                // brings its own latency hiding
-constexpr int SD_LDS_W = SD_W8 ? 0 : 9 * 64 * 64;       // conv 1's weights in LDS: [9 taps][64 rows][64 B] (sixteen-wave form only)
-constexpr int SD_UNROLL = 4;                            // stem tiles whose gathers are in flight together
-#ifndef SD_PRELOAD
-// 1: on a "regular" output row (two new conv-0 rows, every patch inside the image) a wave's first SD_PRE stem tiles are loaded
-// into registers one output row AHEAD -- issued before the previous row's conv phase, which hides their round trip -- and its
-// remaining tiles are requested first thing in the stem phase, so that they land while the preloaded ones are converted,
-// multiplied and stored.  Before, every wave of the workgroup started a row by waiting for its own loads (the stem phase of a
-// row was 40 % idle: in-kernel trace, LABNOTES.md section 4.2a).  Same values through the same MFMAs: bit-identical.
-#define SD_PRELOAD 1
-#endif
-#ifndef SD_TAPBAR
-#define SD_TAPBAR 1
-#endif
-#ifndef SD_PRE_TILES
-#define SD_PRE_TILES 1
-#endif
-// (measured, same box, 608^2 batch 32, us per launch: no preload 302 | 3 tiles 268 | 2 tiles 259-262, 241 | 1 tile 234.5 against 241: what
-//  pays is that NO wave starts its stem phase by waiting -- one tile is there, the other four are requested at once and land while
-//  it is converted and multiplied -- and more tiles held across the conv phase only cost that phase registers)
-constexpr int SD_PRE = SD_PRE_TILES;                    // preloaded stem tiles per wave (8 registers each across the conv phase)
+// Sixteen waves (8 pixel rows x 2 channel halves) that re-read their 18 weight fragments from LDS for every output row: the block is
+// alone on its CU (LDS), so it brings its own latency hiding.  Rejected: eight waves with conv 1's weights in registers, which halves
+// the conv phase's LDS reads but was 10-25 % slower -- two waves per SIMD cannot fill the vector pipe through their own stalls in the
+// stem phase (LABNOTES.md section 4.2a, round 4).
+constexpr int SD_WAVES = 16, SD_WM = 8, SD_WN = 2;
+constexpr int SD_LDS_W = 9 * 64 * 64;                   // conv 1's weights in LDS: [9 taps][64 rows][64 B]
+// On a "regular" output row (two new conv-0 rows, every patch inside the image) a wave's first SD_PRE stem tiles are loaded into
+// registers one output row AHEAD -- issued before the previous row's conv phase, which hides their round trip -- and its remaining
+// tiles are requested first thing in the stem phase, so that they land while the preloaded ones are converted, multiplied and
+// stored: no wave starts its stem phase by waiting.  One tile, not two or three: more tiles held across the conv phase only cost
+// that phase registers (LABNOTES.md section 4.2a, round 4).  Same values through the same MFMAs: bit-identical.
+constexpr int SD_PRE = 1;                               // preloaded stem tiles per wave (8 registers each across the conv phase)
 // the generic stem loop then serves only the rows that are NOT regular (the first row of a band or image, the last of an image:
 // ~2 % of the rows): two tiles in flight instead of four keep its register peak below what the preloaded tiles leave free
-constexpr int SD_GEN_UNROLL = SD_PRELOAD ? 2 : SD_UNROLL;
+constexpr int SD_GEN_UNROLL = 2;
 
 static __device__ __forceinline__ int sd_swz(int row) { return (row >> 1) & 3; }
 
 #ifdef SD_TRACE
-// In-kernel phase trace (kernel experiments only; scripts/stem_trace.py): workgroup SD_TR_WG records s_memtime per wave at fixed
-// points of its output rows SD_TR_R0 .. +3 into sd_trace_buf[row][wave][point]; y4_sd_trace_read() copies it out.
+// In-kernel phase trace (kernel experiments only; scripts/phase_trace.py stem_down): workgroup SD_TR_WG records s_memtime per wave at
+// fixed points of its output rows SD_TR_R0 .. +3 into sd_trace_buf[row][wave][point]; y4_sd_trace_read() copies it out.
 __device__ unsigned long long sd_trace_buf[4 * 16 * 8];
 #define SD_TR_WG 8
 #define SD_TR_R0 5
-#define SD_POINT(P)                                                                                         \
-    do {                                                                                                    \
-        __builtin_amdgcn_sched_barrier(0);                                                                  \
-        if (tr_on) asm volatile("s_memtime %0" : "=s"(tr_t[P]));                                            \
-        __builtin_amdgcn_sched_barrier(0);                                                                  \
-    } while (0)
-#else
-#define SD_POINT(P)
 #endif
 
 template <int DT, int MFW, class IMG>     // MFW = max pixel fragments per wave row: ceil((Wo/16) / SD_WM)
@@ -94,7 +67,7 @@ __global__ __launch_bounds__(64 * SD_WAVES) void stem_down_kernel(const StemDown
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int S = p.S, Wo = S >> 1, PW = Wo + 1;
     const int MF = Wo >> 4;                                   // pixel fragments per output row
-    char* const lds_w = smem;                                 // [9 taps][64 rows][64 B] (SD_W8 = 0)
+    char* const lds_w = smem;                                 // [9 taps][64 rows][64 B]
     char* const lds_s = smem + SD_LDS_W;                      // [3 rows][2 planes][PW slots][64 B]
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int q = lane & 15, g = lane >> 4;
@@ -106,17 +79,6 @@ __global__ __launch_bounds__(64 * SD_WAVES) void stem_down_kernel(const StemDown
     const int wm = wave % SD_WM, wn = wave / SD_WM;
     // ---- 1. c1 weights.  A lane's 16 accumulator values are 16 consecutive channels: MFMA row i = g'*4 + r' of channel fragment
     //         jn holds channel g'*16 + jn*4 + r'.
-#if SD_W8
-    //         Into registers, once: fragment (tap t, channel fragment wn*2 + j) = 8 input channels 8g.. of this lane's row
-    u32x4 wreg[9][2];
-#pragma unroll
-    for (int t = 0; t < 9; ++t)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int ch = (q >> 2) * 16 + (wn * 2 + j) * 4 + (q & 3);
-            wreg[t][j] = *(const u32x4*)(p.w1 + ((ch * 9 + t) * 32 + g * 8) * 2);
-        }
-#else
     //         Into LDS: row (tap*64 + pr), pr = jn*16 + i.
     {
         const __amdgpu_buffer_rsrc_t rs = make_rsrc(p.w1, p.w1_bytes);
@@ -129,7 +91,6 @@ __global__ __launch_bounds__(64 * SD_WAVES) void stem_down_kernel(const StemDown
             buffer_load16_lds(rs, lds_w + __builtin_amdgcn_readfirstlane(u * 1024), voff, 0);
         }
     }
-#endif
 
     if (tid < 3 * 4) {                                        // the zero column left of the image, once for the three slots
         const int row = ((tid >> 2) * 2 + 1) * PW;
@@ -153,7 +114,7 @@ __global__ __launch_bounds__(64 * SD_WAVES) void stem_down_kernel(const StemDown
 #ifdef SD_TRACE
     unsigned long long tr_t[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 #endif
-    // ---- the regular-row machinery (SD_PRELOAD): tile k of this wave on a row with two new conv-0 rows is tile wave + 16 k of
+    // ---- the regular-row machinery (the preload): tile k of this wave on a row with two new conv-0 rows is tile wave + 16 k of
     //      2 * (S / 16); a tile past the end repeats the last one (same values to the same slots)
     const int sd_tpr = S >> 4, sd_nt = 2 * sd_tpr;
     const int sd_lane_off = g < 3 ? ((g - 1) * S + q - 1) * 3 : (-S + q + 1) * 3 + 2;
@@ -193,7 +154,7 @@ __global__ __launch_bounds__(64 * SD_WAVES) void stem_down_kernel(const StemDown
         }
     };
     auto reg_row = [&](int row_i) {                   // is output row `row_i` of this band regular?
-        if (!SD_PRELOAD || row_i >= r_end || row_i == r_begin) return false;
+        if (row_i >= r_end || row_i == r_begin) return false;
         const int ho_ = row_i % Wo;
         return ho_ >= 1 && ho_ <= Wo - 2;
     };
@@ -205,7 +166,7 @@ __global__ __launch_bounds__(64 * SD_WAVES) void stem_down_kernel(const StemDown
 #ifdef SD_TRACE
     const bool tr_on = blockIdx.x == SD_TR_WG && orow_i - r_begin >= SD_TR_R0 && orow_i - r_begin < SD_TR_R0 + 4;
 #endif
-    SD_POINT(0);                          // row start
+    PHASE_POINT(0);                          // row start
     // c0 rows 2ho-1+ry, ry = ry_first .. 2, are new; row 2ho-1 is the previous output row's 2(ho-1)+1, still in its slot
     const int ry_first = (orow_i == r_begin || ho == 0) ? 0 : 1;
     // ---- 2. c0 rows -> LDS ring (MFMA stem: stem_mfma_kernel's arithmetic, stem_common.h's K layout)
@@ -342,10 +303,10 @@ __global__ __launch_bounds__(64 * SD_WAVES) void stem_down_kernel(const StemDown
             }
         }
     }
-    SD_POINT(1);                          // stem tiles done (strip stores issued)
+    PHASE_POINT(1);                          // stem tiles done (strip stores issued)
     if (orow_i == r_begin) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // the c1 weights (staged once)
     __syncthreads();
-    SD_POINT(2);                          // barrier passed
+    PHASE_POINT(2);                          // barrier passed
 
     // ---- L2 prefetch of the image rows the NEXT output row's stem will read for the first time (two rows, contiguous
     //      in memory; three at an image's first row): one LDS-DMA load per wave into a scratch KB -- no registers, nobody
@@ -382,12 +343,8 @@ __global__ __launch_bounds__(64 * SD_WAVES) void stem_down_kernel(const StemDown
         u32x4 wf[2];
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
-#if SD_W8
-            wf[j] = wreg[t][j];
-#else
             const int row = t * 64 + (wn * 2 + j) * 16 + q;
             wf[j] = *(const u32x4*)(lds_w + row * 64 + ((g ^ sd_swz(row)) * 16));
-#endif
         }
         // input column 2wo + kx - 1: kx = 0 -> odd plane slot wo, kx = 1 -> even plane slot wo, kx = 2 -> odd plane slot wo+1
         const int row0 = (((2 * ho + ky) % 3) * 2 + (kx == 1 ? 0 : 1)) * PW + (kx == 2 ? 1 : 0) + q;     // ring slot of c0 row 2ho-1+ky
@@ -401,14 +358,12 @@ __global__ __launch_bounds__(64 * SD_WAVES) void stem_down_kernel(const StemDown
                 Mma<DT>::run(acc[f][1], wf[1], xf);
             }
         }
-#if SD_TAPBAR
         // the preloaded stem tiles stay in registers across this loop: keep the scheduler from pulling several taps' fragment reads
         // forward (it would spill -- and a spill of a register that a load is still filling waits for that load, here)
-        if (t % SD_TAPBAR == SD_TAPBAR - 1) __builtin_amdgcn_sched_barrier(0);
-#endif
+        __builtin_amdgcn_sched_barrier(0);
     }
 
-    SD_POINT(3);                          // conv 1 MFMAs issued
+    PHASE_POINT(3);                          // conv 1 MFMAs issued
     // ---- 4. BN + activation; the lane holds channels g*16 + wn*8 + (0..7) of its pixel -> one 16-byte store
     float sc1[8], sh1[8];
     read_aff8(lds_aff + 64 + g * 16 + wn * 8, sc1);
@@ -427,9 +382,9 @@ __global__ __launch_bounds__(64 * SD_WAVES) void stem_down_kernel(const StemDown
             *(u32x4*)(orow + (int64_t)(frag * 16 + q) * p.out_cstride) = pk;
         }
     }
-    SD_POINT(4);                          // epilogue done, stores issued
+    PHASE_POINT(4);                          // epilogue done, stores issued
     __syncthreads();                  // every wave has read the ring: the next row's stem may overwrite two of its slots
-    SD_POINT(5);                          // second barrier passed
+    PHASE_POINT(5);                          // second barrier passed
 #ifdef SD_TRACE
     if (tr_on && lane == 0) {
 #pragma unroll
@@ -439,19 +394,13 @@ __global__ __launch_bounds__(64 * SD_WAVES) void stem_down_kernel(const StemDown
     }                                 // output rows of the band
 }
 
-#ifdef SD_TRACE
-}  // namespace y4
-extern "C" int y4_sd_trace_read(unsigned long long* dst) {
-    return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(y4::sd_trace_buf), sizeof(unsigned long long) * 4 * 16 * 8);
-}
-namespace y4 {
-#endif
+PHASE_TRACE_READER(y4_sd_trace_read, sd_trace_buf)
 
 // c1 weights + c0 ring + the prefetch's scratch KB
 size_t stem_down_lds_bytes(int S) { return (size_t)SD_LDS_W + (size_t)3 * 2 * (S / 2 + 1) * 64 + 1024 + 1024; }
 
 bool stem_down_supported(int dtype, int S) {
-    return dtype != Y4_F32 && S % 32 == 0 && stem_down_lds_bytes(S) <= 160 * 1024 && (S / 32 + SD_WM - 1) / SD_WM <= (SD_W8 ? 5 : 3);
+    return dtype != Y4_F32 && S % 32 == 0 && stem_down_lds_bytes(S) <= 160 * 1024 && (S / 32 + SD_WM - 1) / SD_WM <= 3;
 }
 
 template <int DT, class IMG>
@@ -466,9 +415,6 @@ static int stem_down_dispatch(const StemDownK& k, hipStream_t stream) {
 #define Y4_SD_CASE(M) case M: return launch_lds<stem_down_kernel<DT, M, IMG>>(160 * 1024, grid, block, lds, stream, k);
     switch (mfw) {
         Y4_SD_CASE(1) Y4_SD_CASE(2) Y4_SD_CASE(3)
-#if SD_W8
-        Y4_SD_CASE(4) Y4_SD_CASE(5)
-#endif
     }
 #undef Y4_SD_CASE
     set_error("stem_down: image side %d not supported", k.S);
