@@ -5,46 +5,9 @@ Decisions (valid counts, kept indices, classes) must be identical; boxes/scores 
 import numpy as np
 import pytest
 
+from decode_nms_cases import _compare, _engine, _heads_with, _random_heads      # shared with tests/test_gpu_decode_nms_paths.py
+
 pytestmark = pytest.mark.gpu
-
-
-def _engine(size, ncls, n):
-    from yolo4hip import weights as W
-    from yolo4hip.config import make_config
-    from yolo4hip.engine import Engine
-    from yolo4hip.plan import build_plan
-    cfg = make_config(size)
-    eng = Engine(ncls, cfg, max_batch=n, dtype="bf16")
-    eng.adopt_packed()          # decode/NMS do not read weights
-    return cfg, eng
-
-
-def _compare(eng, cfg, heads, size, ncls, iou=-1.0, score=-1.0):
-    from oracle import decode_nms as OD
-    n = eng.set_heads(heads)
-    got = [o.cpu().numpy() for o in eng.decode_nms_device(n, None, iou, score)]
-    ref = OD.inference_from_heads(heads, ncls, cfg["anchors"], cfg["xyscale"], size,
-                                  iou_threshold=cfg["iou_threshold"] if iou < 0 else iou,
-                                  score_threshold=cfg["score_threshold"] if score < 0 else score)
-    assert np.array_equal(got[3], ref[3]), (got[3], ref[3])
-    assert np.array_equal(got[4], ref[4])
-    assert np.array_equal(got[2], ref[2])
-    assert np.abs(got[0] - ref[0]).max() < 1e-5
-    assert np.abs(got[1] - ref[1]).max() < 1e-6
-    return got, ref
-
-
-def _random_heads(rng, n, size, ncls, obj_bias, cls_bias, gain=1.5):
-    heads = []
-    nf = 5 + ncls
-    for s in (8, 16, 32):
-        g = size // s
-        h = (rng.standard_normal((n, g, g, 3, nf)) * gain).astype(np.float32)
-        h[..., 2:4] *= 0.3
-        h[..., 4] += obj_bias
-        h[..., 5:] += cls_bias
-        heads.append(h.reshape(n, g, g, 3 * nf))
-    return heads
 
 
 def test_zero_logits_closed_form():
@@ -100,20 +63,6 @@ def test_custom_thresholds_like_predict_nonms():
     _compare(eng, cfg, heads, size, ncls, iou=0.9, score=0.5)
     _compare(eng, cfg, heads, size, ncls, iou=0.0, score=0.05)
     eng.close()
-
-
-def _heads_with(size, ncls, n, boxes):
-    """Logits that are hugely negative everywhere except the listed (image, scale, gy, gx, anchor, class, obj_logit, cls_logit,
-    txywh) cells: exactly those boxes are candidates."""
-    nf = 5 + ncls
-    heads = [np.full((n, size // s, size // s, 3, nf), -20.0, np.float32) for s in (8, 16, 32)]
-    for h in heads:
-        h[..., :4] = 0.0
-    for (b, sc, gy, gx, a, c, lo, lc, t) in boxes:
-        heads[sc][b, gy, gx, a, :4] = t
-        heads[sc][b, gy, gx, a, 4] = lo
-        heads[sc][b, gy, gx, a, 5 + c] = lc
-    return [h.reshape(n, h.shape[1], h.shape[2], 3 * nf) for h in heads]
 
 
 def test_empty_single_and_mixed_images():

@@ -73,15 +73,16 @@ def test_combined_nms_equals_naive_definition():
     from hypothesis import given, settings, strategies as st
 
     @settings(max_examples=60, deadline=None)
-    @given(st.integers(0, 2 ** 31 - 1), st.integers(1, 40), st.integers(1, 4), st.sampled_from([3, 100]))
-    def run(seed, nbox, ncls, total):
+    @given(st.integers(0, 2 ** 31 - 1), st.integers(1, 40), st.integers(1, 4), st.sampled_from([1, 2, 100]),
+           st.sampled_from([1, 3, 7, 100]))
+    def run(seed, nbox, ncls, per_class, total):
         rng = np.random.default_rng(seed)
         ctr = rng.random((nbox, 2)).astype(np.float32)
         wh = (rng.random((nbox, 2)) * 0.5).astype(np.float32)
         boxes = np.concatenate([ctr - wh / 2, ctr + wh / 2], axis=1).astype(np.float32)     # may leave [0,1]: clipping
         scores = rng.choice(np.linspace(0, 1, 21, dtype=np.float32), size=(nbox, ncls))      # many exact ties and 0.3s
-        b, s, c, v, idx = OD.combined_nms(boxes[None], scores[None], 100, total, 0.413, 0.3)
-        want = _naive_class_nms(boxes, scores, np.float32(0.413), np.float32(0.3), 100, total)
+        b, s, c, v, idx = OD.combined_nms(boxes[None], scores[None], per_class, total, 0.413, 0.3)
+        want = _naive_class_nms(boxes, scores, np.float32(0.413), np.float32(0.3), per_class, total)
         assert v[0] == len(want)
         for k, (sc, i, cl) in enumerate(want):
             assert idx[0, k] == i and c[0, k] == cl and s[0, k] == np.float32(sc)
@@ -89,3 +90,38 @@ def test_combined_nms_equals_naive_definition():
         assert not s[0, len(want):].any() and (idx[0, len(want):] == -1).all()
 
     run()
+
+
+def _tf_standin():
+    import importlib.util
+    import os
+    from helpers import GOLDEN
+    spec = importlib.util.spec_from_file_location("tf_standin", os.path.join(GOLDEN, "tf_standin.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+@pytest.mark.parametrize("per_class,total", [(2, 7), (1, 100), (3, 3)])
+def test_cap_semantics_by_three_independent_writings(per_class, total):
+    """max_output_size_per_class and max_total_size as three writings of CombinedNonMaxSuppression have them -- the oracle, the
+    brute force above and the TensorFlow stand-in of tests/golden: a class stops selecting once it has per_class boxes, and a box
+    it turns away suppresses nothing (it is never selected, so nothing is ever compared with it); the classes' selections are then
+    merged by score and cut to total.  Fixed case: 30 boxes in 3 clusters of heavy overlap plus loners, 3 classes, many ties."""
+    rng = np.random.default_rng(2024)
+    ctr = np.concatenate([rng.normal(c, 0.03, (8, 2)) for c in ((0.3, 0.3), (0.7, 0.4), (0.5, 0.8))] + [rng.random((6, 2))])
+    wh = 0.2 + 0.05 * rng.random((30, 2))
+    boxes = np.concatenate([ctr - wh / 2, ctr + wh / 2], axis=1).astype(np.float32)
+    scores = rng.choice(np.linspace(0, 1, 21, dtype=np.float32), size=(30, 3))
+    b, s, c, v, idx = OD.combined_nms(boxes[None], scores[None], per_class, total, 0.413, 0.3)
+    want = _naive_class_nms(boxes, scores, np.float32(0.413), np.float32(0.3), per_class, total)
+    uncapped = _naive_class_nms(boxes, scores, np.float32(0.413), np.float32(0.3), 10 ** 6, 10 ** 6)
+    per = np.bincount([cl for _, _, cl in uncapped], minlength=3)
+    assert per.max() > per_class and np.minimum(per, per_class).sum() >= min(total, 3)     # the per-class cap binds in this case
+    assert v[0] == len(want) == min(total, int(np.minimum(per, per_class).sum()))
+    assert [(int(idx[0, k]), int(c[0, k])) for k in range(v[0])] == [(i, cl) for _, i, cl in want]
+    tb, ts, tc, tv = (t.numpy() for t in _tf_standin().combined_non_max_suppression(
+        boxes[None, :, None, :], scores[None], per_class, total, iou_threshold=0.413, score_threshold=0.3))
+    assert tv[0] == v[0] and np.array_equal(tc, c) and np.array_equal(ts, s) and np.array_equal(tb, b)
+    # a turned-away box suppresses nothing: every box of the capped result is one the uncapped run selected as well
+    assert {(i, cl) for _, i, cl in want} <= {(i, cl) for _, i, cl in uncapped}

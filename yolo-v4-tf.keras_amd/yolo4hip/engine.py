@@ -19,7 +19,7 @@ def _img_hw(config):
     return int(size[0]), int(size[1])
 
 
-def _cfg_struct(config, num_classes, max_batch, dtype):
+def _cfg_struct(config, num_classes, max_batch, dtype, max_per_class=100, max_total=100):
     c = ext.y4_config()
     H, W = _img_hw(config)
     # reference models.py:24, for each side (its models.py:23 'not support yet' for H != W is lifted: y4_create_hw)
@@ -36,17 +36,19 @@ def _cfg_struct(config, num_classes, max_batch, dtype):
         c.strides[i] = int(config["strides"][i])
     c.iou_threshold = float(config["iou_threshold"])
     c.score_threshold = float(config["score_threshold"])
-    c.max_per_class = 100                       # custom_layers.py:293 (hard-coded in the reference)
-    c.max_total = 100                           # custom_layers.py:294
+    c.max_per_class = int(max_per_class)        # custom_layers.py:293 (hard-coded to 100 in the reference)
+    c.max_total = int(max_total)                # custom_layers.py:294 (likewise)
     return c
 
 
 class Engine:
     def __init__(self, num_classes, config=None, max_batch=32, dtype="f32", device=None, alias_workspace=False,
-                 retain_head_inputs=False):
-        self._build(num_classes, config, max_batch, dtype, device, alias_workspace, retain_head_inputs, None)
+                 retain_head_inputs=False, *, max_per_class=100, max_total=100):
+        self._build(num_classes, config, max_batch, dtype, device, alias_workspace, retain_head_inputs, None,
+                    max_per_class=max_per_class, max_total=max_total)
 
-    def _build(self, num_classes, config, max_batch, dtype, device, alias_workspace, retain_head_inputs, parent):
+    def _build(self, num_classes, config, max_batch, dtype, device, alias_workspace, retain_head_inputs, parent, *,
+               max_per_class=100, max_total=100):
         """What `__init__` and `sibling` share: the handle, its workspaces and every attribute.  `parent` is None for an engine
         with weights of its own, or the engine whose packed weights and schedule this one takes over."""
         import torch
@@ -59,7 +61,7 @@ class Engine:
         self.device = torch.device(device if device is not None else f"cuda:{torch.cuda.current_device()}")
         self.num_classes = int(num_classes)
         self.max_batch = int(max_batch)
-        self.cfg = _cfg_struct(self.config, num_classes, max_batch, dtype)
+        self.cfg = _cfg_struct(self.config, num_classes, max_batch, dtype, max_per_class, max_total)
         self.dtype = ext.DTYPE_NAMES[self.cfg.dtype]
         # img_size: the side of a square engine (as before), (H, W) of a rectangular one; img_hw is (H, W) either way
         self.img_hw = _img_hw(self.config)
@@ -113,7 +115,8 @@ class Engine:
         on two HIP streams (`InFlight`): one batch's partial last rounds, its 32-workgroup NMS and its small 19^2 layers
         overlap the other batch's kernels.  Results are those of this engine, bit for bit."""
         e = Engine.__new__(Engine)
-        e._build(self.num_classes, self.config, self.max_batch, self.dtype, self.device, self.alias_workspace, self.retain_level, self)
+        e._build(self.num_classes, self.config, self.max_batch, self.dtype, self.device, self.alias_workspace, self.retain_level, self,
+                 max_per_class=self.cfg.max_per_class, max_total=self.cfg.max_total)
         return e
 
     # what the Python side remembers of the handle's schedule (`stem_fusion`: tests/test_gpu_api.py; `halo2`: the YOLO4HIP_HALO2 switch)
