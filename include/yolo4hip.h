@@ -252,21 +252,22 @@ int y4_head_adam(y4_handle h, const float* dw_dev, float* w_dev, float* m_dev, f
  *     dZ[p, c]         = dA[p, c] * (A[p, c] > 0 ? 1 : 0.1) * s[c]          (TensorFlow's LeakyReLU gradient: 0.1 at exactly 0)
  *     dK[co,ci,kh,kw]  = sum over images, rows, columns of dZ[n,y,x,co] * U[n, y+kh-1, x+kw-1, ci]     ('same' zero padding)
  * dA uses g's structure -- three confidence terms per cell in anchor order, then the cell's records in record order -- and never
- * runs a full-width product over every cell; dZ is kept in scratch in the MFMA operand type (bf16 for a bf16 handle: one rounding
- * to nearest even; float32 for a float32 handle).  dK is an implicit GEMM over K = pixels on the matrix pipes
- * (v_mfma_f32_32x32x16_bf16; v_mfma_f32_32x32x2_f32, exact float32, for a float32 handle) with float32 accumulation: K is cut
+ * runs a full-width product over every cell; dZ is kept in scratch in the MFMA operand type (bf16 / fp16 for a 16-bit handle: one
+ * rounding to nearest even; float32 for a float32 handle).  dK is an implicit GEMM over K = pixels on the matrix pipes
+ * (v_mfma_f32_32x32x16_bf16 / _f16; v_mfma_f32_32x32x2_f32, exact float32, for a float32 handle) with float32 accumulation: K is cut
  * into (image, row strip) slices by the geometry alone, contiguous ranges of slices are summed in order into float32 partials in
  * scratch and a finish kernel adds the partials in range order.  No floating-point atomics: the same call gives the same bits.
  *
  * The gradient, the float32 master copy and the Adam moments use ONE layout: the three kernels one after the other (conv 92, 100,
  * 108), each cout * cin * 9 floats in the Darknet stream's (out, in, kh, kw) order, WITHOUT the four BatchNormalization vectors
  * that precede them in the stream (they lie at y4_layer_info(...).weight_offset + 4 * cout).
- * A float16 handle is refused (Y4_EINVAL): a 16-bit dZ in fp16 needs loss scaling. */
+ * A float16 handle is refused (Y4_EINVAL) by y4_block_grad only: a 16-bit dZ in fp16 needs loss scaling, which
+ * y4_block_grad_scaled provides; the scratch query and y4_block_adam take every dtype. */
 
 /* bytes of scratch y4_block_grad needs for n images (dZ of the three scales, then the partials); 256-byte aligned.
  * Width limit of the weight gradient (two grid rows and their halo in LDS): a grid row of the stride-8 scale of at most 105 cells
- * on a float32 handle (an image 840 wide) and 200 cells on a bf16 handle (1600 wide); beyond it this call and y4_block_grad
- * return Y4_EINVAL before anything is launched. */
+ * on a float32 handle (an image 840 wide) and 200 cells on a bf16 or float16 handle (1600 wide); beyond it this call,
+ * y4_block_grad and y4_block_grad_scaled return Y4_EINVAL before anything is launched. */
 int y4_block_grad_scratch_bytes(y4_handle h, int n, size_t* bytes);
 /* The gradient above for the n images of the last y4_forward: their raw heads, the head convs' inputs AND the inputs of convs
  * 92 / 100 / 108 are read from the workspace (Y4_ESTATE unless the retention level is 2: y4_set_retain_head_inputs(h, 2)).
@@ -276,6 +277,20 @@ int y4_block_grad_scratch_bytes(y4_handle h, int n, size_t* bytes);
 int y4_block_grad(y4_handle h, int n, const int32_t* records_dev, const int32_t* counts_dev, const float* xywh_dev, int max_boxes,
                   float iou_loss_thresh, const float* img_weight_dev, void* scratch_dev, size_t scratch_bytes, float* dk_dev,
                   size_t dk_floats, int accumulate, void* stream);
+/* y4_block_grad with a loss scale, for float32, bf16 and float16 handles.  loss_scale must be a finite positive power of two
+ * (Y4_EINVAL otherwise, before anything is launched): dZ, computed in float32 as above, is multiplied by it BEFORE its single
+ * rounding to the operand type, and the ordered sum of the partials is multiplied by 1 / loss_scale before it is written or
+ * added to dk_dev.  Both products are exact, so on a float32 or bf16 handle, away from under- and overflow, the result has the
+ * bits of y4_block_grad; in fp16 the scale keeps the part of dZ that would round into the subnormals or to zero.
+ * overflow_dev is one int32 in device memory that the call ORs into and never clears (the caller zeroes it, once for all the
+ * chunks of a batch): bit 0 -- a stored dZ is inf or NaN (the scale is too large), bit 1 -- a sum is not finite.  When the word
+ * is non-zero dk_dev holds nothing usable, including what was accumulated before.  It may be null on a float32 or bf16 handle
+ * and is required on a float16 handle (Y4_EINVAL).  y4_block_grad is this call with scale 1 and no word.  The flags are raised
+ * by integer atomicOr, one per workgroup at most, which is order-independent: the same call still gives the same bits. */
+int y4_block_grad_scaled(y4_handle h, int n, const int32_t* records_dev, const int32_t* counts_dev, const float* xywh_dev,
+                         int max_boxes, float iou_loss_thresh, const float* img_weight_dev, float loss_scale,
+                         int32_t* overflow_dev, void* scratch_dev, size_t scratch_bytes, float* dk_dev, size_t dk_floats,
+                         int accumulate, void* stream);
 /* One step of the Adam rule of y4_head_adam (same element rule, lr_t in double on the host; pass the same t for both calls of a
  * step) on the caller's float32 master kernels k_dev and moments m_dev, v_dev (n_floats = the three kernels exactly), followed by
  * the re-pack of the three layers: the new kernels go into the bound packed-weight workspace in the handle's dtype and canonical K

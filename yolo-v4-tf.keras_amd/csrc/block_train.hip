@@ -9,12 +9,19 @@
 //     dZ[p, c]        = dA[p, c] * (A[p, c] > 0 ? 1 : 0.1) * s[c]
 //     dK[co,ci,kh,kw] = sum_{n,y,x} dZ[n,y,x,co] U[n, y+kh-1, x+kw-1, ci]          ('same' zero padding)
 //
+// Loss scale S (a power of two; 1 on the unscaled entry): dZ is multiplied by S in float32 before its single rounding to the operand
+// type, so that fp16 keeps what would otherwise round into its subnormals, and the ordered sum of the partials is multiplied by
+// 1 / S.  Both are exact in float32.  A stored dZ that is inf / NaN raises bit 0 of the caller's overflow word, a non-finite sum
+// bit 1: one integer atomicOr per workgroup at most, which is order-independent.
+//
 // Determinism rule of loss.hip: no floating-point atomics, every sum in an order fixed by the geometry.
 //   dA   one thread per element: the three confidence terms in anchor order, then the cell's records in record order (a cell's
 //        records are its anchors in ascending order), each record's logits in ascending order
 //   dK   K = pixels is cut into slices (image, strip of R rows); a workgroup adds a contiguous range of slices in slice order into
 //        its MFMA accumulators -- inside a slice row pair by row pair, left to right -- and writes one float32 partial;
 //        block_wgrad_finish_kernel adds the partials in range order
+#include <cmath>
+
 #include "conv_common.h"
 #include "grad_common.h"
 
@@ -26,6 +33,22 @@ constexpr int DG_PIX = 16;                 // cells of a dgrad strip: at most 48
 constexpr int DG_VEC = 8;                  // channels per thread and step
 constexpr int WG_TILE = 64;                // a wgrad workgroup owns 64 output x 64 input channels, all nine taps
 constexpr int WG_TARGET = 512;             // workgroups a wgrad launch aims at (2 per compute unit)
+
+// does a 16-byte chunk as Elem<DT>::store_chunk wrote it hold an inf or a NaN?
+template <int DT>
+__device__ __forceinline__ bool chunk_not_finite(const u32x4& c) {
+    bool bad = false;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        if constexpr (DT == Y4_F32) {
+            bad |= (c[i] & 0x7fffffffu) >= 0x7f800000u;
+        } else {
+            constexpr uint32_t EXP = DT == Y4_F16 ? 0x7c00u : 0x7f80u;
+            bad |= (c[i] & 0x7fffu) >= EXP || ((c[i] >> 16) & 0x7fffu) >= EXP;
+        }
+    }
+    return bad;
+}
 
 // ---- head dgrad + activation backward: grid (strips of DG_PIX cells of one image, images)
 template <int DT>
@@ -82,6 +105,7 @@ __global__ __launch_bounds__(LOSS_THREADS) void block_dgrad_kernel(GradK p, Bloc
     const T* act = (const T*)b.a[s] + ((size_t)img * cells + cell0) * cout;
     T* dz = (T*)b.dz[s] + ((size_t)img * cells + cell0) * cout;
     const float* sc = b.bn_scale[s];
+    int bad = 0;
     for (int v = tid; v < DG_PIX * vpc; v += LOSS_THREADS) {
         const int cl = v / vpc, c = (v - cl * vpc) * DG_VEC;
         if (cell0 + cl >= cells) break;                                   // (v ascends: every later one is outside too)
@@ -110,19 +134,26 @@ __global__ __launch_bounds__(LOSS_THREADS) void block_dgrad_kernel(GradK p, Bloc
 #pragma unroll
         for (int q = 0; q < DG_VEC / E::EPC; ++q) E::load_chunk(act + (size_t)cl * cout + c + q * E::EPC, av + q * E::EPC);
 #pragma unroll
-        for (int k = 0; k < DG_VEC; ++k) acc[k] = acc[k] * (av[k] > 0.0f ? 1.0f : 0.1f) * sc[c + k];
+        for (int k = 0; k < DG_VEC; ++k) acc[k] = acc[k] * (av[k] > 0.0f ? 1.0f : 0.1f) * sc[c + k] * b.loss_scale;
 #pragma unroll
-        for (int q = 0; q < DG_VEC / E::EPC; ++q) E::store_chunk(dz + (size_t)cl * cout + c + q * E::EPC, acc + q * E::EPC);
+        for (int q = 0; q < DG_VEC / E::EPC; ++q) {
+            u32x4 pk;
+            E::store_chunk(&pk, acc + q * E::EPC);
+            bad |= chunk_not_finite<DT>(pk);
+            *(u32x4*)(dz + (size_t)cl * cout + c + q * E::EPC) = pk;
+        }
     }
+    // (the break above leaves the loop, not the kernel: every thread votes)
+    if (__syncthreads_or(bad) && tid == 0 && b.overflow) atomicOr(b.overflow, 1);
 }
 
 // ---- the 3x3 weight gradient: grid (cin / 64, cout / 64, K splits), 4 waves; wave (wm, wn) owns 32 output x 32 input channels.
 // LDS holds both operands of a slice TRANSPOSED, [channel][row][column], so that the K axis (pixels) is the contiguous one:
 //     uT  [64 ci][R + 2 halo rows][upitch]     column xh = x + 1 (x = -1 .. ), zero outside the image
 //     dT  [64 co][R rows][Wp]                  zero beyond the image's rows / columns
-// 16-bit: a k-step of v_mfma_f32_32x32x16 is 8 columns of two rows (lane half h takes row 2q + h); the B operand of tap
-// (kh, kw) is the 16-byte row read at column x0 shifted by kw elements in registers (one extra dword), so nine taps cost three
-// wide LDS reads.  float32: a k-step of v_mfma_f32_32x32x2_f32 is one column of two rows, operands are single dwords.
+// 16-bit (bf16 and fp16 alike: the staging only moves bits): a k-step of v_mfma_f32_32x32x16 is 8 columns of two rows (lane half
+// h takes row 2q + h); the B operand of tap (kh, kw) is the 16-byte row read at column x0 shifted by kw elements in registers
+// (one extra dword), so nine taps cost three wide LDS reads.  float32: a k-step of v_mfma_f32_32x32x2_f32 is one column of two rows, operands are single dwords.
 template <int DT>
 __global__ __launch_bounds__(256) void block_wgrad_kernel(WgradK p) {
     using T = typename Elem<DT>::type;
@@ -217,7 +248,7 @@ __global__ __launch_bounds__(256) void block_wgrad_kernel(WgradK p) {
                 }
             } else {
                 for (int x0 = 0; x0 < p.Wp; x0 += 8) {
-                    const bf16x8 a = *(const bf16x8*)(da + yl * p.Wp + x0);
+                    const u32x4 a = *(const u32x4*)(da + yl * p.Wp + x0);
 #pragma unroll
                     for (int kh = 0; kh < 3; ++kh) {
                         const T* row = ub + (yl + kh) * p.upitch + x0;
@@ -225,9 +256,9 @@ __global__ __launch_bounds__(256) void block_wgrad_kernel(WgradK p) {
                         const uint32_t c4 = *(const uint32_t*)(row + 8);
                         const u32x4 b1 = {(c[0] >> 16) | (c[1] << 16), (c[1] >> 16) | (c[2] << 16), (c[2] >> 16) | (c[3] << 16), (c[3] >> 16) | (c4 << 16)};
                         const u32x4 b2 = {c[1], c[2], c[3], c4};
-                        acc[kh * 3 + 0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, __builtin_bit_cast(bf16x8, c), acc[kh * 3 + 0], 0, 0, 0);
-                        acc[kh * 3 + 1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, __builtin_bit_cast(bf16x8, b1), acc[kh * 3 + 1], 0, 0, 0);
-                        acc[kh * 3 + 2] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, __builtin_bit_cast(bf16x8, b2), acc[kh * 3 + 2], 0, 0, 0);
+                        Mma32<DT>::run(acc[kh * 3 + 0], a, c);
+                        Mma32<DT>::run(acc[kh * 3 + 1], a, b1);
+                        Mma32<DT>::run(acc[kh * 3 + 2], a, b2);
                     }
                 }
             }
@@ -242,18 +273,23 @@ __global__ __launch_bounds__(256) void block_wgrad_kernel(WgradK p) {
         for (int j = 0; j < 16; ++j) o[t * plane + (size_t)((j & 3) + 8 * (j >> 2)) * p.cin] = acc[t][j];
 }
 
-// partials [splits][9 taps][cout][cin] -> dK [cout][cin][3][3] (the Darknet stream's order), added in split order
+// partials [splits][9 taps][cout][cin] -> dK [cout][cin][3][3] (the Darknet stream's order), added in split order, then unscaled
 __global__ __launch_bounds__(256) void block_wgrad_finish_kernel(const float* __restrict__ part, float* __restrict__ dk, int cout, int cin,
-                                                                 int splits, int accumulate) {
+                                                                 int splits, int accumulate, float inv_scale, int32_t* overflow) {
     const size_t plane = (size_t)cout * cin, total = 9 * plane;
     const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (e >= total) return;
-    const int t = (int)(e / plane);
-    const size_t oc = e - (size_t)t * plane;
-    float acc = 0.0f;
-    for (int s = 0; s < splits; ++s) acc += part[(size_t)s * total + e];
-    float* o = dk + oc * 9 + t;
-    *o = accumulate ? *o + acc : acc;
+    int bad = 0;
+    if (e < total) {
+        const int t = (int)(e / plane);
+        const size_t oc = e - (size_t)t * plane;
+        float acc = 0.0f;
+        for (int s = 0; s < splits; ++s) acc += part[(size_t)s * total + e];
+        acc *= inv_scale;
+        bad = (__float_as_uint(acc) & 0x7fffffffu) >= 0x7f800000u;
+        float* o = dk + oc * 9 + t;
+        *o = accumulate ? *o + acc : acc;
+    }
+    if (__syncthreads_or(bad) && threadIdx.x == 0 && overflow) atomicOr(overflow, 2);
 }
 
 size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
@@ -271,7 +307,7 @@ int block_dgrad_strips(const int* gh, const int* gw, int* base) {
 
 // the wgrad geometry of one layer for n images of H x W cells: rows per slice, LDS pitches, K splits -> LDS bytes.  0: two rows
 // of the grid with their halo do not fit 160 KB of LDS -- a row of more than 105 cells (float32) or 200 cells (bf16), which is an
-// image wider than 840 / 1600 pixels at the stride-8 scale
+// image wider than 840 / 1600 pixels at the stride-8 scale (fp16 as bf16)
 size_t block_wgrad_geometry(int dtype, int n, int H, int W, int cin, int cout, WgradK& k) {
     const int es = elem_size(dtype);
     k.n = n; k.H = H; k.W = W; k.cin = cin; k.cout = cout;
@@ -333,7 +369,7 @@ static int block_grad_launch_t(const GradK& k, const BlockK& b, int n, hipStream
         if (int r = launch_lds<block_wgrad_kernel<DT>>(160 * 1024, dim3(w[s].cin / WG_TILE, w[s].cout / WG_TILE, w[s].splits), dim3(256), lds[s], stream, w[s])) return r;
         const size_t total = (size_t)9 * w[s].cout * w[s].cin;
         hipLaunchKernelGGL(block_wgrad_finish_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, (const float*)b.part[s],
-                           b.dk + b.dk_off[s], w[s].cout, w[s].cin, w[s].splits, b.accumulate);
+                           b.dk + b.dk_off[s], w[s].cout, w[s].cin, w[s].splits, b.accumulate, 1.0f / b.loss_scale, b.overflow);
     }
     Y4_CHECK_HIP(hipGetLastError());
     return Y4_OK;
@@ -342,13 +378,17 @@ static int block_grad_launch_t(const GradK& k, const BlockK& b, int n, hipStream
 int block_grad_launch(int dtype, const GradK& k, const BlockK& b, int n, hipStream_t stream) {
     Y4_REQUIRE(k.mb >= 1 && k.mb <= LOSS_THREADS, Y4_EINVAL, "block gradient: max_boxes %d outside [1, %d]", k.mb, LOSS_THREADS);
     Y4_REQUIRE((size_t)DG_PIX * 3 * (k.C + 5) * sizeof(float) <= 48 * 1024, Y4_EINVAL, "block gradient: %d classes", k.C);
+    int exp2 = 0;
+    Y4_REQUIRE(std::isnormal(b.loss_scale) && b.loss_scale > 0.0f && std::frexp(b.loss_scale, &exp2) == 0.5f, Y4_EINVAL,
+               "block gradient: loss scale %g is not a finite positive power of two", (double)b.loss_scale);
     for (int s = 0; s < 3; ++s)
         Y4_REQUIRE(b.cin[s] % WG_TILE == 0 && b.cout[s] % WG_TILE == 0 && (int64_t)n * k.gh[s] * k.gw[s] < (1ll << 31), Y4_EINVAL,
                    "block gradient: %d -> %d channels / %d images of scale %d", b.cin[s], b.cout[s], n, s);
     switch (dtype) {
         case Y4_F32: return block_grad_launch_t<Y4_F32>(k, b, n, stream);
         case Y4_BF16: return block_grad_launch_t<Y4_BF16>(k, b, n, stream);
-        default: set_error("block gradient: dtype %d is not supported (f32 and bf16 handles)", dtype); return Y4_EINVAL;
+        case Y4_F16: return block_grad_launch_t<Y4_F16>(k, b, n, stream);
+        default: set_error("block gradient: dtype %d is not supported", dtype); return Y4_EINVAL;
     }
 }
 

@@ -202,6 +202,8 @@ struct BlockK {
     float* dk;                       // the three kernels (out, in, kh, kw), conv 92 / 100 / 108 at dk_off
     size_t dk_off[3];
     int accumulate;
+    float loss_scale;                // a power of two: dZ is stored times it, the summed dK divided by it
+    int32_t* overflow;               // bit 0: an inf / NaN in the stored dZ, bit 1: a non-finite sum; ORed into, may be null
 };
 struct WgradK {
     const void* u;

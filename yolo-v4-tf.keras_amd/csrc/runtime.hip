@@ -1399,7 +1399,6 @@ int y4_head_adam(y4_handle h, const float* dw, float* w, float* m, float* v, siz
 // ---- fine-tuning of the 3x3 convs in front of the heads (block_train.hip)
 
 static int block_check(y4_handle h, const char* who) {
-    Y4_REQUIRE(h->cfg.dtype != Y4_F16, Y4_EINVAL, "%s: an f16 handle is not supported (a 16-bit dZ in fp16 needs loss scaling); use f32 or bf16", who);
     for (int i = 0; i < 3; ++i) {
         const Op* b = block_op(h, i);
         Y4_REQUIRE(b != nullptr, Y4_EINVAL, "%s: no conv in front of head %d", who, i);
@@ -1422,25 +1421,25 @@ int y4_block_grad_scratch_bytes(y4_handle h, int n, size_t* bytes) {
     return Y4_OK;
 }
 
-int y4_block_grad(y4_handle h, int n, const int32_t* records, const int32_t* counts, const float* xywh, int max_boxes,
-                  float iou_loss_thresh, const float* img_weight, void* scratch, size_t scratch_bytes, float* dk, size_t dk_floats,
-                  int accumulate, void* stream) {
-    if (int r = check_ready(h, n)) return r;
-    if (int r = block_check(h, "y4_block_grad")) return r;
-    Y4_REQUIRE(h->retain_block_in, Y4_ESTATE, "y4_block_grad: the inputs of convs 92 / 100 / 108 are not retained (retention level 2: "
-               "y4_set_retain_head_inputs(h, 2) before the workspace is bound)");
+// y4_block_grad (scale 1, no overflow word) and y4_block_grad_scaled
+static int block_grad_impl(y4_handle h, const char* who, int n, const int32_t* records, const int32_t* counts, const float* xywh,
+                           int max_boxes, float iou_loss_thresh, const float* img_weight, float loss_scale, int32_t* overflow,
+                           void* scratch, size_t scratch_bytes, float* dk, size_t dk_floats, int accumulate, void* stream) {
+    if (int r = block_check(h, who)) return r;
+    Y4_REQUIRE(h->retain_block_in, Y4_ESTATE, "%s: the inputs of convs 92 / 100 / 108 are not retained (retention level 2: "
+               "y4_set_retain_head_inputs(h, 2) before the workspace is bound)", who);
     GradK k{};
     BlockK b{};
-    if (int r = grad_front(h, BLOCKS, "y4_block_grad", k, records, counts, xywh, max_boxes, iou_loss_thresh, img_weight, scratch, dk,
-                           dk_floats, b.dk_off))
+    if (int r = grad_front(h, BLOCKS, who, k, records, counts, xywh, max_boxes, iou_loss_thresh, img_weight, scratch, dk, dk_floats,
+                           b.dk_off))
         return r;
-    Y4_REQUIRE(((uintptr_t)scratch & 255) == 0, Y4_EINVAL, "y4_block_grad: scratch must be 256-byte aligned");
+    Y4_REQUIRE(((uintptr_t)scratch & 255) == 0, Y4_EINVAL, "%s: scratch must be 256-byte aligned", who);
     group_channels(h, BLOCKS, b.cin, b.cout);
     block_dgrad_strips(k.gh, k.gw, b.dstrip_base);
     size_t dz_off[3], part_off[3];
     const size_t need = block_grad_scratch_bytes(h->cfg.dtype, n, k.gh, k.gw, b.cin, b.cout, dz_off, part_off);
-    Y4_REQUIRE(need > 0, Y4_EINVAL, "y4_block_grad: a grid row of %d cells does not fit the weight gradient's LDS tile", k.gw[0]);
-    Y4_REQUIRE(scratch_bytes >= need, Y4_ENOMEM, "y4_block_grad: scratch %zu < %zu bytes", scratch_bytes, need);
+    Y4_REQUIRE(need > 0, Y4_EINVAL, "%s: a grid row of %d cells does not fit the weight gradient's LDS tile", who, k.gw[0]);
+    Y4_REQUIRE(scratch_bytes >= need, Y4_ENOMEM, "%s: scratch %zu < %zu bytes", who, scratch_bytes, need);
     for (int i = 0; i < 3; ++i) {
         const Op* ho = head_op(h, i);
         const Op* bo = block_op(h, i);
@@ -1449,7 +1448,27 @@ int y4_block_grad(y4_handle h, int n, const int32_t* records, const int32_t* cou
         b.dz[i] = (char*)scratch + dz_off[i]; b.part[i] = (float*)((char*)scratch + part_off[i]);
     }
     b.dk = dk; b.accumulate = accumulate != 0;
+    b.loss_scale = loss_scale; b.overflow = overflow;
     return block_grad_launch(h->cfg.dtype, k, b, n, (hipStream_t)stream);
+}
+
+int y4_block_grad(y4_handle h, int n, const int32_t* records, const int32_t* counts, const float* xywh, int max_boxes,
+                  float iou_loss_thresh, const float* img_weight, void* scratch, size_t scratch_bytes, float* dk, size_t dk_floats,
+                  int accumulate, void* stream) {
+    if (int r = check_ready(h, n)) return r;
+    Y4_REQUIRE(h->cfg.dtype != Y4_F16, Y4_EINVAL, "y4_block_grad: an f16 handle needs a loss scale (a 16-bit dZ in fp16 underflows "
+               "without one): call y4_block_grad_scaled");
+    return block_grad_impl(h, "y4_block_grad", n, records, counts, xywh, max_boxes, iou_loss_thresh, img_weight, 1.0f, nullptr, scratch,
+                           scratch_bytes, dk, dk_floats, accumulate, stream);
+}
+
+int y4_block_grad_scaled(y4_handle h, int n, const int32_t* records, const int32_t* counts, const float* xywh, int max_boxes,
+                         float iou_loss_thresh, const float* img_weight, float loss_scale, int32_t* overflow, void* scratch,
+                         size_t scratch_bytes, float* dk, size_t dk_floats, int accumulate, void* stream) {
+    if (int r = check_ready(h, n)) return r;
+    Y4_REQUIRE(overflow || h->cfg.dtype != Y4_F16, Y4_EINVAL, "y4_block_grad_scaled: an f16 handle needs the overflow word");
+    return block_grad_impl(h, "y4_block_grad_scaled", n, records, counts, xywh, max_boxes, iou_loss_thresh, img_weight, loss_scale,
+                           overflow, scratch, scratch_bytes, dk, dk_floats, accumulate, stream);
 }
 
 int y4_block_adam(y4_handle h, const float* dk, float* w, float* m, float* v, size_t n_floats, float lr, float beta1, float beta2,

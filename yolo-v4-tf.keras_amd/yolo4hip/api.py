@@ -187,7 +187,7 @@ class Yolov4(object):
     # fine-tuning of the three detection convs on a frozen backbone and neck: in Keras terms every layer trainable = False
     # except conv 93 / 101 / 109.
     def fit(self, train_data_gen, epochs, val_data_gen=None, initial_epoch=0, callbacks=None, *, trainable=None,
-            learning_rate=1e-4):
+            learning_rate=1e-4, loss_scale=None):
         """trainable='heads': Adam (the reference's compile, models.py:83; `learning_rate` replaces its 1e-4) on the weights and
         biases of the three detection convs.  Per batch: `train_data_gen.boxes(i)` -> one upload -> forward in chunks of
         max_batch -> labels assigned on the device -> y4_head_grad accumulated over the chunks (each image weighs 1 / batch
@@ -198,7 +198,14 @@ class Yolov4(object):
 
         trainable='head_blocks' additionally trains the KERNELS of the 3x3 convs in front of the heads (92 / 100 / 108); their
         BatchNormalization stays frozen and runs in inference mode, as Keras runs a frozen BN.  Per chunk y4_block_grad follows
-        y4_head_grad (both use the head weights the forward used), per batch both Adam steps run with the same t.  f32 and bf16.
+        y4_head_grad (both use the head weights the forward used), per batch both Adam steps run with the same t.
+
+        loss_scale (an f16 model with trainable='head_blocks' needs it, nothing else takes it): 'dynamic' -- the rule of Keras'
+        LossScaleOptimizer, yolo4hip.loss_scale.LossScale() -- a LossScale of your own, or a power of two as a static scale.  The
+        block gradient of every chunk runs through y4_block_grad_scaled with the batch's scale: dZ is multiplied by it before
+        its rounding to fp16, the float32 sum divided by it.  One overflow word per batch is read next to the loss; when it is
+        set NEITHER group steps (no Adam step, no step count) and a dynamic scale is halved.  `.history` then also holds
+        'loss_scale' (the scale at the end of each epoch) and 'skipped_steps' (per epoch).
 
         Augmentation: a `train_data_gen` whose `augment` is an `AugmentConfig` (DataGenerator(..., augment=, seed=)) is read
         through `raw(i)`: the raw uint8 images cross PCIe once, `Engine.augment_u8_batch` resizes, shifts, flips and colour-shifts
@@ -219,10 +226,16 @@ class Yolov4(object):
                                       "fine-tunes the three detection convs on a frozen backbone and neck, "
                                       "trainable='head_blocks' also the 3x3 convs in front of them")
         groups = ('heads', 'blocks') if trainable == 'head_blocks' else ('heads',)
-        if 'blocks' in groups and self._dtype == 'f16':
+        scaling = 'blocks' in groups and self._dtype == 'f16'
+        if scaling and loss_scale is None:
             raise NotImplementedError("fit(trainable='head_blocks') on an f16 model: a 16-bit gradient in fp16 needs loss scaling; "
-                                      "use dtype 'bf16' or 'f32'")
+                                      "pass loss_scale='dynamic' or a power of two (or use dtype 'bf16' or 'f32')")
+        if loss_scale is not None and not scaling:
+            raise ValueError("fit: loss_scale is for trainable='head_blocks' on an f16 model; there is nothing to scale on "
+                             f"a {self._dtype} model with trainable={trainable!r}")
         from .engine import combine_loss
+        from .loss_scale import make_loss_scale
+        policy = make_loss_scale(loss_scale) if scaling else None
         self._ensure_tuned()
         if getattr(train_data_gen, 'max_boxes', self.max_boxes) != self.max_boxes:
             raise ValueError(f"the generator's max_boxes {train_data_gen.max_boxes} != config['max_boxes'] {self.max_boxes}")
@@ -235,11 +248,14 @@ class Yolov4(object):
         history = {'loss': []}
         if val_data_gen is not None:
             history['val_loss'] = []
+        if policy is not None:
+            history['loss_scale'], history['skipped_steps'] = [], []
+            overflow = torch.zeros((1,), dtype=torch.int32, device=eng.device)
         for epoch in range(int(initial_epoch), int(epochs)):
             for cb in callbacks or []:
                 if hasattr(cb, 'schedule'):
                     learning_rate = float(cb.schedule(epoch, learning_rate))
-            total, images = 0.0, 0
+            total, images, skipped = 0.0, 0, 0
             for i in range(len(train_data_gen)):
                 if mosaic:
                     raws, tile_src, params, cuts, boxes = train_data_gen.raw_mosaic(i)
@@ -255,6 +271,9 @@ class Yolov4(object):
                 count = boxes_dev.shape[0]
                 weight = torch.full((count,), 1.0 / count, dtype=torch.float32, device=eng.device)
                 parts, i0 = [], 0
+                if policy is not None:
+                    overflow.zero_()
+                scaled = {'blocks': (policy.scale, overflow)} if policy is not None else {}
                 for chunk in eng._chunks(X):
                     n = chunk.shape[0]
                     if i0 + n > count:
@@ -262,16 +281,23 @@ class Yolov4(object):
                     eng.forward_device(chunk)
                     labels = eng.assign_device(boxes_dev[i0:i0 + n])
                     for g in groups:
-                        eng._group_grad_device(g, n, None, labels, self.iou_loss_thresh, weight[i0:i0 + n], grad[g], i0 > 0)
+                        eng._group_grad_device(g, n, None, labels, self.iou_loss_thresh, weight[i0:i0 + n], grad[g], i0 > 0,
+                                               *scaled.get(g, ()))
                     parts.append(eng.loss_device(n, records=labels, iou_loss_thresh=self.iou_loss_thresh))
                     i0 += n
                 if i0 != count:
                     raise ValueError(f'labels for {count} images, but {i0} images')
                 # heads first, and every gradient of the batch before the first step: y4_block_grad must see the head weights
-                # the forward used.  The steps share their t.
-                for g in groups:
-                    eng._group_adam_step(g, state[g], grad[g], lr=learning_rate)
-                total += float(combine_loss(torch.cat(parts).cpu().numpy())[0].sum())
+                # the forward used.  The steps share their t.  An overflow of the scaled block gradient skips the step of both.
+                if policy is not None:
+                    parts.append(overflow.to(torch.float32).expand(1, *parts[0].shape[1:]))
+                losses = torch.cat(parts).cpu().numpy()                     # one copy: the loss and the overflow word
+                if policy is None or policy.update(bool(losses[-1].flat[0] != 0)):
+                    for g in groups:
+                        eng._group_adam_step(g, state[g], grad[g], lr=learning_rate)
+                else:
+                    skipped += 1
+                total += float(combine_loss(losses[:-1] if policy is not None else losses)[0].sum())
                 images += count
             if images == 0:
                 raise ValueError('fit: the generator is empty')
@@ -284,6 +310,9 @@ class Yolov4(object):
                 logs['val_loss'] = self.evaluate(val_data_gen)['loss']
             for k, v in logs.items():
                 history[k].append(v)
+            if policy is not None:
+                history['loss_scale'].append(policy.scale)
+                history['skipped_steps'].append(skipped)
             print(f'Epoch {epoch + 1}/{int(epochs)} - ' + ' - '.join(f'{k}: {v:.4f}' for k, v in logs.items()))
             if hasattr(train_data_gen, 'on_epoch_end'):
                 train_data_gen.on_epoch_end()

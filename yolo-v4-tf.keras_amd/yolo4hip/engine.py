@@ -741,7 +741,9 @@ class Engine:
             scratch = self._block_scratch = torch.empty((size.value,), dtype=torch.uint8, device=self.device)
         return scratch
 
-    def _group_grad_device(self, g, n, boxes_dev, records, iou_loss_thresh, img_weight, dw, accumulate):
+    def _group_grad_device(self, g, n, boxes_dev, records, iou_loss_thresh, img_weight, dw, accumulate, loss_scale=None,
+                           overflow=None):
+        """loss_scale (blocks only): the call goes through y4_block_grad_scaled, which ORs its flags into `overflow`"""
         torch = self.torch
         name, grad, total = self._GROUPS[g]["name"], self._GROUPS[g]["grad"], self._group_floats(g)
         rec, cnt, xywh = self._labels(n, boxes_dev, records)
@@ -753,10 +755,11 @@ class Engine:
         if dw.dtype != torch.float32 or dw.numel() != total or not dw.is_contiguous():
             raise ValueError(f"{grad} must be a contiguous float32 tensor of {total} elements")
         scratch = self._group_scratch(g, n)
+        scaled = () if loss_scale is None else (float(loss_scale), ext.ptr(overflow))
         with torch.cuda.device(self.device):
-            ext.check(getattr(self.lib, f"y4_{name}_grad")(
+            ext.check(getattr(self.lib, f"y4_{name}_grad" + ("_scaled" if scaled else ""))(
                 self.handle, n, ext.ptr(rec), ext.ptr(cnt), ext.ptr(xywh), self._loss_max_boxes(), self._thr(iou_loss_thresh),
-                ext.ptr(w), ext.ptr(scratch), scratch.numel(), ext.ptr(dw), total, 1 if accumulate else 0, ext.stream_ptr()))
+                ext.ptr(w), *scaled, ext.ptr(scratch), scratch.numel(), ext.ptr(dw), total, 1 if accumulate else 0, ext.stream_ptr()))
         return dw
 
     def _group_state(self, g, flat):
@@ -820,11 +823,27 @@ class Engine:
     def block_floats(self):
         return self._group_floats("blocks")
 
-    def block_grad_device(self, n, boxes_dev=None, records=None, iou_loss_thresh=None, img_weight=None, dk=None, accumulate=False):
+    def block_grad_device(self, n, boxes_dev=None, records=None, iou_loss_thresh=None, img_weight=None, dk=None, accumulate=False,
+                          loss_scale=None, overflow=None):
         """y4_block_grad after `forward_device` on n images (an engine with retain_head_inputs=2), BEFORE the step's
         `head_adam_step`: the gradient of sum_i img_weight[i] * loss_i w.r.t. the kernels of convs 92 / 100 / 108 -> float32 cuda
-        tensor [block_floats()] (`block_records` gives the layout), written into `dk` or, with accumulate=True, added to it."""
-        return self._group_grad_device("blocks", n, boxes_dev, records, iou_loss_thresh, img_weight, dk, accumulate)
+        tensor [block_floats()] (`block_records` gives the layout), written into `dk` or, with accumulate=True, added to it.
+
+        loss_scale (a power of two; what an f16 engine needs): y4_block_grad_scaled -- dZ is multiplied by it before its
+        rounding to the operand type and the sum divided by it.  -> (dk, overflow): `overflow` is an int32[1] device tensor the
+        call ORs into and never clears (created zeroed when not given); bit 0 an inf / NaN in the stored dZ, bit 1 a non-finite
+        sum.  When it is non-zero `dk` holds nothing usable."""
+        if loss_scale is None:
+            if overflow is not None:
+                raise ValueError("block_grad_device: overflow needs a loss_scale")
+            return self._group_grad_device("blocks", n, boxes_dev, records, iou_loss_thresh, img_weight, dk, accumulate)
+        torch = self.torch
+        if overflow is None:
+            overflow = torch.zeros((1,), dtype=torch.int32, device=self.device)
+        if overflow.dtype != torch.int32 or overflow.numel() != 1 or overflow.device != self.device:
+            raise ValueError("overflow must be an int32 tensor of one element on the engine's device")
+        dk = self._group_grad_device("blocks", n, boxes_dev, records, iou_loss_thresh, img_weight, dk, accumulate, loss_scale, overflow)
+        return dk, overflow
 
     def block_state(self, flat):
         """The optimiser state for `block_adam_step`: float32 master kernels (the three kernels of the host stream `flat`,
