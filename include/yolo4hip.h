@@ -534,6 +534,34 @@ typedef struct y4_mosaic_cut { int32_t cut_y, cut_x; } y4_mosaic_cut;   /* 8 byt
 int y4_mosaic_u8_ragged(const uint8_t* src_dev, const y4_augment_desc* tiles_dev /* [n][4] */,
                         const y4_mosaic_cut* cuts_dev /* [n] */, int n, uint8_t* out_dev, int H, int W, int pad_value,
                         void* stream);
+/* ---- VOC mAP matching on the device: the per-image matching of `eval_map` (reference models.py:282-330; yolo4hip/evalmap.py) on
+ * the boxes y4_decode_nms(_mapped) left on the device, so that a validation batch returns to the host as flags (yolo4hip/mapeval.py
+ * turns them into AP).  No handle.  Per image, one workgroup:
+ *   - detections are visited by score descending, slot ascending on ties (ranked here; the NMS output order is not relied upon);
+ *   - each is compared with every ground-truth row < gt_count of its own class (int(class) on both sides).  Rows >= gt_count and
+ *     slots >= valid may hold anything, NaN included: they are never read;
+ *   - IoU with the devkit's inclusive-pixel `+ 1` widths and `iw <= 0 or ih <= 0` as "no overlap", in float64 and in the Python
+ *     expression's operation order on the float32 pixel coordinates widened exactly (no contraction): every decision equals
+ *     Python's on the same values;
+ *   - the best row is the first with the strictly largest IoU (`ov > best` from -1); used rows take part in that choice;
+ *   - per threshold t its own walk: true positive iff best >= iou_thresholds[t] and the best row is not yet used at t (it then
+ *     is); otherwise a false positive -- no fallback to the second-best row.
+ * No atomics; image i's outputs are the same bits at any n and at any position in the batch.
+ * Y4_EINVAL: max_total > 256, max_gt > 256, n_thresholds outside 1..16, a negative n / max_total / max_gt, a null pointer.
+ * Device counts are clamped to [0, max_total] / [0, max_gt]. */
+int y4_map_match(const float* boxes_dev,  /* [n, max_total, 4], x1 y1 x2 y2 normalised: what y4_decode_nms(_mapped) wrote */
+                 const float* scores_dev, const float* classes_dev, const int32_t* valid_dev,
+                 int n, int max_total,
+                 const float* scale_dev,      /* [n, 2] (w, h): pixel box = float32 product box * scale, as export_prediction's `*= w` */
+                 const float* gt_dev,         /* [n, max_gt, 5] x1 y1 x2 y2 class, raw-image pixels, annotation order */
+                 const int32_t* gt_count_dev, /* [n] */
+                 int max_gt,
+                 const double* iou_thresholds /* host */, int n_thresholds,
+                 uint32_t* tp_mask_dev,   /* [n, max_total]: bit t = true positive at iou_thresholds[t]; 0 in slots >= valid */
+                 double* best_iou_dev,    /* [n, max_total] or NULL: IoU of the best same-class box, -1 when none overlaps */
+                 int32_t* match_dev,      /* [n, max_total] or NULL: index of that box, -1 */
+                 uint32_t* gt_used_dev,   /* [n, max_gt] or NULL: bit t = used at threshold t when the image is done */
+                 void* stream);
 /* SPP (custom_layers.py:130-134): x = buf[..., 3c:4c] -> buf[..., 0:c]=maxpool13, [c:2c]=maxpool9,
  * [2c:3c]=maxpool5 (stride 1, 'same'), buf is [n,side,side,4c] */
 int y4_spp(int dtype, void* buf_dev, int n, int side, int c, void* stream);

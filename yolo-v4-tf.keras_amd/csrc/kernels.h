@@ -76,6 +76,11 @@ int augment_u8_ragged_launch(const uint8_t* src, const y4_augment_desc* desc, in
 int mosaic_u8_ragged_launch(const uint8_t* src, const y4_augment_desc* tiles, const y4_mosaic_cut* cuts, int n, uint8_t* out, int H,
                             int W, int pad, hipStream_t stream);
 
+// map_match.hip: VOC mAP matching of kept boxes against ground truth, one workgroup per image
+int map_match_launch(const float* boxes, const float* scores, const float* classes, const int32_t* valid, int n, int max_total,
+                     const float* scale, const float* gt, const int32_t* gt_count, int max_gt, const double* iou_thresholds,
+                     int n_thresholds, uint32_t* tp_mask, double* best_iou, int32_t* match, uint32_t* gt_used, hipStream_t stream);
+
 // stem_down.hip: convs 0+1 fused (16-bit dtypes), c0 stays in LDS
 bool stem_down_supported(int dtype, int S);
 int stem_down_launch(int dtype, const void* imgs, int img_u8, int n, int S, const void* stem_wk, const float* s0_scale,

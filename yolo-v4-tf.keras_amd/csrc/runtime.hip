@@ -2062,6 +2062,14 @@ int y4_mosaic_u8_ragged(const uint8_t* src_dev, const y4_augment_desc* tiles_dev
     return mosaic_u8_ragged_launch(src_dev, tiles_dev, cuts_dev, n, out_dev, H, W, pad_value, (hipStream_t)stream);
 }
 
+int y4_map_match(const float* boxes_dev, const float* scores_dev, const float* classes_dev, const int32_t* valid_dev, int n,
+                 int max_total, const float* scale_dev, const float* gt_dev, const int32_t* gt_count_dev, int max_gt,
+                 const double* iou_thresholds, int n_thresholds, uint32_t* tp_mask_dev, double* best_iou_dev, int32_t* match_dev,
+                 uint32_t* gt_used_dev, void* stream) {
+    return map_match_launch(boxes_dev, scores_dev, classes_dev, valid_dev, n, max_total, scale_dev, gt_dev, gt_count_dev, max_gt,
+                            iou_thresholds, n_thresholds, tp_mask_dev, best_iou_dev, match_dev, gt_used_dev, (hipStream_t)stream);
+}
+
 int y4_preprocess_u8(const uint8_t* img_dev, int h, int w, float* out_dev, int out_h, int out_w, void* stream) {
     return preprocess_u8_launch(img_dev, h, w, out_dev, out_h, out_w, (hipStream_t)stream);
 }

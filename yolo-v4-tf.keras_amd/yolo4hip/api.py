@@ -13,7 +13,8 @@ instead of the reference's stretch (Darknet's letter_box=1 geometry) with boxes 
 self-describing checkpoint of this framework (Keras' SavedModel / H5 needs TensorFlow); `eval_map` (models.py:182-507)
 is the VOC mAP tool over the exported text files (yolo4hip/evalmap.py).  `training_model.predict([X, y_s, y_m, y_l, true_xywh])`
 is the reference's yolo_loss FORWARD (models.py:54-65, loss.py) on the device and `evaluate(data_gen)` the validation loss over
-a `DataGenerator`; `fit(..., trainable='heads')` fine-tunes the three detection convs on a frozen backbone and neck (with a
+a `DataGenerator`, `evaluate_map(data)` VOC mAP with the matching on the device (y4_map_match; the numbers of `eval_map` without
+its text files); `fit(..., trainable='heads')` fine-tunes the three detection convs on a frozen backbone and neck (with a
 `DataGenerator(..., augment=AugmentConfig())` under scale, shift, flip and HSV augmentation applied on the device), while
 training every layer (the reference's `fit`) is out of scope and raises.
 """
@@ -187,7 +188,7 @@ class Yolov4(object):
     # fine-tuning of the three detection convs on a frozen backbone and neck: in Keras terms every layer trainable = False
     # except conv 93 / 101 / 109.
     def fit(self, train_data_gen, epochs, val_data_gen=None, initial_epoch=0, callbacks=None, *, trainable=None,
-            learning_rate=1e-4, loss_scale=None):
+            learning_rate=1e-4, loss_scale=None, val_map=False):
         """trainable='heads': Adam (the reference's compile, models.py:83; `learning_rate` replaces its 1e-4) on the weights and
         biases of the three detection convs.  Per batch: `train_data_gen.boxes(i)` -> one upload -> forward in chunks of
         max_batch -> labels assigned on the device -> y4_head_grad accumulated over the chunks (each image weighs 1 / batch
@@ -220,7 +221,12 @@ class Yolov4(object):
         the uint8 batch -- chunks, labels, gradients, Adam -- is the same.
 
         A callback with a `schedule(epoch, lr)` method (yolo4hip.callbacks.CosineAnnealingScheduler; Keras'
-        LearningRateScheduler pattern) is asked at the start of every epoch; its result is that epoch's learning rate."""
+        LearningRateScheduler pattern) is asked at the start of every epoch; its result is that epoch's learning rate.
+
+        val_map=True (needs `val_data_gen`): every epoch's logs and `.history` also hold 'val_mAP', `evaluate_map(val_data_gen)`'s
+        mAP at IoU 0.5 with the epoch's weights."""
+        if val_map and val_data_gen is None:
+            raise ValueError('fit: val_map=True needs val_data_gen')
         if trainable not in ('heads', 'head_blocks'):
             raise NotImplementedError("training every layer is out of scope of the MI355X path; fit(..., trainable='heads') "
                                       "fine-tunes the three detection convs on a frozen backbone and neck, "
@@ -248,6 +254,8 @@ class Yolov4(object):
         history = {'loss': []}
         if val_data_gen is not None:
             history['val_loss'] = []
+            if val_map:
+                history['val_mAP'] = []
         if policy is not None:
             history['loss_scale'], history['skipped_steps'] = [], []
             overflow = torch.zeros((1,), dtype=torch.int32, device=eng.device)
@@ -308,6 +316,8 @@ class Yolov4(object):
             logs = {'loss': total / images}
             if val_data_gen is not None:
                 logs['val_loss'] = self.evaluate(val_data_gen)['loss']
+                if val_map:
+                    logs['val_mAP'] = self.evaluate_map(val_data_gen)['mAP']
             for k, v in logs.items():
                 history[k].append(v)
             if policy is not None:
@@ -376,6 +386,71 @@ class Yolov4(object):
             raise ValueError('evaluate: the generator is empty')
         mean = sums / images
         return {'loss': float(mean[0]), 'box': float(mean[1]), 'conf': float(mean[2]), 'class': float(mean[3]), 'images': images}
+
+    def evaluate_map(self, data, img_folder_path=None, bs=None, *, iou_thresholds=(0.5,), channel_order='rgb'):
+        """VOC mAP with the matching on the device: the numbers of `export_gt` + `export_prediction` + `eval_map`, without the
+        text files.  `data` is an annotation file path (then `img_folder_path` is required, images are looked up by file name as
+        `export_prediction` does, and `bs` defaults to max_batch) or a `DataGenerator`: its `annotation_lines`, `folder_path` and
+        `batch_size` are used, in annotation order -- its shuffle and augmentation are not.  Images are read, batched (`bs`
+        images per batch, in file order) and preprocessed as `export_prediction` does (`preprocess_u8_batch`; the letterbox
+        path with its box map on a letterbox=True model; this model's thresholds).  Per batch the kept boxes stay on the device:
+        `y4_map_match` matches them against the ground truth -- the annotation line's boxes as `export_gt` reads them: raw-image
+        pixels, annotation order, every box (no shuffle, no max_boxes cut; at most 256 per image), as float32 -- and one copy
+        brings scores, classes, valid and the true-positive flags back; `mapeval.MapAccumulator` turns them into AP.
+        iou_thresholds: 1..16 values; -> `eval_map`'s keys (mAP, ap, tp, fp, n_gt, n_images, n_det) at iou_thresholds[0], plus
+        per_threshold {thr: {mAP, ap, tp, fp}} and mAP_mean (with numpy.arange(0.5, 1.0, 0.05) the COCO-style summary under VOC
+        interpolation).  (A class name with a blank in it, COCO's "wine glass", is no obstacle here; the text files cannot carry it.)
+        channel_order: 'rgb' (default) feeds the images as `DataGenerator` and `fit` feed them -- the order the model is trained
+        on; 'bgr' feeds what `export_prediction` feeds, the reference's unflipped cv2.imread, and reproduces that pipeline."""
+        from .data import MAP_MAX_GT, read_map_annotations
+        from .mapeval import MapAccumulator
+        if channel_order not in ('rgb', 'bgr'):
+            raise ValueError(f"channel_order must be 'rgb' or 'bgr', got {channel_order!r}")
+        if isinstance(data, (str, os.PathLike)):
+            if img_folder_path is None:
+                raise ValueError('evaluate_map: an annotation file needs img_folder_path')
+            with open(data) as fh:
+                items = read_map_annotations(fh.readlines(), self.num_classes)
+            paths = [os.path.join(img_folder_path, name.split(os.sep)[-1]) for name, _, _ in items]
+            bs = self._max_batch if bs is None else int(bs)
+        else:
+            items = read_map_annotations(data.annotation_lines, self.num_classes)
+            paths = [os.path.join(data.folder_path, name) for name, _, _ in items]
+            bs = int(data.batch_size) if bs is None else int(bs)
+        if bs < 1:
+            raise ValueError(f'evaluate_map: bs {bs}')
+        if not items:
+            raise ValueError('evaluate_map: no annotation lines')
+        self._ensure_tuned()
+        eng = self.engine
+        torch = eng.torch
+        iou, score = self._thresholds
+        acc = MapAccumulator(self.class_names, iou_thresholds)
+        step = min(bs, eng.max_batch)              # a batch larger than the engine's goes through it in chunks, as predict does
+        for start in range(0, len(items), bs):
+            for i0 in range(start, min(start + bs, len(items)), step):
+                part = items[i0:min(i0 + step, start + bs)]
+                n = len(part)
+                raws = [prepost.imread_rgb(pth) for pth in paths[i0:i0 + n]]
+                if channel_order == 'bgr':
+                    raws = [r[:, :, ::-1] for r in raws]
+                imgs, box_map = eng.preprocess_u8_batch(raws, letterbox=self._letterbox, pad_value=self._pad_value)
+                side = np.zeros((n, MAP_MAX_GT * 5 + 3), dtype=np.float32)      # per image: boxes | w, h | count (as int32 bits)
+                for k, (raw, (_, _, boxes)) in enumerate(zip(raws, part)):
+                    side[k, :boxes.size] = boxes.reshape(-1)
+                    side[k, MAP_MAX_GT * 5:MAP_MAX_GT * 5 + 2] = raw.shape[1], raw.shape[0]
+                    side[k, MAP_MAX_GT * 5 + 2:].view(np.int32)[0] = len(boxes)
+                side_dev = torch.from_numpy(side).to(eng.device)
+                gt_dev = side_dev[:, :MAP_MAX_GT * 5].contiguous().view(n, MAP_MAX_GT, 5)
+                scale_dev = side_dev[:, MAP_MAX_GT * 5:MAP_MAX_GT * 5 + 2].contiguous()
+                count_dev = side_dev[:, MAP_MAX_GT * 5 + 2].contiguous().view(torch.int32)
+                flat, outs, tp_mask = eng.alloc_map_outputs_flat(n)
+                eng.forward_device(imgs)
+                eng.decode_nms_device(n, outs, iou, score, box_map=box_map if self._letterbox else None)
+                eng.map_match_device(outs, scale_dev, gt_dev, count_dev, acc.iou_thresholds, tp_mask=tp_mask)
+                scores, classes, valid, tp = eng.map_outputs_to_host(flat, n)
+                acc.add([stem for _, stem, _ in part], scores, classes, valid, tp, [boxes[:, 4] for _, _, boxes in part])
+        return acc.result()
 
     # ---- reference models.py:95-98
     def preprocess_img(self, img):

@@ -44,6 +44,35 @@ def read_annotation_lines(annotation_path, test_size=None, random_seed=5566):
     return train_test_split(lines, test_size=test_size, random_state=random_seed)
 
 
+MAP_MAX_GT = 256                  # ground-truth rows per image y4_map_match takes
+
+
+def read_map_annotations(annotation_lines, num_classes):
+    """Annotation lines "path x1,y1,x2,y2,cls ..." as `Yolov4.export_gt` reads them, for `Yolov4.evaluate_map`: per line
+    (path field, stem, boxes float32 [k, 5]) with `float(v)` values in raw-image pixels, in annotation order -- not shuffled
+    and not cut to max_boxes (`DataGenerator._read` does both).  The stem is the file name up to its first dot, the name of
+    the text files `export_gt` / `export_prediction` write.  ValueError: more than 256 boxes on an image, a class id outside
+    [0, num_classes), two lines with the same stem."""
+    out, seen = [], set()
+    for line in annotation_lines:
+        if not line.strip():
+            continue
+        fields = line.split(' ')
+        name = fields[0].strip()
+        stem = name.split(os.sep)[-1].split('.')[0]
+        if stem in seen:
+            raise ValueError(f"two annotation lines with the stem {stem!r}")
+        seen.add(stem)
+        rows = [[float(v) for v in obj.strip().split(',')] for obj in fields[1:] if obj.strip()]
+        if len(rows) > MAP_MAX_GT:
+            raise ValueError(f"{name}: {len(rows)} boxes, more than {MAP_MAX_GT}")
+        for row in rows:
+            if len(row) != 5 or not 0 <= int(row[4]) < num_classes:
+                raise ValueError(f"{name}: box {row}: x1,y1,x2,y2,class with class in [0, {num_classes})")
+        out.append((name, stem, np.array(rows, dtype=np.float32).reshape(-1, 5)))
+    return out
+
+
 def _assign(true_boxes, input_shape, anchors, num_classes):
     """The assignment of every used row -> (xy [bs,mb,2], wh [bs,mb,2] float32, per image a list of
     (scale, row, col, anchor, row index k, class id) in row order)."""

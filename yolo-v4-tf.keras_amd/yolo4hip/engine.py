@@ -515,6 +515,65 @@ class Engine:
                                                         ext.ptr(k), ext.stream_ptr()))
         return outs
 
+    # ---------------------------------------------------------------- VOC mAP matching
+    def alloc_map_outputs_flat(self, n):
+        """What `Yolov4.evaluate_map` needs of a batch as views of ONE int32 device block -- scores, classes, valid and the
+        tp mask of `map_match_device` -- so that they reach the host in a single copy (`map_outputs_to_host`); the boxes
+        are a tensor of their own and stay on the device.  -> (flat int32 tensor, outs for `decode_nms_device` (boxes, scores,
+        classes, valid, no kept indices), tp_mask int32 view [n, max_total])."""
+        torch = self.torch
+        T = self.T
+        offs = np.cumsum([0, n * T, n * T, n, n * T])
+        flat = torch.empty(int(offs[-1]), dtype=torch.int32, device=self.device)
+        v = [flat[offs[i]:offs[i + 1]] for i in range(4)]
+        boxes = torch.empty((n, T, 4), dtype=torch.float32, device=self.device)
+        outs = (boxes, v[0].view(torch.float32).view(n, T), v[1].view(torch.float32).view(n, T), v[2], None)
+        return flat, outs, v[3].view(n, T)
+
+    def map_outputs_to_host(self, flat, n):
+        """The one copy of `alloc_map_outputs_flat`'s block -> (scores float32 [n,T], classes float32 [n,T], valid int32 [n],
+        tp_mask uint32 [n,T]) as numpy views of it."""
+        T = self.T
+        host = flat.cpu().numpy()
+        offs = np.cumsum([0, n * T, n * T, n, n * T])
+        return (host[offs[0]:offs[1]].view(np.float32).reshape(n, T), host[offs[1]:offs[2]].view(np.float32).reshape(n, T),
+                host[offs[2]:offs[3]], host[offs[3]:offs[4]].view(np.uint32).reshape(n, T))
+
+    def map_match_device(self, outs, scale_dev, gt_dev, gt_count_dev, iou_thresholds, debug=False, tp_mask=None):
+        """y4_map_match on the outputs of `decode_nms_device` (outs = boxes, scores, classes, valid, ...): the kept boxes of
+        each image, scaled to raw-image pixels by scale_dev (float32 cuda [n,2]: w, h), are matched against gt_dev (float32
+        cuda [n,max_gt,5]: x1, y1, x2, y2, class in raw-image pixels, annotation order; gt_count_dev int32 [n]) by the rule of
+        `evalmap.eval_map`, once per IoU threshold (1..16 of them).  -> tp_mask, an int32 cuda tensor [n,max_total] whose bit t
+        says "true positive at iou_thresholds[t]" (written into `tp_mask` when given); with debug=True
+        (tp_mask, best_iou float64 [n,max_total], match int32 [n,max_total], gt_used int32 [n,max_gt]).  Asynchronous."""
+        torch = self.torch
+        boxes, scores, classes, valid = outs[:4]
+        n, T = scores.shape
+        thr = [float(t) for t in iou_thresholds]
+        if gt_dev.dim() != 3 or gt_dev.shape[0] != n or gt_dev.shape[2] != 5 or gt_dev.dtype != torch.float32 \
+                or not gt_dev.is_contiguous():
+            raise ValueError(f"gt_dev must be a contiguous float32 tensor [{n},max_gt,5], got {gt_dev.dtype} {tuple(gt_dev.shape)}")
+        if tuple(scale_dev.shape) != (n, 2) or scale_dev.dtype != torch.float32 or not scale_dev.is_contiguous():
+            raise ValueError(f"scale_dev must be a contiguous float32 tensor [{n},2], got {scale_dev.dtype} {tuple(scale_dev.shape)}")
+        if tuple(gt_count_dev.shape) != (n,) or gt_count_dev.dtype != torch.int32 or not gt_count_dev.is_contiguous():
+            raise ValueError(f"gt_count_dev must be a contiguous int32 tensor [{n}], got {gt_count_dev.dtype} {tuple(gt_count_dev.shape)}")
+        max_gt = gt_dev.shape[1]
+        if tp_mask is None:
+            tp_mask = torch.empty((n, T), dtype=torch.int32, device=self.device)
+        elif tuple(tp_mask.shape) != (n, T) or tp_mask.dtype != torch.int32 or not tp_mask.is_contiguous():
+            raise ValueError(f"tp_mask must be a contiguous int32 tensor [{n},{T}]")
+        best = match = used = None
+        if debug:
+            best = torch.empty((n, T), dtype=torch.float64, device=self.device)
+            match = torch.empty((n, T), dtype=torch.int32, device=self.device)
+            used = torch.empty((n, max_gt), dtype=torch.int32, device=self.device)
+        arr = (C.c_double * max(len(thr), 1))(*thr)
+        with torch.cuda.device(self.device):
+            ext.check(self.lib.y4_map_match(ext.ptr(boxes), ext.ptr(scores), ext.ptr(classes), ext.ptr(valid), n, T,
+                                            ext.ptr(scale_dev), ext.ptr(gt_dev), ext.ptr(gt_count_dev), max_gt, arr, len(thr),
+                                            ext.ptr(tp_mask), ext.ptr(best), ext.ptr(match), ext.ptr(used), ext.stream_ptr()))
+        return (tp_mask, best, match, used) if debug else tp_mask
+
     def predict_device(self, imgs_dev, outs=None):
         """The whole hot path on device buffers: forward + decode + NMS (async on the current stream)."""
         n = imgs_dev.shape[0]

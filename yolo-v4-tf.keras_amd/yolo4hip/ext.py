@@ -134,6 +134,7 @@ SYMBOLS = {
     "y4_resize_u8_ragged": (_I, [_VP, _VP, _I, _VP, _I, _I, _I, _VP]),
     "y4_augment_u8_ragged": (_I, [_VP, _VP, _I, _VP, _I, _I, _I, _VP]),
     "y4_mosaic_u8_ragged": (_I, [_VP, _VP, _VP, _I, _VP, _I, _I, _I, _VP]),
+    "y4_map_match": (_I, [_VP, _VP, _VP, _VP, _I, _I, _VP, _VP, _VP, _I, C.POINTER(C.c_double), _I, _VP, _VP, _VP, _VP, _VP]),
     "y4_spp": (_I, [_I, _VP, _I, _I, _I, _VP]),
     "y4_spp_hw": (_I, [_I, _VP, _I, _I, _I, _I, _VP]),
 }
