@@ -183,6 +183,23 @@ int y4_loss_scratch_floats(y4_handle h, int n, size_t* floats);
  * outside the grids are ignored. */
 int y4_loss(y4_handle h, int n, const int32_t* records_dev, const int32_t* counts_dev, const float* xywh_dev, int max_boxes,
             float iou_loss_thresh, float* scratch_dev, size_t scratch_floats, float* out_dev, void* stream);
+/* The box term of the handle: kind 0 = GIoU (the default; what loss.py has switched on, loss.py:156), 1 = CIoU (the line under
+ * it, loss.py:157: bbox_ciou, loss.py:63-113).  Host-only state, settable at any time, no effect on the workspace, not a
+ * scheduling choice (y4_copy_schedule does not carry it); any other kind returns Y4_EINVAL.  It is read by y4_loss, y4_loss_grad,
+ * y4_head_grad, y4_block_grad and y4_block_grad_scaled at the call.  With kind 1 the box term of a responsible lane is
+ *     (2 - lw lh / input_area) * (1 - ciou),   ciou = iou - p2 / c2 - a v,
+ *     iou = inter / (union + 1e-9), both areas taken from the corners (the predicted corners after min / max normalisation),
+ *     p2 = squared distance of the centres, c2 = squared diagonal of the enclosing box (a plain division, no divide_no_nan),
+ *     v = 4 (atan(pw / (ph + 1e-9)) - atan(lw / (lh + 1e-9)))^2 / pi^2,   a = v / (1 - iou + v)
+ * with the weight 3.54 and everything around it (decode without xyscale, confidence and class terms, the ignore mask with its
+ * own IoU and 1e-7) unchanged.  Its derivative is what TensorFlow's autodiff of that text gives w.r.t. (tx, ty, tw, th): the
+ * reference has no stop_gradient, so a v = v^2 / (1 - iou + v) is differentiated as a whole (unlike Darknet's constant a), through
+ * both uses of iou, through p2, and through c2 via the enclosing corners; at a tie of a maximum / minimum the strict comparison
+ * decides, as for GIoU.  Where the reference itself is non-finite (1 - iou + v == 0, c2 == 0) the result is some non-finite
+ * value; nothing else is non-finite.  With kind 0 every entry point returns the bits it returned before this switch existed. */
+int y4_set_box_loss(y4_handle h, int kind);
+/* -> the kind (0 / 1), or a negative error code */
+int y4_get_box_loss(y4_handle h);
 
 /* ---- Head fine-tuning: the three detection convs (93 / 101 / 109; reference custom_layers.py yolov4_neck, the three
  * conv(..., activation=None, batch_norm=False) calls) trained on a frozen backbone and neck -- in Keras terms every layer

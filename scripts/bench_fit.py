@@ -5,7 +5,7 @@ gradient + update written in torch ops on the device (autograd through scripts/b
 over heads = X W^T + b, `matmul` for dW, torch.optim.Adam): the thing the kernels replace.  Default: 608^2, 80 classes, batch 32,
 bf16 compute, shipped schedule.  Writes profiles/fit/bench_fit.json.
 
-  python scripts/bench_fit.py [--size 608] [--classes 80] [--batch 32] [--dtype bf16] [--reps 30] [--out PATH]
+  python scripts/bench_fit.py [--size 608] [--classes 80] [--batch 32] [--dtype bf16] [--reps 30] [--box-loss giou|ciou] [--out PATH]
 
 Timing: hip events around one call, 5 warm-up calls, the median of --reps; the shader clock read afterwards is noted."""
 import argparse
@@ -28,6 +28,7 @@ def main():
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--dtype", default="bf16")
     ap.add_argument("--reps", type=int, default=30)
+    ap.add_argument("--box-loss", default="giou", choices=("giou", "ciou"), help="the box term the engine evaluates and differentiates")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "fit", "bench_fit.json"))
     a = ap.parse_args()
     import torch
@@ -44,7 +45,7 @@ def main():
     engines = {}
     for key, retain in (("plain", False), ("retain", True)):
         e = engines[key] = Engine(ncls, cfg, max_batch=n, dtype=a.dtype, device="cuda:0", alias_workspace=True,
-                                  retain_head_inputs=retain)
+                                  retain_head_inputs=retain, box_loss=a.box_loss)
         e.load_weight_blob(flat)
         schedule = e.ensure_schedule(tune=False, verbose=False)
     eng = engines["retain"]
@@ -146,7 +147,7 @@ def main():
     except Exception:
         pass
     step = fwd["retain"][0] + loss_grad[0] + adam[0]
-    doc = {"shape": {"size": a.size, "classes": ncls, "batch": n, "dtype": a.dtype, "max_boxes": LC.MAX_BOXES,
+    doc = {"shape": {"size": a.size, "classes": ncls, "batch": n, "dtype": a.dtype, "max_boxes": LC.MAX_BOXES, "box_loss": a.box_loss,
                      "schedule": list(schedule)[:1]},
            "ms_median_min_max": {"forward_retain_off": fwd["plain"], "forward_retain_on": fwd["retain"],
                                  "assign_plus_loss_plus_head_grad": loss_grad, "head_grad_alone": grad_only,
@@ -157,7 +158,8 @@ def main():
            "speedup_over_torch_baseline": base[0] / (loss_grad[0] + adam[0]),
            "head_input_bytes": x_bytes, "achieved_GBps_head_grad_on_head_inputs": x_bytes / (grad_only[0] * 1e-3) / 1e9,
            "act_bytes": {k: e.act_bytes for k, e in engines.items()},
-           "max_diff_kernel_vs_torch_dw_rel_to_max": rel, "reps": a.reps, "sclk_after": clock}
+           "max_diff_kernel_vs_torch_dw_rel_to_max": rel if a.box_loss == "giou" else None,      # (the torch baseline is the GIoU formula)
+           "reps": a.reps, "sclk_after": clock}
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
     with open(a.out, "w") as fh:
         json.dump(doc, fh, indent=1)

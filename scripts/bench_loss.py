@@ -3,7 +3,7 @@
 formula in torch ops on the GPU over y4_get_heads' dense heads (what a user without the kernel would write), and against
 one forward step.  Default: 608^2, 80 classes, batch 32, bf16 compute.  Writes profiles/loss/bench_loss.json.
 
-  python scripts/bench_loss.py [--size 608] [--classes 80] [--batch 32] [--dtype bf16] [--reps 30] [--out PATH]
+  python scripts/bench_loss.py [--size 608] [--classes 80] [--batch 32] [--dtype bf16] [--reps 30] [--box-loss giou|ciou] [--out PATH]
 
 Timing: hip events around one call, 5 warm-up calls, the median of --reps; the shader clock read afterwards is noted."""
 import argparse
@@ -59,6 +59,7 @@ def main():
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--dtype", default="bf16")
     ap.add_argument("--reps", type=int, default=30)
+    ap.add_argument("--box-loss", default="giou", choices=("giou", "ciou"), help="the box term the engine evaluates and differentiates")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "loss", "bench_loss.json"))
     a = ap.parse_args()
     import torch
@@ -70,7 +71,7 @@ def main():
     from yolo4hip.plan import build_plan
     hw, n, ncls = (a.size, a.size), a.batch, a.classes
     cfg = make_config(a.size)
-    eng = Engine(ncls, cfg, max_batch=n, dtype=a.dtype, device="cuda:0", alias_workspace=True)
+    eng = Engine(ncls, cfg, max_batch=n, dtype=a.dtype, device="cuda:0", alias_workspace=True, box_loss=a.box_loss)
     eng.load_weight_blob(W.flatten(W.synth_weights(build_plan(hw, ncls), seed=1)))
     schedule = eng.ensure_schedule(tune=False, verbose=False)
     imgs = torch.from_numpy(W.synth_images(n, a.size, seed=1)).to(eng.device)
@@ -123,7 +124,7 @@ def main():
         clock = [l.strip() for l in smi.splitlines() if "sclk" in l][:1]
     except Exception:
         pass
-    doc = {"shape": {"size": a.size, "classes": ncls, "batch": n, "dtype": a.dtype, "max_boxes": LC.MAX_BOXES,
+    doc = {"shape": {"size": a.size, "classes": ncls, "batch": n, "dtype": a.dtype, "max_boxes": LC.MAX_BOXES, "box_loss": a.box_loss,
                      "responsible_cells": responsible, "schedule": list(schedule)[:1]},
            "ms_median_min_max": {"forward": forward, "loss_assign_plus_loss": kernel, "loss_alone": loss_only,
                                  "torch_baseline_get_heads_plus_formula": base},
@@ -131,7 +132,8 @@ def main():
            "loss_share_of_forward_step": kernel[0] / forward[0],
            "head_bytes_stored": head_bytes, "head_bytes_touched": touched,
            "achieved_GBps_on_touched_bytes": touched / (loss_only[0] * 1e-3) / 1e9,
-           "max_rel_diff_kernel_vs_torch_baseline": rel, "reps": a.reps, "sclk_after": clock}
+           "max_rel_diff_kernel_vs_torch_baseline": rel if a.box_loss == "giou" else None,      # (the torch baseline is the GIoU formula)
+           "reps": a.reps, "sclk_after": clock}
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
     with open(a.out, "w") as fh:
         json.dump(doc, fh, indent=1)

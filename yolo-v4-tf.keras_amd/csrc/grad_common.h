@@ -26,7 +26,7 @@ __device__ inline float conf_grad(const LossIn& p, const TrueBoxes& tb, int nb, 
 //     d giou = (A - B) d inter + B d area_p + E d enclose,  A = 1 / (union + eps), B = -inter / (union + eps)^2 + 1 / enclose,
 //     E = -union / enclose^2
 // and the corners x1 = px - pw / 2, x2 = px + pw / 2 carry it to px (stride * s (1 - s) to tx) and pw (pw itself to tw).
-__device__ inline void box_grad(const LossIn& p, int s, const PredBox& b, const int32_t* r, float* g) {
+__device__ inline void box_grad_giou(const LossIn& p, int s, const PredBox& b, const int32_t* r, float* g) {
     const float lx = __int_as_float(r[4]), ly = __int_as_float(r[5]), lw = __int_as_float(r[6]), lh = __int_as_float(r[7]);
     const float lx1 = lx - lw * 0.5f, ly1 = ly - lh * 0.5f, lx2 = lx + lw * 0.5f, ly2 = ly + lh * 0.5f;
     const float rx = fminf(b.x2, lx2) - fmaxf(b.x1, lx1), ry = fminf(b.y2, ly2) - fmaxf(b.y1, ly1);
@@ -51,6 +51,46 @@ __device__ inline void box_grad(const LossIn& p, int s, const PredBox& b, const 
     g[1] = k * gpy * p.stride[s] * b.sy * (1.0f - b.sy);
     g[2] = k * gpw * b.pw;
     g[3] = k * gph * b.ph;
+}
+
+// The same for the CIoU box term (y4_set_box_loss(h, 1)), loss.py:63-113 and :156-162 as autodiff runs it: there is no
+// stop_gradient, so a v = v^2 / D, D = 1 - iou + v, is differentiated as a whole, through v and through the iou inside D:
+//     d ciou = (1 - a^2) d iou - (2 a - a^2) d v - d p2 / c2 + p2 / c2^2 d c2
+//     d iou = (A + inter A^2) d inter - inter A^2 d area_p,   A = 1 / (union + 1e-9),   area_p = (x2 - x1) (y2 - y1)
+//     d c2 = 2 ew d ew + 2 eh d eh (the enclosing corners),   d p2 = 2 (px - lx) d px + 2 (py - ly) d py
+//     d v = 8 / pi^2 (atan q - atan ql) / (1 + q^2) d q,   q = pw / (ph + 1e-9):  d q = d pw / (ph + 1e-9) - pw d ph / (ph + 1e-9)^2
+// Ties of a maximum / minimum: the strict comparison decides.  The corner normalisation min(x1, x2) / max(x1, x2) is the identity
+// for pw > 0 and carries the same sum to px at pw == 0, where the chain's factor pw zeroes the width's gradient anyway.
+__device__ inline void box_grad_ciou(const LossIn& p, int s, const PredBox& b, const int32_t* r, float* g) {
+    const float lx = __int_as_float(r[4]), ly = __int_as_float(r[5]), lw = __int_as_float(r[6]), lh = __int_as_float(r[7]);
+    const float px = (b.sx + (float)r[2]) * p.stride[s], py = (b.sy + (float)r[1]) * p.stride[s];     // decode_lane's centre
+    const Ciou c = ciou_parts(b, px, py, lx, ly, lw, lh);
+    const float a2 = c.a * c.a;
+    const float Ki = 1.0f - a2, Kv = a2 - 2.0f * c.a;
+    const float Bi = -c.inter * c.A * c.A;
+    const float cI = Ki * (c.A - Bi), cA = Ki * Bi;
+    const float ic2 = 1.0f / c.c2;
+    const float Ex = 2.0f * c.ew * (c.p2 * ic2 * ic2), Ey = 2.0f * c.eh * (c.p2 * ic2 * ic2);
+    // d ciou / d corner: the intersection and the enclosing diagonal
+    const float gx1 = cI * (c.rx > 0.0f && c.x1 > c.lx1 ? -c.ih : 0.0f) + (c.x1 < c.lx1 ? -Ex : 0.0f);
+    const float gx2 = cI * (c.rx > 0.0f && c.x2 < c.lx2 ? c.ih : 0.0f) + (c.x2 > c.lx2 ? Ex : 0.0f);
+    const float gy1 = cI * (c.ry > 0.0f && c.y1 > c.ly1 ? -c.iw : 0.0f) + (c.y1 < c.ly1 ? -Ey : 0.0f);
+    const float gy2 = cI * (c.ry > 0.0f && c.y2 < c.ly2 ? c.iw : 0.0f) + (c.y2 > c.ly2 ? Ey : 0.0f);
+    const float dvq = Kv * (8.0f / 9.869604401089358f) * c.dat / (1.0f + c.q * c.q);             // (d ciou / d v) (d v / d q)
+    const float gpx = gx1 + gx2 - 2.0f * c.dx * ic2, gpy = gy1 + gy2 - 2.0f * c.dy * ic2;
+    const float gpw = 0.5f * (gx2 - gx1) + cA * c.ch + dvq / c.hq;
+    const float gph = 0.5f * (gy2 - gy1) + cA * c.cw - dvq * (b.pw / (c.hq * c.hq));
+    const float k = -W_BOX * (2.0f - lw * lh / p.input_area);            // d(box term) = -scale * d ciou
+    g[0] = k * gpx * p.stride[s] * b.sx * (1.0f - b.sx);
+    g[1] = k * gpy * p.stride[s] * b.sy * (1.0f - b.sy);
+    g[2] = k * gpw * b.pw;
+    g[3] = k * gph * b.ph;
+}
+
+// the one place the kind (LossIn::box_kind, uniform over a launch) picks the box term's gradient
+__device__ inline void box_grad(const LossIn& p, int s, const PredBox& b, const int32_t* r, float* g) {
+    if (p.box_kind == BOX_CIOU) box_grad_ciou(p, s, b, r, g);
+    else box_grad_giou(p, s, b, r, g);
 }
 
 __device__ inline float class_grad(const int32_t* r, int c, float x) {

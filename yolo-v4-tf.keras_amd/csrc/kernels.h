@@ -166,7 +166,9 @@ struct LossIn {
     const int32_t* counts;           // [n]
     const float* xywh;               // [n, mb, 4]
     const float* imgw;               // [n] weight of each image's loss (1 / N: the batch mean); null for the forward
+    int box_kind;                    // the box term of a responsible lane: BOX_GIOU (loss.py:34-60) or BOX_CIOU (loss.py:63-113)
 };
+enum { BOX_GIOU = 0, BOX_CIOU = 1 };
 struct LossK : LossIn {
     float* partials;                 // [n, strips, 3]
     float* out;                      // [n, 3 scales, 3] box, confidence, class sums

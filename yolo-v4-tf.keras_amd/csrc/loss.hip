@@ -143,6 +143,12 @@ __global__ __launch_bounds__(LOSS_THREADS) void loss_kernel(LossK p) {
             const float enclose = (fmaxf(px2, lx2) - fminf(px1, lx1)) * (fmaxf(py2, ly2) - fminf(py1, ly1));
             const float giou = iou - (enclose == 0.0f ? 0.0f : (enclose - uni) / enclose);      // divide_no_nan
             box_t = (2.0f - lw * lh / p.input_area) * (1.0f - giou);
+            // No if / else on purpose: the GIoU block above stays the text it was, so that its bits cannot move, and CIoU
+            // overwrites its result.  The spare GIoU costs at most max_boxes lanes per image; the kind is uniform over the launch.
+            if (p.box_kind == BOX_CIOU) {                                  // y4_set_box_loss
+                const float px = (pb.sx + (float)col) * p.stride[s], py = (pb.sy + (float)row) * p.stride[s];   // decode_lane's centre
+                box_t = (2.0f - lw * lh / p.input_area) * (1.0f - ciou_parts(pb, px, py, lx, ly, lw, lh).ciou);
+            }
             for (int c = 0; c < p.C; ++c) {
                 const float z = (float)(((uint32_t)r[8 + (c >> 5)] >> (c & 31)) & 1u);
                 cls_t += bce_logits(t[5 + c], z);

@@ -78,6 +78,45 @@ __device__ inline PredBox decode_lane(const LossIn& p, int s, int a, int row, in
     return b;
 }
 
+// CIoU of a responsible lane's decoded box (centre px, py) with its label, loss.py:63-113 as it runs, and what its gradient
+// needs again (grad_common.h: box_grad_ciou):  ciou = iou - p2 / c2 - a v,  iou = inter / (union + 1e-9) with both areas from
+// the corners,  p2 the squared centre distance,  c2 the squared diagonal of the enclosing box (a plain division),
+// v = 4 (atan(pw / (ph + 1e-9)) - atan(lw / (lh + 1e-9)))^2 / pi^2,  a = v / (1 - iou + v).  The reference's min / max
+// normalisation of the corners is kept on the predicted box (a pw underflowed to 0 behaves as there); a label has w, h >= 0.
+struct Ciou {
+    float lx1, ly1, lx2, ly2;        // label corners
+    float x1, y1, x2, y2, cw, ch;    // predicted corners after the normalisation, their differences
+    float rx, ry, iw, ih, inter;     // raw and clamped intersection sides
+    float A;                         // 1 / (union + 1e-9)
+    float iou, ew, eh, c2, dx, dy, p2;
+    float q, hq, dat, v, a;          // q = pw / (ph + 1e-9), hq = ph + 1e-9, dat = atan(q) - atan(label's)
+    float ciou;
+};
+__device__ inline Ciou ciou_parts(const PredBox& b, float px, float py, float lx, float ly, float lw, float lh) {
+    Ciou c;
+    c.lx1 = lx - lw * 0.5f; c.ly1 = ly - lh * 0.5f; c.lx2 = lx + lw * 0.5f; c.ly2 = ly + lh * 0.5f;
+    c.x1 = fminf(b.x1, b.x2); c.y1 = fminf(b.y1, b.y2); c.x2 = fmaxf(b.x1, b.x2); c.y2 = fmaxf(b.y1, b.y2);
+    c.cw = c.x2 - c.x1; c.ch = c.y2 - c.y1;
+    const float area_p = c.cw * c.ch, area_l = (c.lx2 - c.lx1) * (c.ly2 - c.ly1);
+    c.rx = fminf(c.x2, c.lx2) - fmaxf(c.x1, c.lx1); c.ry = fminf(c.y2, c.ly2) - fmaxf(c.y1, c.ly1);
+    c.iw = fmaxf(c.rx, 0.0f); c.ih = fmaxf(c.ry, 0.0f);
+    c.inter = c.iw * c.ih;
+    const float den = area_p + area_l - c.inter + 1e-9f;
+    c.A = 1.0f / den;
+    c.iou = c.inter / den;
+    c.ew = fmaxf(c.x2, c.lx2) - fminf(c.x1, c.lx1); c.eh = fmaxf(c.y2, c.ly2) - fminf(c.y1, c.ly1);
+    c.c2 = c.ew * c.ew + c.eh * c.eh;
+    c.dx = px - lx; c.dy = py - ly;
+    c.p2 = c.dx * c.dx + c.dy * c.dy;
+    c.hq = b.ph + 1e-9f;
+    c.q = b.pw / c.hq;
+    c.dat = atanf(c.q) - atanf(lw / (lh + 1e-9f));
+    c.v = 4.0f * (c.dat * c.dat) / 9.869604401089358f;
+    c.a = c.v / (1.0f - c.iou + c.v);
+    c.ciou = c.iou - c.p2 / c.c2 - c.a * c.v;
+    return c;
+}
+
 // The largest IoU of a lane's decoded box with the image's true boxes, loss.py:166-170
 __device__ inline float max_iou(const TrueBoxes& tb, int nb, const PredBox& b) {
     const float area_p = b.pw * b.ph;

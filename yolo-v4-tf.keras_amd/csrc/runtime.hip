@@ -190,6 +190,9 @@ struct y4_ctx {
     // level 2 of the same switch: the inputs of convs 92 / 100 / 108 (the outputs of convs 91 / 99 / 107) live to the end of the
     // forward too: y4_block_grad reads them
     bool retain_block_in = false;
+    // y4_set_box_loss: the box term y4_loss and the gradient entry points evaluate (kernels.h: BOX_GIOU / BOX_CIOU).  Host-only,
+    // no workspace effect, and no scheduling choice: y4_copy_schedule does not carry it
+    int box_kind = BOX_GIOU;
     // is the head's output of this run written to HBM?  (an LDS pair in front of a head conv: also when that conv's input is retained)
     bool stores_x(const Chain& ch) const { return ch.store_x || (ch.lds_pair && retain_head_in && ops[ch.tail[0]].out_f32); }
 };
@@ -1222,6 +1225,19 @@ static void loss_inputs(y4_handle h, LossIn& k, const int32_t* records, const in
     k.thresh = iou_loss_thresh;
     k.input_area = (float)h->H * (float)h->W;          // input_size ** 2 of the reference (loss.py:158); H * W for a rectangle
     k.records = records; k.counts = counts; k.xywh = xywh; k.imgw = img_weight;
+    k.box_kind = h->box_kind;
+}
+
+int y4_set_box_loss(y4_handle h, int kind) {
+    if (int r = check_handle(h)) return r;
+    Y4_REQUIRE(kind == BOX_GIOU || kind == BOX_CIOU, Y4_EINVAL, "y4_set_box_loss: kind %d (0: GIoU, 1: CIoU)", kind);
+    h->box_kind = kind;
+    return Y4_OK;
+}
+
+int y4_get_box_loss(y4_handle h) {
+    if (int r = check_handle(h)) return r;
+    return h->box_kind;
 }
 
 int y4_loss(y4_handle h, int n, const int32_t* records, const int32_t* counts, const float* xywh, int max_boxes,

@@ -44,7 +44,7 @@ class _KerasLikeModel:
 class Yolov4(object):
     def __init__(self, weight_path=None, class_name_path='coco_classes.txt', config=yolo_config, *,
                  dtype='f32', max_batch=32, synth_seed=0, device=None, device_preprocess=True, tune=None, share_schedule=None,
-                 letterbox=False, pad_value=128):
+                 letterbox=False, pad_value=128, box_loss='giou'):
         # (reference models.py:23 also asserts img_size[0] == img_size[1], 'not support yet': rectangles are supported here)
         assert config['img_size'][0] % config['strides'][-1] == 0, 'must be a multiple of last stride'
         assert config['img_size'][1] % config['strides'][-1] == 0, 'must be a multiple of last stride'
@@ -65,6 +65,11 @@ class Yolov4(object):
         assert self.num_classes > 0, 'no classes detected!'
         self._dtype, self._max_batch, self._synth_seed, self._device = dtype, max_batch, synth_seed, device
         self._device_preprocess = device_preprocess
+        # box_loss: the box term of training_model -- 'giou', what the reference's loss.py has switched on, or 'ciou', its bbox_ciou
+        # (the commented line under it).  training_model.predict, evaluate, fit and its val_loss all run with it; it is no part
+        # of a checkpoint.
+        Engine._box_kind(box_loss)                 # (raises ValueError for an unknown name)
+        self.box_loss = box_loss
         # letterbox=True: predict_img / predict / export_prediction resize each image with its aspect ratio kept, centred on a
         # canvas of uint8 level `pad_value` (Darknet's letterbox_image geometry; the resize is still cv2's uint8 arithmetic and the
         # pad a uint8 level, 128 = 0.502, where Darknet pads 0.5), and the boxes are mapped back to each raw image on the device.
@@ -92,7 +97,7 @@ class Yolov4(object):
         self.plan = build_plan(self.img_size[:2], self.num_classes)
         # alias_workspace: like the reference's Keras model, the facade keeps no intermediate activations (2.7x less HBM)
         self.engine = Engine(self.num_classes, self.config, max_batch=self._max_batch, dtype=self._dtype,
-                             device=self._device, alias_workspace=True)
+                             device=self._device, alias_workspace=True, box_loss=self.box_loss)
         self.yolo_model = _KerasLikeModel(self._tuned_first(self.engine.forward_heads), 'yolo_model')
         print(f"nms iou: {self.config['iou_threshold']} score: {self.config['score_threshold']}")
         self._thresholds = (-1.0, -1.0)  # what inference_model runs with (-1: the config's); load_model changes them
@@ -345,7 +350,7 @@ class Yolov4(object):
         eng = getattr(self, name, None)
         if eng is None:
             eng = Engine(self.num_classes, self.config, max_batch=self._max_batch, dtype=self._dtype,
-                         device=self._device, alias_workspace=True, retain_head_inputs=level)
+                         device=self._device, alias_workspace=True, retain_head_inputs=level, box_loss=self.box_loss)
             setattr(self, name, eng)
         eng.load_weight_blob(self._flat)
         self.engine.copy_schedule_to(eng)

@@ -43,14 +43,15 @@ def _cfg_struct(config, num_classes, max_batch, dtype, max_per_class=100, max_to
 
 class Engine:
     def __init__(self, num_classes, config=None, max_batch=32, dtype="f32", device=None, alias_workspace=False,
-                 retain_head_inputs=False, *, max_per_class=100, max_total=100):
+                 retain_head_inputs=False, *, max_per_class=100, max_total=100, box_loss="giou"):
         self._build(num_classes, config, max_batch, dtype, device, alias_workspace, retain_head_inputs, None,
-                    max_per_class=max_per_class, max_total=max_total)
+                    max_per_class=max_per_class, max_total=max_total, box_loss=box_loss)
 
     def _build(self, num_classes, config, max_batch, dtype, device, alias_workspace, retain_head_inputs, parent, *,
-               max_per_class=100, max_total=100):
+               max_per_class=100, max_total=100, box_loss="giou"):
         """What `__init__` and `sibling` share: the handle, its workspaces and every attribute.  `parent` is None for an engine
         with weights of its own, or the engine whose packed weights and schedule this one takes over."""
+        box_kind = self._box_kind(box_loss)           # (an unknown name is refused before anything is loaded or created)
         import torch
         self.torch = torch
         self.lib = ext.load()
@@ -68,6 +69,11 @@ class Engine:
         self.img_size = self.img_hw[0] if self.img_hw[0] == self.img_hw[1] else self.img_hw
         self.handle = C.c_void_p()
         ext.check(self.lib.y4_create_hw(C.byref(self.cfg), self.img_hw[0], self.img_hw[1], C.byref(self.handle)))
+        # box_loss: the box term of `loss` and of every gradient, 'giou' (what the reference's loss.py has switched on) or 'ciou'
+        # (its bbox_ciou, the line under it); a sibling takes its parent's
+        if box_kind:                              # (the default is the handle's own: nothing to set)
+            ext.check(self.lib.y4_set_box_loss(self.handle, box_kind))
+        self.box_loss = self.BOX_LOSSES[box_kind]
         flops, nbox, hcs, wfl = C.c_int64(), C.c_int32(), C.c_int32(), C.c_int64()
         ext.check(self.lib.y4_model_info(self.handle, C.byref(flops), C.byref(nbox), C.byref(hcs), C.byref(wfl)))
         self.flops_per_image, self.num_boxes = flops.value, nbox.value
@@ -116,8 +122,22 @@ class Engine:
         overlap the other batch's kernels.  Results are those of this engine, bit for bit."""
         e = Engine.__new__(Engine)
         e._build(self.num_classes, self.config, self.max_batch, self.dtype, self.device, self.alias_workspace, self.retain_level, self,
-                 max_per_class=self.cfg.max_per_class, max_total=self.cfg.max_total)
+                 max_per_class=self.cfg.max_per_class, max_total=self.cfg.max_total, box_loss=self.box_loss)
         return e
+
+    BOX_LOSSES = ("giou", "ciou")          # the kinds of y4_set_box_loss, by number
+
+    @classmethod
+    def _box_kind(cls, name):
+        if name not in cls.BOX_LOSSES:
+            raise ValueError(f"box_loss must be one of {cls.BOX_LOSSES}, got {name!r}")
+        return cls.BOX_LOSSES.index(name)
+
+    def set_box_loss(self, name):
+        """The box term `loss_device` / `loss` and every gradient evaluate from now on: 'giou' or 'ciou' (y4_set_box_loss; host
+        state of the handle, settable at any time).  Siblings made later inherit it."""
+        ext.check(self.lib.y4_set_box_loss(self.handle, self._box_kind(name)))
+        self.box_loss = name
 
     # what the Python side remembers of the handle's schedule (`stem_fusion`: tests/test_gpu_api.py; `halo2`: the YOLO4HIP_HALO2 switch)
     _SCHEDULE_SHADOWS = ("stem_fusion", "halo2")

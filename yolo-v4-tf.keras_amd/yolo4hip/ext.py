@@ -90,6 +90,8 @@ SYMBOLS = {
     "y4_loss_assign": (_I, [_VP, _I, _VP, _I, _VP, _VP, _VP, _VP]),
     "y4_loss_scratch_floats": (_I, [_VP, _I, C.POINTER(C.c_size_t)]),
     "y4_loss": (_I, [_VP, _I, _VP, _VP, _VP, _I, _F, _VP, C.c_size_t, _VP, _VP]),
+    "y4_set_box_loss": (_I, [_VP, _I]),
+    "y4_get_box_loss": (_I, [_VP]),
     "y4_set_retain_head_inputs": (_I, [_VP, _I]),
     "y4_loss_grad": (_I, [_VP, _I, _VP, _VP, _VP, _I, _F, _VP, _VP, _VP, _VP, _VP]),
     "y4_head_grad_scratch_floats": (_I, [_VP, _I, C.POINTER(C.c_size_t)]),
