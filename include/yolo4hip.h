@@ -157,6 +157,27 @@ int y4_decode_nms(y4_handle h, int n, float iou_threshold, float score_threshold
 int y4_decode_nms_mapped(y4_handle h, int n, float iou_threshold, float score_threshold, const float* box_map_dev,
                          float* boxes_dev, float* scores_dev, float* classes_dev, int32_t* valid_dev, int32_t* kept_idx_dev,
                          void* stream);
+/* The pair rule of the NMS stage: which earlier kept boxes a candidate is tested against, and with which measure.  Candidates are
+ * visited in the order y4_decode_nms defines (score descending, then box index, then class); a candidate is kept unless an earlier
+ * KEPT candidate -- of its own class (agnostic 0), of any class (agnostic 1) -- has a measure m with m > iou_threshold (strict):
+ *     kind 0 (IoU, the default: tf.image.combined_non_max_suppression):   m = iou
+ *     kind 1 (DIoU-NMS: Zheng et al. 2020, Darknet nms_kind=diounms with beta_nms = beta):
+ *         iou = as for kind 0: corners min / max-normalised per axis, 0 if either area <= 0
+ *         d2  = (cya - cyb)^2 + (cxa - cxb)^2          centres = 0.5 * (lo + hi) of the normalised corners
+ *         c2  = (max(hi) - min(lo))_y^2 + (..)_x^2     squared diagonal of the enclosing box
+ *         m   = c2 == 0 ? iou : iou - pow(d2 / c2, beta)          (beta == 1: the plain quotient, no pow)
+ * all in float32 in this operation order, on the normalised canvas boxes (x / W, y / H) before the clip and before the box map of
+ * y4_decode_nms_mapped -- where the IoU is computed.  On a rectangular canvas the centre distance is therefore in x / W and y / H
+ * units, as in Darknet.  m <= iou: kind 1 keeps a superset of what kind 0 keeps among two boxes.
+ * max_per_class counts per class under both settings of agnostic, and a candidate its class's cap turns away is not kept and
+ * suppresses nothing; max_total is unchanged; with agnostic 1 the up to num_classes candidates of one box collapse to its best class.
+ * Outputs keep their form.  Host-only state, settable at any time, no effect on the workspace, not a scheduling choice
+ * (y4_copy_schedule does not carry it) and not in a checkpoint.  Read at the call by y4_decode_nms, y4_decode_nms_mapped and the
+ * y4_predict* entry points.  Y4_EINVAL for a kind other than 0 / 1, an agnostic other than 0 / 1, and a beta that is not finite or
+ * is <= 0 (beta is validated also for kind 0, which ignores it).  Default (0, 1.0, 0): every entry point returns the bits it
+ * returned before this call existed. */
+int y4_set_nms_rule(y4_handle h, int kind, float beta, int agnostic);
+int y4_get_nms_rule(y4_handle h, int* kind, float* beta, int* agnostic);
 /* ---- Validation loss: the forward of the reference's yolo_loss (loss.py:119-212; training_model, models.py:54-65) over the raw
  * heads y4_forward / y4_set_heads left in the workspace.  (Its gradient: "Head fine-tuning" below.)
  *

@@ -23,6 +23,7 @@
 // later ones, which only an image that has not filled max_total from its best 1024 candidates reaches, of at most
 // SORT_CAP keys through the register bitonic network and wave 0's pass over 64 candidates at a time.
 // IoU is TensorFlow's: corners min/max-normalised, 0 if either area <= 0, suppress iff IoU > threshold.
+// That is the default pair rule; y4_set_nms_rule selects DIoU-NMS (nms_measure) and / or class-agnostic suppression (nms_kernel's AGN).
 #include "kernels.h"
 
 #pragma clang fp contract(off)   // keep the reference's float32 op order (no fused multiply-add)
@@ -285,6 +286,33 @@ __device__ __forceinline__ float iou_tf(const float4 a, const float4 b) {
     return inter / (area_a + area_b - inter);
 }
 
+// The pair rule of y4_set_nms_rule: candidate `a` is suppressed by the kept box `b` iff their measure m > thr (strict).
+// NMS_IOU: m = iou_tf (the call sites below compile to what they were).  NMS_DIOU1 / NMS_DIOU: DIoU-NMS (Zheng et al. 2020; Darknet's
+// nms_kind=diounms),
+//   m = iou - (d2 / c2)^beta,   d2 = squared distance of the centres, c2 = squared diagonal of the enclosing box,
+// on the same min/max-normalised corners as iou_tf and in float32 with this operation order; c2 == 0 (both boxes one point) gives
+// iou.  The boxes are the normalised canvas boxes (x / W, y / H), so on a rectangular canvas the distance is in those units, as in
+// Darknet.  beta == 1 is its own kind: a plain division, no powf.
+// The penalty is >= 0 and a float32 subtraction of it cannot raise iou, so m > thr needs iou > thr: the penalty is computed only for
+// the pairs IoU-NMS would suppress, and for every other pair the value returned is iou, an upper bound of m that is not above thr
+// either -- the same decision on every pair (a NaN iou fails both tests), at IoU's cost for all but a few.
+enum { NMS_IOU = 0, NMS_DIOU1 = 1, NMS_DIOU = 2 };
+template <int KIND>
+__device__ __forceinline__ float nms_measure(const float4 a, const float4 b, float thr, float beta) {
+    const float iou = iou_tf(a, b);
+    if (KIND == NMS_IOU) return iou;
+    if (!(iou > thr)) return iou;
+    const float ay0 = fminf(a.x, a.z), ax0 = fminf(a.y, a.w), ay1 = fmaxf(a.x, a.z), ax1 = fmaxf(a.y, a.w);
+    const float by0 = fminf(b.x, b.z), bx0 = fminf(b.y, b.w), by1 = fmaxf(b.x, b.z), bx1 = fmaxf(b.y, b.w);
+    const float dy = 0.5f * (ay0 + ay1) - 0.5f * (by0 + by1), dx = 0.5f * (ax0 + ax1) - 0.5f * (bx0 + bx1);
+    const float d2 = dy * dy + dx * dx;
+    const float ey = fmaxf(ay1, by1) - fminf(ay0, by0), ex = fmaxf(ax1, bx1) - fminf(ax0, bx0);
+    const float c2 = ey * ey + ex * ex;
+    if (c2 == 0.f) return iou;
+    const float q = d2 / c2;
+    return iou - (KIND == NMS_DIOU1 ? q : powf(q, beta));
+}
+
 // Bitonic sort of skey[0 .. m2) (m2 a power of two >= 64, <= NE * NMS_THREADS), descending, with the keys in registers
 // (element tid + NMS_THREADS * e): partners less than 64 apart are exchanged by wave shuffles and partners NMS_THREADS or
 // more apart sit in the same thread, so only the stages with 64 <= j < NMS_THREADS go through LDS (`xbuf`, m2 keys) and a
@@ -341,6 +369,12 @@ __device__ __forceinline__ void nms_sort_regs(unsigned long long* skey, unsigned
     __syncthreads();
 }
 
+// KIND: the pair measure (nms_measure).  AGN: class-agnostic suppression -- a kept box suppresses later candidates of every class;
+// max_per_class still counts per class, and a candidate its class's cap turns away is not kept and suppresses nothing.  The
+// round-parallel pass keys its heads by class, which is what makes its rounds independent; with one head slot for all classes it
+// would decide one kept box per round behind two workgroup barriers -- the sequence wave 0 walks without them -- so an agnostic
+// launch takes the wave-0 pass on the first chunk too, as C > PAR_MAX_C does.
+template <int KIND, bool AGN>
 __global__ __launch_bounds__(NMS_THREADS) void nms_kernel(const NmsK p) {
     extern __shared__ __attribute__((aligned(16))) char nsm[];
     unsigned long long* skey = (unsigned long long*)nsm;                  // SORT_CAP
@@ -544,7 +578,7 @@ __global__ __launch_bounds__(NMS_THREADS) void nms_kernel(const NmsK p) {
         // ranks in sorted order are their output slots.  Same decisions as the sequential rule (same tests on the same pairs),
         // in as many rounds as the busiest class among the leading candidates has kept boxes (bench input: ~7) of two
         // barriers each, where the wave-0 pass below visits candidates 64 at a time at ~10 us per batch.
-        const bool par = p.C <= PAR_MAX_C && cutoff == ~0ull;      // (the first chunk: m <= NMS_THREADS; the kept lists it leaves are
+        const bool par = !AGN && p.C <= PAR_MAX_C && cutoff == ~0ull;      // (the first chunk: m <= NMS_THREADS; the kept lists it leaves are
                                                                    // what the wave-0 pass of a later chunk continues from)
         if (par) {
             const uint32_t t = (uint32_t)tid;
@@ -588,7 +622,7 @@ __global__ __launch_bounds__(NMS_THREADS) void nms_kernel(const NmsK p) {
                 if (und) {
                     // a head that the class cap turned away suppresses nothing -- and everything later in its class is turned away too
                     if (pflag[h] == 0u) und = false;
-                    else if (iou_tf(cb, sbox[h]) > p.iou_thr) und = false;
+                    else if (nms_measure<KIND>(cb, sbox[h], p.iou_thr, p.beta) > p.iou_thr) und = false;
                 }
             }
             // output slot = number of kept candidates in front (sorted order)
@@ -628,9 +662,12 @@ __global__ __launch_bounds__(NMS_THREADS) void nms_kernel(const NmsK p) {
                     const int kc_reg = j0 + tid < kept ? kcls[j0 + tid] : -2;
                     const int jn = kept - j0 < 64 ? kept - j0 : 64;
                     for (int j = 0; j < jn; ++j) {
-                        if (__builtin_amdgcn_readlane(kc_reg, j) == cls) {
+                        if (AGN) {                                  // every kept box is tested; the class cap counts its own
+                            same += __builtin_amdgcn_readlane(kc_reg, j) == cls ? 1 : 0;
+                            sup = sup || (nms_measure<KIND>(cb, kbox[j0 + j], p.iou_thr, p.beta) > p.iou_thr);
+                        } else if (__builtin_amdgcn_readlane(kc_reg, j) == cls) {
                             ++same;
-                            sup = sup || (iou_tf(cb, kbox[j0 + j]) > p.iou_thr);
+                            sup = sup || (nms_measure<KIND>(cb, kbox[j0 + j], p.iou_thr, p.beta) > p.iou_thr);
                         }
                     }
                 }
@@ -653,9 +690,9 @@ __global__ __launch_bounds__(NMS_THREADS) void nms_kernel(const NmsK p) {
                     }
                     ++kept;
                     bool hit = false;
-                    if (tid > c && !sup && cls == ccls) {
-                        ++same;
-                        hit = iou_tf(cb, kb) > p.iou_thr;
+                    if (tid > c && !sup && (AGN || cls == ccls)) {
+                        if (!AGN || cls == ccls) ++same;
+                        hit = nms_measure<KIND>(cb, kb, p.iou_thr, p.beta) > p.iou_thr;
                     }
                     sup = sup || hit;
                     alive &= ~__ballot(hit);
@@ -725,7 +762,19 @@ int decode_launch(const DecodeK& k, hipStream_t stream, int clear_images) {
 int nms_launch(const NmsK& k, hipStream_t stream) {
     const size_t lds = nms_lds_bytes(k.max_total, k.C);
     Y4_REQUIRE(lds <= 160 * 1024 && k.max_total <= 1024, Y4_EINVAL, "nms: max_total %d needs %zu bytes of LDS", k.max_total, lds);
-    return launch_lds<nms_kernel>(160 * 1024, dim3(k.N), dim3(NMS_THREADS), lds, stream, k);
+    Y4_REQUIRE((k.kind == 0 || k.kind == 1) && (k.agnostic == 0 || k.agnostic == 1) && k.beta > 0.f, Y4_EINVAL,
+               "nms: rule (kind %d, beta %g, agnostic %d)", k.kind, (double)k.beta, k.agnostic);
+    const dim3 g(k.N), b(NMS_THREADS);
+    if (k.kind == 0) {                                   // (beta is not read)
+        if (!k.agnostic) return launch_lds<nms_kernel<NMS_IOU, false>>(160 * 1024, g, b, lds, stream, k);
+        return launch_lds<nms_kernel<NMS_IOU, true>>(160 * 1024, g, b, lds, stream, k);
+    }
+    if (k.beta == 1.0f) {
+        if (!k.agnostic) return launch_lds<nms_kernel<NMS_DIOU1, false>>(160 * 1024, g, b, lds, stream, k);
+        return launch_lds<nms_kernel<NMS_DIOU1, true>>(160 * 1024, g, b, lds, stream, k);
+    }
+    if (!k.agnostic) return launch_lds<nms_kernel<NMS_DIOU, false>>(160 * 1024, g, b, lds, stream, k);
+    return launch_lds<nms_kernel<NMS_DIOU, true>>(160 * 1024, g, b, lds, stream, k);
 }
 
 }  // namespace y4

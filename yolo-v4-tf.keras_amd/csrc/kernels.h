@@ -137,6 +137,9 @@ struct NmsK {
     uint32_t* status;                // [1] bit0: candidate list overflowed its capacity
     FastDiv div_c;                   // id -> (box, class) without integer division (ids < 2^31 checked at y4_create)
     const float* box_map;            // [N][4] {ax, bx, ay, by} applied to the kept boxes before the clip, or null (identity)
+    int kind;                        // y4_set_nms_rule: 0 suppress iff IoU > iou_thr, 1 iff IoU - (d2 / c2)^beta > iou_thr (DIoU-NMS)
+    float beta;                      // (kind 1 only)
+    int agnostic;                    // 1: a kept box suppresses later candidates of every class
 };
 int decode_launch(const DecodeK& k, hipStream_t stream, int clear_images);
 // tuner aid (latency schedules): streams `bytes` of `p` through the L2s so that the next launch starts on cold weights

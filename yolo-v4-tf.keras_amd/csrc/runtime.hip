@@ -11,6 +11,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <cmath>
 #include <vector>
 
 #include "conv_tiles.h"
@@ -193,6 +194,11 @@ struct y4_ctx {
     // y4_set_box_loss: the box term y4_loss and the gradient entry points evaluate (kernels.h: BOX_GIOU / BOX_CIOU).  Host-only,
     // no workspace effect, and no scheduling choice: y4_copy_schedule does not carry it
     int box_kind = BOX_GIOU;
+    // y4_set_nms_rule: the pair rule of the NMS kernel, read at every y4_decode_nms / y4_decode_nms_mapped / y4_predict* call.
+    // Host-only like box_kind: no workspace effect, not carried by y4_copy_schedule, not in a checkpoint
+    int nms_kind = 0;
+    float nms_beta = 1.0f;
+    int nms_agnostic = 0;
     // is the head's output of this run written to HBM?  (an LDS pair in front of a head conv: also when that conv's input is retained)
     bool stores_x(const Chain& ch) const { return ch.store_x || (ch.lds_pair && retain_head_in && ops[ch.tail[0]].out_f32); }
 };
@@ -890,6 +896,7 @@ int run_decode_nms(y4_handle h, int n, float iou_thr, float score_thr, float* bo
         k.status = (uint32_t*)(h->act + h->status_off);
         k.div_c = fastdiv_make((uint32_t)cfg.num_classes);
         k.box_map = box_map;
+        k.kind = h->nms_kind; k.beta = h->nms_beta; k.agnostic = h->nms_agnostic;
         if (int r = nms_launch(k, s)) return r;
         h->counts_clean = h->counts_n <= n;               // (an NMS over fewer images than were decoded leaves counters behind)
     }
@@ -1177,6 +1184,22 @@ int y4_decode_nms_mapped(y4_handle h, int n, float iou_threshold, float score_th
     const float iou = iou_threshold < 0.f ? h->cfg.iou_threshold : iou_threshold;
     const float sc = score_threshold < 0.f ? h->cfg.score_threshold : score_threshold;
     return run_decode_nms(h, n, iou, sc, boxes, scores, classes, valid, kept_idx, (hipStream_t)stream, 0, box_map);
+}
+
+int y4_set_nms_rule(y4_handle h, int kind, float beta, int agnostic) {
+    if (int r = check_handle(h)) return r;
+    Y4_REQUIRE(kind == 0 || kind == 1, Y4_EINVAL, "y4_set_nms_rule: kind %d (0: IoU, 1: DIoU)", kind);
+    Y4_REQUIRE(std::isfinite(beta) && beta > 0.f, Y4_EINVAL, "y4_set_nms_rule: beta %g must be finite and > 0", (double)beta);
+    Y4_REQUIRE(agnostic == 0 || agnostic == 1, Y4_EINVAL, "y4_set_nms_rule: agnostic %d (0 or 1)", agnostic);
+    h->nms_kind = kind; h->nms_beta = beta; h->nms_agnostic = agnostic;
+    return Y4_OK;
+}
+
+int y4_get_nms_rule(y4_handle h, int* kind, float* beta, int* agnostic) {
+    if (int r = check_handle(h)) return r;
+    Y4_REQUIRE(kind && beta && agnostic, Y4_EINVAL, "y4_get_nms_rule: null argument");
+    *kind = h->nms_kind; *beta = h->nms_beta; *agnostic = h->nms_agnostic;
+    return Y4_OK;
 }
 
 static void loss_geometry(y4_handle h, int* gh, int* gw, int* lane_base) {

@@ -44,7 +44,7 @@ class _KerasLikeModel:
 class Yolov4(object):
     def __init__(self, weight_path=None, class_name_path='coco_classes.txt', config=yolo_config, *,
                  dtype='f32', max_batch=32, synth_seed=0, device=None, device_preprocess=True, tune=None, share_schedule=None,
-                 letterbox=False, pad_value=128, box_loss='giou'):
+                 letterbox=False, pad_value=128, box_loss='giou', nms_kind='iou', nms_beta=0.6, nms_agnostic=False):
         # (reference models.py:23 also asserts img_size[0] == img_size[1], 'not support yet': rectangles are supported here)
         assert config['img_size'][0] % config['strides'][-1] == 0, 'must be a multiple of last stride'
         assert config['img_size'][1] % config['strides'][-1] == 0, 'must be a multiple of last stride'
@@ -70,6 +70,13 @@ class Yolov4(object):
         # of a checkpoint.
         Engine._box_kind(box_loss)                 # (raises ValueError for an unknown name)
         self.box_loss = box_loss
+        # nms_kind / nms_beta / nms_agnostic: the pair rule of the NMS stage (Engine.set_nms_rule): 'iou', what the reference's
+        # tf.image.combined_non_max_suppression does, or 'diou' (DIoU-NMS, Darknet's nms_kind=diounms with beta_nms = nms_beta);
+        # nms_agnostic=True lets a kept box suppress later candidates of every class.  It is state of the engines' handles, so
+        # inference_model, predict, predict_img, predict_nonms, export_prediction, evaluate_map and fit(val_map=True) all run with
+        # it, with and without letterbox, before and after load_model and fit; it is no part of a checkpoint.
+        Engine._nms_rule(nms_kind, nms_beta, nms_agnostic)      # (raises ValueError)
+        self.nms_kind, self.nms_beta, self.nms_agnostic = nms_kind, float(nms_beta), bool(nms_agnostic)
         # letterbox=True: predict_img / predict / export_prediction resize each image with its aspect ratio kept, centred on a
         # canvas of uint8 level `pad_value` (Darknet's letterbox_image geometry; the resize is still cv2's uint8 arithmetic and the
         # pad a uint8 level, 128 = 0.502, where Darknet pads 0.5), and the boxes are mapped back to each raw image on the device.
@@ -97,7 +104,8 @@ class Yolov4(object):
         self.plan = build_plan(self.img_size[:2], self.num_classes)
         # alias_workspace: like the reference's Keras model, the facade keeps no intermediate activations (2.7x less HBM)
         self.engine = Engine(self.num_classes, self.config, max_batch=self._max_batch, dtype=self._dtype,
-                             device=self._device, alias_workspace=True, box_loss=self.box_loss)
+                             device=self._device, alias_workspace=True, box_loss=self.box_loss,
+                             nms_kind=self.nms_kind, nms_beta=self.nms_beta, nms_agnostic=self.nms_agnostic)
         self.yolo_model = _KerasLikeModel(self._tuned_first(self.engine.forward_heads), 'yolo_model')
         print(f"nms iou: {self.config['iou_threshold']} score: {self.config['score_threshold']}")
         self._thresholds = (-1.0, -1.0)  # what inference_model runs with (-1: the config's); load_model changes them
@@ -350,7 +358,8 @@ class Yolov4(object):
         eng = getattr(self, name, None)
         if eng is None:
             eng = Engine(self.num_classes, self.config, max_batch=self._max_batch, dtype=self._dtype,
-                         device=self._device, alias_workspace=True, retain_head_inputs=level, box_loss=self.box_loss)
+                         device=self._device, alias_workspace=True, retain_head_inputs=level, box_loss=self.box_loss,
+                         nms_kind=self.nms_kind, nms_beta=self.nms_beta, nms_agnostic=self.nms_agnostic)
             setattr(self, name, eng)
         eng.load_weight_blob(self._flat)
         self.engine.copy_schedule_to(eng)

@@ -43,15 +43,18 @@ def _cfg_struct(config, num_classes, max_batch, dtype, max_per_class=100, max_to
 
 class Engine:
     def __init__(self, num_classes, config=None, max_batch=32, dtype="f32", device=None, alias_workspace=False,
-                 retain_head_inputs=False, *, max_per_class=100, max_total=100, box_loss="giou"):
+                 retain_head_inputs=False, *, max_per_class=100, max_total=100, box_loss="giou",
+                 nms_kind="iou", nms_beta=0.6, nms_agnostic=False):
         self._build(num_classes, config, max_batch, dtype, device, alias_workspace, retain_head_inputs, None,
-                    max_per_class=max_per_class, max_total=max_total, box_loss=box_loss)
+                    max_per_class=max_per_class, max_total=max_total, box_loss=box_loss,
+                    nms_kind=nms_kind, nms_beta=nms_beta, nms_agnostic=nms_agnostic)
 
     def _build(self, num_classes, config, max_batch, dtype, device, alias_workspace, retain_head_inputs, parent, *,
-               max_per_class=100, max_total=100, box_loss="giou"):
+               max_per_class=100, max_total=100, box_loss="giou", nms_kind="iou", nms_beta=0.6, nms_agnostic=False):
         """What `__init__` and `sibling` share: the handle, its workspaces and every attribute.  `parent` is None for an engine
         with weights of its own, or the engine whose packed weights and schedule this one takes over."""
         box_kind = self._box_kind(box_loss)           # (an unknown name is refused before anything is loaded or created)
+        nms_rule = self._nms_rule(nms_kind, nms_beta, nms_agnostic)      # (likewise)
         import torch
         self.torch = torch
         self.lib = ext.load()
@@ -74,6 +77,8 @@ class Engine:
         if box_kind:                              # (the default is the handle's own: nothing to set)
             ext.check(self.lib.y4_set_box_loss(self.handle, box_kind))
         self.box_loss = self.BOX_LOSSES[box_kind]
+        # nms_kind / nms_beta / nms_agnostic: the pair rule of the NMS stage (`set_nms_rule`); a sibling takes its parent's
+        self._apply_nms_rule(nms_rule)
         flops, nbox, hcs, wfl = C.c_int64(), C.c_int32(), C.c_int32(), C.c_int64()
         ext.check(self.lib.y4_model_info(self.handle, C.byref(flops), C.byref(nbox), C.byref(hcs), C.byref(wfl)))
         self.flops_per_image, self.num_boxes = flops.value, nbox.value
@@ -122,7 +127,8 @@ class Engine:
         overlap the other batch's kernels.  Results are those of this engine, bit for bit."""
         e = Engine.__new__(Engine)
         e._build(self.num_classes, self.config, self.max_batch, self.dtype, self.device, self.alias_workspace, self.retain_level, self,
-                 max_per_class=self.cfg.max_per_class, max_total=self.cfg.max_total, box_loss=self.box_loss)
+                 max_per_class=self.cfg.max_per_class, max_total=self.cfg.max_total, box_loss=self.box_loss,
+                 nms_kind=self.nms_kind, nms_beta=self.nms_beta, nms_agnostic=self.nms_agnostic)
         return e
 
     BOX_LOSSES = ("giou", "ciou")          # the kinds of y4_set_box_loss, by number
@@ -138,6 +144,41 @@ class Engine:
         state of the handle, settable at any time).  Siblings made later inherit it."""
         ext.check(self.lib.y4_set_box_loss(self.handle, self._box_kind(name)))
         self.box_loss = name
+
+    NMS_KINDS = ("iou", "diou")            # the kinds of y4_set_nms_rule, by number
+
+    @classmethod
+    def _nms_rule(cls, kind, beta, agnostic):
+        """-> (kind number, beta, agnostic 0 / 1), or ValueError.  beta is validated also for 'iou', which ignores it."""
+        if kind not in cls.NMS_KINDS:
+            raise ValueError(f"nms_kind must be one of {cls.NMS_KINDS}, got {kind!r}")
+        try:
+            b = float(beta)
+        except (TypeError, ValueError):
+            raise ValueError(f"nms_beta must be a finite number > 0, got {beta!r}") from None
+        if not (np.isfinite(b) and b > 0.0):
+            raise ValueError(f"nms_beta must be a finite number > 0, got {beta!r}")
+        if agnostic not in (False, True, 0, 1):
+            raise ValueError(f"nms_agnostic must be False or True, got {agnostic!r}")
+        return cls.NMS_KINDS.index(kind), b, int(bool(agnostic))
+
+    def _apply_nms_rule(self, rule):
+        kind, beta, agnostic = rule
+        if rule != (0, 1.0, 0):                   # (that is the handle's own rule: 'iou' ignores beta, nothing to set)
+            ext.check(self.lib.y4_set_nms_rule(self.handle, kind, 1.0 if kind == 0 else beta, agnostic))
+        self.nms_kind, self.nms_beta, self.nms_agnostic = self.NMS_KINDS[kind], beta, bool(agnostic)
+
+    def set_nms_rule(self, kind, beta=0.6, agnostic=False):
+        """The pair rule every later predict / decode_nms call of this engine runs (y4_set_nms_rule; host state of the handle,
+        settable at any time): kind 'iou' -- suppress iff IoU > iou_threshold, what tf.image.combined_non_max_suppression does --
+        or 'diou' -- iff IoU - (d^2 / c^2)^beta > iou_threshold (DIoU-NMS; Darknet's nms_kind=diounms, beta_nms=0.6); agnostic:
+        a kept box suppresses later candidates of every class, not only its own.  `beta` is ignored by 'iou' but validated.
+        The stream siblings this engine already has follow; siblings made later inherit it."""
+        rule = self._nms_rule(kind, beta, agnostic)
+        ext.check(self.lib.y4_set_nms_rule(self.handle, rule[0], 1.0 if rule[0] == 0 else rule[1], rule[2]))
+        self.nms_kind, self.nms_beta, self.nms_agnostic = self.NMS_KINDS[rule[0]], rule[1], bool(rule[2])
+        for e in getattr(self, "_stream_siblings", []):
+            e.set_nms_rule(kind, beta, agnostic)
 
     # what the Python side remembers of the handle's schedule (`stem_fusion`: tests/test_gpu_api.py; `halo2`: the YOLO4HIP_HALO2 switch)
     _SCHEDULE_SHADOWS = ("stem_fusion", "halo2")
