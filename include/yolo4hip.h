@@ -178,6 +178,46 @@ int y4_decode_nms_mapped(y4_handle h, int n, float iou_threshold, float score_th
  * returned before this call existed. */
 int y4_set_nms_rule(y4_handle h, int kind, float beta, int agnostic);
 int y4_get_nms_rule(y4_handle h, int* kind, float* beta, int* agnostic);
+/* ---- Gathered decode + NMS: ONE NMS over the candidates of several batch rows (tiled inference: the rows are windows of one
+ * photo, see y4_window_u8_ragged).  Row i belongs to group g = row_group_dev[i] (a photo), has slot t = row_slot_dev[i] in it
+ * (0 <= t < max_slots, distinct among a group's rows) and the map m = row_map_dev[i] = {ax, bx, ay, by} from its canvas-normalised
+ * coordinates to the group's normalised coordinates.
+ *
+ * Scratch is the caller's (y4_gather_scratch_bytes; 256-byte aligned), per group: a list of group_cap 64-bit candidate keys, a box
+ * table [max_slots * nbox][4] float32 and one counter on a 256-byte line of its own.  The sequence is
+ *     y4_gather_begin                      zeroes the group counters (one small async memset)
+ *     y4_decode_gather  (any number)       after a y4_forward* / y4_set_heads of n rows: runs the decode stage of y4_decode_nms on rows
+ *                                          0 .. n-1 of the handle and merges every candidate (box b, class c, score s) of row i into
+ *                                          group g's list with the id (t * nbox + b) * C + c, its box mapped with m -- x1, x2 ->
+ *                                          fmaf(x, ax, bx), y1, y2 -> fmaf(y, ay, by), unclipped -- into the group's table.  A
+ *                                          group's rows may lie in different calls (forward chunks).
+ *     y4_nms_gathered                      cand_count_dev[g] = the candidates group g received; then the NMS kernel of y4_decode_nms
+ *                                          over the n_groups lists, under the handle's y4_set_nms_rule, max_total and
+ *                                          max_per_class.  iou_threshold < 0: the config's.
+ * all on one stream, in this order.  Consequences:
+ *   - candidates are visited by score descending, then slot, then box index, then class;
+ *   - the map applies BEFORE the pair measure: IoU / DIoU are taken in the group's (the photo's) normalised coordinates.
+ *     y4_decode_nms_mapped is the opposite: it maps in the output stage, after the decisions;
+ *   - outputs have the form of y4_decode_nms for n_groups images, boxes clipped to [0,1] of the group; kept_idx is
+ *     slot * nbox + box (-1 padded; may be NULL);
+ *   - the order in which candidates arrive in a list varies from run to run; keys are unique and the NMS sorts them, so the outputs
+ *     are the same bits on every run.
+ * CAPACITY: a group that received more than group_cap candidates has lost the excess (which ones is not defined): cand_count_dev[g]
+ * > group_cap tells the caller, who must not use that group's result; the outputs are still written and nothing is accessed out of
+ * range.  group_cap is a capacity to choose, not a measurement: max_slots * nbox * C can never overflow.
+ * Handle state: y4_decode_gather leaves the candidate counters of its n rows at zero, as the NMS stage of y4_decode_nms does, so
+ * plain y4_decode_nms calls and gathered sequences may alternate on one handle.  The row tables live on the device; a row whose
+ * group or slot is out of range contributes nothing; the caller owns everything else about them.
+ * Y4_EINVAL before any launch: n_groups, max_slots or group_cap < 1; max_slots * nbox * C >= 2^31 (the ids a key holds); a null
+ * pointer; scratch not 256-byte aligned; n outside [1, max_batch]. */
+int y4_gather_scratch_bytes(y4_handle h, int n_groups, int max_slots, uint32_t group_cap, size_t* bytes);
+int y4_gather_begin(y4_handle h, int n_groups, int max_slots, uint32_t group_cap, void* scratch_dev, void* stream);
+int y4_decode_gather(y4_handle h, int n, float score_threshold, const int32_t* row_group_dev, const int32_t* row_slot_dev,
+                     const float* row_map_dev /* [n][4] */, int n_groups, int max_slots, uint32_t group_cap, void* scratch_dev,
+                     void* stream);
+int y4_nms_gathered(y4_handle h, int n_groups, int max_slots, uint32_t group_cap, float iou_threshold, void* scratch_dev,
+                    int32_t* cand_count_dev /* [n_groups] */, float* boxes_dev, float* scores_dev, float* classes_dev,
+                    int32_t* valid_dev, int32_t* kept_idx_dev, void* stream);
 /* ---- Validation loss: the forward of the reference's yolo_loss (loss.py:119-212; training_model, models.py:54-65) over the raw
  * heads y4_forward / y4_set_heads left in the workspace.  (Its gradient: "Head fine-tuning" below.)
  *
@@ -530,6 +570,22 @@ typedef struct y4_image_desc {
  * any launch), but the descriptors live on the device and are NOT checked: the caller owns the table's correctness (offsets
  * and sizes inside the source buffer, h, w, out_h, out_w >= 1, the rectangle inside the canvas). */
 int y4_resize_u8_ragged(const uint8_t* src_dev, const y4_image_desc* desc_dev, int n, uint8_t* out_dev, int H, int W,
+                        int pad_value, void* stream);
+/* One WINDOW of a source image for y4_window_u8_ragged: `offset` is the byte offset of the window's first pixel in the source
+ * buffer (image offset + (y0 * image width + x0) * 3), `pitch` the bytes of a source row (3 * image width, >= 3 * w), h x w the
+ * window; the rest as y4_image_desc. */
+typedef struct y4_window_desc {
+    int64_t offset;
+    int32_t pitch;
+    int32_t h, w;
+    int32_t out_h, out_w, pad_top, pad_left;
+} y4_window_desc;                                    /* 40 bytes */
+/* y4_resize_u8_ragged on windows, crop and resize in one launch: slot i of the uint8 [n,H,W,3] batch holds the bytes
+ * y4_resize_u8_ragged writes for a contiguous copy of window i with the same out_h, out_w, pad_top, pad_left.  The bilinear taps
+ * therefore clamp at the WINDOW's edge, not the image's; a window with h == out_h and w == out_w is a plain copy; any number of
+ * descriptors may point into one source image (overlapping tiles of a photo).  Host checks and the caller's ownership of the device
+ * table as for y4_resize_u8_ragged (every window inside its image, pitch >= 3 * w). */
+int y4_window_u8_ragged(const uint8_t* src_dev, const y4_window_desc* desc_dev, int n, uint8_t* out_dev, int H, int W,
                         int pad_value, void* stream);
 /* One image of a ragged batch for y4_augment_u8_ragged: the fields of y4_image_desc, then the augmentation of this image --
  * flip (0 / 1: mirror left-right) and the HSV factors (hue is added, sat and val multiply; 0, 1, 1 change nothing). */

@@ -146,6 +146,29 @@ int decode_launch(const DecodeK& k, hipStream_t stream, int clear_images);
 int l2_flush_launch(const void* p, size_t bytes, void* sink, hipStream_t stream);
 int nms_launch(const NmsK& k, hipStream_t stream);
 
+// tiled.hip: windows of source images -> the uint8 network batch; the decode stage's per-row candidate lists -> one list per group
+int window_u8_ragged_launch(const uint8_t* src, const y4_window_desc* desc, int n, uint8_t* out, int H, int W, int pad,
+                            hipStream_t stream);
+struct GatherK {
+    const float* dboxes;             // [n, nbox, 4] what the decode stage wrote (canvas-normalised)
+    const unsigned long long* keys;  // [n, cap]
+    uint32_t* counts;                // [n * COUNT_STRIDE]; the row's workgroup resets its counter once it has read it
+    uint32_t cap;
+    int C, nbox;
+    const int32_t* row_group;        // [n] group of a row
+    const int32_t* row_slot;         // [n] its slot in the group's box table
+    const float* row_map;            // [n][4] {ax, bx, ay, by}: canvas-normalised -> group-normalised
+    int n_groups, max_slots;
+    uint32_t group_cap;
+    unsigned long long* gkeys;       // [n_groups, group_cap]
+    float* gboxes;                   // [n_groups, max_slots * nbox, 4]
+    uint32_t* gcounts;               // [n_groups * COUNT_STRIDE]
+    uint32_t* status;                // [1] bit0, as NmsK
+    FastDiv div_c;
+};
+int gather_launch(const GatherK& k, int n, hipStream_t stream);
+int gather_counts_launch(const uint32_t* gcounts, int32_t* out, int n_groups, hipStream_t stream);
+
 // loss.hip: the reference's yolo_loss forward over the raw heads, and the label assignment as responsible-cell records
 // (record: int32 words [scale, row, col, anchor, bits of x, y, w, h, class mask words]; sorted by (scale, row, col, anchor))
 struct LossAssignK {

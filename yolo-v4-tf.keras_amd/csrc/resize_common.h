@@ -41,6 +41,31 @@ __device__ __forceinline__ void resize_px_u8(const uint8_t* __restrict__ src, in
     }
 }
 
+// resize_px_u8 on a WINDOW of a larger image (y4_window_u8_ragged): `src` is the window's first pixel, `pitch` the bytes of a
+// source row (>= 3 * w), h x w the window.  The coefficients and the tap clamp are those of the h x w window (lin_coeff clamps at
+// src - 1 = the window's last row / column), never the image around it, so the pixel is what resize_px_u8 gives on a contiguous
+// copy of the window.  A separate overload: the packed callers above keep their int index arithmetic.
+__device__ __forceinline__ void resize_px_u8(const uint8_t* __restrict__ src, int64_t pitch, int h, int w, int dh, int dw, int y, int x,
+                                             int v[3]) {
+    int x0, x1, ax0, ax1, y0, y1, ay0, ay1;
+    lin_coeff(x, dw, w, x0, x1, ax0, ax1);
+    lin_coeff(y, dh, h, y0, y1, ay0, ay1);
+    const bool same = (h == dh && w == dw);
+    const uint8_t* r0 = src + (same ? y : y0) * pitch;
+    const uint8_t* r1 = src + y1 * pitch;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        if (same) {
+            v[c] = r0[x * 3 + c];
+        } else {
+            const int top = r0[x0 * 3 + c] * ax0 + r0[x1 * 3 + c] * ax1;   // x2048
+            const int bot = r1[x0 * 3 + c] * ax0 + r1[x1 * 3 + c] * ax1;
+            const int r = (((ay0 * (top >> 4)) >> 16) + ((ay1 * (bot >> 4)) >> 16) + 2) >> 2;
+            v[c] = r < 0 ? 0 : (r > 255 ? 255 : r);
+        }
+    }
+}
+
 // A thread's PX consecutive RGB pixels -> memory: PX = 4 stores its 12 bytes as three dwords (`o` 4-byte aligned), so that a
 // wave covers 768 contiguous bytes; PX = 1 stores three bytes.
 template <int PX>

@@ -1202,6 +1202,99 @@ int y4_get_nms_rule(y4_handle h, int* kind, float* beta, int* agnostic) {
     return Y4_OK;
 }
 
+// ---- gathered decode + NMS (tiled inference).  The caller's scratch: [n_groups] counters, one per 256-byte line | the groups' key
+// lists [n_groups][group_cap] | the groups' box tables [n_groups][max_slots * nbox][4], each part 256-byte aligned.
+struct GatherLayout { size_t keys_off, boxes_off, bytes; };
+static int gather_layout(y4_handle h, const char* who, int n_groups, int max_slots, uint32_t group_cap, GatherLayout* L) {
+    if (int r = check_handle(h)) return r;
+    Y4_REQUIRE(n_groups >= 1 && max_slots >= 1 && group_cap >= 1, Y4_EINVAL, "%s: n_groups %d, max_slots %d, group_cap %u (all >= 1)", who,
+               n_groups, max_slots, group_cap);
+    Y4_REQUIRE((int64_t)max_slots * h->nbox * h->cfg.num_classes < (1ll << 31), Y4_EINVAL,
+               "%s: %d slots of %d boxes and %d classes exceed the 2^31 candidate ids a key holds", who, max_slots, h->nbox,
+               h->cfg.num_classes);
+    auto up = [](size_t x) { return (x + 255) / 256 * 256; };
+    L->keys_off = up((size_t)n_groups * COUNT_STRIDE * sizeof(uint32_t));
+    L->boxes_off = L->keys_off + up((size_t)n_groups * group_cap * 8);
+    L->bytes = L->boxes_off + up((size_t)n_groups * max_slots * h->nbox * 16);
+    return Y4_OK;
+}
+static int gather_scratch_check(const char* who, const void* scratch) {
+    Y4_REQUIRE(scratch, Y4_EINVAL, "%s: null scratch", who);
+    Y4_REQUIRE(((uintptr_t)scratch & 255) == 0, Y4_EINVAL, "%s: scratch must be 256-byte aligned", who);
+    return Y4_OK;
+}
+
+int y4_gather_scratch_bytes(y4_handle h, int n_groups, int max_slots, uint32_t group_cap, size_t* bytes) {
+    GatherLayout L;
+    if (int r = gather_layout(h, "y4_gather_scratch_bytes", n_groups, max_slots, group_cap, &L)) return r;
+    Y4_REQUIRE(bytes, Y4_EINVAL, "y4_gather_scratch_bytes: null argument");
+    *bytes = L.bytes;
+    return Y4_OK;
+}
+
+int y4_gather_begin(y4_handle h, int n_groups, int max_slots, uint32_t group_cap, void* scratch_dev, void* stream) {
+    GatherLayout L;
+    if (int r = gather_layout(h, "y4_gather_begin", n_groups, max_slots, group_cap, &L)) return r;
+    if (int r = gather_scratch_check("y4_gather_begin", scratch_dev)) return r;
+    Y4_CHECK_HIP(hipMemsetAsync(scratch_dev, 0, (size_t)n_groups * COUNT_STRIDE * sizeof(uint32_t), (hipStream_t)stream));
+    return Y4_OK;
+}
+
+int y4_decode_gather(y4_handle h, int n, float score_threshold, const int32_t* row_group_dev, const int32_t* row_slot_dev,
+                     const float* row_map_dev, int n_groups, int max_slots, uint32_t group_cap, void* scratch_dev, void* stream) {
+    GatherLayout L;
+    if (int r = gather_layout(h, "y4_decode_gather", n_groups, max_slots, group_cap, &L)) return r;
+    if (int r = check_ready(h, n)) return r;
+    if (int r = gather_scratch_check("y4_decode_gather", scratch_dev)) return r;
+    Y4_REQUIRE(row_group_dev && row_slot_dev && row_map_dev, Y4_EINVAL, "y4_decode_gather: null row table");
+    const float sc = score_threshold < 0.f ? h->cfg.score_threshold : score_threshold;
+    hipStream_t s = (hipStream_t)stream;
+    if (int r = run_decode_nms(h, n, 0.f, sc, nullptr, nullptr, nullptr, nullptr, nullptr, s, 1)) return r;
+    GatherK k{};
+    k.dboxes = (const float*)(h->act + h->dbox_off);
+    k.keys = (const unsigned long long*)(h->act + h->keys_off);
+    k.counts = (uint32_t*)(h->act + h->counts_off);
+    k.cap = h->cand_cap; k.C = h->cfg.num_classes; k.nbox = h->nbox;
+    k.row_group = row_group_dev; k.row_slot = row_slot_dev; k.row_map = row_map_dev;
+    k.n_groups = n_groups; k.max_slots = max_slots; k.group_cap = group_cap;
+    char* sp = (char*)scratch_dev;
+    k.gcounts = (uint32_t*)sp; k.gkeys = (unsigned long long*)(sp + L.keys_off); k.gboxes = (float*)(sp + L.boxes_off);
+    k.status = (uint32_t*)(h->act + h->status_off);
+    k.div_c = fastdiv_make((uint32_t)h->cfg.num_classes);
+    if (int r = gather_launch(k, n, s)) return r;
+    // gather_kernel left the counters of rows 0 .. n-1 at zero, the rows this decode counted into: the handle is where an NMS over
+    // n images would have left it (run_decode_nms: counts_clean = counts_n <= n)
+    h->counts_clean = true;
+    return Y4_OK;
+}
+
+int y4_nms_gathered(y4_handle h, int n_groups, int max_slots, uint32_t group_cap, float iou_threshold, void* scratch_dev,
+                    int32_t* cand_count_dev, float* boxes_dev, float* scores_dev, float* classes_dev, int32_t* valid_dev,
+                    int32_t* kept_idx_dev, void* stream) {
+    GatherLayout L;
+    if (int r = gather_layout(h, "y4_nms_gathered", n_groups, max_slots, group_cap, &L)) return r;
+    if (int r = gather_scratch_check("y4_nms_gathered", scratch_dev)) return r;
+    Y4_REQUIRE(h->act, Y4_ESTATE, "workspace not bound (call y4_bind_workspace first)");
+    Y4_REQUIRE(cand_count_dev && boxes_dev && scores_dev && classes_dev && valid_dev, Y4_EINVAL, "y4_nms_gathered: null output");
+    hipStream_t s = (hipStream_t)stream;
+    char* sp = (char*)scratch_dev;
+    if (int r = gather_counts_launch((const uint32_t*)sp, cand_count_dev, n_groups, s)) return r;
+    const y4_config& cfg = h->cfg;
+    NmsK k{};
+    k.dboxes = (const float*)(sp + L.boxes_off);
+    k.keys = (const unsigned long long*)(sp + L.keys_off);
+    k.counts = (uint32_t*)sp;
+    k.cap = group_cap; k.N = n_groups; k.C = cfg.num_classes; k.nbox = max_slots * h->nbox;
+    k.max_total = cfg.max_total; k.max_per_class = cfg.max_per_class;
+    k.iou_thr = iou_threshold < 0.f ? cfg.iou_threshold : iou_threshold;
+    k.out_boxes = boxes_dev; k.out_scores = scores_dev; k.out_classes = classes_dev; k.out_valid = valid_dev; k.out_idx = kept_idx_dev;
+    k.status = (uint32_t*)(h->act + h->status_off);
+    k.div_c = fastdiv_make((uint32_t)cfg.num_classes);
+    k.box_map = nullptr;
+    k.kind = h->nms_kind; k.beta = h->nms_beta; k.agnostic = h->nms_agnostic;
+    return nms_launch(k, s);
+}
+
 static void loss_geometry(y4_handle h, int* gh, int* gw, int* lane_base) {
     int lanes = 0;
     for (int i = 0; i < 3; ++i) {
@@ -2089,6 +2182,11 @@ int y4_resize_u8(const uint8_t* imgs_dev, int n, int h, int w, uint8_t* out_dev,
 int y4_resize_u8_ragged(const uint8_t* src_dev, const y4_image_desc* desc_dev, int n, uint8_t* out_dev, int H, int W,
                         int pad_value, void* stream) {
     return resize_u8_ragged_launch(src_dev, desc_dev, n, out_dev, H, W, pad_value, (hipStream_t)stream);
+}
+
+int y4_window_u8_ragged(const uint8_t* src_dev, const y4_window_desc* desc_dev, int n, uint8_t* out_dev, int H, int W,
+                        int pad_value, void* stream) {
+    return window_u8_ragged_launch(src_dev, desc_dev, n, out_dev, H, W, pad_value, (hipStream_t)stream);
 }
 
 int y4_augment_u8_ragged(const uint8_t* src_dev, const y4_augment_desc* desc_dev, int n, uint8_t* out_dev, int H, int W,

@@ -1,0 +1,120 @@
+// tiled.hip -- the two kernels of tiled (sliced) inference, Engine.predict_tiled:
+//   window_u8_ragged_kernel  y4_window_u8_ragged: crop + resize of WINDOWS of source images in one launch -- the ragged resize of
+//                            misc_kernels.hip (resize_u8_ragged_kernel) with a source row pitch that is not the window's width;
+//   gather_kernel            y4_decode_gather: the candidate lists the decode stage left for several batch rows (tiles) are merged
+//                            into ONE list per group (photo), boxes mapped to the photo's normalised coordinates, on which the
+//                            NMS kernel of decode_nms.hip then runs unchanged (y4_nms_gathered).
+#include "kernels.h"
+#include "resize_common.h"
+
+#pragma clang fp contract(off)   // the box map is an explicit fmaf; nothing else may fuse
+
+namespace y4 {
+
+// The shape of resize_u8_ragged_kernel: grid y = row (its descriptor is a wave-uniform load), grid x = PX consecutive canvas
+// pixels per thread, 12 bytes stored as three dwords with PX = 4.  Many rows may read one source image.
+template <int PX>
+__global__ __launch_bounds__(256) void window_u8_ragged_kernel(const uint8_t* __restrict__ src, const y4_window_desc* __restrict__ desc,
+                                                               uint8_t* __restrict__ out, int H, int W, int pad) {
+    const int b = blockIdx.y;
+    const y4_window_desc d = desc[b];
+    const int hw = H * W;                                  // < 2^31 (checked on the host)
+    const int p0 = (blockIdx.x * 256 + threadIdx.x) * PX;
+    if (p0 >= hw) return;
+    const uint8_t* win = src + d.offset;
+    uint8_t px[PX * 3];
+#pragma unroll
+    for (int k = 0; k < PX; ++k) {
+        const int p = p0 + k;
+        const int y = p / W, x = p - y * W;
+        const int yy = y - d.pad_top, xx = x - d.pad_left;
+        int v[3] = {pad, pad, pad};
+        if (yy >= 0 && yy < d.out_h && xx >= 0 && xx < d.out_w) resize_px_u8(win, (int64_t)d.pitch, d.h, d.w, d.out_h, d.out_w, yy, xx, v);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) px[k * 3 + c] = (uint8_t)v[c];
+    }
+    store_px_u8<PX>(out + ((int64_t)b * hw + p0) * 3, px);
+}
+
+int window_u8_ragged_launch(const uint8_t* src, const y4_window_desc* desc, int n, uint8_t* out, int H, int W, int pad,
+                            hipStream_t stream) {
+    if (int rc = ragged_args_check("window_u8_ragged", src, desc, out, n, H, W, pad)) return rc;
+    const int hw = H * W;
+    if (hw % 4 == 0 && ((uintptr_t)out & 3) == 0)
+        hipLaunchKernelGGL(window_u8_ragged_kernel<4>, dim3((hw / 4 + 255) / 256, n), dim3(256), 0, stream, src, desc, out, H, W, pad);
+    else
+        hipLaunchKernelGGL(window_u8_ragged_kernel<1>, dim3((hw + 255) / 256, n), dim3(256), 0, stream, src, desc, out, H, W, pad);
+    Y4_CHECK_HIP(hipGetLastError());
+    return Y4_OK;
+}
+
+// ------------------------------------------------------------------------------------------- gather
+// One workgroup per batch row i (a tile): the row's whole candidate list is read by this one workgroup, which is what lets it
+// leave the row's counter at zero behind a single barrier -- the duty nms_kernel has on the plain path.  Per pass of
+// GATHER_THREADS keys: the id (box, class) of a key is re-based to the group's box table, slot * nbox + box, the key is appended to
+// the group's list with ONE returning atomic per wave (ballot + popcount, as the decode kernels append), and the box is written,
+// mapped to the photo, to its own place in the group's table: rows of one group write disjoint slots, and the up to C
+// candidates of one box store the same four floats.  The order of a group's list varies from run to run; its keys are unique
+// and nms_kernel sorts them.
+constexpr int GATHER_THREADS = 1024;
+__global__ __launch_bounds__(GATHER_THREADS) void gather_kernel(const GatherK p) {
+    const int i = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
+    uint32_t cnt = p.counts[(size_t)i * COUNT_STRIDE];
+    if (cnt > p.cap) {                                   // cannot happen (cap = nbox * C is exact); kept as on the plain path
+        if (tid == 0) atomicOr(p.status, 1u);
+        cnt = p.cap;
+    }
+    __syncthreads();
+    if (tid == 0) p.counts[(size_t)i * COUNT_STRIDE] = 0;   // every thread has read it: zero for the handle's next decode
+    const int g = p.row_group[i], t = p.row_slot[i];
+    if (g < 0 || g >= p.n_groups || t < 0 || t >= p.max_slots) return;      // (uniform) a bad table row writes nothing
+    const float ax = p.row_map[4 * i], bx = p.row_map[4 * i + 1], ay = p.row_map[4 * i + 2], by = p.row_map[4 * i + 3];
+    const unsigned long long* keys = p.keys + (int64_t)i * p.cap;
+    const float* rb = p.dboxes + (int64_t)i * p.nbox * 4;
+    unsigned long long* gkeys = p.gkeys + (int64_t)g * p.group_cap;
+    float* gb = p.gboxes + ((int64_t)g * p.max_slots + t) * p.nbox * 4;
+    uint32_t* gcount = p.gcounts + (size_t)g * COUNT_STRIDE;
+    const uint32_t id0 = (uint32_t)t * (uint32_t)p.nbox * (uint32_t)p.C;    // < 2^31 with every id of the slot (checked on the host)
+    for (uint32_t k0 = 0; k0 < cnt; k0 += GATHER_THREADS) {                  // (uniform trip count)
+        const uint32_t k = k0 + (uint32_t)tid;
+        const bool have = k < cnt;
+        const unsigned long long key = have ? keys[k] : 0ull;
+        const uint32_t id = ~(uint32_t)(key & 0xffffffffull);
+        const uint32_t b = have ? fastdiv(id, p.div_c) : 0u;
+        const bool ok = have && b < (uint32_t)p.nbox;                        // (a key is (box < nbox, class < C) by construction)
+        const unsigned long long mask = __ballot(ok);
+        if (mask) {                                                          // wave-uniform
+            uint32_t base = 0;
+            if (lane == __ffsll((long long)mask) - 1) base = atomicAdd(gcount, (uint32_t)__popcll(mask));
+            base = __shfl(base, __ffsll((long long)mask) - 1);
+            if (ok) {
+                const uint32_t pos = base + (uint32_t)__popcll(mask & ((1ull << lane) - 1ull));
+                if (pos < p.group_cap) gkeys[pos] = (key & 0xffffffff00000000ull) | (unsigned long long)(~(id0 + id));
+                float4 o = *(const float4*)(rb + (int64_t)b * 4);
+                o.x = fmaf(o.x, ax, bx); o.y = fmaf(o.y, ay, by);
+                o.z = fmaf(o.z, ax, bx); o.w = fmaf(o.w, ay, by);
+                *(float4*)(gb + (int64_t)b * 4) = o;
+            }
+        }
+    }
+}
+
+int gather_launch(const GatherK& k, int n, hipStream_t stream) {
+    hipLaunchKernelGGL(gather_kernel, dim3(n), dim3(GATHER_THREADS), 0, stream, k);
+    Y4_CHECK_HIP(hipGetLastError());
+    return Y4_OK;
+}
+
+// The groups' raw candidate counts -> a dense int32 array, read before nms_kernel consumes and zeroes the counters
+__global__ __launch_bounds__(256) void gather_counts_kernel(const uint32_t* __restrict__ gcounts, int32_t* __restrict__ out, int n_groups) {
+    const int g = blockIdx.x * 256 + threadIdx.x;
+    if (g < n_groups) out[g] = (int32_t)gcounts[(size_t)g * COUNT_STRIDE];
+}
+
+int gather_counts_launch(const uint32_t* gcounts, int32_t* out, int n_groups, hipStream_t stream) {
+    hipLaunchKernelGGL(gather_counts_kernel, dim3((n_groups + 255) / 256), dim3(256), 0, stream, gcounts, out, n_groups);
+    Y4_CHECK_HIP(hipGetLastError());
+    return Y4_OK;
+}
+
+}  // namespace y4

@@ -16,7 +16,8 @@ is the reference's yolo_loss FORWARD (models.py:54-65, loss.py) on the device an
 a `DataGenerator`, `evaluate_map(data)` VOC mAP with the matching on the device (y4_map_match; the numbers of `eval_map` without
 its text files); `fit(..., trainable='heads')` fine-tunes the three detection convs on a frozen backbone and neck (with a
 `DataGenerator(..., augment=AugmentConfig())` under scale, shift, flip and HSV augmentation applied on the device), while
-training every layer (the reference's `fit`) is out of scope and raises.
+training every layer (the reference's `fit`) is out of scope and raises.  `predict_tiled` / `predict_img_tiled` (not in the reference)
+cut a photo much larger than the network input into overlapping windows and run one NMS per photo over all of them on the device.
 """
 import json
 import os
@@ -501,6 +502,34 @@ class Yolov4(object):
             img = self.preprocess_img(raw_img)
             imgs = np.expand_dims(img, axis=0)
             pred_output = self.inference_model.predict(imgs)
+        detections = prepost.get_detection_data(img=raw_img, model_outputs=pred_output, class_names=self.class_names)
+        output_img = prepost.draw_bbox(raw_img, detections, cmap=self.class_color, random_color=random_color,
+                                       figsize=figsize, show_text=show_text, show_img=plot_img)
+        if return_output:
+            return output_img, detections
+        return detections
+
+    # ---- tiled (sliced) inference: not in the reference.  A photo much larger than the network input is cut into overlapping
+    # windows at native resolution (yolo4hip/tiling.py), the windows run as batch rows, and one NMS per photo runs over all rows
+    # in the photo's coordinates (Engine.predict_tiled).  Honours this object's letterbox / pad_value (how a window that is not of
+    # the network's size, and the full image, go on the canvas), thresholds and NMS rule.  uint8 images only.
+    def predict_tiled(self, raw_imgs, *, tile=None, overlap=0.2, full_image=True, tile_candidates=1 << 18):
+        """raw_imgs: one uint8 RGB photo [h,w,3] or a list of them, any sizes -> (boxes [P,100,4] normalised to each photo,
+        scores, classes, valid), the form of inference_model.predict.  tile: window size, an int or (th, tw), default the network
+        input; overlap: fraction of a tile neighbouring windows share at least; full_image: the whole photo, resized as
+        predict_img resizes it, takes part as one more row (large objects); tile_candidates: candidate capacity per photo."""
+        self._ensure_tuned()
+        iou, score = self._thresholds
+        b, s, c, v = self.engine.predict_tiled(raw_imgs, tile=tile, overlap=overlap, full_image=full_image,
+                                               letterbox=self._letterbox, pad_value=self._pad_value, iou_threshold=iou,
+                                               score_threshold=score, tile_candidates=tile_candidates)
+        return b, s, c, v
+
+    def predict_img_tiled(self, raw_img, random_color=True, plot_img=True, figsize=(10, 10), show_text=True,
+                          return_output=False, *, tile=None, overlap=0.2, full_image=True):
+        """`predict_img` through `predict_tiled`: the same prints, drawing and DataFrame, boxes in the photo's pixels."""
+        print('img shape: ', raw_img.shape)
+        pred_output = self.predict_tiled([raw_img], tile=tile, overlap=overlap, full_image=full_image)
         detections = prepost.get_detection_data(img=raw_img, model_outputs=pred_output, class_names=self.class_names)
         output_img = prepost.draw_bbox(raw_img, detections, cmap=self.class_color, random_color=random_color,
                                        figsize=figsize, show_text=show_text, show_img=plot_img)

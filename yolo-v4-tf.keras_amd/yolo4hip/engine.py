@@ -414,11 +414,13 @@ class Engine:
                 raise ValueError(f"expected uint8 [h,w,3] images, got {getattr(a, 'dtype', type(a))} {getattr(a, 'shape', '')}")
         return raw_imgs, pad_value
 
-    def _upload_ragged(self, raw_imgs, desc, extra=None, rows=None):
-        """The one upload of a ragged batch (`preprocess_u8_batch`, `augment_u8_batch`, `mosaic_u8_batch`): fills offset, h, w of
-        every row of `desc` (a ctypes array of y4_image_desc or y4_augment_desc; row k describes image k, or image rows[k]
-        where `rows` is given: rows may share an image), packs descriptors | `extra` (a numpy array, or None) | the images into
-        the pinned staging buffer (kept across calls) and copies it to a fresh device block in one copy.
+    def _upload_ragged(self, raw_imgs, desc, extra=None, rows=None, windows=None):
+        """The one upload of a ragged batch (`preprocess_u8_batch`, `augment_u8_batch`, `mosaic_u8_batch`, `predict_tiled`): fills
+        offset, h, w of every row of `desc` (a ctypes array of y4_image_desc or y4_augment_desc; row k describes image k, or image
+        rows[k] where `rows` is given: rows may share an image), packs descriptors | `extra` (a numpy array, or None) | the images
+        into the pinned staging buffer (kept across calls) and copies it to a fresh device block in one copy.  With `windows` (one
+        (y0, x0, wh, ww) per row, inside image rows[k]) `desc` is an array of y4_window_desc: offset is then the window's first
+        pixel, pitch the image's row, h and w the window's.
         -> (device block, descriptor bytes, bytes before the first image); descriptor offsets count from the first image byte."""
         torch = self.torch
         n = len(raw_imgs)
@@ -428,8 +430,15 @@ class Engine:
         for a in raw_imgs:
             offs.append(off)
             off += a.shape[0] * a.shape[1] * 3
-        for d, k in zip(desc, range(n) if rows is None else rows):
-            d.offset, d.h, d.w = offs[k], raw_imgs[k].shape[0], raw_imgs[k].shape[1]
+        if windows is not None:
+            for d, k, (y0, x0, wh, ww) in zip(desc, rows, windows):
+                ih, iw = raw_imgs[k].shape[:2]
+                if not (0 <= y0 and 0 <= x0 and wh >= 1 and ww >= 1 and y0 + wh <= ih and x0 + ww <= iw):
+                    raise ValueError(f"window ({y0}, {x0}, {wh}, {ww}) is not inside its {ih} x {iw} image")
+                d.offset, d.pitch, d.h, d.w = offs[k] + (y0 * iw + x0) * 3, iw * 3, wh, ww
+        else:
+            for d, k in zip(desc, range(n) if rows is None else rows):
+                d.offset, d.h, d.w = offs[k], raw_imgs[k].shape[0], raw_imgs[k].shape[1]
         total = head + off
         pin = getattr(self, "_batch_pin", None)
         if pin is None or pin.numel() < total:
@@ -474,6 +483,145 @@ class Engine:
             ext.check(self.lib.y4_resize_u8_ragged(ext.ptr(src_dev), ext.ptr(desc_dev), int(n), ext.ptr(out), H, W,
                                                    int(pad_value), ext.stream_ptr()))
         return out[:n]
+
+    def window_u8_ragged(self, src_dev, desc_dev, n, out, pad_value=128):
+        """y4_window_u8_ragged on device buffers: `desc_dev` holds n y4_window_desc rows (windows of images in `src_dev`), `out`
+        is a uint8 cuda tensor of at least [n,H,W,3].  Asynchronous on the current stream; returns out[:n]."""
+        H, W = self.img_hw
+        with self.torch.cuda.device(self.device):
+            ext.check(self.lib.y4_window_u8_ragged(ext.ptr(src_dev), ext.ptr(desc_dev), int(n), ext.ptr(out), H, W,
+                                                   int(pad_value), ext.stream_ptr()))
+        return out[:n]
+
+    # ---------------------------------------------------------------- tiled inference: one NMS over the rows of a group
+    def gather_begin(self, n_groups, max_slots, group_cap):
+        """Scratch for a gathered decode + NMS sequence (y4_gather_scratch_bytes, y4_gather_begin): -> the state `decode_gather`
+        and `nms_gathered` take.  n_groups photos of at most max_slots rows each, group_cap candidate keys per photo."""
+        torch = self.torch
+        geo = (int(n_groups), int(max_slots), int(group_cap))
+        if geo[2] < 1 or geo[2] >= 1 << 32:
+            raise ValueError(f"group_cap must be in [1, 2^32), got {group_cap}")
+        nbytes = C.c_size_t()
+        ext.check(self.lib.y4_gather_scratch_bytes(self.handle, *geo, C.byref(nbytes)))
+        with torch.cuda.device(self.device):
+            scratch = torch.empty(nbytes.value, dtype=torch.uint8, device=self.device)
+            ext.check(self.lib.y4_gather_begin(self.handle, *geo, ext.ptr(scratch), ext.stream_ptr()))
+        return geo, scratch
+
+    def decode_gather(self, state, n, row_group, row_slot, row_map, score_threshold=-1.0):
+        """y4_decode_gather: the decode stage on rows 0 .. n-1 of the workspace, their candidates merged into the groups of
+        `state`.  row_group / row_slot: int32 cuda tensors [n], row_map float32 cuda [n,4] (contiguous).  Asynchronous."""
+        torch = self.torch
+        geo, scratch = state
+        for t, dt, shape in ((row_group, torch.int32, (n,)), (row_slot, torch.int32, (n,)), (row_map, torch.float32, (n, 4))):
+            if t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous() or not t.is_cuda:
+                raise ValueError(f"decode_gather: expected a contiguous {dt} cuda tensor {shape}, got {t.dtype} {tuple(t.shape)}")
+        with torch.cuda.device(self.device):
+            ext.check(self.lib.y4_decode_gather(self.handle, int(n), float(score_threshold), ext.ptr(row_group), ext.ptr(row_slot),
+                                                ext.ptr(row_map), *geo, ext.ptr(scratch), ext.stream_ptr()))
+
+    def alloc_tiled_outputs_flat(self, n_groups):
+        """`alloc_outputs_flat(n_groups)` with the groups' candidate counts behind it, ONE int32 device block for one copy back:
+        -> (flat, (boxes, scores, classes, valid, kept) views, cand_count int32 view [n_groups]); the first part of `flat` has
+        the layout of `alloc_outputs_flat`."""
+        torch = self.torch
+        n, T = int(n_groups), self.T
+        offs = np.cumsum([0, n * T * 4, n * T, n * T, n, n * T, n])
+        flat = torch.empty(int(offs[-1]), dtype=torch.int32, device=self.device)
+        v = [flat[offs[i]:offs[i + 1]] for i in range(6)]
+        return flat, (v[0].view(torch.float32).view(n, T, 4), v[1].view(torch.float32).view(n, T),
+                      v[2].view(torch.float32).view(n, T), v[3], v[4].view(n, T)), v[5]
+
+    def tiled_outputs_to_host(self, flat, n_groups):
+        """The one copy of `alloc_tiled_outputs_flat`'s block -> ([boxes, scores, classes, valid, kept], cand_count) as fresh
+        writable numpy arrays."""
+        n, T = int(n_groups), self.T
+        host = flat.cpu().numpy()
+        offs = np.cumsum([0, n * T * 4, n * T, n * T, n, n * T, n])
+        p = [host[offs[i]:offs[i + 1]] for i in range(6)]
+        return [p[0].view(np.float32).reshape(n, T, 4).copy(), p[1].view(np.float32).reshape(n, T).copy(),
+                p[2].view(np.float32).reshape(n, T).copy(), p[3].copy(), p[4].reshape(n, T).copy()], p[5].copy()
+
+    def nms_gathered(self, state, outs=None, cand_count=None, iou_threshold=-1.0):
+        """y4_nms_gathered over the groups of `state`: -> (outs as `decode_nms_device` for n_groups images, boxes normalised to
+        each group; cand_count int32 cuda [n_groups]: the candidates each group received -- above group_cap: that group's
+        result is not defined).  Asynchronous."""
+        torch = self.torch
+        geo, scratch = state
+        outs = outs or self.alloc_outputs(geo[0])
+        if cand_count is None:
+            cand_count = torch.empty((geo[0],), dtype=torch.int32, device=self.device)
+        b, s, c, v, k = outs
+        with torch.cuda.device(self.device):
+            ext.check(self.lib.y4_nms_gathered(self.handle, *geo, float(iou_threshold), ext.ptr(scratch), ext.ptr(cand_count),
+                                               ext.ptr(b), ext.ptr(s), ext.ptr(c), ext.ptr(v), ext.ptr(k), ext.stream_ptr()))
+        return outs, cand_count
+
+    def predict_tiled_device(self, raw_imgs, tile=None, overlap=0.2, full_image=True, letterbox=False, pad_value=128,
+                             iou_threshold=-1.0, score_threshold=-1.0, tile_candidates=1 << 18):
+        """`predict_tiled` with the results left on the device: -> (flat, outs, cand_count, group_cap) in the form of
+        `alloc_tiled_outputs_flat(len(raw_imgs))` -- outs are what `decode_nms_device` returns for that many images, boxes
+        normalised to each photo, ready for `map_match_device`.  The caller checks cand_count <= group_cap.  Asynchronous."""
+        torch = self.torch
+        from . import tiling
+        raw_imgs, pad_value = self._check_ragged(raw_imgs, pad_value, "predict_tiled")
+        if int(tile_candidates) < 1:
+            raise ValueError(f"tile_candidates must be >= 1, got {tile_candidates}")
+        H, W = self.img_hw
+        tile_hw = None if tile is None else ((int(tile), int(tile)) if np.ndim(tile) == 0 else (int(tile[0]), int(tile[1])))
+        photo, slot, windows, rects, maps = [], [], [], [], []
+        for p, a in enumerate(raw_imgs):
+            rows = tiling.tile_rows(a.shape[0], a.shape[1], (H, W), tile_hw, overlap, full_image, letterbox)
+            for t, (win, rect, m) in enumerate(rows):
+                photo.append(p); slot.append(t); windows.append(win); rects.append(rect); maps.append(m)
+        R, P, max_slots = len(photo), len(raw_imgs), max(slot) + 1
+        desc = (ext.y4_window_desc * R)()
+        for d, rect in zip(desc, rects):
+            d.out_h, d.out_w, d.pad_top, d.pad_left = rect
+        # maps | groups | slots travel behind the descriptors in the one upload
+        extra = np.concatenate([np.asarray(maps, np.float32).reshape(-1).view(np.int32), np.asarray(photo, np.int32),
+                                np.asarray(slot, np.int32)])
+        dev, desc_bytes, head = self._upload_ragged(raw_imgs, desc, extra, rows=photo, windows=windows)
+        tab = dev[desc_bytes:head].view(torch.int32)
+        row_map, row_group, row_slot = tab[:4 * R].view(torch.float32).view(R, 4), tab[4 * R:5 * R], tab[5 * R:6 * R]
+        # a photo cannot yield more candidates than its rows have (box, class) pairs: no larger list is ever needed
+        group_cap = int(min(int(tile_candidates), max_slots * self.num_boxes * self.num_classes))
+        state = self.gather_begin(P, max_slots, group_cap)
+        flat, outs, cand_count = self.alloc_tiled_outputs_flat(P)
+        step = C.sizeof(ext.y4_window_desc)
+        with torch.cuda.device(self.device):
+            canvas = torch.empty((min(R, self.max_batch), H, W, 3), dtype=torch.uint8, device=self.device)
+            src = C.c_void_p(dev.data_ptr() + head)
+            for r0 in range(0, R, self.max_batch):
+                n = min(self.max_batch, R - r0)
+                ext.check(self.lib.y4_window_u8_ragged(src, C.c_void_p(dev.data_ptr() + r0 * step), n, ext.ptr(canvas), H, W,
+                                                       pad_value, ext.stream_ptr()))
+                ext.check(self.lib.y4_forward_u8(self.handle, ext.ptr(canvas), n, ext.stream_ptr()))
+                self.decode_gather(state, n, row_group[r0:r0 + n], row_slot[r0:r0 + n], row_map[r0:r0 + n], score_threshold)
+            self.nms_gathered(state, outs, cand_count, iou_threshold)
+        return flat, outs, cand_count, group_cap
+
+    def predict_tiled(self, raw_imgs, tile=None, overlap=0.2, full_image=True, letterbox=False, pad_value=128,
+                      iou_threshold=-1.0, score_threshold=-1.0, tile_candidates=1 << 18, with_indices=False):
+        """Tiled (sliced) inference of uint8 RGB photos [h,w,3] of any sizes: each photo is cut into overlapping windows of `tile`
+        (an int or (th, tw); None: the network input, so interior windows are 1:1 copies) at native resolution
+        (yolo4hip.tiling.tile_rows; full_image=True adds the whole photo as one more row), the windows run through the network
+        as batch rows, and ONE NMS per photo runs over all of its rows' candidates in the photo's coordinates -- an object two
+        windows see comes back once.  One upload (photos, descriptors, maps), per chunk of max_batch rows y4_window_u8_ragged ->
+        y4_forward_u8 -> y4_decode_gather, then y4_nms_gathered and one copy back.  letterbox / pad_value: how a window (and the
+        full image) that is not of the network's size is placed on the canvas.  tile_candidates: the candidate keys a photo may
+        have (8 bytes each); RuntimeError when a photo has more.
+        -> [boxes [P,max_total,4] normalised to each photo, scores, classes, valid], with_indices also kept = slot * num_boxes +
+        box, as fresh host arrays, like `predict`."""
+        raws = [raw_imgs] if isinstance(raw_imgs, np.ndarray) and raw_imgs.ndim == 3 else list(raw_imgs)
+        flat, _, _, group_cap = self.predict_tiled_device(raws, tile, overlap, full_image, letterbox, pad_value, iou_threshold,
+                                                          score_threshold, tile_candidates)
+        res, cand = self.tiled_outputs_to_host(flat, len(raws))
+        if (cand > group_cap).any():
+            g = int(np.argmax(cand))
+            raise RuntimeError(f"predict_tiled: photo {g} has {int(cand[g])} candidates, more than tile_candidates = {group_cap} "
+                               f"holds; raise tile_candidates")
+        return res if with_indices else res[:4]
 
     def resize_u8(self, frames_dev, out=None):
         """Device-side stretch resize (cv2.resize to width W, height H) on a uint8 cuda batch [n,h,w,3] -> uint8 [n,H,W,3]
