@@ -8,7 +8,7 @@ sizes (VGA to 1080p, portrait and landscape) through
 
 Each step is timed on the host from the call to the finished result (torch.cuda.synchronize), which is what a caller waits
 for; the median and the minimum over --steps are reported.  The device time of the resize kernels alone is best read with
-`rocprofv3 --kernel-trace --stats -- python scripts/bench_letterbox.py` (resize_u8_kernel against resize_u8_ragged_kernel).
+`rocprofv3 --kernel-trace --stats -- python scripts/bench_letterbox.py` (resize_u8_kernel against canvas_u8_kernel).
 The stretch results of both paths are compared byte for byte first.  Prints one JSON line.
 
   python scripts/bench_letterbox.py [--images 32] [--steps 50] [--warmup 5] [--size 608x608]

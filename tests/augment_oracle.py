@@ -1,4 +1,4 @@
-"""Float64 NumPy statement of the augmentation rule of yolo4hip/augment.py and csrc/augment.hip: the colour transform
+"""Float64 NumPy statement of the augmentation rule of yolo4hip/augment.py and csrc/canvas_u8.hip: the colour transform
 (`rgb_to_hsv` / `hsv_to_rgb` follow the standard library's `colorsys`, to which tests/test_augment_cpu.py holds them) and the
 geometry, written per canvas pixel (index arithmetic, where `augment.augment_host` works on slices).  The uint8 bilinear resize
 itself is `prepost.resize_bilinear` (integer arithmetic, pinned by the letterbox tests)."""

@@ -1,4 +1,4 @@
-"""y4_augment_u8_ragged on the GPU (csrc/augment.hip) against y4_resize_u8_ragged, `augment.augment_host` and the float64
+"""y4_augment_u8_ragged on the GPU (csrc/canvas_u8.hip) against y4_resize_u8_ragged, `augment.augment_host` and the float64
 oracle of tests/augment_oracle.py, and `Yolov4.fit` over an augmenting `DataGenerator` (`Engine.augment_u8_batch`).
 
 Geometry is integer arithmetic: byte identity.  Colour: every byte within 1 level of the float64 oracle and at most 1e-3 of
@@ -105,6 +105,51 @@ def test_deterministic_and_independent_of_batch_and_slot():
     order = [5, 3, 0, 0, 2]
     again = _augment([imgs[i] for i in order], params[order], H, W, 128)
     assert np.array_equal(again, full[order])
+
+
+@pytest.mark.parametrize("entry", ["y4_resize_u8_ragged", "y4_augment_u8_ragged"])
+def test_output_off_a_dword_same_bytes_and_guards_untouched(entry):
+    """An output one byte into a larger buffer takes the one-pixel-per-thread store (H * W % 4 == 0 here, so the aligned call
+    stores dwords): the same bytes, and the bytes before and behind the batch stay as they were.  Mixed sizes with 1 x N, N x 1
+    and one image of the canvas's size; the augment rows carry flip, colour and rectangles off the canvas."""
+    import torch
+    from yolo4hip import ext, prepost
+    from test_gpu_letterbox import _images
+    H, W = 96, 160
+    imgs = _images([(1, 77), (77, 1), (H, W), (333, 501), (45, 37), (200, 90)], seed=96160)
+    n, size = len(imgs), len(imgs) * H * W * 3
+    if entry == "y4_resize_u8_ragged":
+        desc = (ext.y4_image_desc * n)()
+        rects = [prepost.letterbox_rect(a.shape[0], a.shape[1], H, W) for a in imgs[:3]] + [(H, W, 0, 0), (H - 9, W - 6, 3, 5), (H, W, 0, 0)]
+        for d, r in zip(desc, rects):
+            d.out_h, d.out_w, d.pad_top, d.pad_left = r
+    else:
+        desc = (ext.y4_augment_desc * n)()
+        rows = [(H, W, 0, 0, 1, 0, 1, 1), (H + 9, W + 13, -4, -7, 0, 0.07, 1.3, 0.8), (H, W, 0, 0, 0, 0, 1, 1),
+                (H - 11, W + 30, 5, -17, 1, -0.04, 0.75, 1.2), (7, 5, H - 3, W - 2, 1, 0, 1, 1), (H + 21, W - 5, -13, 3, 0, 0, 1, 1.1)]
+        for d, p in zip(desc, make_params(rows)):
+            d.out_h, d.out_w, d.pad_top, d.pad_left = int(p["out_h"]), int(p["out_w"]), int(p["pad_top"]), int(p["pad_left"])
+            d.flip, d.hue, d.sat, d.val = int(p["flip"]), float(p["hue"]), float(p["sat"]), float(p["val"])
+    off = 0
+    for d, a in zip(desc, imgs):
+        d.offset, d.h, d.w = off, a.shape[0], a.shape[1]
+        off += a.size
+    src = torch.from_numpy(np.concatenate([a.reshape(-1) for a in imgs])).to(DEV)
+    desc_dev = torch.from_numpy(np.frombuffer(desc, dtype=np.uint8).copy()).to(DEV)
+    fn = getattr(ext.load(), entry)
+    aligned = torch.full((size,), 7, dtype=torch.uint8, device=DEV)
+    assert aligned.data_ptr() % 4 == 0
+    ext.check(fn(ext.ptr(src), ext.ptr(desc_dev), n, ext.ptr(aligned), H, W, 128, ext.stream_ptr()))
+    flat = torch.full((size + 8,), 0xA5, dtype=torch.uint8, device=DEV)
+    assert flat[1:].data_ptr() % 4 == 1
+    ext.check(fn(ext.ptr(src), ext.ptr(desc_dev), n, ext.ptr(flat[1:]), H, W, 128, ext.stream_ptr()))
+    torch.cuda.synchronize()
+    aligned, flat = aligned.cpu().numpy(), flat.cpu().numpy()
+    assert np.array_equal(flat[1:1 + size], aligned)
+    assert flat[0] == 0xA5 and (flat[1 + size:] == 0xA5).all()
+    got = aligned.reshape(n, H, W, 3)
+    assert np.array_equal(got[2], imgs[2])                                  # the image of the canvas's size, unflipped, uncoloured
+    assert (got != 7).any(axis=-1).mean() > 0.99                            # the aligned call wrote the batch
 
 
 def test_argument_refusals_on_device_buffers():

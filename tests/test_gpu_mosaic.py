@@ -1,4 +1,4 @@
-"""y4_mosaic_u8_ragged on the GPU (csrc/augment.hip) against y4_augment_u8_ragged on the same device, `augment.mosaic_host` and
+"""y4_mosaic_u8_ragged on the GPU (csrc/canvas_u8.hip) against y4_augment_u8_ragged on the same device, `augment.mosaic_host` and
 the float64 oracle of tests/augment_oracle.py, and `Yolov4.fit` over a mosaic `DataGenerator` (`Engine.mosaic_u8_batch`).
 
 The rule is a composition (tests/test_mosaic_cpu.py: `compose`): byte identity with np.where over four outputs of the existing

@@ -123,6 +123,36 @@ def test_window_kernel_equals_the_ragged_resize_of_contiguous_copies():
     assert lib.y4_window_u8_ragged(ext.ptr(src), ext.ptr(src), 0, ext.ptr(out), H, W, 0, None) == -22
 
 
+def test_whole_image_windows_equal_the_ragged_resize_of_the_same_table():
+    """A window that is its whole image (pitch == 3 * w, the image's own offset) is the packed case: y4_window_u8_ragged writes the
+    bytes y4_resize_u8_ragged writes for the same offsets, sizes and rectangles.  Up- and down-scaled, 1 x N, N x 1, one image of
+    the canvas's size, stretched and letterboxed."""
+    import torch
+    from yolo4hip import ext, prepost
+    _, eng = _eng(3)
+    H = W = TC.SIZE
+    rng = np.random.default_rng(9600)
+    imgs = [rng.integers(0, 256, (h, w, 3), dtype=np.uint8) for h, w in ((131, 173), (40, 31), (1, 77), (77, 1), (H, W), (200, 55))]
+    rects = [(H, W, 0, 0)] * len(imgs) + [prepost.letterbox_rect(a.shape[0], a.shape[1], H, W) for a in imgs]
+    imgs = imgs + imgs
+    n = len(imgs)
+    src = torch.from_numpy(np.concatenate([a.reshape(-1) for a in imgs])).to(eng.device)
+    rdesc, wdesc = (ext.y4_image_desc * n)(), (ext.y4_window_desc * n)()
+    off = 0
+    for r, w_, a, rect in zip(rdesc, wdesc, imgs, rects):
+        r.offset, r.h, r.w = off, a.shape[0], a.shape[1]
+        w_.offset, w_.pitch, w_.h, w_.w = off, 3 * a.shape[1], a.shape[0], a.shape[1]
+        r.out_h, r.out_w, r.pad_top, r.pad_left = rect
+        w_.out_h, w_.out_w, w_.pad_top, w_.pad_left = rect
+        off += a.size
+    want = eng.resize_u8_ragged(src, _desc_tensor(eng, rdesc), n, torch.zeros((n, H, W, 3), dtype=torch.uint8, device=eng.device), 77)
+    got = eng.window_u8_ragged(src, _desc_tensor(eng, wdesc), n, torch.ones((n, H, W, 3), dtype=torch.uint8, device=eng.device), 77)
+    want, got = want.cpu().numpy(), got.cpu().numpy()
+    for k in range(n):
+        assert np.array_equal(got[k], want[k]), (k, imgs[k].shape, rects[k], int((got[k] != want[k]).sum()))
+    assert np.array_equal(want[4], imgs[4])                                  # the image of the canvas's size is a plain copy
+
+
 # ------------------------------------------------------------------------------------------------ 2. gather + NMS vs the oracle
 @pytest.mark.parametrize("ncls,seed,rule", sorted(TC.MARGINS))
 def test_gathered_nms_equals_the_oracle(ncls, seed, rule):

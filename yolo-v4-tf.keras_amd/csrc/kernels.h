@@ -60,8 +60,6 @@ int pack_conv_frag32(int dtype, int cout, int cin, const void* packed, void* fra
 int stem_conv_launch(int dtype, const void* imgs, int img_u8, int n, int h, int w, const float* wk, const float* scale,
                      const float* shift, int cout, int act, void* out, int out_cstride, int out_coff, hipStream_t stream);
 int resize_u8_launch(const uint8_t* img, int n, int h, int w, uint8_t* out, int H, int W, hipStream_t stream);
-int resize_u8_ragged_launch(const uint8_t* src, const y4_image_desc* desc, int n, uint8_t* out, int H, int W, int pad,
-                            hipStream_t stream);
 int pack_stem_weights(const float* w_oihw, float* wk, int cout, hipStream_t stream);
 int preprocess_u8_launch(const uint8_t* img, int h, int w, float* out, int H, int W, hipStream_t stream);
 int spp_launch(int dtype, void* buf, int n, int h, int w, int c, hipStream_t stream);
@@ -70,7 +68,11 @@ int view_to_f32_launch(int dtype, const void* src, float* dst, int64_t pixels, i
 int f32_to_view_launch(const float* src, float* dst, int64_t pixels, int cstride, int c, hipStream_t stream);
 int fold_bn_launch(const float* rec, float* scale, float* shift, int cout, int cout_pad, int has_bn, hipStream_t stream);
 
-// augment.hip
+// canvas_u8.hip: packed uint8 sources + a device-resident descriptor table -> the uint8 network batch, one kernel template
+int resize_u8_ragged_launch(const uint8_t* src, const y4_image_desc* desc, int n, uint8_t* out, int H, int W, int pad,
+                            hipStream_t stream);
+int window_u8_ragged_launch(const uint8_t* src, const y4_window_desc* desc, int n, uint8_t* out, int H, int W, int pad,
+                            hipStream_t stream);
 int augment_u8_ragged_launch(const uint8_t* src, const y4_augment_desc* desc, int n, uint8_t* out, int H, int W, int pad,
                              hipStream_t stream);
 int mosaic_u8_ragged_launch(const uint8_t* src, const y4_augment_desc* tiles, const y4_mosaic_cut* cuts, int n, uint8_t* out, int H,
@@ -146,9 +148,7 @@ int decode_launch(const DecodeK& k, hipStream_t stream, int clear_images);
 int l2_flush_launch(const void* p, size_t bytes, void* sink, hipStream_t stream);
 int nms_launch(const NmsK& k, hipStream_t stream);
 
-// tiled.hip: windows of source images -> the uint8 network batch; the decode stage's per-row candidate lists -> one list per group
-int window_u8_ragged_launch(const uint8_t* src, const y4_window_desc* desc, int n, uint8_t* out, int H, int W, int pad,
-                            hipStream_t stream);
+// tiled.hip: the decode stage's per-row candidate lists -> one list per group
 struct GatherK {
     const float* dboxes;             // [n, nbox, 4] what the decode stage wrote (canvas-normalised)
     const unsigned long long* keys;  // [n, cap]

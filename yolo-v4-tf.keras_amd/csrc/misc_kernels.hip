@@ -394,23 +394,10 @@ __global__ void preprocess_u8_kernel(const uint8_t* __restrict__ img, int h, int
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= H * W) return;
     const int y = i / W, x = i - y * W;
-    int x0, x1, ax0, ax1, y0, y1, ay0, ay1;
-    lin_coeff(x, W, w, x0, x1, ax0, ax1);
-    lin_coeff(y, H, h, y0, y1, ay0, ay1);
-    const bool same = (h == H && w == W);
+    int v[3];
+    resize_px_u8(img, 3 * w, h, w, H, W, y, x, v);
 #pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        int v;
-        if (same) {
-            v = img[(y * w + x) * 3 + c];
-        } else {
-            const int top = img[(y0 * w + x0) * 3 + c] * ax0 + img[(y0 * w + x1) * 3 + c] * ax1;   // x2048
-            const int bot = img[(y1 * w + x0) * 3 + c] * ax0 + img[(y1 * w + x1) * 3 + c] * ax1;
-            v = (((ay0 * (top >> 4)) >> 16) + ((ay1 * (bot >> 4)) >> 16) + 2) >> 2;
-            v = v < 0 ? 0 : (v > 255 ? 255 : v);
-        }
-        out[i * 3 + c] = (float)((double)v / 255.0);
-    }
+    for (int c = 0; c < 3; ++c) out[i * 3 + c] = (float)((double)v[c] / 255.0);
 }
 
 // The resize half alone, batched: uint8 [n,h,w,3] -> uint8 [n,H,W,3] (cv2.resize's own output type); the `/ 255.` then
@@ -421,7 +408,7 @@ __global__ void resize_u8_kernel(const uint8_t* __restrict__ img, int n, int h, 
     const int b = (int)(i / (H * W)), r = (int)(i - (int64_t)b * H * W);
     const int y = r / W, x = r - y * W;
     int v[3];
-    resize_px_u8(img + (int64_t)b * h * w * 3, h, w, H, W, y, x, v);
+    resize_px_u8(img + (int64_t)b * h * w * 3, 3 * w, h, w, H, W, y, x, v);
 #pragma unroll
     for (int c = 0; c < 3; ++c) out[i * 3 + c] = (uint8_t)v[c];
 }
@@ -431,47 +418,6 @@ int resize_u8_launch(const uint8_t* img, int n, int h, int w, uint8_t* out, int 
     Y4_REQUIRE((int64_t)n * h * w * 3 < (1ll << 31) && (int64_t)n * H * W * 3 < (1ll << 31), Y4_EINVAL, "resize_u8: batch too large");
     const int64_t total = (int64_t)n * H * W;
     hipLaunchKernelGGL(resize_u8_kernel, dim3((int)((total + 255) / 256)), dim3(256), 0, stream, img, n, h, w, out, H, W);
-    Y4_CHECK_HIP(hipGetLastError());
-    return Y4_OK;
-}
-
-// Ragged batch (y4_resize_u8_ragged): images of different sizes, each stretched to its own target rectangle of the H x W canvas
-// (the whole canvas: stretch; the centred aspect-keeping rectangle: letterbox), the rest of the canvas `pad`.  Grid y = image
-// (its descriptor is a wave-uniform load: scalar registers), grid x = PX consecutive canvas pixels per thread.  The source reads
-// are gathers (two rows, bilinear taps) served from L1/L2; the writes are what this kernel can shape: with PX = 4 a thread
-// stores its 12 bytes as three dwords and a wave covers 768 contiguous bytes, instead of 3 byte stores per pixel.  PX = 4 needs
-// H * W % 4 == 0 (every network size: sides are multiples of 32) and a 4-byte aligned output; otherwise PX = 1.
-template <int PX>
-__global__ __launch_bounds__(256) void resize_u8_ragged_kernel(const uint8_t* __restrict__ src, const y4_image_desc* __restrict__ desc,
-                                                               uint8_t* __restrict__ out, int H, int W, int pad) {
-    const int b = blockIdx.y;
-    const y4_image_desc d = desc[b];
-    const int hw = H * W;                                  // < 2^31 (checked on the host)
-    const int p0 = (blockIdx.x * 256 + threadIdx.x) * PX;
-    if (p0 >= hw) return;
-    const uint8_t* img = src + d.offset;
-    uint8_t px[PX * 3];
-#pragma unroll
-    for (int k = 0; k < PX; ++k) {
-        const int p = p0 + k;
-        const int y = p / W, x = p - y * W;
-        const int yy = y - d.pad_top, xx = x - d.pad_left;
-        int v[3] = {pad, pad, pad};
-        if (yy >= 0 && yy < d.out_h && xx >= 0 && xx < d.out_w) resize_px_u8(img, d.h, d.w, d.out_h, d.out_w, yy, xx, v);
-#pragma unroll
-        for (int c = 0; c < 3; ++c) px[k * 3 + c] = (uint8_t)v[c];
-    }
-    store_px_u8<PX>(out + ((int64_t)b * hw + p0) * 3, px);
-}
-
-int resize_u8_ragged_launch(const uint8_t* src, const y4_image_desc* desc, int n, uint8_t* out, int H, int W, int pad,
-                            hipStream_t stream) {
-    if (int rc = ragged_args_check("resize_u8_ragged", src, desc, out, n, H, W, pad)) return rc;
-    const int hw = H * W;
-    if (hw % 4 == 0 && ((uintptr_t)out & 3) == 0)
-        hipLaunchKernelGGL(resize_u8_ragged_kernel<4>, dim3((hw / 4 + 255) / 256, n), dim3(256), 0, stream, src, desc, out, H, W, pad);
-    else
-        hipLaunchKernelGGL(resize_u8_ragged_kernel<1>, dim3((hw + 255) / 256, n), dim3(256), 0, stream, src, desc, out, H, W, pad);
     Y4_CHECK_HIP(hipGetLastError());
     return Y4_OK;
 }

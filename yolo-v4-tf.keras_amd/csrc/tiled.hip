@@ -1,52 +1,12 @@
-// tiled.hip -- the two kernels of tiled (sliced) inference, Engine.predict_tiled:
-//   window_u8_ragged_kernel  y4_window_u8_ragged: crop + resize of WINDOWS of source images in one launch -- the ragged resize of
-//                            misc_kernels.hip (resize_u8_ragged_kernel) with a source row pitch that is not the window's width;
+// tiled.hip -- the gather of tiled (sliced) inference, Engine.predict_tiled (its window crops are canvas_u8.hip's):
 //   gather_kernel            y4_decode_gather: the candidate lists the decode stage left for several batch rows (tiles) are merged
 //                            into ONE list per group (photo), boxes mapped to the photo's normalised coordinates, on which the
 //                            NMS kernel of decode_nms.hip then runs unchanged (y4_nms_gathered).
 #include "kernels.h"
-#include "resize_common.h"
 
 #pragma clang fp contract(off)   // the box map is an explicit fmaf; nothing else may fuse
 
 namespace y4 {
-
-// The shape of resize_u8_ragged_kernel: grid y = row (its descriptor is a wave-uniform load), grid x = PX consecutive canvas
-// pixels per thread, 12 bytes stored as three dwords with PX = 4.  Many rows may read one source image.
-template <int PX>
-__global__ __launch_bounds__(256) void window_u8_ragged_kernel(const uint8_t* __restrict__ src, const y4_window_desc* __restrict__ desc,
-                                                               uint8_t* __restrict__ out, int H, int W, int pad) {
-    const int b = blockIdx.y;
-    const y4_window_desc d = desc[b];
-    const int hw = H * W;                                  // < 2^31 (checked on the host)
-    const int p0 = (blockIdx.x * 256 + threadIdx.x) * PX;
-    if (p0 >= hw) return;
-    const uint8_t* win = src + d.offset;
-    uint8_t px[PX * 3];
-#pragma unroll
-    for (int k = 0; k < PX; ++k) {
-        const int p = p0 + k;
-        const int y = p / W, x = p - y * W;
-        const int yy = y - d.pad_top, xx = x - d.pad_left;
-        int v[3] = {pad, pad, pad};
-        if (yy >= 0 && yy < d.out_h && xx >= 0 && xx < d.out_w) resize_px_u8(win, (int64_t)d.pitch, d.h, d.w, d.out_h, d.out_w, yy, xx, v);
-#pragma unroll
-        for (int c = 0; c < 3; ++c) px[k * 3 + c] = (uint8_t)v[c];
-    }
-    store_px_u8<PX>(out + ((int64_t)b * hw + p0) * 3, px);
-}
-
-int window_u8_ragged_launch(const uint8_t* src, const y4_window_desc* desc, int n, uint8_t* out, int H, int W, int pad,
-                            hipStream_t stream) {
-    if (int rc = ragged_args_check("window_u8_ragged", src, desc, out, n, H, W, pad)) return rc;
-    const int hw = H * W;
-    if (hw % 4 == 0 && ((uintptr_t)out & 3) == 0)
-        hipLaunchKernelGGL(window_u8_ragged_kernel<4>, dim3((hw / 4 + 255) / 256, n), dim3(256), 0, stream, src, desc, out, H, W, pad);
-    else
-        hipLaunchKernelGGL(window_u8_ragged_kernel<1>, dim3((hw + 255) / 256, n), dim3(256), 0, stream, src, desc, out, H, W, pad);
-    Y4_CHECK_HIP(hipGetLastError());
-    return Y4_OK;
-}
 
 // ------------------------------------------------------------------------------------------- gather
 // One workgroup per batch row i (a tile): the row's whole candidate list is read by this one workgroup, which is what lets it

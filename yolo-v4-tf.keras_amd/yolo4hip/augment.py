@@ -183,7 +183,7 @@ def transform_boxes(raw_boxes, size_hw, param, canvas_hw, max_boxes):
 
 
 def hsv_shift_u8(rgb, hue, sat, val):
-    """The colour rule on uint8 [..., 3], float32 arithmetic in the kernel's order of operations (csrc/augment.hip: hsv_px_u8)."""
+    """The colour rule on uint8 [..., 3], float32 arithmetic in the kernel's order of operations (csrc/canvas_u8.hip: hsv_px_u8)."""
     f32 = np.float32
     hue, sat, val = f32(hue), f32(sat), f32(val)
     if hue == 0 and sat == 1 and val == 1:

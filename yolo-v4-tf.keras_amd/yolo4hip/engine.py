@@ -333,10 +333,8 @@ class Engine:
             d.out_h, d.out_w, d.pad_top, d.pad_left = rect
             maps[i] = prepost.box_map(h, w, H, W, rect)
         dev, desc_bytes, head = self._upload_ragged(raw_imgs, desc, maps)
-        with torch.cuda.device(self.device):
-            out = torch.empty((n, H, W, 3), dtype=torch.uint8, device=self.device)
-            ext.check(self.lib.y4_resize_u8_ragged(C.c_void_p(dev.data_ptr() + head), ext.ptr(dev), n, ext.ptr(out), H, W,
-                                                   pad_value, ext.stream_ptr()))
+        out = self._canvas_launch(self.lib.y4_resize_u8_ragged, C.c_void_p(dev.data_ptr() + head), (ext.ptr(dev),), n, None,
+                                  pad_value)
         return out, dev[desc_bytes:head].view(torch.float32).view(n, 4)
 
     def augment_u8_batch(self, raw_imgs, params, pad_value=128):
@@ -345,24 +343,13 @@ class Engine:
         `forward_device`, through one pinned staging buffer, one copy and one launch (`y4_augment_u8_ragged`): resize into a
         rectangle that may stick out of the canvas, left-right flip and the HSV transform; `augment.augment_host` is the same
         function on the host.  Asynchronous on the current stream."""
-        torch = self.torch
         raw_imgs, pad_value = self._check_ragged(raw_imgs, pad_value, "augment_u8_batch")
         n = len(raw_imgs)
         if len(params) != n:
             raise ValueError(f"augment_u8_batch: {n} images, {len(params)} parameter rows")
-        desc = (ext.y4_augment_desc * n)()
-        for d, p in zip(desc, params):
-            d.out_h, d.out_w, d.pad_top, d.pad_left = int(p["out_h"]), int(p["out_w"]), int(p["pad_top"]), int(p["pad_left"])
-            d.flip, d.hue, d.sat, d.val = int(p["flip"]), float(p["hue"]), float(p["sat"]), float(p["val"])
-            if d.out_h < 1 or d.out_w < 1 or not np.isfinite([d.hue, d.sat, d.val]).all():
-                raise ValueError(f"augment_u8_batch: rectangle {d.out_h} x {d.out_w}, factors {d.hue}, {d.sat}, {d.val}")
-        dev, _, head = self._upload_ragged(raw_imgs, desc)
-        H, W = self.img_hw
-        with torch.cuda.device(self.device):
-            out = torch.empty((n, H, W, 3), dtype=torch.uint8, device=self.device)
-            ext.check(self.lib.y4_augment_u8_ragged(C.c_void_p(dev.data_ptr() + head), ext.ptr(dev), n, ext.ptr(out), H, W,
-                                                    pad_value, ext.stream_ptr()))
-        return out
+        dev, _, head = self._upload_ragged(raw_imgs, self._augment_desc(params, "augment_u8_batch"))
+        return self._canvas_launch(self.lib.y4_augment_u8_ragged, C.c_void_p(dev.data_ptr() + head), (ext.ptr(dev),), n, None,
+                                   pad_value)
 
     def mosaic_u8_batch(self, images, tile_src, params, cuts, pad_value=128):
         """Mosaic canvases on the device (`DataGenerator.raw_mosaic`): `images` the DISTINCT uint8 RGB photos [h,w,3] of the
@@ -372,7 +359,6 @@ class Engine:
         one staging buffer and the one copy of `augment_u8_batch`; one launch (`y4_mosaic_u8_ragged`) follows.
         `augment.mosaic_host` is the same function on the host.  What the kernel does not check is checked here (ValueError):
         0 <= cut <= (H, W), tile_src inside `images`, out_h, out_w >= 1, finite factors.  Asynchronous on the current stream."""
-        torch = self.torch
         images, pad_value = self._check_ragged(images, pad_value, "mosaic_u8_batch")
         H, W = self.img_hw
         tile_src, cuts = np.asarray(tile_src), np.ascontiguousarray(cuts, dtype=np.int32)
@@ -384,19 +370,33 @@ class Engine:
             raise ValueError(f"mosaic_u8_batch: tile_src must index the {len(images)} images")
         if (cuts < 0).any() or (cuts[:, 0] > H).any() or (cuts[:, 1] > W).any():
             raise ValueError(f"mosaic_u8_batch: cuts (cut_y, cut_x) must lie in [0, {H}] x [0, {W}]")
-        desc = (ext.y4_augment_desc * (4 * n))()
-        for d, p in zip(desc, np.asarray(params).reshape(-1)):
+        desc = self._augment_desc(np.asarray(params).reshape(-1), "mosaic_u8_batch")
+        dev, desc_bytes, head = self._upload_ragged(images, desc, cuts, rows=tile_src.reshape(-1))
+        return self._canvas_launch(self.lib.y4_mosaic_u8_ragged, C.c_void_p(dev.data_ptr() + head),
+                                   (ext.ptr(dev), C.c_void_p(dev.data_ptr() + desc_bytes)), n, None, pad_value)
+
+    @staticmethod
+    def _augment_desc(params, who):
+        """yolo4hip.augment.PARAM_DTYPE rows -> a ctypes array of y4_augment_desc with the rectangle, flip and HSV factors filled
+        in (offset, h, w are `_upload_ragged`'s), or ValueError for what the kernel does not check."""
+        desc = (ext.y4_augment_desc * len(params))()
+        for d, p in zip(desc, params):
             d.out_h, d.out_w, d.pad_top, d.pad_left = int(p["out_h"]), int(p["out_w"]), int(p["pad_top"]), int(p["pad_left"])
             d.flip, d.hue, d.sat, d.val = int(p["flip"]), float(p["hue"]), float(p["sat"]), float(p["val"])
             if d.out_h < 1 or d.out_w < 1 or not np.isfinite([d.hue, d.sat, d.val]).all():
-                raise ValueError(f"mosaic_u8_batch: rectangle {d.out_h} x {d.out_w}, factors {d.hue}, {d.sat}, {d.val}")
-        dev, desc_bytes, head = self._upload_ragged(images, desc, cuts, rows=tile_src.reshape(-1))
-        with torch.cuda.device(self.device):
-            out = torch.empty((n, H, W, 3), dtype=torch.uint8, device=self.device)
-            ext.check(self.lib.y4_mosaic_u8_ragged(C.c_void_p(dev.data_ptr() + head), ext.ptr(dev),
-                                                   C.c_void_p(dev.data_ptr() + desc_bytes), n, ext.ptr(out), H, W, pad_value,
-                                                   ext.stream_ptr()))
-        return out
+                raise ValueError(f"{who}: rectangle {d.out_h} x {d.out_w}, factors {d.hue}, {d.sat}, {d.val}")
+        return desc
+
+    def _canvas_launch(self, fn, src, tables, n, out, pad_value):
+        """One launch of a canvas entry point (y4_resize / window / augment / mosaic _u8_ragged) on the current stream: `src` the
+        first image byte, `tables` the descriptor table(s) as pointers, `out` a uint8 cuda tensor of at least [n,H,W,3] (None: a
+        fresh one) -> out[:n]."""
+        H, W = self.img_hw
+        with self.torch.cuda.device(self.device):
+            if out is None:
+                out = self.torch.empty((n, H, W, 3), dtype=self.torch.uint8, device=self.device)
+            ext.check(fn(src, *tables, int(n), ext.ptr(out), H, W, int(pad_value), ext.stream_ptr()))
+        return out[:n]
 
     @staticmethod
     def _check_ragged(raw_imgs, pad_value, who):
@@ -478,20 +478,12 @@ class Engine:
     def resize_u8_ragged(self, src_dev, desc_dev, n, out, pad_value=128):
         """y4_resize_u8_ragged on device buffers: `desc_dev` holds n y4_image_desc rows (offsets into `src_dev`), `out` is a
         uint8 cuda tensor of at least [n,H,W,3].  Asynchronous on the current stream; returns out[:n]."""
-        H, W = self.img_hw
-        with self.torch.cuda.device(self.device):
-            ext.check(self.lib.y4_resize_u8_ragged(ext.ptr(src_dev), ext.ptr(desc_dev), int(n), ext.ptr(out), H, W,
-                                                   int(pad_value), ext.stream_ptr()))
-        return out[:n]
+        return self._canvas_launch(self.lib.y4_resize_u8_ragged, ext.ptr(src_dev), (ext.ptr(desc_dev),), n, out, pad_value)
 
     def window_u8_ragged(self, src_dev, desc_dev, n, out, pad_value=128):
         """y4_window_u8_ragged on device buffers: `desc_dev` holds n y4_window_desc rows (windows of images in `src_dev`), `out`
         is a uint8 cuda tensor of at least [n,H,W,3].  Asynchronous on the current stream; returns out[:n]."""
-        H, W = self.img_hw
-        with self.torch.cuda.device(self.device):
-            ext.check(self.lib.y4_window_u8_ragged(ext.ptr(src_dev), ext.ptr(desc_dev), int(n), ext.ptr(out), H, W,
-                                                   int(pad_value), ext.stream_ptr()))
-        return out[:n]
+        return self._canvas_launch(self.lib.y4_window_u8_ragged, ext.ptr(src_dev), (ext.ptr(desc_dev),), n, out, pad_value)
 
     # ---------------------------------------------------------------- tiled inference: one NMS over the rows of a group
     def gather_begin(self, n_groups, max_slots, group_cap):
@@ -594,8 +586,8 @@ class Engine:
             src = C.c_void_p(dev.data_ptr() + head)
             for r0 in range(0, R, self.max_batch):
                 n = min(self.max_batch, R - r0)
-                ext.check(self.lib.y4_window_u8_ragged(src, C.c_void_p(dev.data_ptr() + r0 * step), n, ext.ptr(canvas), H, W,
-                                                       pad_value, ext.stream_ptr()))
+                self._canvas_launch(self.lib.y4_window_u8_ragged, src, (C.c_void_p(dev.data_ptr() + r0 * step),), n, canvas,
+                                    pad_value)
                 ext.check(self.lib.y4_forward_u8(self.handle, ext.ptr(canvas), n, ext.stream_ptr()))
                 self.decode_gather(state, n, row_group[r0:r0 + n], row_slot[r0:r0 + n], row_map[r0:r0 + n], score_threshold)
             self.nms_gathered(state, outs, cand_count, iou_threshold)
