@@ -127,6 +127,33 @@ RANDOM_CASES = [
 ]
 
 
+# ---- a rule that goes on in a LATER chunk: the stack-and-disjoint images of decode_nms_cases under a non-default rule.  The first
+# chunk leaves its kept lists through the DIoU round-parallel pass, or through the agnostic wave-0 pass; the later chunk is sorted
+# (rank sort for s1300, nms_sort_regs for s2500) and decided by the wave-0 pass of that rule, continuing from those lists.
+LATER_CHUNK_CASES = [(name, rule) for name in ("s1300", "s2500") for rule in ("diou06", "agn_iou")]
+
+
+@functools.lru_cache(maxsize=None)
+def later_chunk_reference(name, rule):
+    _, b, s = DC.chunk_case(name)
+    kind, beta, agn = RULES[rule]
+    return NR.combined_nms_rule(b, s, 100, 100, IOU_THR, SCORE_THR, kind, beta, agn)
+
+
+def rank_of_last_kept_under(scores, ref):
+    """Position of the last kept box of `ref` (image 0) in the candidate order of `scores` [nbox, C]."""
+    return DC.rank_of_last_kept(DC.candidate_order(scores, SCORE_THR), ref[4][0], ref[2][0], ref[3][0])
+
+
+def later_chunk_witness(name, rule):
+    """`DC.chunk_witness` of the input under the rule, with the ranks of all kept boxes."""
+    _, _, s = DC.chunk_case(name)
+    ref = later_chunk_reference(name, rule)
+    w = DC.chunk_witness(s[0], SCORE_THR, (ref[4][0], ref[2][0], ref[3][0]))
+    w["ranks"] = DC.ranks_of_kept(DC.candidate_order(s[0], SCORE_THR), ref[4][0], ref[2][0], ref[3][0])
+    return w
+
+
 RANDOM_N, RANDOM_SIZE = 2, 160
 RANDOM_BIAS = {3: (1.0, 0.0), 80: (-0.5, -1.5)}       # C -> (objectness bias, class bias): crowded classes at either count
 

@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 import decode_nms_cases as DC
+import nms_rule_cases as RC
 from decode_nms_cases import NMS_THREADS, SORT_CAP
 
 
@@ -91,6 +92,25 @@ def test_s5400_needs_a_select_with_a_finite_cutoff_and_a_third_chunk():
     assert w["rem_lo"] > SORT_CAP                                         # more than a chunk remains: exact select below the cutoff
     assert w["rank"] >= NMS_THREADS + SORT_CAP                           # the first two chunks cannot hold the last kept box
     assert w["rem_hi"] - SORT_CAP <= NMS_THREADS                          # the third chunk is rank sorted
+
+
+@pytest.mark.parametrize("name,rule", RC.LATER_CHUNK_CASES)
+def test_rule_cases_are_decided_in_a_later_chunk(name, rule):
+    """The inputs of test_gpu_nms_rule.test_rule_goes_on_in_a_later_chunk: under the rule, the oracle's last kept box still ranks
+    behind everything a first chunk can hold, and the first chunk has kept boxes for the later pass to continue from."""
+    w = RC.later_chunk_witness(name, rule)
+    ref = RC.later_chunk_reference(name, rule)
+    assert w["T"] > NMS_THREADS and w["rank"] >= NMS_THREADS, w
+    assert any(r < NMS_THREADS // 2 for r in w["ranks"])                  # kept by the first chunk's pass, whatever its pivot
+    assert sum(1 for r in w["ranks"] if r >= NMS_THREADS) > 1             # more than one box is kept by the later chunk's pass
+    if name == "s1300":
+        assert 0 < w["rem_lo"] and w["rem_hi"] <= NMS_THREADS             # the later chunk is rank sorted
+    else:
+        assert w["rem_lo"] > NMS_THREADS and w["rem_hi"] <= SORT_CAP      # ... goes through nms_sort_regs, no select
+    # no tested pair hangs on the last bits of the measure: it is some ten float32 operations on values <= 1 (half an ulp, 6e-8,
+    # each) and one powf (a few ulp of a penalty < 0.1), so two correct float32 evaluations differ by well under 1e-6
+    assert ref[5] >= 1e-6, ref[5]
+    assert ref[3][0] == 100
 
 
 def test_iou_zero_dense_case_visits_more_than_two_chunks():

@@ -3,6 +3,7 @@ every place nms_kernel evaluates it, with inputs whose witnesses (tests/nms_rule
 tests/test_nms_rule_cpu.py) say that the deciding pair is tested there.  Bars: tests/decode_nms_cases.assert_same_detections
 (decisions identical, boxes within 1e-5, scores within 1e-6)."""
 import ctypes as C
+import functools
 import os
 import shutil
 
@@ -97,6 +98,90 @@ def test_agnostic_capped_candidate_suppresses_nothing():
         assert_same_detections(got, ref[:5])
         assert list(got[4][0][:2]) == kept and got[3][0] == 2
         eng.close()
+
+
+# ------------------------------------------------------------------------------------------------ 3b. the rule in a later chunk
+def _device_decode(eng, heads, boxes, scores):
+    """What the DEVICE's decode stage makes of `heads` (one image): -> (boxes [1, nbox, 4], scores [1, nbox, C]) holding its
+    float32 score of every candidate (0 elsewhere) and its unclipped box of every box that has one (the oracle's `boxes`
+    elsewhere: NMS never reads those).  Read from the scratch of a gathered decode of one row into one group under the identity
+    map (fmaf(x, 1, 0) is x): counters | keys | box table, each part on a 256-byte boundary (runtime.hip, GatherLayout)."""
+    import torch
+    _, nbox, ncls = scores.shape
+    cap = nbox * ncls                                          # can never overflow
+    assert eng.set_heads(heads) == 1
+    state = eng.gather_begin(1, 1, cap)
+    dev = eng.device
+    eng.decode_gather(state, 1, torch.zeros(1, dtype=torch.int32, device=dev), torch.zeros(1, dtype=torch.int32, device=dev),
+                      torch.tensor([[1.0, 0.0, 1.0, 0.0]], dtype=torch.float32, device=dev))
+    raw = state[1].cpu().numpy()
+    up = lambda x: (x + 255) // 256 * 256                      # noqa: E731
+    keys_off = up(64 * 4)
+    boxes_off = keys_off + up(cap * 8)
+    assert raw.size == boxes_off + up(nbox * 16)               # the layout assumed here is the library's
+    count = int(raw[:4].view(np.uint32)[0])
+    keys = raw[keys_off:keys_off + 8 * count].view(np.uint64)
+    ids = ~(keys & np.uint64(0xffffffff)).astype(np.uint32)
+    bi, ci = (ids // np.uint32(ncls)).astype(np.int64), (ids % np.uint32(ncls)).astype(np.int64)
+    dev_scores = np.zeros_like(scores)
+    dev_scores[0, bi, ci] = (keys >> np.uint64(32)).astype(np.uint32).view(np.float32)
+    dev_boxes = boxes.copy()
+    dev_boxes[0, bi] = raw[boxes_off:boxes_off + nbox * 16].view(np.float32).reshape(nbox, 4)[bi]
+    return dev_boxes, dev_scores
+
+
+@functools.lru_cache(maxsize=None)
+def _later_chunk_run(name, rule):
+    """A LATER_CHUNK_CASES input under its rule on the device (shared by the two tests below): -> (the five outputs, the device's
+    decoded boxes and scores)."""
+    heads, b, s = DC.chunk_case(name)
+    _, eng = _engine(DC.SIZE_CHUNK, 2, 1)
+    eng.set_nms_rule(*RC.RULES[rule])
+    decoded = _device_decode(eng, heads, b, s)
+    got = _run(eng, heads)
+    eng.close()
+    return got, decoded
+
+
+@pytest.mark.parametrize("name,rule", RC.LATER_CHUNK_CASES)
+def test_rule_goes_on_in_a_later_chunk(name, rule):
+    """The stack-and-disjoint images under a non-default rule: the later chunk's sort and wave-0 pass continue from the kept
+    lists that the first chunk's pass of that rule left (witness: tests/test_decode_nms_cases_cpu.py).  Against the oracle from
+    the raw heads on, decode included: decisions identical -- valid, kept indices and classes on int32 views -- and boxes and
+    scores within the project's bars."""
+    assert RC.later_chunk_witness(name, rule)["rank"] >= DC.NMS_THREADS
+    got, ref = _later_chunk_run(name, rule)[0], RC.later_chunk_reference(name, rule)
+    for k in (2, 3, 4):
+        assert got[k].dtype == ref[k].dtype and np.array_equal(got[k].view(np.int32), ref[k].view(np.int32))
+    assert_same_detections(got, ref[:5])
+    assert got[3][0] == 100
+
+
+@pytest.mark.parametrize("name,rule", RC.LATER_CHUNK_CASES)
+def test_rule_in_a_later_chunk_equals_the_oracle_bit_for_bit(name, rule):
+    """The same runs, ALL five outputs equal to the oracle of the rule on int32 views.  The oracle's greedy pass runs on the boxes
+    and scores the device's own decode stage computed from the heads (`_device_decode`): the same float32 values nms_kernel read,
+    so every bit of the result is the NMS kernel's to get right.  (With the ORACLE's decode in front, 8 to 10 of the 400 box
+    words and 10 or 11 of the 100 score words differ in their last bit or two -- the device's expf against NumPy's float32 exp,
+    measured on an MI355X with this build and the one before it alike -- which is why that comparison, the test above, has bars.)
+    The device's decode is itself held to the oracle's here: the same candidates, values within those bars."""
+    _, b, s = DC.chunk_case(name)
+    got, (dev_b, dev_s) = _later_chunk_run(name, rule)
+    thr = np.float32(RC.SCORE_THR)
+    assert np.array_equal(dev_s > thr, s > thr) and (s > thr).sum() > DC.NMS_THREADS
+    cand = (s > thr).any(axis=2)
+    print(f"device decode against the oracle's: scores {float(np.abs(dev_s - np.where(s > thr, s, 0)).max()):.3e}, "
+          f"boxes relative {float((np.abs(dev_b[cand] - b[cand]) / np.abs(b[cand]).max()).max()):.3e}")
+    assert np.abs(dev_s - np.where(s > thr, s, 0)).max() < 1e-6
+    assert (np.abs(dev_b[cand] - b[cand]) <= 1e-5 * np.maximum(1.0, np.abs(b[cand]))).all()
+    kind, beta, agn = RC.RULES[rule]
+    ref = NR.combined_nms_rule(dev_b, dev_s, 100, 100, RC.IOU_THR, RC.SCORE_THR, kind, beta, agn)
+    assert ref[5] >= 1e-6 and ref[3][0] == 100
+    assert RC.rank_of_last_kept_under(dev_s[0], ref) >= DC.NMS_THREADS
+    for what, g, r in zip(("boxes", "scores", "classes", "valid", "kept"), got, ref[:5]):
+        print(f"{what}: {int((g.view(np.int32) != r.view(np.int32)).sum())} of {g.size} words differ")
+    for k in (2, 3, 4, 0, 1):
+        assert got[k].dtype == ref[k].dtype and np.array_equal(got[k].view(np.int32), ref[k].view(np.int32)), ("output", k)
 
 
 # ------------------------------------------------------------------------------------------------ 4. state

@@ -6,8 +6,8 @@
 // score threshold cannot yield candidates and are dropped at once; the wave then sweeps the class logits of
 // the surviving boxes (coalesced), forms score = sigmoid(obj)*sigmoid(cls) and appends the ones with
 // score > score_threshold (strict) to the image's candidate list with ONE wave-aggregated atomic per pass
-// (ballot + popcount).  Only surviving boxes are decoded to coordinates.  A candidate is a 64-bit key  (score bits << 32) | ~(box_index*C + class): sorting keys
-// descending gives (score desc, box index asc, class asc) -- the tie order this build defines.
+// (ballot + popcount).  Only surviving boxes are decoded to coordinates.  A candidate is a 64-bit key (candidates.h), which also
+// defines the tie order.
 // Rectangular inputs (H x W): scale s has gh = H / stride rows and gw = W / stride columns, cells row-major; box index =
 // box_off[s] + (row * gw + col) * 3 + anchor.  x1 and x2 are divided by W, y1 and y2 by H (the reference divides all four by
 // input_shape[0], custom_layers.py:284 -- for a square input the same float32 division, bit for bit).
@@ -24,6 +24,7 @@
 // SORT_CAP keys through the register bitonic network and wave 0's pass over 64 candidates at a time.
 // IoU is TensorFlow's: corners min/max-normalised, 0 if either area <= 0, suppress iff IoU > threshold.
 // That is the default pair rule; y4_set_nms_rule selects DIoU-NMS (nms_measure) and / or class-agnostic suppression (nms_kernel's AGN).
+#include "candidates.h"
 #include "kernels.h"
 
 #pragma clang fp contract(off)   // keep the reference's float32 op order (no fused multiply-add)
@@ -31,6 +32,31 @@
 namespace y4 {
 
 __device__ __forceinline__ float sigmoid_f(float x) { return 1.0f / (1.0f + expf(-x)); }
+
+// score = sigmoid(obj) * sigmoid(class logit x) > score_thr (strict)?  -> *score when it is.  Cheap screen first (v_exp_f32 +
+// v_rcp_f32, ~1e-6 relative): the exact float32 sigmoid (IEEE expf + division, what the decision is defined on) runs only for
+// scores within 0.2 % of the cut.  (A NaN logit fails the screen: it is no candidate at any threshold.)
+__device__ __forceinline__ bool decode_score(float s_obj, float x, float score_thr, float* score) {
+    const float approx = s_obj * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.4426950408889634f * x));
+    if (!(approx > 0.998f * score_thr)) return false;
+    *score = s_obj * sigmoid_f(x);
+    return *score > score_thr;
+}
+
+// custom_layers.py:251-256: the four box logits t of anchor `a` in cell (row, col) of scale s -> normalised x1, y1, x2, y2
+// (cells are row-major: row over H, column over W)
+__device__ __forceinline__ float4 decode_box(const DecodeK& p, int s, int a, int row, int col, float t0, float t1, float t2, float t3) {
+    const float bx = ((sigmoid_f(t0) * p.xyscale[s]) - p.xyoff[s] + (float)col) * (float)p.stride[s];
+    const float by = ((sigmoid_f(t1) * p.xyscale[s]) - p.xyoff[s] + (float)row) * (float)p.stride[s];
+    const float bw = expf(t2) * p.anchors[(s * 3 + a) * 2 + 0];
+    const float bh = expf(t3) * p.anchors[(s * 3 + a) * 2 + 1];
+    float4 o;
+    o.x = (bx - bw / 2.0f) / p.img_w;
+    o.y = (by - bh / 2.0f) / p.img_h;
+    o.z = (bx + bw / 2.0f) / p.img_w;
+    o.w = (by + bh / 2.0f) / p.img_h;
+    return o;
+}
 
 // One lane per (cell, anchor) box.  Because score = sigmoid(obj)*sigmoid(cls) <= sigmoid(obj) in float32
 // (sigmoid <= 1), a box whose objectness alone is not > score_threshold cannot produce a candidate: each lane
@@ -66,45 +92,16 @@ __global__ __launch_bounds__(256) void decode_kernel(const DecodeK p) {
         unsigned long long* keys = p.keys + (int64_t)bn * p.cap;
         for (int c0 = 0; c0 < p.C; c0 += 64) {
             const int c = c0 + lane;
-            bool hit = false;
-            unsigned long long key = 0;
-            if (c < p.C) {
-                // cheap screen first (v_exp_f32 + v_rcp_f32, ~1e-6 relative): the exact float32 sigmoid (IEEE
-                // expf + division, what the decision is defined on) runs only for scores within 0.2 % of the cut
-                const float x = bp[5 + c];
-                const float approx = so * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.4426950408889634f * x));
-                const float sc = approx > 0.998f * p.score_thr ? so * sigmoid_f(x) : 0.f;
-                if (sc > p.score_thr) {
-                    hit = true;
-                    const uint32_t id = (uint32_t)bb * (uint32_t)p.C + (uint32_t)c;
-                    key = ((unsigned long long)__float_as_uint(sc) << 32) | (unsigned long long)(~id);
-                }
-            }
-            const unsigned long long mask = __ballot(hit);
-            if (mask) {
-                uint32_t base = 0;
-                if (lane == 0) base = atomicAdd(p.counts + (size_t)bn * COUNT_STRIDE, (uint32_t)__popcll(mask));
-                base = __shfl(base, 0);
-                if (hit) {
-                    const uint32_t pos = base + (uint32_t)__popcll(mask & ((1ull << lane) - 1ull));
-                    if (pos < p.cap) keys[pos] = key;
-                }
-            }
+            float sc = 0.f;
+            const bool hit = c < p.C && decode_score(so, bp[5 + c], p.score_thr, &sc);
+            const uint32_t pos = wave_append(p.counts + (size_t)bn * COUNT_STRIDE, hit, lane);
+            if (hit && pos < p.cap) keys[pos] = cand_key(sc, cand_make_id((uint32_t)bb, (uint32_t)c, p.C));
         }
         if (lane == j) {
-            // custom_layers.py:251-256 (only boxes that can be candidates are ever read back by the NMS stage)
+            // (only boxes that can be candidates are ever read back by the NMS stage)
             const int gw = p.gw[s];
-            const int row = cell / gw, col = cell - row * gw;          // cells are row-major: row over H, column over W
-            const float bx = ((sigmoid_f(cellp[0]) * p.xyscale[s]) - p.xyoff[s] + (float)col) * (float)p.stride[s];
-            const float by = ((sigmoid_f(cellp[1]) * p.xyscale[s]) - p.xyoff[s] + (float)row) * (float)p.stride[s];
-            const float bw = expf(cellp[2]) * p.anchors[(s * 3 + a) * 2 + 0];
-            const float bh = expf(cellp[3]) * p.anchors[(s * 3 + a) * 2 + 1];
-            float4 o;
-            o.x = (bx - bw / 2.0f) / p.img_w;
-            o.y = (by - bh / 2.0f) / p.img_h;
-            o.z = (bx + bw / 2.0f) / p.img_w;
-            o.w = (by + bh / 2.0f) / p.img_h;
-            *(float4*)(p.dboxes + ((int64_t)n * p.nbox + b) * 4) = o;
+            const int row = cell / gw, col = cell - row * gw;
+            *(float4*)(p.dboxes + ((int64_t)n * p.nbox + b) * 4) = decode_box(p, s, a, row, col, cellp[0], cellp[1], cellp[2], cellp[3]);
         }
     }
 }
@@ -135,9 +132,7 @@ constexpr int DC_STAGE = 512;               // keys per wave slice; a cell yield
 struct DecodeStage { unsigned long long* slice; uint32_t fill; int img; };
 __device__ __forceinline__ void decode_flush(const DecodeK& p, DecodeStage& st, int lane) {
     if (st.fill) {
-        uint32_t base = 0;
-        if (lane == 0) base = atomicAdd(p.counts + (size_t)st.img * COUNT_STRIDE, st.fill);
-        base = __shfl(base, 0);
+        const uint32_t base = wave_reserve(p.counts + (size_t)st.img * COUNT_STRIDE, st.fill, lane);
         unsigned long long* keys = p.keys + (int64_t)st.img * p.cap;
         for (uint32_t i = lane; i < st.fill; i += 64)
             if (base + i < p.cap) keys[base + i] = st.slice[i];
@@ -152,7 +147,6 @@ __device__ __forceinline__ void decode_one_cell(const DecodeK& p, const DecodeCe
     // so[a] = sigmoid(objectness of anchor a): the screen's value for this cell (the same float32 logit through the same sigmoid_f)
     const int box0 = p.box_off[s] + rem * 3;
     if (n != st.img || st.fill + 3 * p.C > DC_STAGE) { decode_flush(p, st, lane); st.img = n; }     // wave-uniform
-    const float cut = 0.998f * p.score_thr;
     unsigned long long key[4];
     unsigned long long mask[4];
     uint32_t total = 0;
@@ -165,16 +159,10 @@ __device__ __forceinline__ void decode_one_cell(const DecodeK& p, const DecodeCe
             const int a = e >= 2 * nf ? 2 : (e >= nf ? 1 : 0);
             const int f = e - a * nf;
             const float sa = a == 0 ? so[0] : (a == 1 ? so[1] : so[2]);
-            if (f >= 5 && sa > p.score_thr) {
-                const float approx = sa * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.4426950408889634f * v[k]));
-                if (approx > cut) {
-                    const float sc = sa * sigmoid_f(v[k]);
-                    if (sc > p.score_thr) {
-                        hit = true;
-                        const uint32_t id = (uint32_t)(box0 + a) * (uint32_t)p.C + (uint32_t)(f - 5);
-                        key[k] = ((unsigned long long)__float_as_uint(sc) << 32) | (unsigned long long)(~id);
-                    }
-                }
+            float sc;
+            if (f >= 5 && sa > p.score_thr && decode_score(sa, v[k], p.score_thr, &sc)) {
+                hit = true;
+                key[k] = cand_key(sc, cand_make_id((uint32_t)(box0 + a), (uint32_t)(f - 5), p.C));
             }
         }
         mask[k] = __ballot(hit);
@@ -220,24 +208,15 @@ __global__ __launch_bounds__(256) void decode_cell_kernel(const DecodeK p) {
         pass = sig > p.score_thr;
     }
     // Round 4: the box of every (cell, anchor) that passed -- the condition under which decode_one_cell used to compute it on 3 of its
-    // 64 lanes, once per flagged cell -- is computed HERE, one per lane, for all of the wave's cells at once (custom_layers.py:251-256;
-    // the four box logits come from the cell: its lines are read by the full-cell load anyway)
+    // 64 lanes, once per flagged cell -- is computed HERE, one per lane, for all of the wave's cells at once (decode_box; the four
+    // box logits come from the cell: its lines are read by the full-cell load anyway)
     if (pass) {
         const DecodeCell cl = decode_locate(p, cell0 + c);
         const int s = cl.s, gw = p.gw[s];
         const float* tp = cl.src + a * nf;
         const float t0 = tp[0], t1 = tp[1], t2 = tp[2], t3 = tp[3];
         const int row = (int)fastdiv((uint32_t)cl.rem, p.div_gw[s]), col = cl.rem - row * gw;
-        const float bx = ((sigmoid_f(t0) * p.xyscale[s]) - p.xyoff[s] + (float)col) * (float)p.stride[s];
-        const float by = ((sigmoid_f(t1) * p.xyscale[s]) - p.xyoff[s] + (float)row) * (float)p.stride[s];
-        const float bw = expf(t2) * p.anchors[(s * 3 + a) * 2 + 0];
-        const float bh = expf(t3) * p.anchors[(s * 3 + a) * 2 + 1];
-        float4 o;
-        o.x = (bx - bw / 2.0f) / p.img_w;
-        o.y = (by - bh / 2.0f) / p.img_h;
-        o.z = (bx + bw / 2.0f) / p.img_w;
-        o.w = (by + bh / 2.0f) / p.img_h;
-        *(float4*)(p.dboxes + ((int64_t)cl.n * p.nbox + p.box_off[s] + cl.rem * 3 + a) * 4) = o;
+        *(float4*)(p.dboxes + ((int64_t)cl.n * p.nbox + p.box_off[s] + cl.rem * 3 + a) * 4) = decode_box(p, s, a, row, col, t0, t1, t2, t3);
     }
     unsigned long long m = __ballot(pass);
     if (!m) return;
@@ -316,7 +295,7 @@ __device__ __forceinline__ float nms_measure(const float4 a, const float4 b, flo
 // Bitonic sort of skey[0 .. m2) (m2 a power of two >= 64, <= NE * NMS_THREADS), descending, with the keys in registers
 // (element tid + NMS_THREADS * e): partners less than 64 apart are exchanged by wave shuffles and partners NMS_THREADS or
 // more apart sit in the same thread, so only the stages with 64 <= j < NMS_THREADS go through LDS (`xbuf`, m2 keys) and a
-// workgroup barrier -- 14 of the 78 stages at 4096 keys.  (Chunks of at most 1024 keys take the rank sort in nms_kernel.)
+// workgroup barrier -- 14 of the 78 stages at 4096 keys.  (Chunks of at most 1024 keys take nms_rank_sort.)
 template <int NE>
 __device__ __forceinline__ void nms_sort_regs(unsigned long long* skey, unsigned long long* xbuf, uint32_t m2, int tid) {
     unsigned long long v[NE];
@@ -369,347 +348,375 @@ __device__ __forceinline__ void nms_sort_regs(unsigned long long* skey, unsigned
     __syncthreads();
 }
 
-// KIND: the pair measure (nms_measure).  AGN: class-agnostic suppression -- a kept box suppresses later candidates of every class;
-// max_per_class still counts per class, and a candidate its class's cap turns away is not kept and suppresses nothing.  The
-// round-parallel pass keys its heads by class, which is what makes its rounds independent; with one head slot for all classes it
-// would decide one kept box per round behind two workgroup barriers -- the sequence wave 0 walks without them -- so an agnostic
-// launch takes the wave-0 pass on the first chunk too, as C > PAR_MAX_C does.
-template <int KIND, bool AGN>
-__global__ __launch_bounds__(NMS_THREADS) void nms_kernel(const NmsK p) {
-    extern __shared__ __attribute__((aligned(16))) char nsm[];
-    unsigned long long* skey = (unsigned long long*)nsm;                  // SORT_CAP
-    float4* sbox = (float4*)(nsm + SORT_CAP * 8);                          // SORT_CAP
-    float4* kbox = (float4*)(nsm + SORT_CAP * 24);                         // max_total
-    int* kcls = (int*)(kbox + p.max_total);                                // max_total
-    float* kscore = (float*)(kcls + p.max_total);                          // max_total
-    int* kidx = (int*)(kscore + p.max_total);                              // max_total
-    uint32_t* hist = (uint32_t*)(kidx + p.max_total);                      // 256
-    uint32_t* sh = hist + 256;                                             // scratch words
-    // sh[0]=count in chunk, sh[1]=kept, sh[2]=remaining below cutoff, sh[3..4]=pivot lo/hi, sh[5]=need;
-    // round-parallel pass: sh[8..9] = lowest undecided position (two alternating buffers), sh[10..11] = kept below it
-    uint32_t* pfirst = sh + 16;                                            // [2][C] lowest undecided position of a class
-    uint32_t* pcount = pfirst + 2 * (p.C <= PAR_MAX_C ? p.C : 0);          // [C] kept boxes of a class
-    uint32_t* pflag = pcount + (p.C <= PAR_MAX_C ? p.C : 0);               // [NMS_THREADS] candidate was kept; then [16] per-wave kept counts
+// ---- nms_kernel's dynamic LDS.  nms_lds_layout states it ONCE: the kernel carves by it (NmsLds) and the host asks it for the size.
+struct NmsLdsLayout { uint32_t skey, sbox, kbox, kcls, kscore, kidx, hist, words, pfirst, pcount, pflag, bytes; };
+__host__ __device__ inline NmsLdsLayout nms_lds_layout(int max_total, int C) {
+    const uint32_t T = (uint32_t)max_total, par_c = C <= PAR_MAX_C ? (uint32_t)C : 0u;
+    NmsLdsLayout o;
+    uint32_t at = 0;
+    o.skey = at;   at += SORT_CAP * 8;               // [SORT_CAP] the chunk's keys
+    o.sbox = at;   at += SORT_CAP * 16;              // [SORT_CAP] the chunk's boxes; scratch of the selectors and sorts before that
+    o.kbox = at;   at += T * 16;                     // [max_total] the kept list: box, class, score, box index
+    o.kcls = at;   at += T * 4;
+    o.kscore = at; at += T * 4;
+    o.kidx = at;   at += T * 4;
+    o.hist = at;   at += 256 * 4;                    // [256] digit histogram of the exact select
+    o.words = at;  at += 64;                         // NmsWords
+    o.pfirst = at; at += 2 * par_c * 4;              // [2][C] lowest undecided position of a class
+    o.pcount = at; at += par_c * 4;                  // [C] kept boxes of a class
+    o.pflag = at;  at += (NMS_THREADS + 16) * 4;     // [NMS_THREADS] candidate was kept; then [16] per-wave kept counts
+    o.bytes = at;
+    return o;
+}
 
-    const int n = blockIdx.x, tid = threadIdx.x;
-    uint32_t cnt = p.counts[(size_t)n * COUNT_STRIDE];
-    if (cnt > p.cap) {
-        if (tid == 0) atomicOr(p.status, 1u);
-        cnt = p.cap;
+// The words through which the phases of nms_kernel talk to each other
+struct NmsWords {
+    uint32_t chunk_count;      // keys taken into the chunk (nms_take_chunk)
+    uint32_t kept;             // kept boxes so far
+    uint32_t remaining;        // keys below the cutoff (nms_count_below)
+    uint32_t pivot_bin1;       // nms_histogram_pivot: 1 + the pivot bin; stays 0 when not even the top bin fits
+    uint32_t suffix;           // ... the keys in the bins from the pivot bin up
+    uint32_t digit;            // nms_select_pivot: the digit chosen in this pass
+    uint32_t need;             // ... keys still needed inside that digit
+    uint32_t unused0;
+    uint32_t undecided[2];     // nms_pass_parallel: lowest undecided position (two alternating buffers)
+    uint32_t kept_front[2];    // ... kept candidates in front of it
+    uint32_t unused1[4];
+};
+static_assert(sizeof(NmsWords) == 64, "nms_lds_layout reserves 64 bytes");
+
+struct NmsLds {
+    unsigned long long* skey;
+    float4* sbox;
+    float4* kbox;
+    int* kcls;
+    float* kscore;
+    int* kidx;
+    uint32_t* hist;
+    NmsWords* w;
+    uint32_t *pfirst, *pcount, *pflag;
+    __device__ __forceinline__ NmsLds(char* base, int max_total, int C) {
+        const NmsLdsLayout o = nms_lds_layout(max_total, C);
+        skey = (unsigned long long*)(base + o.skey);
+        sbox = (float4*)(base + o.sbox);
+        kbox = (float4*)(base + o.kbox);
+        kcls = (int*)(base + o.kcls);
+        kscore = (float*)(base + o.kscore);
+        kidx = (int*)(base + o.kidx);
+        hist = (uint32_t*)(base + o.hist);
+        w = (NmsWords*)(base + o.words);
+        pfirst = (uint32_t*)(base + o.pfirst);
+        pcount = (uint32_t*)(base + o.pcount);
+        pflag = (uint32_t*)(base + o.pflag);
     }
-    const unsigned long long* gk = p.keys + (int64_t)n * p.cap;
-    const float* gb = p.dboxes + (int64_t)n * p.nbox * 4;
-    if (tid == 0) sh[1] = 0;
-    unsigned long long cutoff = ~0ull;           // exclusive upper bound of keys still to visit
-    __syncthreads();
-    // every thread has read the image's candidate count: leave the counter at zero for the next step's decode (which therefore needs
-    // no memset launch in front of it; decode_launch clears only when a decode was NOT followed by its NMS)
-    if (tid == 0) p.counts[(size_t)n * COUNT_STRIDE] = 0;
+    // The box slots hold boxes from nms_load_boxes on.  Before that, within one chunk, they are:
+    __device__ __forceinline__ uint32_t* score_bins() const { return (uint32_t*)sbox; }               // [1024] nms_histogram_pivot's bins
+    __device__ __forceinline__ uint32_t* wave_suffix() const { return (uint32_t*)sbox + 1024; }       // [16] ... and its per-wave sums
+    __device__ __forceinline__ unsigned long long* xbuf() const { return (unsigned long long*)sbox; } // [SORT_CAP] the sorts' exchange buffer
+    __device__ __forceinline__ uint32_t* wave_kept() const { return pflag + NMS_THREADS; }            // [16] behind the flags
+    // one entry of the kept list
+    __device__ __forceinline__ void keep(uint32_t slot, const float4 box, int cls, unsigned long long key, uint32_t box_index) const {
+        kbox[slot] = box;
+        kcls[slot] = cls;
+        kscore[slot] = cand_score(key);
+        kidx[slot] = (int)box_index;
+    }
+};
 
-    while (true) {
-        // ---- how many keys remain below the cutoff?
-        if (tid == 0) sh[2] = 0;
+// ---- how many keys remain below the cutoff?
+__device__ __forceinline__ uint32_t nms_count_below(const NmsLds& L, const unsigned long long* gk, uint32_t cnt, unsigned long long cutoff, int tid) {
+    if (tid == 0) L.w->remaining = 0;
+    __syncthreads();
+    {
+        uint32_t local = 0;
+        for (uint32_t i = tid; i < cnt; i += NMS_THREADS) local += gk[i] < cutoff ? 1u : 0u;
+        for (int o = 32; o > 0; o >>= 1) local += __shfl_down(local, o);
+        if ((tid & 63) == 0 && local) atomicAdd(&L.w->remaining, local);
+    }
+    __syncthreads();
+    return L.w->remaining;
+}
+
+// The FIRST chunk's pivot.  The first chunk need not hold EXACTLY chunk_cap keys: one histogram pass over 1024 score bins (score
+// bits >> 14 from 0.25 up: any monotonic map of the key would do) and a suffix sum say from which bin up at most chunk_cap keys lie;
+// that bin's lowest key is the pivot.  ~2 us where the exact radix select (nms_select_pivot) takes eight passes, each with a
+// serial scan of its 256 bins.  (A top bin that alone overflows the chunk -- a thousand equal scores -- falls through
+// to the exact select.)  -> true and *pivot when the histogram gave one.
+__device__ __forceinline__ bool nms_histogram_pivot(const NmsLds& L, const unsigned long long* gk, uint32_t cnt, uint32_t chunk_cap, int tid,
+                                                    unsigned long long* pivot) {
+    constexpr uint32_t BASE = 0x3e800000u >> 14;
+    uint32_t* const hb = L.score_bins();                        // (the box slots are not in use yet)
+    uint32_t* const wsum = L.wave_suffix();
+    const int lane = tid & 63, wv = tid >> 6;
+    hb[tid] = 0;
+    if (tid == 0) L.w->pivot_bin1 = 0;
+    __syncthreads();
+    for (uint32_t i = tid; i < cnt; i += NMS_THREADS) {
+        const int x = (int)((uint32_t)(gk[i] >> 46)) - (int)BASE;
+        atomicAdd(&hb[x < 0 ? 0 : (x > 1023 ? 1023 : x)], 1u);
+    }
+    __syncthreads();
+    uint32_t suf = hb[tid];                                 // keys in bins tid .. 1023: the wave's suffix sum, then the later waves'
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const uint32_t v = __shfl_down(suf, o);
+        suf += lane + o < 64 ? v : 0u;
+    }
+    if (lane == 0) wsum[wv] = suf;
+    __syncthreads();
+    for (int w = wv + 1; w < NMS_THREADS / 64; ++w) suf += wsum[w];
+    // the lowest bin whose suffix fits the chunk (bin 0's suffix is `remaining`: it never does)
+    if (tid > 0 && suf <= chunk_cap && suf + hb[tid - 1] > chunk_cap) { L.w->pivot_bin1 = (uint32_t)tid + 1u; L.w->suffix = suf; }
+    __syncthreads();
+    // (one 2^-9-wide score bin holding more than a chunk while the bins above it are nearly empty would give a first
+    //  chunk of a few keys and leave the image to the slow later passes: a suffix under half a chunk falls through to the exact
+    //  radix select, which fills the chunk)
+    const uint32_t pb = L.w->pivot_bin1 != 0 && 2u * L.w->suffix >= chunk_cap ? L.w->pivot_bin1 : 0u;
+    if (pb != 0) *pivot = (unsigned long long)((pb - 1u + BASE) << 14) << 32;       // the bin's lowest key
+    __syncthreads();
+    return pb != 0;
+}
+
+// Exact radix select: -> the chunk_cap-th largest key below the cutoff, eight passes of one digit each.
+__device__ __forceinline__ unsigned long long nms_select_pivot(const NmsLds& L, const unsigned long long* gk, uint32_t cnt, unsigned long long cutoff,
+                                                               uint32_t chunk_cap, int tid) {
+    unsigned long long prefix = 0, pmask = 0;
+    uint32_t need = chunk_cap;
+    for (int shift = 56; shift >= 0; shift -= 8) {
+        for (int i = tid; i < 256; i += NMS_THREADS) L.hist[i] = 0;
         __syncthreads();
+        for (uint32_t i = tid; i < cnt; i += NMS_THREADS) {
+            const unsigned long long k = gk[i];
+            if (k < cutoff && (k & pmask) == prefix) atomicAdd(&L.hist[(k >> shift) & 255], 1u);
+        }
+        __syncthreads();
+        if (tid == 0) {
+            uint32_t acc = 0;
+            int d = 255;
+            for (; d > 0; --d) {
+                if (acc + L.hist[d] >= need) break;
+                acc += L.hist[d];
+            }
+            L.w->need = need - acc;                  // still needed inside digit d
+            L.w->digit = (uint32_t)d;
+        }
+        __syncthreads();
+        need = L.w->need;
+        prefix |= (unsigned long long)L.w->digit << shift;
+        pmask |= 255ull << shift;
+        __syncthreads();
+    }
+    return prefix;                                    // keys are unique: exactly chunk_cap keys in [pivot, cutoff)
+}
+
+// ---- gather the chunk: the keys in [pivot, cutoff) -> skey[0 .. m), zero padded to m2, the next power of two (>= 64).  -> m
+__device__ __forceinline__ uint32_t nms_take_chunk(const NmsLds& L, const unsigned long long* gk, uint32_t cnt, unsigned long long cutoff,
+                                                   unsigned long long pivot, uint32_t chunk_cap, int tid, uint32_t* m2_out) {
+    if (tid == 0) L.w->chunk_count = 0;
+    __syncthreads();
+    for (uint32_t i0 = 0; i0 < cnt; i0 += NMS_THREADS) {      // one LDS atomic per wave and pass, not per key (wave_append)
+        const uint32_t i = i0 + tid;
+        const unsigned long long k = i < cnt ? gk[i] : 0ull;
+        const bool take = i < cnt && k < cutoff && k >= pivot;
+        const uint32_t pos = wave_append(&L.w->chunk_count, take, tid & 63);
+        if (take && pos < chunk_cap) L.skey[pos] = k;
+    }
+    __syncthreads();
+    const uint32_t m = L.w->chunk_count < chunk_cap ? L.w->chunk_count : chunk_cap;
+    uint32_t m2 = 64;
+    while (m2 < m) m2 <<= 1;
+    for (uint32_t i = m + tid; i < m2; i += NMS_THREADS) L.skey[i] = 0;
+    __syncthreads();
+    *m2_out = m2;
+    return m;
+}
+
+// Rank sort of skey[0 .. m2), m2 <= NMS_THREADS, descending: a thread's key goes to position (number of larger keys); keys are
+// unique.  No dependent chain, two barriers.  In-kernel timestamps at ~1000 keys: 22 us, the same as the 55 dependent exchange
+// stages of a bitonic network in LDS or in registers with shuffles, and as broadcasting the keys with v_readlane instead of LDS
+// reads (16 waves on one CU: LDS cycles of the broadcast reads here, instruction issue there) -- kept because it is the
+// shortest; the whole kernel went 80 -> 76.5 us with it and the wave-aggregated gather of nms_take_chunk.
+// Round 4: the ranks come from a merge instead of all pairs -- every wave sorts its 64 keys in registers (21 shuffle
+// stages), the sorted runs go back to LDS, and a key's rank is its place in its own run plus, per other run, the number
+// of larger keys found by a 6-step binary search (the searches of the runs are independent chains): ~600 instructions
+// per thread instead of ~3 500.
+__device__ __forceinline__ void nms_rank_sort(const NmsLds& L, uint32_t m, uint32_t m2, int tid) {
+    unsigned long long* const skey = L.skey;
+    unsigned long long* const xbuf = L.xbuf();
+    unsigned long long key = (uint32_t)tid < m2 ? skey[tid] : 0ull;
+    const int lane = tid & 63, wv = tid >> 6;
+    for (int k = 2; k <= 64; k <<= 1)
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            const unsigned long long o = __shfl_xor(key, j);
+            const bool want_max = ((lane & j) == 0) == ((lane & k) == 0);      // descending run
+            key = (want_max ? o > key : o < key) ? o : key;
+        }
+    __syncthreads();
+    if ((uint32_t)tid < m2) skey[tid] = key;
+    __syncthreads();
+    uint32_t rank = (uint32_t)lane;
+    const int nruns = (int)(m2 >> 6);
+    for (int r = 0; r < nruns; ++r) {
+        if (r == wv) continue;                               // (wave-uniform)
+        const unsigned long long* run = skey + r * 64;
+        uint32_t lo = 0;                                     // number of keys of the run known to be larger
+#pragma unroll
+        for (int st = 32; st > 0; st >>= 1) lo += run[lo + st - 1] > key ? (uint32_t)st : 0u;
+        lo += run[lo] > key ? 1u : 0u;                       // (lo <= 63 here)
+        rank += lo;
+    }
+    __syncthreads();
+    if ((uint32_t)tid < m2 && key != 0ull) xbuf[rank] = key;  // (keys are unique and non-zero; the zero padding stays behind position m)
+    __syncthreads();
+    if ((uint32_t)tid < m) skey[tid] = xbuf[tid];
+    __syncthreads();
+}
+
+// ---- gather the chunk's boxes into LDS
+__device__ __forceinline__ void nms_load_boxes(const NmsLds& L, const float* gb, const NmsK& p, uint32_t m, int tid) {
+    for (uint32_t i = tid; i < m; i += NMS_THREADS)
+        L.sbox[i] = *(const float4*)(gb + (int64_t)cand_box_class(L.skey[i], p.C, p.div_c).box * 4);
+    __syncthreads();
+}
+
+// ---- greedy pass, ROUND-PARALLEL on every wave: the usual case (all of the image's candidates in one chunk of at most
+// NMS_THREADS; round 4).  One candidate per thread; in a round the lowest undecided candidate of every class (an LDS atomicMin per
+// class) is final -- every earlier kept box of its class was such a head in an earlier round and it survived the test
+// against it then -- so it is kept (class cap permitting) and the class's other undecided candidates test against it.
+// The rounds stop once the candidates in front of the lowest undecided one hold max_total kept boxes; the kept boxes'
+// ranks in sorted order are their output slots.  Same decisions as the sequential rule (same tests on the same pairs),
+// in as many rounds as the busiest class among the leading candidates has kept boxes (bench input: ~7) of two
+// barriers each, where the wave-0 pass below visits candidates 64 at a time at ~10 us per batch.
+// (The first chunk: m <= NMS_THREADS; the kept lists it leaves are what the wave-0 pass of a later chunk continues from.)
+template <int KIND>
+__device__ __forceinline__ void nms_pass_parallel(const NmsK& p, const NmsLds& L, uint32_t m, int tid) {
+    NmsWords* const w = L.w;
+    uint32_t* const pfirst = L.pfirst;
+    uint32_t* const pcount = L.pcount;
+    uint32_t* const pflag = L.pflag;
+    const uint32_t t = (uint32_t)tid;
+    const int lane = tid & 63;
+    const bool cap_binds = p.max_per_class < p.max_total;
+    bool und = t < m, keptf = false;
+    const unsigned long long key = und ? L.skey[t] : 0ull;
+    const float4 cb = und ? L.sbox[t] : make_float4(0.f, 0.f, 0.f, 0.f);
+    const CandBoxClass bc = cand_box_class(key, p.C, p.div_c);
+    const int cls = und ? bc.cls : 0;
+    for (int c = tid; c < p.C; c += NMS_THREADS) { pfirst[c] = PAR_NONE; pfirst[p.C + c] = PAR_NONE; pcount[c] = 0; }
+    if (tid == 0) { w->undecided[0] = PAR_NONE; w->undecided[1] = PAR_NONE; w->kept_front[0] = 0; w->kept_front[1] = 0; }
+    __syncthreads();
+    for (int r = 0;; ++r) {
+        const int b = r & 1;
+        uint32_t* const first = pfirst + b * p.C;
+        if (und) atomicMin(&first[cls], t);
         {
-            uint32_t local = 0;
-            for (uint32_t i = tid; i < cnt; i += NMS_THREADS) local += gk[i] < cutoff ? 1u : 0u;
-            for (int o = 32; o > 0; o >>= 1) local += __shfl_down(local, o);
-            if ((tid & 63) == 0 && local) atomicAdd(&sh[2], local);
+            const unsigned long long mk = __ballot(und);
+            if (mk && lane == __ffsll((long long)mk) - 1) atomicMin(&w->undecided[b], t);
         }
         __syncthreads();
-        const uint32_t remaining = sh[2];
-        if (remaining == 0) break;
-        // ---- pivot = chunk_cap-th largest key below the cutoff (0 when everything fits).  The FIRST chunk is at most NMS_THREADS
-        // keys -- what the merge-rank sort and the round-parallel pass take, and nearly always all that max_total kept boxes
-        // need; the later ones SORT_CAP
-        const uint32_t chunk_cap = cutoff == ~0ull ? (uint32_t)NMS_THREADS : (uint32_t)SORT_CAP;
-        unsigned long long pivot = 0;
-        bool have_pivot = false;
-        if (cutoff == ~0ull && remaining > chunk_cap) {
-            // The first chunk need not hold EXACTLY chunk_cap keys: one histogram pass over 1024 score bins (score bits >> 14 from
-            // 0.25 up: any monotonic map of the key would do) and a suffix sum say from which bin up at most chunk_cap keys lie;
-            // that bin's lowest key is the pivot.  ~2 us where the exact radix select below takes eight passes, each with a
-            // serial scan of its 256 bins.  (A top bin that alone overflows the chunk -- a thousand equal scores -- falls through
-            // to the exact select.)
-            constexpr uint32_t BASE = 0x3e800000u >> 14;
-            uint32_t* const hb = (uint32_t*)sbox;                   // (the box slots are not in use yet)
-            const int lane = tid & 63, wv = tid >> 6;
-            hb[tid] = 0;
-            if (tid == 0) sh[3] = 0;                                // 1 + the pivot bin; stays 0 when not even the top bin fits
-            __syncthreads();
-            for (uint32_t i = tid; i < cnt; i += NMS_THREADS) {
-                const int x = (int)((uint32_t)(gk[i] >> 46)) - (int)BASE;
-                atomicAdd(&hb[x < 0 ? 0 : (x > 1023 ? 1023 : x)], 1u);
-            }
-            __syncthreads();
-            uint32_t suf = hb[tid];                                 // keys in bins tid .. 1023: the wave's suffix sum, then the later waves'
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) {
-                const uint32_t v = __shfl_down(suf, o);
-                suf += lane + o < 64 ? v : 0u;
-            }
-            if (lane == 0) hb[1024 + wv] = suf;
-            __syncthreads();
-            for (int w = wv + 1; w < NMS_THREADS / 64; ++w) suf += hb[1024 + w];
-            // the lowest bin whose suffix fits the chunk (bin 0's suffix is `remaining`: it never does)
-            if (tid > 0 && suf <= chunk_cap && suf + hb[tid - 1] > chunk_cap) { sh[3] = (uint32_t)tid + 1u; sh[4] = suf; }
-            __syncthreads();
-            // (one 2^-9-wide score bin holding more than a chunk while the bins above it are nearly empty would give a first
-            //  chunk of a few keys and leave the image to the slow later passes: a suffix under half a chunk falls through to the exact
-            //  radix select below, which fills the chunk)
-            const uint32_t pb = sh[3] != 0 && 2u * sh[4] >= chunk_cap ? sh[3] : 0u;
-            if (pb != 0) {
-                pivot = (unsigned long long)((pb - 1u + BASE) << 14) << 32;       // the bin's lowest key
-                have_pivot = true;
-            }
-            __syncthreads();
+        const uint32_t U = w->undecided[b];                 // every candidate in front of U is decided
+        {
+            const unsigned long long mk = __ballot(keptf && t < U);
+            if (mk && lane == 0) atomicAdd(&w->kept_front[b], (uint32_t)__popcll(mk));
         }
-        if (remaining > chunk_cap && !have_pivot) {
-            unsigned long long prefix = 0, pmask = 0;
-            uint32_t need = chunk_cap;
-            for (int shift = 56; shift >= 0; shift -= 8) {
-                for (int i = tid; i < 256; i += NMS_THREADS) hist[i] = 0;
-                __syncthreads();
-                for (uint32_t i = tid; i < cnt; i += NMS_THREADS) {
-                    const unsigned long long k = gk[i];
-                    if (k < cutoff && (k & pmask) == prefix) atomicAdd(&hist[(k >> shift) & 255], 1u);
-                }
-                __syncthreads();
-                if (tid == 0) {
-                    uint32_t acc = 0;
-                    int d = 255;
-                    for (; d > 0; --d) {
-                        if (acc + hist[d] >= need) break;
-                        acc += hist[d];
-                    }
-                    sh[5] = need - acc;                  // still needed inside digit d
-                    sh[3] = (uint32_t)d;
-                }
-                __syncthreads();
-                need = sh[5];
-                prefix |= (unsigned long long)sh[3] << shift;
-                pmask |= 255ull << shift;
-                __syncthreads();
-            }
-            pivot = prefix;                               // keys are unique: exactly chunk_cap keys in [pivot, cutoff)
+        const uint32_t h = und ? first[cls] : PAR_NONE;
+        const bool head = und && h == t;
+        if (head) {
+            keptf = !cap_binds || (int)pcount[cls] < p.max_per_class;      // (the class's only head this round)
+            if (keptf) pcount[cls] = pcount[cls] + 1;
+            pflag[t] = keptf ? 1u : 0u;
+            und = false;
         }
-        // ---- gather the chunk, sort it descending
-        if (tid == 0) sh[0] = 0;
+        if (tid == 0) { w->undecided[b ^ 1] = PAR_NONE; w->kept_front[b ^ 1] = 0; }     // (last read before this round's first barrier)
         __syncthreads();
-        for (uint32_t i0 = 0; i0 < cnt; i0 += NMS_THREADS) {      // one LDS atomic per wave and pass, not per key: a thousand
-            const uint32_t i = i0 + tid;                           // same-address atomics serialise
-            const unsigned long long k = i < cnt ? gk[i] : 0ull;
-            const bool take = i < cnt && k < cutoff && k >= pivot;
-            const unsigned long long mask = __ballot(take);
-            if (mask) {                                            // wave-uniform
-                uint32_t base = 0;
-                if ((tid & 63) == 0) base = atomicAdd(&sh[0], (uint32_t)__popcll(mask));
-                base = __shfl(base, 0);
-                const uint32_t pos = base + (uint32_t)__popcll(mask & ((1ull << (tid & 63)) - 1ull));
-                if (take && pos < chunk_cap) skey[pos] = k;
-            }
+        if (U == PAR_NONE || w->kept_front[b] >= (uint32_t)p.max_total) break;   // uniform
+        if (head) first[cls] = PAR_NONE;                    // (every thread read it before the barrier; next use: round r + 2)
+        if (und) {
+            // a head that the class cap turned away suppresses nothing -- and everything later in its class is turned away too
+            if (pflag[h] == 0u) und = false;
+            else if (nms_measure<KIND>(cb, L.sbox[h], p.iou_thr, p.beta) > p.iou_thr) und = false;
         }
-        __syncthreads();
-        const uint32_t m = sh[0] < chunk_cap ? sh[0] : chunk_cap;
-        uint32_t m2 = 64;
-        while (m2 < m) m2 <<= 1;
-        for (uint32_t i = m + tid; i < m2; i += NMS_THREADS) skey[i] = 0;
-        __syncthreads();
-        // sort the chunk, descending
-        if (m2 <= (uint32_t)NMS_THREADS) {
-            // Rank sort: a thread's key goes to position (number of larger keys); keys are unique.  No dependent chain, two
-            // barriers.  In-kernel timestamps at ~1000 keys: 22 us, the same as the 55 dependent exchange stages of a bitonic
-            // network in LDS or in registers with shuffles, and as broadcasting the keys with v_readlane instead of LDS reads
-            // (16 waves on one CU: LDS cycles of the broadcast reads here, instruction issue there) -- kept because it is the
-            // shortest; the whole kernel went 80 -> 76.5 us with it and the wave-aggregated gather above.
-            // Round 4: the ranks come from a merge instead of all pairs -- every wave sorts its 64 keys in registers (21 shuffle
-            // stages), the sorted runs go back to LDS, and a key's rank is its place in its own run plus, per other run, the number
-            // of larger keys found by a 6-step binary search (the searches of the runs are independent chains): ~600 instructions
-            // per thread instead of ~3 500.
-            unsigned long long* const xbuf = (unsigned long long*)sbox;
-            unsigned long long key = (uint32_t)tid < m2 ? skey[tid] : 0ull;
-            const int lane = tid & 63, wv = tid >> 6;
-            for (int k = 2; k <= 64; k <<= 1)
-                for (int j = k >> 1; j > 0; j >>= 1) {
-                    const unsigned long long o = __shfl_xor(key, j);
-                    const bool want_max = ((lane & j) == 0) == ((lane & k) == 0);      // descending run
-                    key = (want_max ? o > key : o < key) ? o : key;
-                }
-            __syncthreads();
-            if ((uint32_t)tid < m2) skey[tid] = key;
-            __syncthreads();
-            uint32_t rank = (uint32_t)lane;
-            const int nruns = (int)(m2 >> 6);
-            for (int r = 0; r < nruns; ++r) {
-                if (r == wv) continue;                               // (wave-uniform)
-                const unsigned long long* run = skey + r * 64;
-                uint32_t lo = 0;                                     // number of keys of the run known to be larger
-#pragma unroll
-                for (int st = 32; st > 0; st >>= 1) lo += run[lo + st - 1] > key ? (uint32_t)st : 0u;
-                lo += run[lo] > key ? 1u : 0u;                       // (lo <= 63 here)
-                rank += lo;
-            }
-            __syncthreads();
-            if ((uint32_t)tid < m2 && key != 0ull) xbuf[rank] = key;  // (keys are unique and non-zero; the zero padding stays behind position m)
-            __syncthreads();
-            if ((uint32_t)tid < m) skey[tid] = xbuf[tid];
-            __syncthreads();
-        } else {
-            nms_sort_regs<SORT_CAP / NMS_THREADS>(skey, (unsigned long long*)sbox, m2, tid);
-        }
-        // ---- gather the chunk's boxes into LDS
-        for (uint32_t i = tid; i < m; i += NMS_THREADS) {
-            const uint32_t id = ~(uint32_t)(skey[i] & 0xffffffffull);
-            sbox[i] = *(const float4*)(gb + (int64_t)fastdiv(id, p.div_c) * 4);
-        }
-        __syncthreads();
-        // ---- greedy pass (wave 0), 64 sorted candidates at a time, one per lane.  The sequential rule "keep a candidate
-        // unless an EARLIER KEPT box of its class overlaps it" is evaluated in two steps that give exactly the sequential
-        // result: (1) every lane tests its candidate against the boxes kept before this batch (uniform loop over the kept
-        // list in LDS; the IoU only for the rare same-class pairs); (2) the batch's survivors are visited in order -- the
-        // lowest surviving lane is final, it is kept, its class and box are broadcast, and later same-class lanes test
-        // against it.  Per candidate that is a few instructions instead of the ~90 of one-candidate-per-iteration on a wave
-        // that retires one instruction per ~10 cycles (in-kernel timestamps: 41 us of this kernel were this pass).
-        // Round 4 -- the usual case (all of the image's candidates in one chunk of at most NMS_THREADS) runs ROUND-PARALLEL on every
-        // wave instead: one candidate per thread; in a round the lowest undecided candidate of every class (an LDS atomicMin per
-        // class) is final -- every earlier kept box of its class was such a head in an earlier round and it survived the test
-        // against it then -- so it is kept (class cap permitting) and the class's other undecided candidates test against it.
-        // The rounds stop once the candidates in front of the lowest undecided one hold max_total kept boxes; the kept boxes'
-        // ranks in sorted order are their output slots.  Same decisions as the sequential rule (same tests on the same pairs),
-        // in as many rounds as the busiest class among the leading candidates has kept boxes (bench input: ~7) of two
-        // barriers each, where the wave-0 pass below visits candidates 64 at a time at ~10 us per batch.
-        const bool par = !AGN && p.C <= PAR_MAX_C && cutoff == ~0ull;      // (the first chunk: m <= NMS_THREADS; the kept lists it leaves are
-                                                                   // what the wave-0 pass of a later chunk continues from)
-        if (par) {
-            const uint32_t t = (uint32_t)tid;
-            const int lane = tid & 63;
-            const bool cap_binds = p.max_per_class < p.max_total;
-            bool und = t < m, keptf = false;
-            const unsigned long long key = und ? skey[t] : 0ull;
-            const float4 cb = und ? sbox[t] : make_float4(0.f, 0.f, 0.f, 0.f);
-            const uint32_t id = ~(uint32_t)(key & 0xffffffffull);
-            const uint32_t bi = fastdiv(id, p.div_c);
-            const int cls = und ? (int)(id - bi * (uint32_t)p.C) : 0;
-            for (int c = tid; c < p.C; c += NMS_THREADS) { pfirst[c] = PAR_NONE; pfirst[p.C + c] = PAR_NONE; pcount[c] = 0; }
-            if (tid == 0) { sh[8] = PAR_NONE; sh[9] = PAR_NONE; sh[10] = 0; sh[11] = 0; }
-            __syncthreads();
-            for (int r = 0;; ++r) {
-                const int b = r & 1;
-                uint32_t* const first = pfirst + b * p.C;
-                if (und) atomicMin(&first[cls], t);
-                {
-                    const unsigned long long mk = __ballot(und);
-                    if (mk && lane == __ffsll((long long)mk) - 1) atomicMin(&sh[8 + b], t);
-                }
-                __syncthreads();
-                const uint32_t U = sh[8 + b];                       // every candidate in front of U is decided
-                {
-                    const unsigned long long mk = __ballot(keptf && t < U);
-                    if (mk && lane == 0) atomicAdd(&sh[10 + b], (uint32_t)__popcll(mk));
-                }
-                const uint32_t h = und ? first[cls] : PAR_NONE;
-                const bool head = und && h == t;
-                if (head) {
-                    keptf = !cap_binds || (int)pcount[cls] < p.max_per_class;      // (the class's only head this round)
-                    if (keptf) pcount[cls] = pcount[cls] + 1;
-                    pflag[t] = keptf ? 1u : 0u;
-                    und = false;
-                }
-                if (tid == 0) { sh[8 + (b ^ 1)] = PAR_NONE; sh[10 + (b ^ 1)] = 0; }     // (last read before this round's first barrier)
-                __syncthreads();
-                if (U == PAR_NONE || sh[10 + b] >= (uint32_t)p.max_total) break;   // uniform
-                if (head) first[cls] = PAR_NONE;                    // (every thread read it before the barrier; next use: round r + 2)
-                if (und) {
-                    // a head that the class cap turned away suppresses nothing -- and everything later in its class is turned away too
-                    if (pflag[h] == 0u) und = false;
-                    else if (nms_measure<KIND>(cb, sbox[h], p.iou_thr, p.beta) > p.iou_thr) und = false;
-                }
-            }
-            // output slot = number of kept candidates in front (sorted order)
-            const unsigned long long mk = __ballot(keptf);
-            uint32_t* const wtot = pflag + NMS_THREADS;
-            if (lane == 0) wtot[tid >> 6] = (uint32_t)__popcll(mk);
-            __syncthreads();
-            uint32_t slot = (uint32_t)__popcll(mk & ((1ull << lane) - 1ull)), total = 0;
-            for (int w = 0; w < NMS_THREADS / 64; ++w) {
-                const uint32_t c = wtot[w];
-                slot += w < (tid >> 6) ? c : 0u;
-                total += c;
-            }
-            if (keptf && slot < (uint32_t)p.max_total) {
-                kbox[slot] = cb;
-                kcls[slot] = cls;
-                kscore[slot] = __uint_as_float((uint32_t)(key >> 32));
-                kidx[slot] = (int)bi;
-            }
-            if (tid == 0) sh[1] = total < (uint32_t)p.max_total ? total : (uint32_t)p.max_total;
-        } else if (tid < 64) {
-            int kept = (int)sh[1];
-            const bool cap_binds = p.max_per_class < p.max_total;
-            for (uint32_t t0 = 0; t0 < m && kept < p.max_total; t0 += 64) {
-                const uint32_t t = t0 + (uint32_t)tid;
-                const bool valid = t < m;
-                const unsigned long long key = valid ? skey[t] : 0ull;
-                const float4 cb = valid ? sbox[t] : make_float4(0.f, 0.f, 0.f, 0.f);
-                const uint32_t id = ~(uint32_t)(key & 0xffffffffull);
-                const uint32_t bi = fastdiv(id, p.div_c);
-                const int cls = valid ? (int)(id - bi * (uint32_t)p.C) : -1;
-                bool sup = !valid;
-                int same = 0;                                   // kept boxes of this lane's class so far
-                // (1) against the boxes kept before this batch: their classes come into registers 64 at a time and are
-                // broadcast with v_readlane (an LDS read per kept box would put its latency into every iteration)
-                for (int j0 = 0; j0 < kept; j0 += 64) {
-                    const int kc_reg = j0 + tid < kept ? kcls[j0 + tid] : -2;
-                    const int jn = kept - j0 < 64 ? kept - j0 : 64;
-                    for (int j = 0; j < jn; ++j) {
-                        if (AGN) {                                  // every kept box is tested; the class cap counts its own
-                            same += __builtin_amdgcn_readlane(kc_reg, j) == cls ? 1 : 0;
-                            sup = sup || (nms_measure<KIND>(cb, kbox[j0 + j], p.iou_thr, p.beta) > p.iou_thr);
-                        } else if (__builtin_amdgcn_readlane(kc_reg, j) == cls) {
-                            ++same;
-                            sup = sup || (nms_measure<KIND>(cb, kbox[j0 + j], p.iou_thr, p.beta) > p.iou_thr);
-                        }
-                    }
-                }
-                unsigned long long alive = __ballot(!sup);      // (2) survivors in order
-                while (alive && kept < p.max_total) {
-                    const int c = __ffsll((long long)alive) - 1;           // wave-uniform
-                    alive &= alive - 1;
-                    const int ccls = __builtin_amdgcn_readlane(cls, c);
-                    if (cap_binds && __builtin_amdgcn_readlane(same, c) >= p.max_per_class) continue;   // class is full
-                    float4 kb;
-                    kb.x = __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(cb.x), c));
-                    kb.y = __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(cb.y), c));
-                    kb.z = __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(cb.z), c));
-                    kb.w = __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(cb.w), c));
-                    if (tid == c) {
-                        kbox[kept] = cb;
-                        kcls[kept] = cls;
-                        kscore[kept] = __uint_as_float((uint32_t)(key >> 32));
-                        kidx[kept] = (int)bi;
-                    }
-                    ++kept;
-                    bool hit = false;
-                    if (tid > c && !sup && (AGN || cls == ccls)) {
-                        if (!AGN || cls == ccls) ++same;
-                        hit = nms_measure<KIND>(cb, kb, p.iou_thr, p.beta) > p.iou_thr;
-                    }
-                    sup = sup || hit;
-                    alive &= ~__ballot(hit);
-                }
-            }
-            if (tid == 0) sh[1] = (uint32_t)kept;
-        }
-        __syncthreads();
-        if ((int)sh[1] >= p.max_total || pivot == 0) break;
-        cutoff = pivot;
-        __syncthreads();
     }
+    // output slot = number of kept candidates in front (sorted order)
+    const unsigned long long mk = __ballot(keptf);
+    uint32_t* const wtot = L.wave_kept();
+    if (lane == 0) wtot[tid >> 6] = (uint32_t)__popcll(mk);
     __syncthreads();
-    // ---- outputs: clipped boxes, zero padded (clip_boxes=True, pad to max_total); with a box map (y4_decode_nms_mapped) each
-    // kept box is first mapped from the canvas to its source image, x -> fmaf(x, ax, bx), y -> fmaf(y, ay, by), so the clip is to
-    // the image.  Only the written boxes change: which boxes are kept was decided above on the canvas boxes.
-    const int kept = (int)sh[1];
+    uint32_t slot = (uint32_t)__popcll(mk & ((1ull << lane) - 1ull)), total = 0;
+    for (int wv = 0; wv < NMS_THREADS / 64; ++wv) {
+        const uint32_t c = wtot[wv];
+        slot += wv < (tid >> 6) ? c : 0u;
+        total += c;
+    }
+    if (keptf && slot < (uint32_t)p.max_total) L.keep(slot, cb, cls, key, bc.box);
+    if (tid == 0) w->kept = total < (uint32_t)p.max_total ? total : (uint32_t)p.max_total;
+}
+
+// ---- greedy pass on wave 0 (call it with tid < 64), 64 sorted candidates at a time, one per lane, continuing from the kept
+// list.  The sequential rule "keep a candidate unless an EARLIER KEPT box of its class overlaps it" is evaluated in two steps
+// that give exactly the sequential result: (1) every lane tests its candidate against the boxes kept before this batch (uniform
+// loop over the kept list in LDS; the IoU only for the rare same-class pairs); (2) the batch's survivors are visited in order --
+// the lowest surviving lane is final, it is kept, its class and box are broadcast, and later same-class lanes test
+// against it.  Per candidate that is a few instructions instead of the ~90 of one-candidate-per-iteration on a wave
+// that retires one instruction per ~10 cycles (in-kernel timestamps: 41 us of this kernel were this pass).
+template <int KIND, bool AGN>
+__device__ __forceinline__ void nms_pass_wave0(const NmsK& p, const NmsLds& L, uint32_t m, int tid) {
+    int kept = (int)L.w->kept;
+    const bool cap_binds = p.max_per_class < p.max_total;
+    for (uint32_t t0 = 0; t0 < m && kept < p.max_total; t0 += 64) {
+        const uint32_t t = t0 + (uint32_t)tid;
+        const bool valid = t < m;
+        const unsigned long long key = valid ? L.skey[t] : 0ull;
+        const float4 cb = valid ? L.sbox[t] : make_float4(0.f, 0.f, 0.f, 0.f);
+        const CandBoxClass bc = cand_box_class(key, p.C, p.div_c);
+        const int cls = valid ? bc.cls : -1;
+        bool sup = !valid;
+        int same = 0;                                   // kept boxes of this lane's class so far
+        // (1) against the boxes kept before this batch: their classes come into registers 64 at a time and are
+        // broadcast with v_readlane (an LDS read per kept box would put its latency into every iteration)
+        for (int j0 = 0; j0 < kept; j0 += 64) {
+            const int kc_reg = j0 + tid < kept ? L.kcls[j0 + tid] : -2;
+            const int jn = kept - j0 < 64 ? kept - j0 : 64;
+            for (int j = 0; j < jn; ++j) {
+                if (AGN) {                                  // every kept box is tested; the class cap counts its own
+                    same += __builtin_amdgcn_readlane(kc_reg, j) == cls ? 1 : 0;
+                    sup = sup || (nms_measure<KIND>(cb, L.kbox[j0 + j], p.iou_thr, p.beta) > p.iou_thr);
+                } else if (__builtin_amdgcn_readlane(kc_reg, j) == cls) {
+                    ++same;
+                    sup = sup || (nms_measure<KIND>(cb, L.kbox[j0 + j], p.iou_thr, p.beta) > p.iou_thr);
+                }
+            }
+        }
+        unsigned long long alive = __ballot(!sup);      // (2) survivors in order
+        while (alive && kept < p.max_total) {
+            const int c = __ffsll((long long)alive) - 1;           // wave-uniform
+            alive &= alive - 1;
+            const int ccls = __builtin_amdgcn_readlane(cls, c);
+            if (cap_binds && __builtin_amdgcn_readlane(same, c) >= p.max_per_class) continue;   // class is full
+            float4 kb;
+            kb.x = __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(cb.x), c));
+            kb.y = __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(cb.y), c));
+            kb.z = __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(cb.z), c));
+            kb.w = __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(cb.w), c));
+            if (tid == c) L.keep((uint32_t)kept, cb, cls, key, bc.box);
+            ++kept;
+            bool hit = false;
+            if (tid > c && !sup && (AGN || cls == ccls)) {
+                if (!AGN || cls == ccls) ++same;
+                hit = nms_measure<KIND>(cb, kb, p.iou_thr, p.beta) > p.iou_thr;
+            }
+            sup = sup || hit;
+            alive &= ~__ballot(hit);
+        }
+    }
+    if (tid == 0) L.w->kept = (uint32_t)kept;
+}
+
+// ---- outputs: clipped boxes, zero padded (clip_boxes=True, pad to max_total); with a box map (y4_decode_nms_mapped) each
+// kept box is first mapped from the canvas to its source image, x -> fmaf(x, ax, bx), y -> fmaf(y, ay, by), so the clip is to
+// the image.  Only the written boxes change: which boxes are kept was decided before, on the canvas boxes.
+__device__ __forceinline__ void nms_write_outputs(const NmsK& p, const NmsLds& L, int n, int tid) {
+    const int kept = (int)L.w->kept;
     float ax = 1.f, bx = 0.f, ay = 1.f, by = 0.f;
     if (p.box_map) { ax = p.box_map[4 * n]; bx = p.box_map[4 * n + 1]; ay = p.box_map[4 * n + 2]; by = p.box_map[4 * n + 3]; }
     for (int i = tid; i < p.max_total; i += NMS_THREADS) {
@@ -717,14 +724,14 @@ __global__ __launch_bounds__(NMS_THREADS) void nms_kernel(const NmsK p) {
         float s = 0.f, c = 0.f;
         int id = -1;
         if (i < kept) {
-            b = kbox[i];
+            b = L.kbox[i];
             if (p.box_map) {
                 b.x = fmaf(b.x, ax, bx); b.y = fmaf(b.y, ay, by);
                 b.z = fmaf(b.z, ax, bx); b.w = fmaf(b.w, ay, by);
             }
             b.x = fmaxf(fminf(b.x, 1.f), 0.f); b.y = fmaxf(fminf(b.y, 1.f), 0.f);
             b.z = fmaxf(fminf(b.z, 1.f), 0.f); b.w = fmaxf(fminf(b.w, 1.f), 0.f);
-            s = kscore[i]; c = (float)kcls[i]; id = kidx[i];
+            s = L.kscore[i]; c = (float)L.kcls[i]; id = L.kidx[i];
         }
         *(float4*)(p.out_boxes + ((int64_t)n * p.max_total + i) * 4) = b;
         p.out_scores[(int64_t)n * p.max_total + i] = s;
@@ -734,10 +741,61 @@ __global__ __launch_bounds__(NMS_THREADS) void nms_kernel(const NmsK p) {
     if (tid == 0) p.out_valid[n] = kept;
 }
 
-size_t nms_lds_bytes(int max_total, int classes) {
-    return (size_t)SORT_CAP * 24 + (size_t)max_total * (16 + 12) + 256 * 4 + 64 + (classes <= PAR_MAX_C ? (size_t)classes * 12 : 0) +
-           (size_t)(NMS_THREADS + 16) * 4;
+// The driver: chunks of the image's candidates in descending key order until max_total boxes are kept or none remain.
+// KIND: the pair measure (nms_measure).  AGN: class-agnostic suppression -- a kept box suppresses later candidates of every class;
+// max_per_class still counts per class, and a candidate its class's cap turns away is not kept and suppresses nothing.  The
+// round-parallel pass keys its heads by class, which is what makes its rounds independent; with one head slot for all classes it
+// would decide one kept box per round behind two workgroup barriers -- the sequence wave 0 walks without them -- so an agnostic
+// launch takes the wave-0 pass on the first chunk too, as C > PAR_MAX_C does.
+template <int KIND, bool AGN>
+__global__ __launch_bounds__(NMS_THREADS) void nms_kernel(const NmsK p) {
+    extern __shared__ __attribute__((aligned(16))) char nsm[];
+    const NmsLds L(nsm, p.max_total, p.C);
+    const int n = blockIdx.x, tid = threadIdx.x;
+    uint32_t cnt = p.counts[(size_t)n * COUNT_STRIDE];
+    if (cnt > p.cap) {
+        if (tid == 0) atomicOr(p.status, 1u);
+        cnt = p.cap;
+    }
+    const unsigned long long* gk = p.keys + (int64_t)n * p.cap;
+    const float* gb = p.dboxes + (int64_t)n * p.nbox * 4;
+    if (tid == 0) L.w->kept = 0;
+    unsigned long long cutoff = ~0ull;           // exclusive upper bound of keys still to visit
+    __syncthreads();
+    // every thread has read the image's candidate count: leave the counter at zero for the next step's decode (which therefore needs
+    // no memset launch in front of it; decode_launch clears only when a decode was NOT followed by its NMS)
+    if (tid == 0) p.counts[(size_t)n * COUNT_STRIDE] = 0;
+
+    while (true) {
+        const uint32_t remaining = nms_count_below(L, gk, cnt, cutoff, tid);
+        if (remaining == 0) break;
+        // pivot = chunk_cap-th largest key below the cutoff (0 when everything fits).  The FIRST chunk is at most NMS_THREADS
+        // keys -- what the merge-rank sort and the round-parallel pass take, and nearly always all that max_total kept boxes
+        // need; the later ones SORT_CAP
+        const uint32_t chunk_cap = cutoff == ~0ull ? (uint32_t)NMS_THREADS : (uint32_t)SORT_CAP;
+        unsigned long long pivot = 0;
+        bool have_pivot = false;
+        if (cutoff == ~0ull && remaining > chunk_cap) have_pivot = nms_histogram_pivot(L, gk, cnt, chunk_cap, tid, &pivot);
+        if (remaining > chunk_cap && !have_pivot) pivot = nms_select_pivot(L, gk, cnt, cutoff, chunk_cap, tid);
+        uint32_t m2;
+        const uint32_t m = nms_take_chunk(L, gk, cnt, cutoff, pivot, chunk_cap, tid, &m2);
+        // sort the chunk, descending
+        if (m2 <= (uint32_t)NMS_THREADS) nms_rank_sort(L, m, m2, tid);
+        else nms_sort_regs<SORT_CAP / NMS_THREADS>(L.skey, L.xbuf(), m2, tid);
+        nms_load_boxes(L, gb, p, m, tid);
+        const bool par = !AGN && p.C <= PAR_MAX_C && cutoff == ~0ull;
+        if (par) nms_pass_parallel<KIND>(p, L, m, tid);
+        else if (tid < 64) nms_pass_wave0<KIND, AGN>(p, L, m, tid);
+        __syncthreads();
+        if ((int)L.w->kept >= p.max_total || pivot == 0) break;
+        cutoff = pivot;
+        __syncthreads();
+    }
+    __syncthreads();
+    nms_write_outputs(p, L, n, tid);
 }
+
+size_t nms_lds_bytes(int max_total, int classes) { return nms_lds_layout(max_total, classes).bytes; }
 
 int decode_launch(const DecodeK& k, hipStream_t stream, int clear_images) {
     // the per-image candidate counters are zero between steps (nms_kernel resets its image's); `clear_images` > 0: the caller
@@ -764,17 +822,15 @@ int nms_launch(const NmsK& k, hipStream_t stream) {
     Y4_REQUIRE(lds <= 160 * 1024 && k.max_total <= 1024, Y4_EINVAL, "nms: max_total %d needs %zu bytes of LDS", k.max_total, lds);
     Y4_REQUIRE((k.kind == 0 || k.kind == 1) && (k.agnostic == 0 || k.agnostic == 1) && k.beta > 0.f, Y4_EINVAL,
                "nms: rule (kind %d, beta %g, agnostic %d)", k.kind, (double)k.beta, k.agnostic);
-    const dim3 g(k.N), b(NMS_THREADS);
-    if (k.kind == 0) {                                   // (beta is not read)
-        if (!k.agnostic) return launch_lds<nms_kernel<NMS_IOU, false>>(160 * 1024, g, b, lds, stream, k);
-        return launch_lds<nms_kernel<NMS_IOU, true>>(160 * 1024, g, b, lds, stream, k);
-    }
-    if (k.beta == 1.0f) {
-        if (!k.agnostic) return launch_lds<nms_kernel<NMS_DIOU1, false>>(160 * 1024, g, b, lds, stream, k);
-        return launch_lds<nms_kernel<NMS_DIOU1, true>>(160 * 1024, g, b, lds, stream, k);
-    }
-    if (!k.agnostic) return launch_lds<nms_kernel<NMS_DIOU, false>>(160 * 1024, g, b, lds, stream, k);
-    return launch_lds<nms_kernel<NMS_DIOU, true>>(160 * 1024, g, b, lds, stream, k);
+    // [measure][agnostic]; kind 0 does not read beta, kind 1 with beta == 1 is its own measure
+    using Launch = int (*)(int, dim3, dim3, size_t, hipStream_t, const NmsK&);
+    static const Launch table[3][2] = {
+        {launch_lds<nms_kernel<NMS_IOU, false>, NmsK>, launch_lds<nms_kernel<NMS_IOU, true>, NmsK>},
+        {launch_lds<nms_kernel<NMS_DIOU1, false>, NmsK>, launch_lds<nms_kernel<NMS_DIOU1, true>, NmsK>},
+        {launch_lds<nms_kernel<NMS_DIOU, false>, NmsK>, launch_lds<nms_kernel<NMS_DIOU, true>, NmsK>},
+    };
+    const int measure = k.kind == 0 ? NMS_IOU : (k.beta == 1.0f ? NMS_DIOU1 : NMS_DIOU);
+    return table[measure][k.agnostic](160 * 1024, dim3(k.N), dim3(NMS_THREADS), lds, stream, k);
 }
 
 }  // namespace y4

@@ -857,49 +857,70 @@ int run_op(y4_handle h, int oi, const void* imgs, int n, hipStream_t s, int img0
                             "conv %d: one image's input (%lld B) exceeds the 2 GiB buffer-descriptor range", op.conv);
 }
 
-int run_decode_nms(y4_handle h, int n, float iou_thr, float score_thr, float* boxes, float* scores, float* classes,
-                   int32_t* valid, int32_t* kept_idx, hipStream_t s, int stage /*0 both, 1 decode, 2 nms*/,
-                   const float* box_map = nullptr /*[n][4] per image, NMS output stage (y4_decode_nms_mapped)*/) {
+// A candidate store: what the decode stage fills and an NMS or a gather reads -- the workspace's, one list per batch row, or a
+// gather scratch's, one list per group (y4_nms_gathered)
+struct CandStore {
+    float* dboxes;                   // [rows, nbox, 4]
+    unsigned long long* keys;        // [rows, cap]
+    uint32_t* counts;                // [rows * COUNT_STRIDE]
+    uint32_t cap;
+    int nbox;
+    uint32_t* status;                // the handle's overflow word
+    FastDiv div_c;
+};
+CandStore cand_store(y4_handle h, float* dboxes, unsigned long long* keys, uint32_t* counts, uint32_t cap, int nbox) {
+    return CandStore{dboxes, keys, counts, cap, nbox, (uint32_t*)(h->act + h->status_off), fastdiv_make((uint32_t)h->cfg.num_classes)};
+}
+CandStore workspace_cands(y4_handle h) {
+    return cand_store(h, (float*)(h->act + h->dbox_off), (unsigned long long*)(h->act + h->keys_off), (uint32_t*)(h->act + h->counts_off),
+                      h->cand_cap, h->nbox);
+}
+
+int run_decode(y4_handle h, int n, float score_thr, hipStream_t s) {
     const y4_config& cfg = h->cfg;
-    if (stage != 2) {
-        DecodeK k{};
-        int off = 0, cells = 0;
-        for (int i = 0; i < 3; ++i) {
-            k.head[i] = (const float*)buf_ptr(h, h->heads[i]);
-            k.gh[i] = h->heads[i].h; k.gw[i] = h->heads[i].w; k.stride[i] = cfg.strides[i]; k.box_off[i] = off;
-            off += 3 * k.gh[i] * k.gw[i]; cells += k.gh[i] * k.gw[i];
-            k.xyscale[i] = cfg.xyscale[i];
-            k.xyoff[i] = (float)(0.5 * ((double)cfg.xyscale[i] - 1.0));
-        }
-        memcpy(k.anchors, cfg.anchors, sizeof(k.anchors));
-        k.cells_per_img = cells; k.N = n; k.C = cfg.num_classes; k.hcs = h->hcs; k.nbox = h->nbox;
-        k.div_cells = fastdiv_make((uint32_t)cells);
-        for (int i = 0; i < 3; ++i) k.div_gw[i] = fastdiv_make((uint32_t)k.gw[i]);
-        k.img_h = (float)h->H; k.img_w = (float)h->W; k.score_thr = score_thr;
-        k.dboxes = (float*)(h->act + h->dbox_off);
-        k.keys = (unsigned long long*)(h->act + h->keys_off);
-        k.counts = (uint32_t*)(h->act + h->counts_off);
-        k.cap = h->cand_cap;
-        k.obj = h->obj_n[0] >= n && h->obj_n[1] >= n && h->obj_n[2] >= n ? (const float*)(h->act + h->obj_off) : nullptr;
-        if (int r = decode_launch(k, s, h->counts_clean ? 0 : cfg.max_batch)) return r;
-        h->counts_clean = false;                          // ... until this decode's NMS has been enqueued behind it
-        h->counts_n = n;
+    const CandStore c = workspace_cands(h);
+    DecodeK k{};
+    int off = 0, cells = 0;
+    for (int i = 0; i < 3; ++i) {
+        k.head[i] = (const float*)buf_ptr(h, h->heads[i]);
+        k.gh[i] = h->heads[i].h; k.gw[i] = h->heads[i].w; k.stride[i] = cfg.strides[i]; k.box_off[i] = off;
+        off += 3 * k.gh[i] * k.gw[i]; cells += k.gh[i] * k.gw[i];
+        k.xyscale[i] = cfg.xyscale[i];
+        k.xyoff[i] = (float)(0.5 * ((double)cfg.xyscale[i] - 1.0));
     }
-    if (stage != 1) {
-        NmsK k{};
-        k.dboxes = (const float*)(h->act + h->dbox_off);
-        k.keys = (const unsigned long long*)(h->act + h->keys_off);
-        k.counts = (uint32_t*)(h->act + h->counts_off);
-        k.cap = h->cand_cap; k.N = n; k.C = cfg.num_classes; k.nbox = h->nbox;
-        k.max_total = cfg.max_total; k.max_per_class = cfg.max_per_class; k.iou_thr = iou_thr;
-        k.out_boxes = boxes; k.out_scores = scores; k.out_classes = classes; k.out_valid = valid; k.out_idx = kept_idx;
-        k.status = (uint32_t*)(h->act + h->status_off);
-        k.div_c = fastdiv_make((uint32_t)cfg.num_classes);
-        k.box_map = box_map;
-        k.kind = h->nms_kind; k.beta = h->nms_beta; k.agnostic = h->nms_agnostic;
-        if (int r = nms_launch(k, s)) return r;
-        h->counts_clean = h->counts_n <= n;               // (an NMS over fewer images than were decoded leaves counters behind)
-    }
+    memcpy(k.anchors, cfg.anchors, sizeof(k.anchors));
+    k.cells_per_img = cells; k.N = n; k.C = cfg.num_classes; k.hcs = h->hcs; k.nbox = c.nbox;
+    k.div_cells = fastdiv_make((uint32_t)cells);
+    for (int i = 0; i < 3; ++i) k.div_gw[i] = fastdiv_make((uint32_t)k.gw[i]);
+    k.img_h = (float)h->H; k.img_w = (float)h->W; k.score_thr = score_thr;
+    k.dboxes = c.dboxes; k.keys = c.keys; k.counts = c.counts; k.cap = c.cap;
+    k.obj = h->obj_n[0] >= n && h->obj_n[1] >= n && h->obj_n[2] >= n ? (const float*)(h->act + h->obj_off) : nullptr;
+    if (int r = decode_launch(k, s, h->counts_clean ? 0 : cfg.max_batch)) return r;
+    h->counts_clean = false;                          // ... until this decode's NMS (or gather) has been enqueued behind it
+    h->counts_n = n;
+    return Y4_OK;
+}
+
+struct NmsOutputs { float* boxes; float* scores; float* classes; int32_t* valid; int32_t* kept_idx; };
+// NMS of the first n lists of a candidate store under the handle's rule and caps.  box_map: [n][4] per list, applied in the
+// output stage (y4_decode_nms_mapped), or null
+int nms_over(y4_handle h, const CandStore& c, int n, float iou_thr, const NmsOutputs& o, const float* box_map, hipStream_t s) {
+    const y4_config& cfg = h->cfg;
+    NmsK k{};
+    k.dboxes = c.dboxes; k.keys = c.keys; k.counts = c.counts; k.cap = c.cap;
+    k.N = n; k.C = cfg.num_classes; k.nbox = c.nbox;
+    k.max_total = cfg.max_total; k.max_per_class = cfg.max_per_class; k.iou_thr = iou_thr;
+    k.out_boxes = o.boxes; k.out_scores = o.scores; k.out_classes = o.classes; k.out_valid = o.valid; k.out_idx = o.kept_idx;
+    k.status = c.status; k.div_c = c.div_c;
+    k.box_map = box_map;
+    k.kind = h->nms_kind; k.beta = h->nms_beta; k.agnostic = h->nms_agnostic;
+    return nms_launch(k, s);
+}
+
+// ... of the workspace's lists, behind run_decode
+int run_nms(y4_handle h, int n, float iou_thr, const NmsOutputs& o, const float* box_map, hipStream_t s) {
+    if (int r = nms_over(h, workspace_cands(h), n, iou_thr, o, box_map, s)) return r;
+    h->counts_clean = h->counts_n <= n;               // (an NMS over fewer images than were decoded leaves counters behind)
     return Y4_OK;
 }
 
@@ -1183,7 +1204,8 @@ int y4_decode_nms_mapped(y4_handle h, int n, float iou_threshold, float score_th
     Y4_REQUIRE(boxes && scores && classes && valid, Y4_EINVAL, "y4_decode_nms: null output");
     const float iou = iou_threshold < 0.f ? h->cfg.iou_threshold : iou_threshold;
     const float sc = score_threshold < 0.f ? h->cfg.score_threshold : score_threshold;
-    return run_decode_nms(h, n, iou, sc, boxes, scores, classes, valid, kept_idx, (hipStream_t)stream, 0, box_map);
+    if (int r = run_decode(h, n, sc, (hipStream_t)stream)) return r;
+    return run_nms(h, n, iou, NmsOutputs{boxes, scores, classes, valid, kept_idx}, box_map, (hipStream_t)stream);
 }
 
 int y4_set_nms_rule(y4_handle h, int kind, float beta, int agnostic) {
@@ -1218,6 +1240,11 @@ static int gather_layout(y4_handle h, const char* who, int n_groups, int max_slo
     L->bytes = L->boxes_off + up((size_t)n_groups * max_slots * h->nbox * 16);
     return Y4_OK;
 }
+// the groups' lists in the scratch as a candidate store: a group's box table is max_slots rows' boxes
+static CandStore gathered_cands(y4_handle h, void* scratch, const GatherLayout& L, int max_slots, uint32_t group_cap) {
+    char* sp = (char*)scratch;
+    return cand_store(h, (float*)(sp + L.boxes_off), (unsigned long long*)(sp + L.keys_off), (uint32_t*)sp, group_cap, max_slots * h->nbox);
+}
 static int gather_scratch_check(const char* who, const void* scratch) {
     Y4_REQUIRE(scratch, Y4_EINVAL, "%s: null scratch", who);
     Y4_REQUIRE(((uintptr_t)scratch & 255) == 0, Y4_EINVAL, "%s: scratch must be 256-byte aligned", who);
@@ -1249,21 +1276,18 @@ int y4_decode_gather(y4_handle h, int n, float score_threshold, const int32_t* r
     Y4_REQUIRE(row_group_dev && row_slot_dev && row_map_dev, Y4_EINVAL, "y4_decode_gather: null row table");
     const float sc = score_threshold < 0.f ? h->cfg.score_threshold : score_threshold;
     hipStream_t s = (hipStream_t)stream;
-    if (int r = run_decode_nms(h, n, 0.f, sc, nullptr, nullptr, nullptr, nullptr, nullptr, s, 1)) return r;
+    if (int r = run_decode(h, n, sc, s)) return r;
+    const CandStore c = workspace_cands(h), g = gathered_cands(h, scratch_dev, L, max_slots, group_cap);
     GatherK k{};
-    k.dboxes = (const float*)(h->act + h->dbox_off);
-    k.keys = (const unsigned long long*)(h->act + h->keys_off);
-    k.counts = (uint32_t*)(h->act + h->counts_off);
-    k.cap = h->cand_cap; k.C = h->cfg.num_classes; k.nbox = h->nbox;
+    k.dboxes = c.dboxes; k.keys = c.keys; k.counts = c.counts; k.cap = c.cap;
+    k.C = h->cfg.num_classes; k.nbox = c.nbox;
     k.row_group = row_group_dev; k.row_slot = row_slot_dev; k.row_map = row_map_dev;
-    k.n_groups = n_groups; k.max_slots = max_slots; k.group_cap = group_cap;
-    char* sp = (char*)scratch_dev;
-    k.gcounts = (uint32_t*)sp; k.gkeys = (unsigned long long*)(sp + L.keys_off); k.gboxes = (float*)(sp + L.boxes_off);
-    k.status = (uint32_t*)(h->act + h->status_off);
-    k.div_c = fastdiv_make((uint32_t)h->cfg.num_classes);
+    k.n_groups = n_groups; k.max_slots = max_slots; k.group_cap = g.cap;
+    k.gcounts = g.counts; k.gkeys = g.keys; k.gboxes = g.dboxes;
+    k.status = c.status; k.div_c = c.div_c;
     if (int r = gather_launch(k, n, s)) return r;
     // gather_kernel left the counters of rows 0 .. n-1 at zero, the rows this decode counted into: the handle is where an NMS over
-    // n images would have left it (run_decode_nms: counts_clean = counts_n <= n)
+    // n images would have left it (run_nms: counts_clean = counts_n <= n)
     h->counts_clean = true;
     return Y4_OK;
 }
@@ -1277,22 +1301,10 @@ int y4_nms_gathered(y4_handle h, int n_groups, int max_slots, uint32_t group_cap
     Y4_REQUIRE(h->act, Y4_ESTATE, "workspace not bound (call y4_bind_workspace first)");
     Y4_REQUIRE(cand_count_dev && boxes_dev && scores_dev && classes_dev && valid_dev, Y4_EINVAL, "y4_nms_gathered: null output");
     hipStream_t s = (hipStream_t)stream;
-    char* sp = (char*)scratch_dev;
-    if (int r = gather_counts_launch((const uint32_t*)sp, cand_count_dev, n_groups, s)) return r;
-    const y4_config& cfg = h->cfg;
-    NmsK k{};
-    k.dboxes = (const float*)(sp + L.boxes_off);
-    k.keys = (const unsigned long long*)(sp + L.keys_off);
-    k.counts = (uint32_t*)sp;
-    k.cap = group_cap; k.N = n_groups; k.C = cfg.num_classes; k.nbox = max_slots * h->nbox;
-    k.max_total = cfg.max_total; k.max_per_class = cfg.max_per_class;
-    k.iou_thr = iou_threshold < 0.f ? cfg.iou_threshold : iou_threshold;
-    k.out_boxes = boxes_dev; k.out_scores = scores_dev; k.out_classes = classes_dev; k.out_valid = valid_dev; k.out_idx = kept_idx_dev;
-    k.status = (uint32_t*)(h->act + h->status_off);
-    k.div_c = fastdiv_make((uint32_t)cfg.num_classes);
-    k.box_map = nullptr;
-    k.kind = h->nms_kind; k.beta = h->nms_beta; k.agnostic = h->nms_agnostic;
-    return nms_launch(k, s);
+    const CandStore g = gathered_cands(h, scratch_dev, L, max_slots, group_cap);
+    if (int r = gather_counts_launch(g.counts, cand_count_dev, n_groups, s)) return r;
+    return nms_over(h, g, n_groups, iou_threshold < 0.f ? h->cfg.iou_threshold : iou_threshold,
+                    NmsOutputs{boxes_dev, scores_dev, classes_dev, valid_dev, kept_idx_dev}, nullptr, s);
 }
 
 static void loss_geometry(y4_handle h, int* gh, int* gw, int* lane_base) {
@@ -1651,12 +1663,10 @@ static int predict_impl(y4_handle h, const void* imgs, int n, float* boxes, floa
         if (int r = run_op(h, l.op, imgs, l.cnt, s, l.img0)) return r;
         if (ev && h->t_rec[k]) Y4_CHECK_HIP(hipEventRecord(ev[++i], s));
     }
-    for (int stage = 1; stage <= 2; ++stage) {
-        if (int r = run_decode_nms(h, n, h->cfg.iou_threshold, h->cfg.score_threshold, boxes, scores, classes, valid,
-                                   kept_idx, s, stage))
-            return r;
-        if (ev) Y4_CHECK_HIP(hipEventRecord(ev[++i], s));
-    }
+    if (int r = run_decode(h, n, h->cfg.score_threshold, s)) return r;
+    if (ev) Y4_CHECK_HIP(hipEventRecord(ev[++i], s));
+    if (int r = run_nms(h, n, h->cfg.iou_threshold, NmsOutputs{boxes, scores, classes, valid, kept_idx}, nullptr, s)) return r;
+    if (ev) Y4_CHECK_HIP(hipEventRecord(ev[++i], s));
     return Y4_OK;
 }
 

@@ -2,6 +2,7 @@
 //   gather_kernel            y4_decode_gather: the candidate lists the decode stage left for several batch rows (tiles) are merged
 //                            into ONE list per group (photo), boxes mapped to the photo's normalised coordinates, on which the
 //                            NMS kernel of decode_nms.hip then runs unchanged (y4_nms_gathered).
+#include "candidates.h"
 #include "kernels.h"
 
 #pragma clang fp contract(off)   // the box map is an explicit fmaf; nothing else may fuse
@@ -12,7 +13,7 @@ namespace y4 {
 // One workgroup per batch row i (a tile): the row's whole candidate list is read by this one workgroup, which is what lets it
 // leave the row's counter at zero behind a single barrier -- the duty nms_kernel has on the plain path.  Per pass of
 // GATHER_THREADS keys: the id (box, class) of a key is re-based to the group's box table, slot * nbox + box, the key is appended to
-// the group's list with ONE returning atomic per wave (ballot + popcount, as the decode kernels append), and the box is written,
+// the group's list with ONE returning atomic per wave (wave_append, as the decode kernels append), and the box is written,
 // mapped to the photo, to its own place in the group's table: rows of one group write disjoint slots, and the up to C
 // candidates of one box store the same four floats.  The order of a group's list varies from run to run; its keys are unique
 // and nms_kernel sorts them.
@@ -39,22 +40,15 @@ __global__ __launch_bounds__(GATHER_THREADS) void gather_kernel(const GatherK p)
         const uint32_t k = k0 + (uint32_t)tid;
         const bool have = k < cnt;
         const unsigned long long key = have ? keys[k] : 0ull;
-        const uint32_t id = ~(uint32_t)(key & 0xffffffffull);
-        const uint32_t b = have ? fastdiv(id, p.div_c) : 0u;
+        const uint32_t b = have ? cand_box_class(key, p.C, p.div_c).box : 0u;
         const bool ok = have && b < (uint32_t)p.nbox;                        // (a key is (box < nbox, class < C) by construction)
-        const unsigned long long mask = __ballot(ok);
-        if (mask) {                                                          // wave-uniform
-            uint32_t base = 0;
-            if (lane == __ffsll((long long)mask) - 1) base = atomicAdd(gcount, (uint32_t)__popcll(mask));
-            base = __shfl(base, __ffsll((long long)mask) - 1);
-            if (ok) {
-                const uint32_t pos = base + (uint32_t)__popcll(mask & ((1ull << lane) - 1ull));
-                if (pos < p.group_cap) gkeys[pos] = (key & 0xffffffff00000000ull) | (unsigned long long)(~(id0 + id));
-                float4 o = *(const float4*)(rb + (int64_t)b * 4);
-                o.x = fmaf(o.x, ax, bx); o.y = fmaf(o.y, ay, by);
-                o.z = fmaf(o.z, ax, bx); o.w = fmaf(o.w, ay, by);
-                *(float4*)(gb + (int64_t)b * 4) = o;
-            }
+        const uint32_t pos = wave_append(gcount, ok, lane);
+        if (ok) {
+            if (pos < p.group_cap) gkeys[pos] = cand_key(cand_score(key), id0 + cand_id(key));     // the score word stays
+            float4 o = *(const float4*)(rb + (int64_t)b * 4);
+            o.x = fmaf(o.x, ax, bx); o.y = fmaf(o.y, ay, by);
+            o.z = fmaf(o.z, ax, bx); o.w = fmaf(o.w, ay, by);
+            *(float4*)(gb + (int64_t)b * 4) = o;
         }
     }
 }

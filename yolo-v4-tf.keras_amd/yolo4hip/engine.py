@@ -41,6 +41,30 @@ def _cfg_struct(config, num_classes, max_batch, dtype, max_per_class=100, max_to
     return c
 
 
+# Several results as views of ONE int32 block, so that they cross PCIe in a single copy.  A block is described by its fields,
+# [(dtype name, shape)] in element order, every dtype four bytes wide.
+def _detection_fields(n, T):
+    """boxes, scores, classes, valid, kept of n images (`Engine.alloc_outputs`)."""
+    return [("float32", (n, T, 4)), ("float32", (n, T)), ("float32", (n, T)), ("int32", (n,)), ("int32", (n, T))]
+
+
+def _block_len(fields):
+    return sum(int(np.prod(shape)) for _, shape in fields)
+
+
+def _block_views(flat, fields):
+    """The fields of a block as views of `flat`, a 1-D int32 torch tensor (device or pinned host) or numpy array."""
+    lib = np
+    if not isinstance(flat, np.ndarray):
+        import torch as lib
+    views, at = [], 0
+    for dtype, shape in fields:
+        part = flat[at:at + int(np.prod(shape))]
+        at += int(np.prod(shape))
+        views.append((part if dtype == "int32" else part.view(getattr(lib, dtype))).reshape(shape))
+    return views
+
+
 class Engine:
     def __init__(self, num_classes, config=None, max_batch=32, dtype="f32", device=None, alias_workspace=False,
                  retain_head_inputs=False, *, max_per_class=100, max_total=100, box_loss="giou",
@@ -516,23 +540,18 @@ class Engine:
         """`alloc_outputs_flat(n_groups)` with the groups' candidate counts behind it, ONE int32 device block for one copy back:
         -> (flat, (boxes, scores, classes, valid, kept) views, cand_count int32 view [n_groups]); the first part of `flat` has
         the layout of `alloc_outputs_flat`."""
-        torch = self.torch
-        n, T = int(n_groups), self.T
-        offs = np.cumsum([0, n * T * 4, n * T, n * T, n, n * T, n])
-        flat = torch.empty(int(offs[-1]), dtype=torch.int32, device=self.device)
-        v = [flat[offs[i]:offs[i + 1]] for i in range(6)]
-        return flat, (v[0].view(torch.float32).view(n, T, 4), v[1].view(torch.float32).view(n, T),
-                      v[2].view(torch.float32).view(n, T), v[3], v[4].view(n, T)), v[5]
+        flat, v = self._alloc_block(self._tiled_fields(n_groups))
+        return flat, tuple(v[:5]), v[5]
+
+    def _tiled_fields(self, n_groups):
+        n = int(n_groups)
+        return _detection_fields(n, self.T) + [("int32", (n,))]
 
     def tiled_outputs_to_host(self, flat, n_groups):
         """The one copy of `alloc_tiled_outputs_flat`'s block -> ([boxes, scores, classes, valid, kept], cand_count) as fresh
         writable numpy arrays."""
-        n, T = int(n_groups), self.T
-        host = flat.cpu().numpy()
-        offs = np.cumsum([0, n * T * 4, n * T, n * T, n, n * T, n])
-        p = [host[offs[i]:offs[i + 1]] for i in range(6)]
-        return [p[0].view(np.float32).reshape(n, T, 4).copy(), p[1].view(np.float32).reshape(n, T).copy(),
-                p[2].view(np.float32).reshape(n, T).copy(), p[3].copy(), p[4].reshape(n, T).copy()], p[5].copy()
+        p = [a.copy() for a in _block_views(flat.cpu().numpy(), self._tiled_fields(n_groups))]
+        return p[:5], p[5]
 
     def nms_gathered(self, state, outs=None, cand_count=None, iou_threshold=-1.0):
         """y4_nms_gathered over the groups of `state`: -> (outs as `decode_nms_device` for n_groups images, boxes normalised to
@@ -689,14 +708,13 @@ class Engine:
     def alloc_outputs_flat(self, n):
         """The five outputs of `alloc_outputs` as views of ONE int32 device block, so that a step's results return to
         the host in a single copy: -> (flat int32 tensor, (boxes, scores, classes, valid, kept) views)."""
-        torch = self.torch
-        T = self.T
-        sizes = [n * T * 4, n * T, n * T, n, n * T]
-        offs = np.cumsum([0] + sizes)
-        flat = torch.empty(int(offs[-1]), dtype=torch.int32, device=self.device)
-        v = [flat[offs[i]:offs[i + 1]] for i in range(5)]
-        return flat, (v[0].view(torch.float32).view(n, T, 4), v[1].view(torch.float32).view(n, T),
-                      v[2].view(torch.float32).view(n, T), v[3], v[4].view(n, T))
+        flat, v = self._alloc_block(_detection_fields(n, self.T))
+        return flat, tuple(v)
+
+    def _alloc_block(self, fields):
+        """-> (a new int32 device block for `fields`, its views)."""
+        flat = self.torch.empty(_block_len(fields), dtype=self.torch.int32, device=self.device)
+        return flat, _block_views(flat, fields)
 
     def decode_nms_device(self, n, outs=None, iou_threshold=-1.0, score_threshold=-1.0, box_map=None):
         """Decode + NMS of the heads in the workspace.  box_map: a contiguous float32 cuda tensor [n,4] of (ax, bx, ay, by) rows
@@ -722,23 +740,18 @@ class Engine:
         tp mask of `map_match_device` -- so that they reach the host in a single copy (`map_outputs_to_host`); the boxes
         are a tensor of their own and stay on the device.  -> (flat int32 tensor, outs for `decode_nms_device` (boxes, scores,
         classes, valid, no kept indices), tp_mask int32 view [n, max_total])."""
-        torch = self.torch
+        flat, (scores, classes, valid, tp_mask) = self._alloc_block(self._map_fields(n, "int32"))
+        boxes = self.torch.empty((n, self.T, 4), dtype=self.torch.float32, device=self.device)
+        return flat, (boxes, scores, classes, valid, None), tp_mask
+
+    def _map_fields(self, n, mask_dtype):
         T = self.T
-        offs = np.cumsum([0, n * T, n * T, n, n * T])
-        flat = torch.empty(int(offs[-1]), dtype=torch.int32, device=self.device)
-        v = [flat[offs[i]:offs[i + 1]] for i in range(4)]
-        boxes = torch.empty((n, T, 4), dtype=torch.float32, device=self.device)
-        outs = (boxes, v[0].view(torch.float32).view(n, T), v[1].view(torch.float32).view(n, T), v[2], None)
-        return flat, outs, v[3].view(n, T)
+        return [("float32", (n, T)), ("float32", (n, T)), ("int32", (n,)), (mask_dtype, (n, T))]
 
     def map_outputs_to_host(self, flat, n):
         """The one copy of `alloc_map_outputs_flat`'s block -> (scores float32 [n,T], classes float32 [n,T], valid int32 [n],
         tp_mask uint32 [n,T]) as numpy views of it."""
-        T = self.T
-        host = flat.cpu().numpy()
-        offs = np.cumsum([0, n * T, n * T, n, n * T])
-        return (host[offs[0]:offs[1]].view(np.float32).reshape(n, T), host[offs[1]:offs[2]].view(np.float32).reshape(n, T),
-                host[offs[2]:offs[3]], host[offs[3]:offs[4]].view(np.uint32).reshape(n, T))
+        return tuple(_block_views(flat.cpu().numpy(), self._map_fields(n, "uint32")))
 
     def map_match_device(self, outs, scale_dev, gt_dev, gt_count_dev, iou_thresholds, debug=False, tp_mask=None):
         """y4_map_match on the outputs of `decode_nms_device` (outs = boxes, scores, classes, valid, ...): the kept boxes of
@@ -1165,15 +1178,8 @@ class Engine:
                 sl["done"].synchronize()
         pending = []
 
-        T, nb = self.T, self.max_batch
         # one flat int32 block per slot holds all five outputs, so that results return in ONE small D2H copy
-        sizes = [nb * T * 4, nb * T, nb * T, nb, nb * T]
-        offs = np.cumsum([0] + sizes)
-
-        def views(flat):
-            v = [flat[offs[i]:offs[i + 1]] for i in range(5)]
-            return (v[0].view(torch.float32).view(nb, T, 4), v[1].view(torch.float32).view(nb, T),
-                    v[2].view(torch.float32).view(nb, T), v[3], v[4].view(nb, T))
+        fields = _detection_fields(self.max_batch, self.T)
 
         def finish(sl):
             sl["done"].synchronize()
@@ -1215,9 +1221,9 @@ class Engine:
                         sl["desc"] = torch.from_numpy(np.frombuffer(desc, dtype=np.uint8).copy()).to(dev)
                         sl["map"] = torch.from_numpy(np.tile(prepost.box_map(fh, fw, H, W, rect), (self.max_batch, 1))).to(dev)
                         torch.cuda.current_stream().synchronize()   # (read by the compute streams)
-                    sl["flat"] = torch.empty(int(offs[-1]), dtype=torch.int32, device=dev)
-                    sl["flat_host"] = torch.empty(int(offs[-1]), dtype=torch.int32).pin_memory()
-                    sl["outs"], sl["host"] = views(sl["flat"]), views(sl["flat_host"])
+                    sl["flat"], sl["outs"] = self._alloc_block(fields)
+                    sl["flat_host"] = torch.empty(_block_len(fields), dtype=torch.int32).pin_memory()
+                    sl["host"] = _block_views(sl["flat_host"], fields)
                     sl["up"], sl["done"], sl["free"], sl["ran"] = (torch.cuda.Event() for _ in range(4))
                     sl["free"].record(compute)
                 n = a.shape[0]
