@@ -172,8 +172,8 @@ int y4_decode_nms_mapped(y4_handle h, int n, float iou_threshold, float score_th
  * max_per_class counts per class under both settings of agnostic, and a candidate its class's cap turns away is not kept and
  * suppresses nothing; max_total is unchanged; with agnostic 1 the up to num_classes candidates of one box collapse to its best class.
  * Outputs keep their form.  Host-only state, settable at any time, no effect on the workspace, not a scheduling choice
- * (y4_copy_schedule does not carry it) and not in a checkpoint.  Read at the call by y4_decode_nms, y4_decode_nms_mapped and the
- * y4_predict* entry points.  Y4_EINVAL for a kind other than 0 / 1, an agnostic other than 0 / 1, and a beta that is not finite or
+ * (y4_copy_schedule does not carry it) and not in a checkpoint.  Read at the call by y4_decode_nms, y4_decode_nms_mapped, the
+ * y4_predict* entry points, y4_nms_gathered and the merged forms of these (y4_decode_nms_merged, y4_nms_gathered_merged).  Y4_EINVAL for a kind other than 0 / 1, an agnostic other than 0 / 1, and a beta that is not finite or
  * is <= 0 (beta is validated also for kind 0, which ignores it).  Default (0, 1.0, 0): every entry point returns the bits it
  * returned before this call existed. */
 int y4_set_nms_rule(y4_handle h, int kind, float beta, int agnostic);
@@ -218,6 +218,36 @@ int y4_decode_gather(y4_handle h, int n, float score_threshold, const int32_t* r
 int y4_nms_gathered(y4_handle h, int n_groups, int max_slots, uint32_t group_cap, float iou_threshold, void* scratch_dev,
                     int32_t* cand_count_dev /* [n_groups] */, float* boxes_dev, float* scores_dev, float* classes_dev,
                     int32_t* valid_dev, int32_t* kept_idx_dev, void* stream);
+/* ---- Merge-NMS (box voting; YOLOv5's merge=True, the box step of weighted box fusion): y4_decode_nms_mapped / y4_nms_gathered
+ * followed by one more kernel that replaces each kept box by the score-weighted mean of the candidates it absorbed.  The kept set,
+ * its order, scores, classes, valid and kept_idx are those of the plain entry point bit for bit; only the four floats of each kept
+ * box change.  No handle state: the plain entry points are untouched, and these read the handle's y4_set_nms_rule as they do.
+ *
+ * For a kept box k with unclipped box B_k, class c_k and candidate id, in the coordinates where the pair measure is taken (the
+ * canvas-normalised boxes before the clip and the box map; for a gathered group the group-normalised boxes behind the row map),
+ * a candidate j of the list is a MEMBER when
+ *     class_j == c_k (any class when the rule is agnostic)   and   m(B_j, B_k) > iou_threshold
+ * with m the measure of y4_set_nms_rule: the same float32 function, operation order and strict comparison that suppresses.
+ * Candidate k itself is a member by its id.  The list is every key below min(count, capacity), also the candidates the NMS never
+ * visited because it had its max_total boxes, and those a cap turned away.  A candidate with a component that is not finite or of
+ * magnitude above 2^8 is never a member; a kept box with such a component is written as the plain entry point writes it.
+ * Accumulation is in integers, so the result does not depend on the order of the list (which varies from run to run):
+ *     wq_j = llrint((double)score_j * 2^30),   t_j[c] = llrint((double)score_j * (double)B_j[c] * 2^30)    (nearest even)
+ *     S_w = sum wq_j,  S[c] = sum t_j[c]  in int64;     B'_k[c] = (float)((double)S[c] / (double)S_w)      (S_w == 0: B_k stays)
+ * componentwise on the four stored floats (no corner normalisation); then the box map (fmaf) and the clip to [0,1], as before.
+ * A member's rounding is at most 2^-31 in numerator and denominator: B' lies within 2^-31 (1 + |mean|) / s_min of the float64
+ * weighted mean (s_min the smallest member score), plus one float32 rounding.
+ * cand_count_dev [n] / [n_groups] is an output: the lists' raw candidate counts (the merge reads them; the counters themselves
+ * are zeroed by the NMS kernel).  kept_idx_dev is required.  A gathered group with more than group_cap candidates is reported
+ * through cand_count_dev as by y4_nms_gathered and merged over its first group_cap keys; the caller discards its result.
+ * Y4_EINVAL before any launch: a null output; a list capacity (nbox * C, or group_cap) of 2^25 keys or more, which the int64 sums
+ * do not cover; otherwise as the plain entry points.  Same handle-state rules as the plain entry points. */
+int y4_decode_nms_merged(y4_handle h, int n, float iou_threshold, float score_threshold, const float* box_map_dev /* may be NULL */,
+                         int32_t* cand_count_dev /* [n] out */, float* boxes_dev, float* scores_dev, float* classes_dev,
+                         int32_t* valid_dev, int32_t* kept_idx_dev /* required */, void* stream);
+int y4_nms_gathered_merged(y4_handle h, int n_groups, int max_slots, uint32_t group_cap, float iou_threshold, void* scratch_dev,
+                           int32_t* cand_count_dev /* [n_groups] */, float* boxes_dev, float* scores_dev, float* classes_dev,
+                           int32_t* valid_dev, int32_t* kept_idx_dev /* required */, void* stream);
 /* ---- Validation loss: the forward of the reference's yolo_loss (loss.py:119-212; training_model, models.py:54-65) over the raw
  * heads y4_forward / y4_set_heads left in the workspace.  (Its gradient: "Head fine-tuning" below.)
  *

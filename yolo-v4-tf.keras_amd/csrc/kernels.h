@@ -169,6 +169,29 @@ struct GatherK {
 int gather_launch(const GatherK& k, int n, hipStream_t stream);
 int gather_counts_launch(const uint32_t* gcounts, int32_t* out, int n_groups, hipStream_t stream);
 
+// box_merge.hip: merge-NMS (box voting) behind nms_kernel -- each kept box becomes the score-weighted mean of the candidates of
+// its list that it absorbed.  Reads the candidate store nms_kernel read and the outputs it wrote; rewrites kept boxes only.
+constexpr uint32_t MERGE_MAX_CAP = 1u << 25;   // list capacities below this keep the int64 sums in range (box_merge.hip)
+struct MergeK {
+    const float* dboxes;             // [N, nbox, 4] the unclipped boxes the pair measure is taken on
+    const unsigned long long* keys;  // [N, cap]
+    const int32_t* counts;           // [N] dense: the lists' raw counts, saved before nms_kernel zeroed the counters
+    uint32_t cap;
+    int N, C, nbox, max_total;
+    float iou_thr;
+    float* out_boxes;                // [N, max_total, 4] nms_kernel's boxes; the first out_valid[n] are rewritten
+    const float* out_scores;         // [N, max_total]
+    const float* out_classes;        // [N, max_total]
+    const int32_t* out_valid;        // [N]
+    const int32_t* out_idx;          // [N, max_total] box index of every kept box
+    FastDiv div_c;
+    const float* box_map;            // as NmsK: applied to the mean before the clip, or null
+    int kind;                        // the handle's rule, as NmsK
+    float beta;
+    int agnostic;
+};
+int box_merge_launch(const MergeK& k, hipStream_t stream);
+
 // loss.hip: the reference's yolo_loss forward over the raw heads, and the label assignment as responsible-cell records
 // (record: int32 words [scale, row, col, anchor, bits of x, y, w, h, class mask words]; sorted by (scale, row, col, anchor))
 struct LossAssignK {

@@ -924,6 +924,20 @@ int run_nms(y4_handle h, int n, float iou_thr, const NmsOutputs& o, const float*
     return Y4_OK;
 }
 
+// Merge-NMS behind an NMS of the same lists: every kept box becomes the score-weighted mean of the candidates it absorbed
+// (box_merge.hip).  counts_dev: [n] the lists' raw counts, saved before nms_kernel zeroed the counters
+int merge_over(y4_handle h, const CandStore& c, int n, float iou_thr, const NmsOutputs& o, const int32_t* counts_dev, const float* box_map,
+               hipStream_t s) {
+    MergeK k{};
+    k.dboxes = c.dboxes; k.keys = c.keys; k.counts = counts_dev; k.cap = c.cap;
+    k.N = n; k.C = h->cfg.num_classes; k.nbox = c.nbox; k.max_total = h->cfg.max_total; k.iou_thr = iou_thr;
+    k.out_boxes = o.boxes; k.out_scores = o.scores; k.out_classes = o.classes; k.out_valid = o.valid; k.out_idx = o.kept_idx;
+    k.div_c = c.div_c;
+    k.box_map = box_map;
+    k.kind = h->nms_kind; k.beta = h->nms_beta; k.agnostic = h->nms_agnostic;
+    return box_merge_launch(k, s);
+}
+
 }  // namespace
 
 extern "C" {
@@ -1208,6 +1222,22 @@ int y4_decode_nms_mapped(y4_handle h, int n, float iou_threshold, float score_th
     return run_nms(h, n, iou, NmsOutputs{boxes, scores, classes, valid, kept_idx}, box_map, (hipStream_t)stream);
 }
 
+int y4_decode_nms_merged(y4_handle h, int n, float iou_threshold, float score_threshold, const float* box_map, int32_t* cand_count,
+                         float* boxes, float* scores, float* classes, int32_t* valid, int32_t* kept_idx, void* stream) {
+    if (int r = check_ready(h, n)) return r;
+    Y4_REQUIRE(cand_count && boxes && scores && classes && valid && kept_idx, Y4_EINVAL, "y4_decode_nms_merged: null output");
+    const CandStore c = workspace_cands(h);
+    Y4_REQUIRE(c.cap < MERGE_MAX_CAP, Y4_EINVAL, "y4_decode_nms_merged: %u candidate keys per image are not below the 2^25 the merge allows", c.cap);
+    const float iou = iou_threshold < 0.f ? h->cfg.iou_threshold : iou_threshold;
+    const float sc = score_threshold < 0.f ? h->cfg.score_threshold : score_threshold;
+    hipStream_t s = (hipStream_t)stream;
+    const NmsOutputs o{boxes, scores, classes, valid, kept_idx};
+    if (int r = run_decode(h, n, sc, s)) return r;
+    if (int r = gather_counts_launch(c.counts, cand_count, n, s)) return r;      // nms_kernel zeroes the counters it has read
+    if (int r = run_nms(h, n, iou, o, box_map, s)) return r;
+    return merge_over(h, c, n, iou, o, cand_count, box_map, s);
+}
+
 int y4_set_nms_rule(y4_handle h, int kind, float beta, int agnostic) {
     if (int r = check_handle(h)) return r;
     Y4_REQUIRE(kind == 0 || kind == 1, Y4_EINVAL, "y4_set_nms_rule: kind %d (0: IoU, 1: DIoU)", kind);
@@ -1305,6 +1335,25 @@ int y4_nms_gathered(y4_handle h, int n_groups, int max_slots, uint32_t group_cap
     if (int r = gather_counts_launch(g.counts, cand_count_dev, n_groups, s)) return r;
     return nms_over(h, g, n_groups, iou_threshold < 0.f ? h->cfg.iou_threshold : iou_threshold,
                     NmsOutputs{boxes_dev, scores_dev, classes_dev, valid_dev, kept_idx_dev}, nullptr, s);
+}
+
+int y4_nms_gathered_merged(y4_handle h, int n_groups, int max_slots, uint32_t group_cap, float iou_threshold, void* scratch_dev,
+                           int32_t* cand_count_dev, float* boxes_dev, float* scores_dev, float* classes_dev, int32_t* valid_dev,
+                           int32_t* kept_idx_dev, void* stream) {
+    GatherLayout L;
+    if (int r = gather_layout(h, "y4_nms_gathered_merged", n_groups, max_slots, group_cap, &L)) return r;
+    if (int r = gather_scratch_check("y4_nms_gathered_merged", scratch_dev)) return r;
+    Y4_REQUIRE(h->act, Y4_ESTATE, "workspace not bound (call y4_bind_workspace first)");
+    Y4_REQUIRE(cand_count_dev && boxes_dev && scores_dev && classes_dev && valid_dev && kept_idx_dev, Y4_EINVAL,
+               "y4_nms_gathered_merged: null output");
+    Y4_REQUIRE(group_cap < MERGE_MAX_CAP, Y4_EINVAL, "y4_nms_gathered_merged: group_cap %u is not below the 2^25 the merge allows", group_cap);
+    hipStream_t s = (hipStream_t)stream;
+    const CandStore g = gathered_cands(h, scratch_dev, L, max_slots, group_cap);
+    const float iou = iou_threshold < 0.f ? h->cfg.iou_threshold : iou_threshold;
+    const NmsOutputs o{boxes_dev, scores_dev, classes_dev, valid_dev, kept_idx_dev};
+    if (int r = gather_counts_launch(g.counts, cand_count_dev, n_groups, s)) return r;
+    if (int r = nms_over(h, g, n_groups, iou, o, nullptr, s)) return r;
+    return merge_over(h, g, n_groups, iou, o, cand_count_dev, nullptr, s);
 }
 
 static void loss_geometry(y4_handle h, int* gh, int* gw, int* lane_base) {

@@ -45,7 +45,8 @@ class _KerasLikeModel:
 class Yolov4(object):
     def __init__(self, weight_path=None, class_name_path='coco_classes.txt', config=yolo_config, *,
                  dtype='f32', max_batch=32, synth_seed=0, device=None, device_preprocess=True, tune=None, share_schedule=None,
-                 letterbox=False, pad_value=128, box_loss='giou', nms_kind='iou', nms_beta=0.6, nms_agnostic=False):
+                 letterbox=False, pad_value=128, box_loss='giou', nms_kind='iou', nms_beta=0.6, nms_agnostic=False,
+                 nms_merge=False):
         # (reference models.py:23 also asserts img_size[0] == img_size[1], 'not support yet': rectangles are supported here)
         assert config['img_size'][0] % config['strides'][-1] == 0, 'must be a multiple of last stride'
         assert config['img_size'][1] % config['strides'][-1] == 0, 'must be a multiple of last stride'
@@ -78,6 +79,12 @@ class Yolov4(object):
         # it, with and without letterbox, before and after load_model and fit; it is no part of a checkpoint.
         Engine._nms_rule(nms_kind, nms_beta, nms_agnostic)      # (raises ValueError)
         self.nms_kind, self.nms_beta, self.nms_agnostic = nms_kind, float(nms_beta), bool(nms_agnostic)
+        # nms_merge=True: merge-NMS (box voting, YOLOv5's merge=True) -- each kept box is replaced by the score-weighted mean of the
+        # candidates it absorbed under that pair rule (Engine.set_nms_merge); the kept set, scores and classes do not change.  Like
+        # the rule it is state of both engines and in force for inference_model, predict, predict_img, predict_nonms,
+        # export_prediction, evaluate_map, fit(val_map=True), predict_tiled and predict_img_tiled, with and without letterbox, before
+        # and after load_model and fit; it is no part of a checkpoint or a schedule.
+        self.nms_merge = Engine._merge_flag(nms_merge)          # (raises ValueError)
         # letterbox=True: predict_img / predict / export_prediction resize each image with its aspect ratio kept, centred on a
         # canvas of uint8 level `pad_value` (Darknet's letterbox_image geometry; the resize is still cv2's uint8 arithmetic and the
         # pad a uint8 level, 128 = 0.502, where Darknet pads 0.5), and the boxes are mapped back to each raw image on the device.
@@ -106,7 +113,8 @@ class Yolov4(object):
         # alias_workspace: like the reference's Keras model, the facade keeps no intermediate activations (2.7x less HBM)
         self.engine = Engine(self.num_classes, self.config, max_batch=self._max_batch, dtype=self._dtype,
                              device=self._device, alias_workspace=True, box_loss=self.box_loss,
-                             nms_kind=self.nms_kind, nms_beta=self.nms_beta, nms_agnostic=self.nms_agnostic)
+                             nms_kind=self.nms_kind, nms_beta=self.nms_beta, nms_agnostic=self.nms_agnostic,
+                             nms_merge=self.nms_merge)
         self.yolo_model = _KerasLikeModel(self._tuned_first(self.engine.forward_heads), 'yolo_model')
         print(f"nms iou: {self.config['iou_threshold']} score: {self.config['score_threshold']}")
         self._thresholds = (-1.0, -1.0)  # what inference_model runs with (-1: the config's); load_model changes them
@@ -360,7 +368,8 @@ class Yolov4(object):
         if eng is None:
             eng = Engine(self.num_classes, self.config, max_batch=self._max_batch, dtype=self._dtype,
                          device=self._device, alias_workspace=True, retain_head_inputs=level, box_loss=self.box_loss,
-                         nms_kind=self.nms_kind, nms_beta=self.nms_beta, nms_agnostic=self.nms_agnostic)
+                         nms_kind=self.nms_kind, nms_beta=self.nms_beta, nms_agnostic=self.nms_agnostic,
+                             nms_merge=self.nms_merge)
             setattr(self, name, eng)
         eng.load_weight_blob(self._flat)
         self.engine.copy_schedule_to(eng)

@@ -68,17 +68,19 @@ def _block_views(flat, fields):
 class Engine:
     def __init__(self, num_classes, config=None, max_batch=32, dtype="f32", device=None, alias_workspace=False,
                  retain_head_inputs=False, *, max_per_class=100, max_total=100, box_loss="giou",
-                 nms_kind="iou", nms_beta=0.6, nms_agnostic=False):
+                 nms_kind="iou", nms_beta=0.6, nms_agnostic=False, nms_merge=False):
         self._build(num_classes, config, max_batch, dtype, device, alias_workspace, retain_head_inputs, None,
                     max_per_class=max_per_class, max_total=max_total, box_loss=box_loss,
-                    nms_kind=nms_kind, nms_beta=nms_beta, nms_agnostic=nms_agnostic)
+                    nms_kind=nms_kind, nms_beta=nms_beta, nms_agnostic=nms_agnostic, nms_merge=nms_merge)
 
     def _build(self, num_classes, config, max_batch, dtype, device, alias_workspace, retain_head_inputs, parent, *,
-               max_per_class=100, max_total=100, box_loss="giou", nms_kind="iou", nms_beta=0.6, nms_agnostic=False):
+               max_per_class=100, max_total=100, box_loss="giou", nms_kind="iou", nms_beta=0.6, nms_agnostic=False,
+               nms_merge=False):
         """What `__init__` and `sibling` share: the handle, its workspaces and every attribute.  `parent` is None for an engine
         with weights of its own, or the engine whose packed weights and schedule this one takes over."""
         box_kind = self._box_kind(box_loss)           # (an unknown name is refused before anything is loaded or created)
         nms_rule = self._nms_rule(nms_kind, nms_beta, nms_agnostic)      # (likewise)
+        self.nms_merge = self._merge_flag(nms_merge)                     # (likewise); a sibling takes its parent's
         import torch
         self.torch = torch
         self.lib = ext.load()
@@ -152,7 +154,7 @@ class Engine:
         e = Engine.__new__(Engine)
         e._build(self.num_classes, self.config, self.max_batch, self.dtype, self.device, self.alias_workspace, self.retain_level, self,
                  max_per_class=self.cfg.max_per_class, max_total=self.cfg.max_total, box_loss=self.box_loss,
-                 nms_kind=self.nms_kind, nms_beta=self.nms_beta, nms_agnostic=self.nms_agnostic)
+                 nms_kind=self.nms_kind, nms_beta=self.nms_beta, nms_agnostic=self.nms_agnostic, nms_merge=self.nms_merge)
         return e
 
     BOX_LOSSES = ("giou", "ciou")          # the kinds of y4_set_box_loss, by number
@@ -203,6 +205,30 @@ class Engine:
         self.nms_kind, self.nms_beta, self.nms_agnostic = self.NMS_KINDS[rule[0]], rule[1], bool(rule[2])
         for e in getattr(self, "_stream_siblings", []):
             e.set_nms_rule(kind, beta, agnostic)
+
+    @staticmethod
+    def _merge_flag(on):
+        if not isinstance(on, (bool, np.bool_)):
+            raise ValueError(f"nms_merge must be False or True, got {on!r}")
+        return bool(on)
+
+    def set_nms_merge(self, on):
+        """Merge-NMS (box voting) on or off for every later predict / decode_nms / nms_gathered / predict_tiled call of this
+        engine: each kept box is then replaced by the score-weighted mean of the candidates it absorbed -- same class (any class
+        under an agnostic rule) and a pair measure above the iou threshold of the call, under the rule of `set_nms_rule`
+        (y4_decode_nms_merged, y4_nms_gathered_merged).  The kept set, scores, classes, valid and kept indices are unchanged,
+        bit for bit; only the boxes move.  Host state of this object: with the flag off every call is the plain entry point.
+        The stream siblings this engine already has follow; siblings made later inherit it."""
+        self.nms_merge = self._merge_flag(on)
+        for e in getattr(self, "_stream_siblings", []):
+            e.set_nms_merge(on)
+
+    def _merge_counts(self, n):
+        """The [n] int32 device words the merged entry points save the candidate counts in (kept for the engine's lifetime)."""
+        buf = getattr(self, "_merge_count_buf", None)
+        if buf is None or buf.numel() < n:
+            buf = self._merge_count_buf = self.torch.empty((max(int(n), self.max_batch),), dtype=self.torch.int32, device=self.device)
+        return buf[:n]
 
     # what the Python side remembers of the handle's schedule (`stem_fusion`: tests/test_gpu_api.py; `halo2`: the YOLO4HIP_HALO2 switch)
     _SCHEDULE_SHADOWS = ("stem_fusion", "halo2")
@@ -563,9 +589,12 @@ class Engine:
         if cand_count is None:
             cand_count = torch.empty((geo[0],), dtype=torch.int32, device=self.device)
         b, s, c, v, k = outs
+        if self.nms_merge and k is None:                   # (the merge reads the kept indices)
+            k = torch.empty((geo[0], self.T), dtype=torch.int32, device=self.device)
+        fn = self.lib.y4_nms_gathered_merged if self.nms_merge else self.lib.y4_nms_gathered
         with torch.cuda.device(self.device):
-            ext.check(self.lib.y4_nms_gathered(self.handle, *geo, float(iou_threshold), ext.ptr(scratch), ext.ptr(cand_count),
-                                               ext.ptr(b), ext.ptr(s), ext.ptr(c), ext.ptr(v), ext.ptr(k), ext.stream_ptr()))
+            ext.check(fn(self.handle, *geo, float(iou_threshold), ext.ptr(scratch), ext.ptr(cand_count),
+                         ext.ptr(b), ext.ptr(s), ext.ptr(c), ext.ptr(v), ext.ptr(k), ext.stream_ptr()))
         return outs, cand_count
 
     def predict_tiled_device(self, raw_imgs, tile=None, overlap=0.2, full_image=True, letterbox=False, pad_value=128,
@@ -719,16 +748,22 @@ class Engine:
     def decode_nms_device(self, n, outs=None, iou_threshold=-1.0, score_threshold=-1.0, box_map=None):
         """Decode + NMS of the heads in the workspace.  box_map: a contiguous float32 cuda tensor [n,4] of (ax, bx, ay, by) rows
         (`preprocess_u8_batch`, prepost.box_map) -- the kept boxes are then mapped to each source image before the clip
-        (y4_decode_nms_mapped); everything but the boxes is unchanged."""
+        (y4_decode_nms_mapped); everything but the boxes is unchanged.  With `nms_merge` on both go through y4_decode_nms_merged."""
         outs = outs or self.alloc_outputs(n)
         b, s, c, v, k = outs
+        if box_map is not None and (tuple(box_map.shape) != (n, 4) or box_map.dtype != self.torch.float32 or not box_map.is_contiguous()):
+            raise ValueError(f"box_map must be a contiguous float32 tensor [{n},4], got {box_map.dtype} {tuple(box_map.shape)}")
         with self.torch.cuda.device(self.device):
-            if box_map is None:
+            if self.nms_merge:
+                if k is None:                              # (the merge reads the kept indices)
+                    k = self.torch.empty((n, self.T), dtype=self.torch.int32, device=self.device)
+                ext.check(self.lib.y4_decode_nms_merged(self.handle, n, float(iou_threshold), float(score_threshold),
+                                                        ext.ptr(box_map), ext.ptr(self._merge_counts(n)), ext.ptr(b), ext.ptr(s),
+                                                        ext.ptr(c), ext.ptr(v), ext.ptr(k), ext.stream_ptr()))
+            elif box_map is None:
                 ext.check(self.lib.y4_decode_nms(self.handle, n, float(iou_threshold), float(score_threshold), ext.ptr(b),
                                                  ext.ptr(s), ext.ptr(c), ext.ptr(v), ext.ptr(k), ext.stream_ptr()))
             else:
-                if tuple(box_map.shape) != (n, 4) or box_map.dtype != self.torch.float32 or not box_map.is_contiguous():
-                    raise ValueError(f"box_map must be a contiguous float32 tensor [{n},4], got {box_map.dtype} {tuple(box_map.shape)}")
                 ext.check(self.lib.y4_decode_nms_mapped(self.handle, n, float(iou_threshold), float(score_threshold),
                                                         ext.ptr(box_map), ext.ptr(b), ext.ptr(s), ext.ptr(c), ext.ptr(v),
                                                         ext.ptr(k), ext.stream_ptr()))
@@ -789,10 +824,14 @@ class Engine:
         return (tp_mask, best, match, used) if debug else tp_mask
 
     def predict_device(self, imgs_dev, outs=None):
-        """The whole hot path on device buffers: forward + decode + NMS (async on the current stream)."""
+        """The whole hot path on device buffers: forward + decode + NMS (async on the current stream).  With `nms_merge` on:
+        the forward, then the merged decode + NMS entry, on the same stream."""
         n = imgs_dev.shape[0]
         u8 = self._check_device_images(imgs_dev)
         outs = outs or self.alloc_outputs(n)
+        if self.nms_merge:
+            self.forward_device(imgs_dev)
+            return self.decode_nms_device(n, outs)
         b, s, c, v, k = outs
         with self.torch.cuda.device(self.device):
             fn = self.lib.y4_predict_u8 if u8 else self.lib.y4_predict

@@ -92,6 +92,7 @@ SYMBOLS = {
     "y4_get_conv_output": (_I, [_VP, _I, _I, _VP, C.c_size_t, _VP]),
     "y4_decode_nms": (_I, [_VP, _I, _F, _F, _VP, _VP, _VP, _VP, _VP, _VP]),
     "y4_decode_nms_mapped": (_I, [_VP, _I, _F, _F, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "y4_decode_nms_merged": (_I, [_VP, _I, _F, _F, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "y4_loss_assign": (_I, [_VP, _I, _VP, _I, _VP, _VP, _VP, _VP]),
     "y4_loss_scratch_floats": (_I, [_VP, _I, C.POINTER(C.c_size_t)]),
     "y4_loss": (_I, [_VP, _I, _VP, _VP, _VP, _I, _F, _VP, C.c_size_t, _VP, _VP]),
@@ -146,6 +147,7 @@ SYMBOLS = {
     "y4_gather_begin": (_I, [_VP, _I, _I, C.c_uint32, _VP, _VP]),
     "y4_decode_gather": (_I, [_VP, _I, _F, _VP, _VP, _VP, _I, _I, C.c_uint32, _VP, _VP]),
     "y4_nms_gathered": (_I, [_VP, _I, _I, C.c_uint32, _F, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "y4_nms_gathered_merged": (_I, [_VP, _I, _I, C.c_uint32, _F, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "y4_augment_u8_ragged": (_I, [_VP, _VP, _I, _VP, _I, _I, _I, _VP]),
     "y4_mosaic_u8_ragged": (_I, [_VP, _VP, _VP, _I, _VP, _I, _I, _I, _VP]),
     "y4_map_match": (_I, [_VP, _VP, _VP, _VP, _I, _I, _VP, _VP, _VP, _I, C.POINTER(C.c_double), _I, _VP, _VP, _VP, _VP, _VP]),
