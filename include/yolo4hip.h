@@ -218,6 +218,16 @@ int y4_decode_gather(y4_handle h, int n, float score_threshold, const int32_t* r
 int y4_nms_gathered(y4_handle h, int n_groups, int max_slots, uint32_t group_cap, float iou_threshold, void* scratch_dev,
                     int32_t* cand_count_dev /* [n_groups] */, float* boxes_dev, float* scores_dev, float* classes_dev,
                     int32_t* valid_dev, int32_t* kept_idx_dev, void* stream);
+/* y4_decode_gather for rows whose map may MIRROR (test-time augmentation: a row is a flipped view of its photo, see
+ * y4_view_u8_ragged): the same arguments, sequence, ids, capacity, status and handle-state rules as y4_decode_gather, and calls of
+ * both may feed one group.  The only difference is which corner an axis reads when its scale is negative:
+ *     x1' = fmaf(ax < 0 ? x2 : x1, ax, bx),   x2' = fmaf(ax < 0 ? x1 : x2, ax, bx),   and the same for y with ay.
+ * fmaf is monotone, so a decoded box with x1 <= x2 is stored with x1' <= x2' (y alike) under every sign of the scale -- what
+ * the pair measure of y4_nms_gathered and the componentwise mean of y4_nms_gathered_merged (no corner normalisation) take for
+ * granted.  With ax >= 0 and ay >= 0 it stores the bits y4_decode_gather stores.  Same call, same bits. */
+int y4_decode_gather_views(y4_handle h, int n, float score_threshold, const int32_t* row_group_dev, const int32_t* row_slot_dev,
+                           const float* row_map_dev /* [n][4] */, int n_groups, int max_slots, uint32_t group_cap, void* scratch_dev,
+                           void* stream);
 /* ---- Merge-NMS (box voting; YOLOv5's merge=True, the box step of weighted box fusion): y4_decode_nms_mapped / y4_nms_gathered
  * followed by one more kernel that replaces each kept box by the score-weighted mean of the candidates it absorbed.  The kept set,
  * its order, scores, classes, valid and kept_idx are those of the plain entry point bit for bit; only the four floats of each kept
@@ -617,6 +627,25 @@ typedef struct y4_window_desc {
  * table as for y4_resize_u8_ragged (every window inside its image, pitch >= 3 * w). */
 int y4_window_u8_ragged(const uint8_t* src_dev, const y4_window_desc* desc_dev, int n, uint8_t* out_dev, int H, int W,
                         int pad_value, void* stream);
+/* One VIEW of a window for y4_view_u8_ragged: the fields of y4_window_desc, then `flip` -- bit 0 mirrors the canvas left-right,
+ * bit 1 up-down (0..3) --, padded to 48 bytes. */
+typedef struct y4_view_desc {
+    int64_t offset;
+    int32_t pitch;
+    int32_t h, w;
+    int32_t out_h, out_w, pad_top, pad_left;         /* as y4_window_desc */
+    int32_t flip;                                    /* bits 0 (left-right) and 1 (up-down) */
+    int32_t reserved[2];                             /* not read */
+} y4_view_desc;                                      /* 48 bytes */
+/* y4_window_u8_ragged with a mirror of the CANVAS, still one launch: canvas pixel (y, x) of slot i is sourced from canvas pixel
+ * (y', x') of the unflipped canvas, x' = W - 1 - x under bit 0 of flip and y' = H - 1 - y under bit 1 (the rule of
+ * y4_augment_u8_ragged's flip, on both axes).  Slot i therefore holds np.flip, along the flipped axes, of the bytes
+ * y4_window_u8_ragged writes for the same descriptor without `flip`, padding included; at flip == 0 it holds exactly those bytes.
+ * The mirror applies to the coordinate a pixel is sourced from, never to where it is stored.  Any number of descriptors may point
+ * into one source image (the views of one photo).  Host checks and the caller's ownership of the device table as for
+ * y4_window_u8_ragged. */
+int y4_view_u8_ragged(const uint8_t* src_dev, const y4_view_desc* desc_dev, int n, uint8_t* out_dev, int H, int W, int pad_value,
+                      void* stream);
 /* One image of a ragged batch for y4_augment_u8_ragged: the fields of y4_image_desc, then the augmentation of this image --
  * flip (0 / 1: mirror left-right) and the HSV factors (hue is added, sat and val multiply; 0, 1, 1 change nothing). */
 typedef struct y4_augment_desc {

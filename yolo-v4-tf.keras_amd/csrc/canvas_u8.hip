@@ -1,6 +1,7 @@
 // canvas_u8.hip -- every launch that writes the uint8 network batch [n,H,W,3] from packed uint8 sources through a device-resident
 // descriptor table: y4_resize_u8_ragged (letterbox / mixed-size batches), y4_window_u8_ragged (tiled inference),
-// y4_augment_u8_ragged and y4_mosaic_u8_ragged (the training input of Yolov4.fit).  One kernel template, one launcher; the four
+// y4_view_u8_ragged (test-time augmentation: a window, mirrored left-right and / or up-down), y4_augment_u8_ragged and
+// y4_mosaic_u8_ragged (the training input of Yolov4.fit).  One kernel template, one launcher; the
 // entry points differ only in the row source that says which descriptor governs a canvas pixel.  All randomness of the training
 // input is drawn on the host (yolo4hip/augment.py: draw_params): the kernel is a pure function of its table.  Host restatements:
 // prepost.py: letterbox, augment.py: augment_host / mosaic_host; tests/augment_oracle.py is the float64 colour oracle.
@@ -71,12 +72,13 @@ __device__ __forceinline__ void store_px_u8(uint8_t* __restrict__ o, const uint8
 // ---------------------------------------------------------------------------------------- row sources
 // A row source answers: which descriptor governs canvas pixel (y, x) of slot b.  `open(b)` is called by every thread of the
 // workgroup; `at(y, x)` gives the descriptor.  What a descriptor type carries beyond offset, h, w and the canvas rectangle decides
-// at compile time what the kernel does with it: a `pitch` (y4_window_desc) is the source row's bytes, and a y4_augment_desc has
-// flip and HSV.
+// at compile time what the kernel does with it: a `pitch` (y4_window_desc, y4_view_desc) is the source row's bytes, a
+// y4_view_desc has flip bits for both axes, and a y4_augment_desc has a left-right flip and HSV.
 //
 // One descriptor per slot, a wave-uniform load (scalar registers):
 //   SlotRow<y4_image_desc>    a packed image;
 //   SlotRow<y4_window_desc>   adds the pitch: a window of a larger image, many rows may read one image;
+//   SlotRow<y4_view_desc>     a window whose canvas is mirrored (bit 0: left-right, bit 1: up-down);
 //   SlotRow<y4_augment_desc>  adds flip and HSV, and a rectangle that may stick out of the canvas.
 template <class D>
 struct SlotRow {
@@ -117,13 +119,15 @@ struct MosaicRows {
 // The bytes of a source row: the packed callers keep their int index arithmetic, a window's pitch indexes in 64 bits.
 template <class D> __device__ __forceinline__ int src_pitch(const D& d) { return 3 * d.w; }
 __device__ __forceinline__ int64_t src_pitch(const y4_window_desc& d) { return d.pitch; }
+__device__ __forceinline__ int64_t src_pitch(const y4_view_desc& d) { return d.pitch; }
 
 // ------------------------------------------------------------------------------------------- kernel
 // Grid y = canvas slot, grid x = PX consecutive CANVAS pixels per thread.  Pixels inside the descriptor's rectangle
 // [pad_top, pad_top + out_h) x [pad_left, pad_left + out_w) are cv2.resize's uint8 INTER_LINEAR resize of the source to
 // out_w x out_h (resize_px_u8), every other pixel is `pad` without the colour transform; the rectangle may lie partly or wholly
 // outside the canvas (only its visible part is computed).  A flipped row mirrors the column a canvas pixel is SOURCED from
-// (x' = W - 1 - x), never where it is stored, so a flipped thread's stores are the same three dwords.  The source reads are
+// (x' = W - 1 - x; a view's bit 1 likewise the row, y' = H - 1 - y), never where it is stored, so a flipped thread's stores are
+// the same three dwords.  The source reads are
 // gathers (two rows, bilinear taps) served from L1/L2; the writes are what this kernel can shape: with PX = 4 a thread stores its
 // 12 bytes as three dwords and a wave covers 768 contiguous bytes, instead of 3 byte stores per pixel.  PX = 4 needs
 // H * W % 4 == 0 (every network size: sides are multiples of 32) and a 4-byte aligned output; otherwise PX = 1.
@@ -132,6 +136,7 @@ __global__ __launch_bounds__(256) void canvas_u8_kernel(const uint8_t* __restric
                                                         int H, int W, int pad) {
     using D = typename S::Desc;
     constexpr bool AUGMENT = std::is_same<D, y4_augment_desc>::value;
+    constexpr bool VIEW = std::is_same<D, y4_view_desc>::value;
     const int b = blockIdx.y;
     const typename S::Slot slot = rows.open(b);            // every thread: a source may stage its rows behind a barrier
     const int hw = H * W;                                  // < 2^31 (checked on the host)
@@ -143,9 +148,13 @@ __global__ __launch_bounds__(256) void canvas_u8_kernel(const uint8_t* __restric
         const int p = p0 + k;
         const int y = p / W, x = p - y * W;
         const D d = slot.at(y, x);
-        int xs = x;
+        int xs = x, ys = y;
         if constexpr (AUGMENT) xs = d.flip ? W - 1 - x : x;
-        const int yy = y - d.pad_top, xx = xs - d.pad_left;
+        if constexpr (VIEW) {
+            xs = (d.flip & 1) ? W - 1 - x : x;
+            ys = (d.flip & 2) ? H - 1 - y : y;
+        }
+        const int yy = ys - d.pad_top, xx = xs - d.pad_left;
         int v[3] = {pad, pad, pad};
         if (yy >= 0 && yy < d.out_h && xx >= 0 && xx < d.out_w) {
             resize_px_u8(src + d.offset, src_pitch(d), d.h, d.w, d.out_h, d.out_w, yy, xx, v);
@@ -186,6 +195,11 @@ int resize_u8_ragged_launch(const uint8_t* src, const y4_image_desc* desc, int n
 int window_u8_ragged_launch(const uint8_t* src, const y4_window_desc* desc, int n, uint8_t* out, int H, int W, int pad,
                             hipStream_t stream) {
     return canvas_u8_launch("window_u8_ragged", src, SlotRow<y4_window_desc>{desc}, n, out, H, W, pad, stream);
+}
+
+int view_u8_ragged_launch(const uint8_t* src, const y4_view_desc* desc, int n, uint8_t* out, int H, int W, int pad,
+                          hipStream_t stream) {
+    return canvas_u8_launch("view_u8_ragged", src, SlotRow<y4_view_desc>{desc}, n, out, H, W, pad, stream);
 }
 
 int augment_u8_ragged_launch(const uint8_t* src, const y4_augment_desc* desc, int n, uint8_t* out, int H, int W, int pad,

@@ -73,6 +73,8 @@ int resize_u8_ragged_launch(const uint8_t* src, const y4_image_desc* desc, int n
                             hipStream_t stream);
 int window_u8_ragged_launch(const uint8_t* src, const y4_window_desc* desc, int n, uint8_t* out, int H, int W, int pad,
                             hipStream_t stream);
+int view_u8_ragged_launch(const uint8_t* src, const y4_view_desc* desc, int n, uint8_t* out, int H, int W, int pad,
+                          hipStream_t stream);
 int augment_u8_ragged_launch(const uint8_t* src, const y4_augment_desc* desc, int n, uint8_t* out, int H, int W, int pad,
                              hipStream_t stream);
 int mosaic_u8_ragged_launch(const uint8_t* src, const y4_augment_desc* tiles, const y4_mosaic_cut* cuts, int n, uint8_t* out, int H,
@@ -166,7 +168,8 @@ struct GatherK {
     uint32_t* status;                // [1] bit0, as NmsK
     FastDiv div_c;
 };
-int gather_launch(const GatherK& k, int n, hipStream_t stream);
+// oriented (y4_decode_gather_views): an axis whose scale is negative reads its two corners swapped, so x1 <= x2 stays
+int gather_launch(const GatherK& k, int n, bool oriented, hipStream_t stream);
 int gather_counts_launch(const uint32_t* gcounts, int32_t* out, int n_groups, hipStream_t stream);
 
 // box_merge.hip: merge-NMS (box voting) behind nms_kernel -- each kept box becomes the score-weighted mean of the candidates of

@@ -1297,13 +1297,14 @@ int y4_gather_begin(y4_handle h, int n_groups, int max_slots, uint32_t group_cap
     return Y4_OK;
 }
 
-int y4_decode_gather(y4_handle h, int n, float score_threshold, const int32_t* row_group_dev, const int32_t* row_slot_dev,
-                     const float* row_map_dev, int n_groups, int max_slots, uint32_t group_cap, void* scratch_dev, void* stream) {
+static int decode_gather(y4_handle h, const char* who, bool oriented, int n, float score_threshold, const int32_t* row_group_dev,
+                         const int32_t* row_slot_dev, const float* row_map_dev, int n_groups, int max_slots, uint32_t group_cap,
+                         void* scratch_dev, void* stream) {
     GatherLayout L;
-    if (int r = gather_layout(h, "y4_decode_gather", n_groups, max_slots, group_cap, &L)) return r;
+    if (int r = gather_layout(h, who, n_groups, max_slots, group_cap, &L)) return r;
     if (int r = check_ready(h, n)) return r;
-    if (int r = gather_scratch_check("y4_decode_gather", scratch_dev)) return r;
-    Y4_REQUIRE(row_group_dev && row_slot_dev && row_map_dev, Y4_EINVAL, "y4_decode_gather: null row table");
+    if (int r = gather_scratch_check(who, scratch_dev)) return r;
+    Y4_REQUIRE(row_group_dev && row_slot_dev && row_map_dev, Y4_EINVAL, "%s: null row table", who);
     const float sc = score_threshold < 0.f ? h->cfg.score_threshold : score_threshold;
     hipStream_t s = (hipStream_t)stream;
     if (int r = run_decode(h, n, sc, s)) return r;
@@ -1315,11 +1316,24 @@ int y4_decode_gather(y4_handle h, int n, float score_threshold, const int32_t* r
     k.n_groups = n_groups; k.max_slots = max_slots; k.group_cap = g.cap;
     k.gcounts = g.counts; k.gkeys = g.keys; k.gboxes = g.dboxes;
     k.status = c.status; k.div_c = c.div_c;
-    if (int r = gather_launch(k, n, s)) return r;
+    if (int r = gather_launch(k, n, oriented, s)) return r;
     // gather_kernel left the counters of rows 0 .. n-1 at zero, the rows this decode counted into: the handle is where an NMS over
     // n images would have left it (run_nms: counts_clean = counts_n <= n)
     h->counts_clean = true;
     return Y4_OK;
+}
+
+int y4_decode_gather(y4_handle h, int n, float score_threshold, const int32_t* row_group_dev, const int32_t* row_slot_dev,
+                     const float* row_map_dev, int n_groups, int max_slots, uint32_t group_cap, void* scratch_dev, void* stream) {
+    return decode_gather(h, "y4_decode_gather", false, n, score_threshold, row_group_dev, row_slot_dev, row_map_dev, n_groups,
+                         max_slots, group_cap, scratch_dev, stream);
+}
+
+int y4_decode_gather_views(y4_handle h, int n, float score_threshold, const int32_t* row_group_dev, const int32_t* row_slot_dev,
+                           const float* row_map_dev, int n_groups, int max_slots, uint32_t group_cap, void* scratch_dev,
+                           void* stream) {
+    return decode_gather(h, "y4_decode_gather_views", true, n, score_threshold, row_group_dev, row_slot_dev, row_map_dev, n_groups,
+                         max_slots, group_cap, scratch_dev, stream);
 }
 
 int y4_nms_gathered(y4_handle h, int n_groups, int max_slots, uint32_t group_cap, float iou_threshold, void* scratch_dev,
@@ -2246,6 +2260,11 @@ int y4_resize_u8_ragged(const uint8_t* src_dev, const y4_image_desc* desc_dev, i
 int y4_window_u8_ragged(const uint8_t* src_dev, const y4_window_desc* desc_dev, int n, uint8_t* out_dev, int H, int W,
                         int pad_value, void* stream) {
     return window_u8_ragged_launch(src_dev, desc_dev, n, out_dev, H, W, pad_value, (hipStream_t)stream);
+}
+
+int y4_view_u8_ragged(const uint8_t* src_dev, const y4_view_desc* desc_dev, int n, uint8_t* out_dev, int H, int W, int pad_value,
+                      void* stream) {
+    return view_u8_ragged_launch(src_dev, desc_dev, n, out_dev, H, W, pad_value, (hipStream_t)stream);
 }
 
 int y4_augment_u8_ragged(const uint8_t* src_dev, const y4_augment_desc* desc_dev, int n, uint8_t* out_dev, int H, int W,

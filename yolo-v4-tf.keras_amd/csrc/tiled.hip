@@ -1,7 +1,9 @@
 // tiled.hip -- the gather of tiled (sliced) inference, Engine.predict_tiled (its window crops are canvas_u8.hip's):
 //   gather_kernel            y4_decode_gather: the candidate lists the decode stage left for several batch rows (tiles) are merged
 //                            into ONE list per group (photo), boxes mapped to the photo's normalised coordinates, on which the
-//                            NMS kernel of decode_nms.hip then runs unchanged (y4_nms_gathered).
+//                            NMS kernel of decode_nms.hip then runs unchanged (y4_nms_gathered).  ORIENTED
+//                            (y4_decode_gather_views, test-time augmentation) swaps the corners an axis reads when its
+//                            scale is negative: a mirrored row stores x1 <= x2, which the merge's componentwise mean needs.
 #include "candidates.h"
 #include "kernels.h"
 
@@ -18,6 +20,7 @@ namespace y4 {
 // candidates of one box store the same four floats.  The order of a group's list varies from run to run; its keys are unique
 // and nms_kernel sorts them.
 constexpr int GATHER_THREADS = 1024;
+template <bool ORIENTED>
 __global__ __launch_bounds__(GATHER_THREADS) void gather_kernel(const GatherK p) {
     const int i = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
     uint32_t cnt = p.counts[(size_t)i * COUNT_STRIDE];
@@ -46,6 +49,11 @@ __global__ __launch_bounds__(GATHER_THREADS) void gather_kernel(const GatherK p)
         if (ok) {
             if (pos < p.group_cap) gkeys[pos] = cand_key(cand_score(key), id0 + cand_id(key));     // the score word stays
             float4 o = *(const float4*)(rb + (int64_t)b * 4);
+            if constexpr (ORIENTED) {                    // (uniform per row) a mirrored axis: its low corner comes from the high one
+                const float x1 = ax < 0.f ? o.z : o.x, x2 = ax < 0.f ? o.x : o.z;
+                const float y1 = ay < 0.f ? o.w : o.y, y2 = ay < 0.f ? o.y : o.w;
+                o.x = x1; o.y = y1; o.z = x2; o.w = y2;
+            }
             o.x = fmaf(o.x, ax, bx); o.y = fmaf(o.y, ay, by);
             o.z = fmaf(o.z, ax, bx); o.w = fmaf(o.w, ay, by);
             *(float4*)(gb + (int64_t)b * 4) = o;
@@ -53,8 +61,9 @@ __global__ __launch_bounds__(GATHER_THREADS) void gather_kernel(const GatherK p)
     }
 }
 
-int gather_launch(const GatherK& k, int n, hipStream_t stream) {
-    hipLaunchKernelGGL(gather_kernel, dim3(n), dim3(GATHER_THREADS), 0, stream, k);
+int gather_launch(const GatherK& k, int n, bool oriented, hipStream_t stream) {
+    if (oriented) hipLaunchKernelGGL(gather_kernel<true>, dim3(n), dim3(GATHER_THREADS), 0, stream, k);
+    else hipLaunchKernelGGL(gather_kernel<false>, dim3(n), dim3(GATHER_THREADS), 0, stream, k);
     Y4_CHECK_HIP(hipGetLastError());
     return Y4_OK;
 }

@@ -17,14 +17,15 @@ a `DataGenerator`, `evaluate_map(data)` VOC mAP with the matching on the device 
 its text files); `fit(..., trainable='heads')` fine-tunes the three detection convs on a frozen backbone and neck (with a
 `DataGenerator(..., augment=AugmentConfig())` under scale, shift, flip and HSV augmentation applied on the device), while
 training every layer (the reference's `fit`) is out of scope and raises.  `predict_tiled` / `predict_img_tiled` (not in the reference)
-cut a photo much larger than the network input into overlapping windows and run one NMS per photo over all of them on the device.
+cut a photo much larger than the network input into overlapping windows and run one NMS per photo over all of them on the device;
+`predict_tta` / `predict_img_tta` (not in the reference either) run a photo under flipped and scaled views, again under one NMS.
 """
 import json
 import os
 
 import numpy as np
 
-from . import prepost, weights as W
+from . import prepost, tiling, weights as W
 from .config import yolo_config
 from .engine import Engine
 from .plan import build_plan
@@ -411,7 +412,8 @@ class Yolov4(object):
         mean = sums / images
         return {'loss': float(mean[0]), 'box': float(mean[1]), 'conf': float(mean[2]), 'class': float(mean[3]), 'images': images}
 
-    def evaluate_map(self, data, img_folder_path=None, bs=None, *, iou_thresholds=(0.5,), channel_order='rgb'):
+    def evaluate_map(self, data, img_folder_path=None, bs=None, *, iou_thresholds=(0.5,), channel_order='rgb', views=None,
+                     tile_candidates=1 << 18):
         """VOC mAP with the matching on the device: the numbers of `export_gt` + `export_prediction` + `eval_map`, without the
         text files.  `data` is an annotation file path (then `img_folder_path` is required, images are looked up by file name as
         `export_prediction` does, and `bs` defaults to max_batch) or a `DataGenerator`: its `annotation_lines`, `folder_path` and
@@ -425,7 +427,11 @@ class Yolov4(object):
         per_threshold {thr: {mAP, ap, tp, fp}} and mAP_mean (with numpy.arange(0.5, 1.0, 0.05) the COCO-style summary under VOC
         interpolation).  (A class name with a blank in it, COCO's "wine glass", is no obstacle here; the text files cannot carry it.)
         channel_order: 'rgb' (default) feeds the images as `DataGenerator` and `fit` feed them -- the order the model is trained
-        on; 'bgr' feeds what `export_prediction` feeds, the reference's unflipped cv2.imread, and reproduces that pipeline."""
+        on; 'bgr' feeds what `export_prediction` feeds, the reference's unflipped cv2.imread, and reproduces that pipeline.
+        views: None, or a list of (scale, flip) views: each batch then goes through `Engine.predict_tta_device` (test-time
+        augmentation: one NMS per image over all its views, merged under nms_merge) instead of the forward and decode + NMS; its
+        boxes arrive normalised to each raw image and stay on the device for the matching.  RuntimeError when an image has more
+        than tile_candidates candidates, as `predict_tiled`."""
         from .data import MAP_MAX_GT, read_map_annotations
         from .mapeval import MapAccumulator
         if channel_order not in ('rgb', 'bgr'):
@@ -445,6 +451,9 @@ class Yolov4(object):
             raise ValueError(f'evaluate_map: bs {bs}')
         if not items:
             raise ValueError('evaluate_map: no annotation lines')
+        if views is not None:
+            tiling.check_views(views)                      # ValueError before anything is uploaded
+            views = list(views)
         self._ensure_tuned()
         eng = self.engine
         torch = eng.torch
@@ -458,7 +467,8 @@ class Yolov4(object):
                 raws = [prepost.imread_rgb(pth) for pth in paths[i0:i0 + n]]
                 if channel_order == 'bgr':
                     raws = [r[:, :, ::-1] for r in raws]
-                imgs, box_map = eng.preprocess_u8_batch(raws, letterbox=self._letterbox, pad_value=self._pad_value)
+                if views is None:
+                    imgs, box_map = eng.preprocess_u8_batch(raws, letterbox=self._letterbox, pad_value=self._pad_value)
                 side = np.zeros((n, MAP_MAX_GT * 5 + 3), dtype=np.float32)      # per image: boxes | w, h | count (as int32 bits)
                 for k, (raw, (_, _, boxes)) in enumerate(zip(raws, part)):
                     side[k, :boxes.size] = boxes.reshape(-1)
@@ -468,11 +478,25 @@ class Yolov4(object):
                 gt_dev = side_dev[:, :MAP_MAX_GT * 5].contiguous().view(n, MAP_MAX_GT, 5)
                 scale_dev = side_dev[:, MAP_MAX_GT * 5:MAP_MAX_GT * 5 + 2].contiguous()
                 count_dev = side_dev[:, MAP_MAX_GT * 5 + 2].contiguous().view(torch.int32)
-                flat, outs, tp_mask = eng.alloc_map_outputs_flat(n)
-                eng.forward_device(imgs)
-                eng.decode_nms_device(n, outs, iou, score, box_map=box_map if self._letterbox else None)
-                eng.map_match_device(outs, scale_dev, gt_dev, count_dev, acc.iou_thresholds, tp_mask=tp_mask)
-                scores, classes, valid, tp = eng.map_outputs_to_host(flat, n)
+                if views is None:
+                    flat, outs, tp_mask = eng.alloc_map_outputs_flat(n)
+                    eng.forward_device(imgs)
+                    eng.decode_nms_device(n, outs, iou, score, box_map=box_map if self._letterbox else None)
+                    eng.map_match_device(outs, scale_dev, gt_dev, count_dev, acc.iou_thresholds, tp_mask=tp_mask)
+                    scores, classes, valid, tp = eng.map_outputs_to_host(flat, n)
+                else:
+                    # the boxes arrive normalised to each raw image (no box map) and are matched where they lie; the block of
+                    # predict_tta_device comes back in its one copy, the true-positive flags in a second small one
+                    flat, outs, _, group_cap = eng.predict_tta_device(
+                        raws, views, letterbox=self._letterbox, pad_value=self._pad_value, iou_threshold=iou,
+                        score_threshold=score, tile_candidates=tile_candidates)
+                    tp = eng.map_match_device(outs, scale_dev, gt_dev, count_dev, acc.iou_thresholds)
+                    (_, scores, classes, valid, _), cand = eng.tiled_outputs_to_host(flat, n)
+                    if (cand > group_cap).any():
+                        g = int(np.argmax(cand))
+                        raise RuntimeError(f'evaluate_map: image {i0 + g} has {int(cand[g])} candidates, more than '
+                                           f'tile_candidates = {group_cap} holds; raise tile_candidates')
+                    tp = tp.cpu().numpy().view(np.uint32)
                 acc.add([stem for _, stem, _ in part], scores, classes, valid, tp, [boxes[:, 4] for _, _, boxes in part])
         return acc.result()
 
@@ -522,29 +546,55 @@ class Yolov4(object):
     # windows at native resolution (yolo4hip/tiling.py), the windows run as batch rows, and one NMS per photo runs over all rows
     # in the photo's coordinates (Engine.predict_tiled).  Honours this object's letterbox / pad_value (how a window that is not of
     # the network's size, and the full image, go on the canvas), thresholds and NMS rule.  uint8 images only.
-    def predict_tiled(self, raw_imgs, *, tile=None, overlap=0.2, full_image=True, tile_candidates=1 << 18):
+    def predict_tiled(self, raw_imgs, *, tile=None, overlap=0.2, full_image=True, tile_candidates=1 << 18, views=None):
         """raw_imgs: one uint8 RGB photo [h,w,3] or a list of them, any sizes -> (boxes [P,100,4] normalised to each photo,
         scores, classes, valid), the form of inference_model.predict.  tile: window size, an int or (th, tw), default the network
         input; overlap: fraction of a tile neighbouring windows share at least; full_image: the whole photo, resized as
-        predict_img resizes it, takes part as one more row (large objects); tile_candidates: candidate capacity per photo."""
+        predict_img resizes it, takes part as one more row (large objects); tile_candidates: candidate capacity per photo;
+        views: None, or (scale, flip) views every row also runs under (see `predict_tta`)."""
         self._ensure_tuned()
         iou, score = self._thresholds
         b, s, c, v = self.engine.predict_tiled(raw_imgs, tile=tile, overlap=overlap, full_image=full_image,
                                                letterbox=self._letterbox, pad_value=self._pad_value, iou_threshold=iou,
-                                               score_threshold=score, tile_candidates=tile_candidates)
+                                               score_threshold=score, tile_candidates=tile_candidates, views=views)
         return b, s, c, v
 
-    def predict_img_tiled(self, raw_img, random_color=True, plot_img=True, figsize=(10, 10), show_text=True,
-                          return_output=False, *, tile=None, overlap=0.2, full_image=True):
-        """`predict_img` through `predict_tiled`: the same prints, drawing and DataFrame, boxes in the photo's pixels."""
-        print('img shape: ', raw_img.shape)
-        pred_output = self.predict_tiled([raw_img], tile=tile, overlap=overlap, full_image=full_image)
+    def _show(self, raw_img, pred_output, random_color, plot_img, figsize, show_text, return_output):
+        """The DataFrame and drawing of `predict_img` for outputs normalised to the photo."""
         detections = prepost.get_detection_data(img=raw_img, model_outputs=pred_output, class_names=self.class_names)
         output_img = prepost.draw_bbox(raw_img, detections, cmap=self.class_color, random_color=random_color,
                                        figsize=figsize, show_text=show_text, show_img=plot_img)
         if return_output:
             return output_img, detections
         return detections
+
+    def predict_img_tiled(self, raw_img, random_color=True, plot_img=True, figsize=(10, 10), show_text=True,
+                          return_output=False, *, tile=None, overlap=0.2, full_image=True, views=None):
+        """`predict_img` through `predict_tiled`: the same prints, drawing and DataFrame, boxes in the photo's pixels."""
+        print('img shape: ', raw_img.shape)
+        pred_output = self.predict_tiled([raw_img], tile=tile, overlap=overlap, full_image=full_image, views=views)
+        return self._show(raw_img, pred_output, random_color, plot_img, figsize, show_text, return_output)
+
+    # ---- test-time augmentation: not in the reference (YOLOv5's augment=True).  The photo runs under several views -- the
+    # rectangle it occupies shrunk about its centre, the canvas mirrored (yolo4hip/tiling.py: view_rows) -- as batch rows, and one
+    # NMS per photo runs over the candidates of all views in the photo's coordinates (Engine.predict_tta); with nms_merge the
+    # copies of an object become one score-weighted box.  Views are call arguments, not state.  uint8 images only.
+    def predict_tta(self, raw_imgs, *, views=tiling.DEFAULT_VIEWS, tile_candidates=1 << 18):
+        """raw_imgs: one uint8 RGB photo [h,w,3] or a list of them, any sizes -> (boxes [P,100,4] normalised to each photo,
+        scores, classes, valid), the form of inference_model.predict.  views: a list of (scale in (0, 1], flip in '', 'lr', 'ud',
+        'lrud'), at most 16, no duplicates; ((1.0, ''),) is `predict_img`'s own path."""
+        self._ensure_tuned()
+        iou, score = self._thresholds
+        b, s, c, v = self.engine.predict_tta(raw_imgs, views=views, letterbox=self._letterbox, pad_value=self._pad_value,
+                                             iou_threshold=iou, score_threshold=score, tile_candidates=tile_candidates)
+        return b, s, c, v
+
+    def predict_img_tta(self, raw_img, random_color=True, plot_img=True, figsize=(10, 10), show_text=True,
+                        return_output=False, *, views=tiling.DEFAULT_VIEWS):
+        """`predict_img` through `predict_tta`: the same prints, drawing and DataFrame, boxes in the photo's pixels."""
+        print('img shape: ', raw_img.shape)
+        pred_output = self.predict_tta([raw_img], views=views)
+        return self._show(raw_img, pred_output, random_color, plot_img, figsize, show_text, return_output)
 
     # ---- reference models.py:125-127
     def predict(self, img_path, random_color=True, plot_img=True, figsize=(10, 10), show_text=True):

@@ -9,7 +9,7 @@ import os
 
 import numpy as np
 
-from . import ext, schedule
+from . import ext, schedule, tiling
 from .config import yolo_config
 
 
@@ -535,6 +535,12 @@ class Engine:
         is a uint8 cuda tensor of at least [n,H,W,3].  Asynchronous on the current stream; returns out[:n]."""
         return self._canvas_launch(self.lib.y4_window_u8_ragged, ext.ptr(src_dev), (ext.ptr(desc_dev),), n, out, pad_value)
 
+    def view_u8_ragged(self, src_dev, desc_dev, n, out, pad_value=128):
+        """y4_view_u8_ragged on device buffers: `desc_dev` holds n y4_view_desc rows (windows of images in `src_dev`, each with
+        its flip bits: the canvas mirrored left-right / up-down), `out` is a uint8 cuda tensor of at least [n,H,W,3].
+        Asynchronous on the current stream; returns out[:n]."""
+        return self._canvas_launch(self.lib.y4_view_u8_ragged, ext.ptr(src_dev), (ext.ptr(desc_dev),), n, out, pad_value)
+
     # ---------------------------------------------------------------- tiled inference: one NMS over the rows of a group
     def gather_begin(self, n_groups, max_slots, group_cap):
         """Scratch for a gathered decode + NMS sequence (y4_gather_scratch_bytes, y4_gather_begin): -> the state `decode_gather`
@@ -550,17 +556,20 @@ class Engine:
             ext.check(self.lib.y4_gather_begin(self.handle, *geo, ext.ptr(scratch), ext.stream_ptr()))
         return geo, scratch
 
-    def decode_gather(self, state, n, row_group, row_slot, row_map, score_threshold=-1.0):
+    def decode_gather(self, state, n, row_group, row_slot, row_map, score_threshold=-1.0, oriented=False):
         """y4_decode_gather: the decode stage on rows 0 .. n-1 of the workspace, their candidates merged into the groups of
-        `state`.  row_group / row_slot: int32 cuda tensors [n], row_map float32 cuda [n,4] (contiguous).  Asynchronous."""
+        `state`.  row_group / row_slot: int32 cuda tensors [n], row_map float32 cuda [n,4] (contiguous).  oriented=True is
+        y4_decode_gather_views: a map with a negative scale (a mirrored view) swaps the corners it reads, so that stored boxes
+        keep x1 <= x2 and y1 <= y2.  Asynchronous."""
         torch = self.torch
         geo, scratch = state
         for t, dt, shape in ((row_group, torch.int32, (n,)), (row_slot, torch.int32, (n,)), (row_map, torch.float32, (n, 4))):
             if t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous() or not t.is_cuda:
                 raise ValueError(f"decode_gather: expected a contiguous {dt} cuda tensor {shape}, got {t.dtype} {tuple(t.shape)}")
+        fn = self.lib.y4_decode_gather_views if oriented else self.lib.y4_decode_gather
         with torch.cuda.device(self.device):
-            ext.check(self.lib.y4_decode_gather(self.handle, int(n), float(score_threshold), ext.ptr(row_group), ext.ptr(row_slot),
-                                                ext.ptr(row_map), *geo, ext.ptr(scratch), ext.stream_ptr()))
+            ext.check(fn(self.handle, int(n), float(score_threshold), ext.ptr(row_group), ext.ptr(row_slot),
+                         ext.ptr(row_map), *geo, ext.ptr(scratch), ext.stream_ptr()))
 
     def alloc_tiled_outputs_flat(self, n_groups):
         """`alloc_outputs_flat(n_groups)` with the groups' candidate counts behind it, ONE int32 device block for one copy back:
@@ -597,27 +606,35 @@ class Engine:
                          ext.ptr(b), ext.ptr(s), ext.ptr(c), ext.ptr(v), ext.ptr(k), ext.stream_ptr()))
         return outs, cand_count
 
-    def predict_tiled_device(self, raw_imgs, tile=None, overlap=0.2, full_image=True, letterbox=False, pad_value=128,
-                             iou_threshold=-1.0, score_threshold=-1.0, tile_candidates=1 << 18):
-        """`predict_tiled` with the results left on the device: -> (flat, outs, cand_count, group_cap) in the form of
-        `alloc_tiled_outputs_flat(len(raw_imgs))` -- outs are what `decode_nms_device` returns for that many images, boxes
-        normalised to each photo, ready for `map_match_device`.  The caller checks cand_count <= group_cap.  Asynchronous."""
+    def _rows_device(self, who, raw_imgs, rows_of, views, pad_value, iou_threshold, score_threshold, tile_candidates):
+        """The loop of `predict_tiled_device` and `predict_tta_device`: rows_of(h, w) -> the base rows (window, rect, map) of a
+        photo.  views=None: the rows as they are, through y4_window_u8_ragged and y4_decode_gather; a view list: every row under
+        every view (tiling.view_rows, slot = its index there), through y4_view_u8_ragged and y4_decode_gather_views."""
         torch = self.torch
-        from . import tiling
-        raw_imgs, pad_value = self._check_ragged(raw_imgs, pad_value, "predict_tiled")
+        raw_imgs, pad_value = self._check_ragged(raw_imgs, pad_value, who)
         if int(tile_candidates) < 1:
             raise ValueError(f"tile_candidates must be >= 1, got {tile_candidates}")
+        if views is not None:
+            tiling.check_views(views)                      # ValueError before anything is uploaded
+            views = list(views)
         H, W = self.img_hw
-        tile_hw = None if tile is None else ((int(tile), int(tile)) if np.ndim(tile) == 0 else (int(tile[0]), int(tile[1])))
-        photo, slot, windows, rects, maps = [], [], [], [], []
+        photo, slot, windows, rects, maps, flips = [], [], [], [], [], []
         for p, a in enumerate(raw_imgs):
-            rows = tiling.tile_rows(a.shape[0], a.shape[1], (H, W), tile_hw, overlap, full_image, letterbox)
-            for t, (win, rect, m) in enumerate(rows):
-                photo.append(p); slot.append(t); windows.append(win); rects.append(rect); maps.append(m)
+            rows = rows_of(a.shape[0], a.shape[1])
+            if views is None:
+                rows = [(win, rect, 0, m) for win, rect, m in rows]
+            else:
+                rows = tiling.view_rows(rows, views, a.shape[:2], (H, W))
+            for t, (win, rect, bits, m) in enumerate(rows):
+                photo.append(p); slot.append(t); windows.append(win); rects.append(rect); maps.append(m); flips.append(bits)
         R, P, max_slots = len(photo), len(raw_imgs), max(slot) + 1
-        desc = (ext.y4_window_desc * R)()
-        for d, rect in zip(desc, rects):
+        Desc, launch = ((ext.y4_window_desc, self.lib.y4_window_u8_ragged) if views is None
+                        else (ext.y4_view_desc, self.lib.y4_view_u8_ragged))
+        desc = (Desc * R)()
+        for d, rect, bits in zip(desc, rects, flips):
             d.out_h, d.out_w, d.pad_top, d.pad_left = rect
+            if views is not None:
+                d.flip = bits
         # maps | groups | slots travel behind the descriptors in the one upload
         extra = np.concatenate([np.asarray(maps, np.float32).reshape(-1).view(np.int32), np.asarray(photo, np.int32),
                                 np.asarray(slot, np.int32)])
@@ -628,21 +645,41 @@ class Engine:
         group_cap = int(min(int(tile_candidates), max_slots * self.num_boxes * self.num_classes))
         state = self.gather_begin(P, max_slots, group_cap)
         flat, outs, cand_count = self.alloc_tiled_outputs_flat(P)
-        step = C.sizeof(ext.y4_window_desc)
+        step = C.sizeof(Desc)
         with torch.cuda.device(self.device):
             canvas = torch.empty((min(R, self.max_batch), H, W, 3), dtype=torch.uint8, device=self.device)
             src = C.c_void_p(dev.data_ptr() + head)
             for r0 in range(0, R, self.max_batch):
                 n = min(self.max_batch, R - r0)
-                self._canvas_launch(self.lib.y4_window_u8_ragged, src, (C.c_void_p(dev.data_ptr() + r0 * step),), n, canvas,
-                                    pad_value)
-                ext.check(self.lib.y4_forward_u8(self.handle, ext.ptr(canvas), n, ext.stream_ptr()))
-                self.decode_gather(state, n, row_group[r0:r0 + n], row_slot[r0:r0 + n], row_map[r0:r0 + n], score_threshold)
+                self.forward_device(self._canvas_launch(launch, src, (C.c_void_p(dev.data_ptr() + r0 * step),), n, canvas, pad_value))
+                self.decode_gather(state, n, row_group[r0:r0 + n], row_slot[r0:r0 + n], row_map[r0:r0 + n], score_threshold,
+                                   oriented=views is not None)
             self.nms_gathered(state, outs, cand_count, iou_threshold)
         return flat, outs, cand_count, group_cap
 
+    def _rows_to_host(self, who, device_result, n, with_indices):
+        """The one copy back of `_rows_device`'s result and the capacity check."""
+        flat, _, _, group_cap = device_result
+        res, cand = self.tiled_outputs_to_host(flat, n)
+        if (cand > group_cap).any():
+            g = int(np.argmax(cand))
+            raise RuntimeError(f"{who}: photo {g} has {int(cand[g])} candidates, more than tile_candidates = {group_cap} "
+                               f"holds; raise tile_candidates")
+        return res if with_indices else res[:4]
+
+    def predict_tiled_device(self, raw_imgs, tile=None, overlap=0.2, full_image=True, letterbox=False, pad_value=128,
+                             iou_threshold=-1.0, score_threshold=-1.0, tile_candidates=1 << 18, views=None):
+        """`predict_tiled` with the results left on the device: -> (flat, outs, cand_count, group_cap) in the form of
+        `alloc_tiled_outputs_flat(len(raw_imgs))` -- outs are what `decode_nms_device` returns for that many images, boxes
+        normalised to each photo, ready for `map_match_device`.  The caller checks cand_count <= group_cap.  Asynchronous."""
+        H, W = self.img_hw
+        tile_hw = None if tile is None else ((int(tile), int(tile)) if np.ndim(tile) == 0 else (int(tile[0]), int(tile[1])))
+        return self._rows_device("predict_tiled", raw_imgs,
+                                 lambda h, w: tiling.tile_rows(h, w, (H, W), tile_hw, overlap, full_image, letterbox),
+                                 views, pad_value, iou_threshold, score_threshold, tile_candidates)
+
     def predict_tiled(self, raw_imgs, tile=None, overlap=0.2, full_image=True, letterbox=False, pad_value=128,
-                      iou_threshold=-1.0, score_threshold=-1.0, tile_candidates=1 << 18, with_indices=False):
+                      iou_threshold=-1.0, score_threshold=-1.0, tile_candidates=1 << 18, with_indices=False, views=None):
         """Tiled (sliced) inference of uint8 RGB photos [h,w,3] of any sizes: each photo is cut into overlapping windows of `tile`
         (an int or (th, tw); None: the network input, so interior windows are 1:1 copies) at native resolution
         (yolo4hip.tiling.tile_rows; full_image=True adds the whole photo as one more row), the windows run through the network
@@ -651,17 +688,36 @@ class Engine:
         y4_forward_u8 -> y4_decode_gather, then y4_nms_gathered and one copy back.  letterbox / pad_value: how a window (and the
         full image) that is not of the network's size is placed on the canvas.  tile_candidates: the candidate keys a photo may
         have (8 bytes each); RuntimeError when a photo has more.
+        views: None, or a list of (scale, flip) views (yolo4hip.tiling.view_rows): every row then runs under every view -- rows x
+        views slots per photo, through y4_view_u8_ragged and y4_decode_gather_views -- still under the one NMS.
         -> [boxes [P,max_total,4] normalised to each photo, scores, classes, valid], with_indices also kept = slot * num_boxes +
         box, as fresh host arrays, like `predict`."""
         raws = [raw_imgs] if isinstance(raw_imgs, np.ndarray) and raw_imgs.ndim == 3 else list(raw_imgs)
-        flat, _, _, group_cap = self.predict_tiled_device(raws, tile, overlap, full_image, letterbox, pad_value, iou_threshold,
-                                                          score_threshold, tile_candidates)
-        res, cand = self.tiled_outputs_to_host(flat, len(raws))
-        if (cand > group_cap).any():
-            g = int(np.argmax(cand))
-            raise RuntimeError(f"predict_tiled: photo {g} has {int(cand[g])} candidates, more than tile_candidates = {group_cap} "
-                               f"holds; raise tile_candidates")
-        return res if with_indices else res[:4]
+        res = self.predict_tiled_device(raws, tile, overlap, full_image, letterbox, pad_value, iou_threshold, score_threshold,
+                                        tile_candidates, views)
+        return self._rows_to_host("predict_tiled", res, len(raws), with_indices)
+
+    def predict_tta_device(self, raw_imgs, views=tiling.DEFAULT_VIEWS, letterbox=False, pad_value=128, iou_threshold=-1.0, score_threshold=-1.0,
+                           tile_candidates=1 << 18):
+        """`predict_tta` with the results left on the device, in the form of `predict_tiled_device`: -> (flat, outs, cand_count,
+        group_cap), boxes normalised to each photo, ready for `map_match_device`."""
+        H, W = self.img_hw
+        return self._rows_device("predict_tta", raw_imgs,
+                                 lambda h, w: tiling.tile_rows(h, w, (H, W), None, 0.0, True, letterbox)[-1:],
+                                 views, pad_value, iou_threshold, score_threshold, tile_candidates)
+
+    def predict_tta(self, raw_imgs, views=tiling.DEFAULT_VIEWS, letterbox=False, pad_value=128, iou_threshold=-1.0, score_threshold=-1.0,
+                    tile_candidates=1 << 18, with_indices=False):
+        """Test-time augmentation of uint8 RGB photos [h,w,3] of any sizes: each photo's full-image row (stretch, or letterbox)
+        runs under every view (scale, flip) of `views` (default: YOLOv5's three) as one batch row each --
+        the rectangle shrunk about its centre, the canvas mirrored --, and ONE NMS per photo runs over the candidates of all its
+        views in the photo's coordinates (merged into score-weighted boxes when `nms_merge` is on).  The loop of
+        `predict_tiled`: one upload, per chunk of max_batch rows y4_view_u8_ragged -> y4_forward_u8 -> y4_decode_gather_views,
+        then y4_nms_gathered, one copy back.  RuntimeError when a photo has more than tile_candidates candidates.
+        -> what `predict_tiled` returns; kept = slot * num_boxes + box with slot the view's index."""
+        raws = [raw_imgs] if isinstance(raw_imgs, np.ndarray) and raw_imgs.ndim == 3 else list(raw_imgs)
+        res = self.predict_tta_device(raws, views, letterbox, pad_value, iou_threshold, score_threshold, tile_candidates)
+        return self._rows_to_host("predict_tta", res, len(raws), with_indices)
 
     def resize_u8(self, frames_dev, out=None):
         """Device-side stretch resize (cv2.resize to width W, height H) on a uint8 cuda batch [n,h,w,3] -> uint8 [n,H,W,3]

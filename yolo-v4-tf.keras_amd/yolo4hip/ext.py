@@ -58,6 +58,10 @@ class y4_window_desc(C.Structure):
                 ("out_w", C.c_int32), ("pad_top", C.c_int32), ("pad_left", C.c_int32)]
 
 
+class y4_view_desc(C.Structure):
+    _fields_ = y4_window_desc._fields_ + [("flip", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
 class y4_augment_desc(C.Structure):
     _fields_ = y4_image_desc._fields_ + [("flip", C.c_int32), ("hue", C.c_float), ("sat", C.c_float), ("val", C.c_float)]
 
@@ -143,9 +147,11 @@ SYMBOLS = {
     "y4_resize_u8": (_I, [_VP, _I, _I, _I, _VP, _I, _I, _VP]),
     "y4_resize_u8_ragged": (_I, [_VP, _VP, _I, _VP, _I, _I, _I, _VP]),
     "y4_window_u8_ragged": (_I, [_VP, _VP, _I, _VP, _I, _I, _I, _VP]),
+    "y4_view_u8_ragged": (_I, [_VP, _VP, _I, _VP, _I, _I, _I, _VP]),
     "y4_gather_scratch_bytes": (_I, [_VP, _I, _I, C.c_uint32, C.POINTER(C.c_size_t)]),
     "y4_gather_begin": (_I, [_VP, _I, _I, C.c_uint32, _VP, _VP]),
     "y4_decode_gather": (_I, [_VP, _I, _F, _VP, _VP, _VP, _I, _I, C.c_uint32, _VP, _VP]),
+    "y4_decode_gather_views": (_I, [_VP, _I, _F, _VP, _VP, _VP, _I, _I, C.c_uint32, _VP, _VP]),
     "y4_nms_gathered": (_I, [_VP, _I, _I, C.c_uint32, _F, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "y4_nms_gathered_merged": (_I, [_VP, _I, _I, C.c_uint32, _F, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "y4_augment_u8_ragged": (_I, [_VP, _VP, _I, _VP, _I, _I, _I, _VP]),
