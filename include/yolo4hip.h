@@ -715,6 +715,39 @@ int y4_map_match(const float* boxes_dev,  /* [n, max_total, 4], x1 y1 x2 y2 norm
                  int32_t* match_dev,      /* [n, max_total] or NULL: index of that box, -1 */
                  uint32_t* gt_used_dev,   /* [n, max_gt] or NULL: bit t = used at threshold t when the image is done */
                  void* stream);
+/* ---- COCO bbox matching on the device: COCOeval's per-image matching without crowd regions, beside the VOC rule above, on the
+ * same inputs (yolo4hip/cocoeval.py turns the flags into AP / AR).  No handle.  Per image, one workgroup:
+ *   - boxes as above: detection = float32 product box * scale, ground truth = the float32 annotation value, both widened to float64;
+ *     all arithmetic float64 in the stated order, no contraction.  area = (x2 - x1) * (y2 - y1);
+ *     iw = min(dx2, gx2) - max(dx1, gx1), ih likewise; iw <= 0 or ih <= 0: IoU 0, else i = iw * ih, IoU = i / (da + ga - i).  No `+ 1`;
+ *   - per area range [lo, hi] a ground-truth row is ignored when area < lo or area > hi (both strict), a detection is out of range
+ *     by the same test on its own area;
+ *   - per (range, threshold) one walk over the detections by score descending, slot ascending on ties (a NaN score is never
+ *     walked).  A detection takes, among the rows < gt_count of its class (int(class) on both sides) not yet matched in this
+ *     walk, the non-ignored row with the largest IoU >= min(thr, 1 - 1e-10), the LAST such row in annotation order on equal IoU;
+ *     if there is none, the ignored row chosen by the same rule.  That row is then matched.  The detection is matched, and
+ *     ignored iff the row is; an unmatched detection is ignored iff it is out of range;
+ *   - cls_rank: the 0-based position of the detection among the image's detections of its class in walk order (the host applies
+ *     COCO's maxDets as cls_rank < maxDet: the walk is greedy in score order, so the cut changes no earlier decision).
+ * No atomics; image i's outputs are the same bits at any n and at any position in the batch.
+ * Y4_EINVAL: max_total > 256, max_gt > 256, n_thresholds outside 1..16, n_areas outside 1..4, a negative n / max_total / max_gt,
+ * a null pointer (match_row_dev may be NULL).  Device counts are clamped to [0, max_total] / [0, max_gt]; slots >= valid and
+ * rows >= gt_count are never read and are written as 0 / -1. */
+int y4_coco_match(const float* boxes_dev,  /* [n, max_total, 4], x1 y1 x2 y2 normalised */
+                  const float* scores_dev, const float* classes_dev, const int32_t* valid_dev,
+                  int n, int max_total,
+                  const float* scale_dev,      /* [n, 2] (w, h) */
+                  const float* gt_dev,         /* [n, max_gt, 5] x1 y1 x2 y2 class, raw-image pixels, annotation order */
+                  const int32_t* gt_count_dev, /* [n] */
+                  int max_gt,
+                  const double* area_ranges /* host [n_areas][2]: lo, hi */, int n_areas,
+                  const double* iou_thresholds /* host */, int n_thresholds,
+                  uint32_t* dt_match_dev,   /* [n, n_areas, max_total]: bit t = matched at iou_thresholds[t] under that range */
+                  uint32_t* dt_ignore_dev,  /* [n, n_areas, max_total]: bit t = ignored there */
+                  int32_t* cls_rank_dev,    /* [n, max_total]; -1 in slots that are not walked */
+                  uint32_t* gt_ignore_dev,  /* [n, max_gt]: bit a = ignored under range a */
+                  int32_t* match_row_dev,   /* [n, n_areas, n_thresholds, max_total] or NULL: the matched row, -1 */
+                  void* stream);
 /* SPP (custom_layers.py:130-134): x = buf[..., 3c:4c] -> buf[..., 0:c]=maxpool13, [c:2c]=maxpool9,
  * [2c:3c]=maxpool5 (stride 1, 'same'), buf is [n,side,side,4c] */
 int y4_spp(int dtype, void* buf_dev, int n, int side, int c, void* stream);

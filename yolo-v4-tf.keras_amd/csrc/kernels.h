@@ -85,6 +85,12 @@ int map_match_launch(const float* boxes, const float* scores, const float* class
                      const float* scale, const float* gt, const int32_t* gt_count, int max_gt, const double* iou_thresholds,
                      int n_thresholds, uint32_t* tp_mask, double* best_iou, int32_t* match, uint32_t* gt_used, hipStream_t stream);
 
+// coco_match.hip: COCO bbox matching (area ranges, ignore flags, matched rows leave the pool), one workgroup per image
+int coco_match_launch(const float* boxes, const float* scores, const float* classes, const int32_t* valid, int n, int max_total,
+                      const float* scale, const float* gt, const int32_t* gt_count, int max_gt, const double* area_ranges,
+                      int n_areas, const double* iou_thresholds, int n_thresholds, uint32_t* dt_match, uint32_t* dt_ignore,
+                      int32_t* cls_rank, uint32_t* gt_ignore, int32_t* match_row, hipStream_t stream);
+
 // stem_down.hip: convs 0+1 fused (16-bit dtypes), c0 stays in LDS
 bool stem_down_supported(int dtype, int S);
 int stem_down_launch(int dtype, const void* imgs, int img_u8, int n, int S, const void* stem_wk, const float* s0_scale,

@@ -2285,6 +2285,15 @@ int y4_map_match(const float* boxes_dev, const float* scores_dev, const float* c
                             iou_thresholds, n_thresholds, tp_mask_dev, best_iou_dev, match_dev, gt_used_dev, (hipStream_t)stream);
 }
 
+int y4_coco_match(const float* boxes_dev, const float* scores_dev, const float* classes_dev, const int32_t* valid_dev, int n,
+                  int max_total, const float* scale_dev, const float* gt_dev, const int32_t* gt_count_dev, int max_gt,
+                  const double* area_ranges, int n_areas, const double* iou_thresholds, int n_thresholds, uint32_t* dt_match_dev,
+                  uint32_t* dt_ignore_dev, int32_t* cls_rank_dev, uint32_t* gt_ignore_dev, int32_t* match_row_dev, void* stream) {
+    return coco_match_launch(boxes_dev, scores_dev, classes_dev, valid_dev, n, max_total, scale_dev, gt_dev, gt_count_dev, max_gt,
+                             area_ranges, n_areas, iou_thresholds, n_thresholds, dt_match_dev, dt_ignore_dev, cls_rank_dev,
+                             gt_ignore_dev, match_row_dev, (hipStream_t)stream);
+}
+
 int y4_preprocess_u8(const uint8_t* img_dev, int h, int w, float* out_dev, int out_h, int out_w, void* stream) {
     return preprocess_u8_launch(img_dev, h, w, out_dev, out_h, out_w, (hipStream_t)stream);
 }

@@ -14,7 +14,8 @@ self-describing checkpoint of this framework (Keras' SavedModel / H5 needs Tenso
 is the VOC mAP tool over the exported text files (yolo4hip/evalmap.py).  `training_model.predict([X, y_s, y_m, y_l, true_xywh])`
 is the reference's yolo_loss FORWARD (models.py:54-65, loss.py) on the device and `evaluate(data_gen)` the validation loss over
 a `DataGenerator`, `evaluate_map(data)` VOC mAP with the matching on the device (y4_map_match; the numbers of `eval_map` without
-its text files); `fit(..., trainable='heads')` fine-tunes the three detection convs on a frozen backbone and neck (with a
+its text files) and `evaluate_coco(data, views=..., tiled=...)` COCO's AP / AR (y4_coco_match; over the plain, the view or the tiled
+path); `fit(..., trainable='heads')` fine-tunes the three detection convs on a frozen backbone and neck (with a
 `DataGenerator(..., augment=AugmentConfig())` under scale, shift, flip and HSV augmentation applied on the device), while
 training every layer (the reference's `fit`) is out of scope and raises.  `predict_tiled` / `predict_img_tiled` (not in the reference)
 cut a photo much larger than the network input into overlapping windows and run one NMS per photo over all of them on the device;
@@ -432,13 +433,46 @@ class Yolov4(object):
         augmentation: one NMS per image over all its views, merged under nms_merge) instead of the forward and decode + NMS; its
         boxes arrive normalised to each raw image and stay on the device for the matching.  RuntimeError when an image has more
         than tile_candidates candidates, as `predict_tiled`."""
-        from .data import MAP_MAX_GT, read_map_annotations
         from .mapeval import MapAccumulator
+        items, paths, bs = self._eval_items('evaluate_map', data, img_folder_path, bs, channel_order)
+        if views is not None:
+            tiling.check_views(views)                      # ValueError before anything is uploaded
+            views = list(views)
+        self._ensure_tuned()
+        eng = self.engine
+        iou, score = self._thresholds
+        acc = MapAccumulator(self.class_names, iou_thresholds)
+        for i0, part, raws, gt_dev, scale_dev, count_dev in self._eval_batches(items, paths, bs, channel_order):
+            n = len(part)
+            if views is None:
+                imgs, box_map = eng.preprocess_u8_batch(raws, letterbox=self._letterbox, pad_value=self._pad_value)
+                flat, outs, tp_mask = eng.alloc_map_outputs_flat(n)
+                eng.forward_device(imgs)
+                eng.decode_nms_device(n, outs, iou, score, box_map=box_map if self._letterbox else None)
+                eng.map_match_device(outs, scale_dev, gt_dev, count_dev, acc.iou_thresholds, tp_mask=tp_mask)
+                scores, classes, valid, tp = eng.map_outputs_to_host(flat, n)
+            else:
+                # the boxes arrive normalised to each raw image (no box map) and are matched where they lie; the block of
+                # predict_tta_device comes back in its one copy, the true-positive flags in a second small one
+                flat, outs, _, group_cap = eng.predict_tta_device(
+                    raws, views, letterbox=self._letterbox, pad_value=self._pad_value, iou_threshold=iou,
+                    score_threshold=score, tile_candidates=tile_candidates)
+                tp = eng.map_match_device(outs, scale_dev, gt_dev, count_dev, acc.iou_thresholds)
+                (_, scores, classes, valid, _), cand = eng.tiled_outputs_to_host(flat, n)
+                self._check_candidates('evaluate_map', i0, cand, group_cap)
+                tp = tp.cpu().numpy().view(np.uint32)
+            acc.add([stem for _, stem, _ in part], scores, classes, valid, tp, [boxes[:, 4] for _, _, boxes in part])
+        return acc.result()
+
+    def _eval_items(self, who, data, img_folder_path, bs, channel_order):
+        """The arguments `evaluate_map` and `evaluate_coco` share -> (items of `read_map_annotations`, image paths, bs);
+        ValueError before anything is read or uploaded."""
+        from .data import read_map_annotations
         if channel_order not in ('rgb', 'bgr'):
             raise ValueError(f"channel_order must be 'rgb' or 'bgr', got {channel_order!r}")
         if isinstance(data, (str, os.PathLike)):
             if img_folder_path is None:
-                raise ValueError('evaluate_map: an annotation file needs img_folder_path')
+                raise ValueError(f'{who}: an annotation file needs img_folder_path')
             with open(data) as fh:
                 items = read_map_annotations(fh.readlines(), self.num_classes)
             paths = [os.path.join(img_folder_path, name.split(os.sep)[-1]) for name, _, _ in items]
@@ -448,18 +482,20 @@ class Yolov4(object):
             paths = [os.path.join(data.folder_path, name) for name, _, _ in items]
             bs = int(data.batch_size) if bs is None else int(bs)
         if bs < 1:
-            raise ValueError(f'evaluate_map: bs {bs}')
+            raise ValueError(f'{who}: bs {bs}')
         if not items:
-            raise ValueError('evaluate_map: no annotation lines')
-        if views is not None:
-            tiling.check_views(views)                      # ValueError before anything is uploaded
-            views = list(views)
-        self._ensure_tuned()
+            raise ValueError(f'{who}: no annotation lines')
+        return items, paths, bs
+
+    def _eval_batches(self, items, paths, bs, channel_order):
+        """The batch loop `evaluate_map` and `evaluate_coco` share: `bs` images per batch in file order, a batch larger than the
+        engine's in chunks, as predict does.  Per chunk the images are read, put into the channel order, and the side block --
+        per image: boxes | w, h | count (as int32 bits) -- is uploaded in one copy.
+        -> (index of the first image, items, raw images, gt_dev [n,256,5], scale_dev [n,2], count_dev int32 [n])."""
+        from .data import MAP_MAX_GT
         eng = self.engine
         torch = eng.torch
-        iou, score = self._thresholds
-        acc = MapAccumulator(self.class_names, iou_thresholds)
-        step = min(bs, eng.max_batch)              # a batch larger than the engine's goes through it in chunks, as predict does
+        step = min(bs, eng.max_batch)
         for start in range(0, len(items), bs):
             for i0 in range(start, min(start + bs, len(items)), step):
                 part = items[i0:min(i0 + step, start + bs)]
@@ -467,9 +503,7 @@ class Yolov4(object):
                 raws = [prepost.imread_rgb(pth) for pth in paths[i0:i0 + n]]
                 if channel_order == 'bgr':
                     raws = [r[:, :, ::-1] for r in raws]
-                if views is None:
-                    imgs, box_map = eng.preprocess_u8_batch(raws, letterbox=self._letterbox, pad_value=self._pad_value)
-                side = np.zeros((n, MAP_MAX_GT * 5 + 3), dtype=np.float32)      # per image: boxes | w, h | count (as int32 bits)
+                side = np.zeros((n, MAP_MAX_GT * 5 + 3), dtype=np.float32)
                 for k, (raw, (_, _, boxes)) in enumerate(zip(raws, part)):
                     side[k, :boxes.size] = boxes.reshape(-1)
                     side[k, MAP_MAX_GT * 5:MAP_MAX_GT * 5 + 2] = raw.shape[1], raw.shape[0]
@@ -478,26 +512,76 @@ class Yolov4(object):
                 gt_dev = side_dev[:, :MAP_MAX_GT * 5].contiguous().view(n, MAP_MAX_GT, 5)
                 scale_dev = side_dev[:, MAP_MAX_GT * 5:MAP_MAX_GT * 5 + 2].contiguous()
                 count_dev = side_dev[:, MAP_MAX_GT * 5 + 2].contiguous().view(torch.int32)
-                if views is None:
-                    flat, outs, tp_mask = eng.alloc_map_outputs_flat(n)
-                    eng.forward_device(imgs)
-                    eng.decode_nms_device(n, outs, iou, score, box_map=box_map if self._letterbox else None)
-                    eng.map_match_device(outs, scale_dev, gt_dev, count_dev, acc.iou_thresholds, tp_mask=tp_mask)
-                    scores, classes, valid, tp = eng.map_outputs_to_host(flat, n)
-                else:
-                    # the boxes arrive normalised to each raw image (no box map) and are matched where they lie; the block of
-                    # predict_tta_device comes back in its one copy, the true-positive flags in a second small one
-                    flat, outs, _, group_cap = eng.predict_tta_device(
-                        raws, views, letterbox=self._letterbox, pad_value=self._pad_value, iou_threshold=iou,
-                        score_threshold=score, tile_candidates=tile_candidates)
-                    tp = eng.map_match_device(outs, scale_dev, gt_dev, count_dev, acc.iou_thresholds)
-                    (_, scores, classes, valid, _), cand = eng.tiled_outputs_to_host(flat, n)
-                    if (cand > group_cap).any():
-                        g = int(np.argmax(cand))
-                        raise RuntimeError(f'evaluate_map: image {i0 + g} has {int(cand[g])} candidates, more than '
-                                           f'tile_candidates = {group_cap} holds; raise tile_candidates')
-                    tp = tp.cpu().numpy().view(np.uint32)
-                acc.add([stem for _, stem, _ in part], scores, classes, valid, tp, [boxes[:, 4] for _, _, boxes in part])
+                yield i0, part, raws, gt_dev, scale_dev, count_dev
+
+    @staticmethod
+    def _check_candidates(who, i0, cand, group_cap):
+        if (cand > group_cap).any():
+            g = int(np.argmax(cand))
+            raise RuntimeError(f'{who}: image {i0 + g} has {int(cand[g])} candidates, more than '
+                               f'tile_candidates = {group_cap} holds; raise tile_candidates')
+
+    def evaluate_coco(self, data, img_folder_path=None, bs=None, *, channel_order='rgb', views=None, tiled=False, tile=None,
+                      overlap=0.2, full_image=True, tile_candidates=1 << 18, max_dets=(1, 10, 100), area_ranges=None):
+        """COCO-protocol AP / AR (COCOeval's bbox protocol without crowd regions) with the matching on the device, over the plain,
+        the test-time-view or the tiled inference path -- one call answers "what does tiling do to APs on my data".
+        `data`, `img_folder_path`, `bs`, `channel_order`, the annotation reading (raw-image pixels, annotation order, every box,
+        at most 256 per image, as float32) and the batching are `evaluate_map`'s.  The inference path:
+          plain (default)   forward + `decode_nms_device`, as `evaluate_map`;
+          views=[...]       `Engine.predict_tta_device`: (scale, flip) views under one NMS per image;
+          tiled=True        `Engine.predict_tiled_device(raws, tile, overlap, full_image, ..., views=views)`: windows of `tile`
+                            (default the network input) with `overlap`, plus the whole photo when full_image, under one NMS per
+                            photo; RuntimeError when a photo has more than tile_candidates candidates (also with views=).
+        Every path runs under this object's thresholds, letterbox, pad value, NMS rule and nms_merge.  Per batch the kept boxes
+        stay on the device: `y4_coco_match` matches them (the rule: csrc/coco_match.hip) at IoU .50:.05:.95 under `area_ranges`
+        (default COCO's all / small / medium / large = [0, 1e10], [0, 32^2], [32^2, 96^2], [96^2, 1e10] in raw-image pixels; 1..4
+        rows in that order), and ONE copy brings scores, classes, valid, the class ranks and the flags back;
+        `cocoeval.CocoAccumulator` turns them into precision and recall under `max_dets`.
+        -> AP, AP50, AP75, APs, APm, APl, AR1, AR10, AR100, ARs, ARm, ARl by name, `stats` (the twelve in COCO's order),
+        `per_class` {class name: AP}, `precision` [T,R,K,A,M], `recall` [T,K,A,M], `n_gt` and `n_det` {class name: count}.  A number
+        without ground truth in its range is -1.0.
+        COCO numbers are normally taken at a very low score_threshold (0.001) with up to 100 boxes per image, so that the
+        precision-recall curve reaches far to the right; this method uses the model's own score_threshold as it is -- lower it on
+        the model to compare with published tables."""
+        from .cocoeval import CocoAccumulator
+        from .data import MAP_MAX_GT
+        items, paths, bs = self._eval_items('evaluate_coco', data, img_folder_path, bs, channel_order)
+        acc = CocoAccumulator(self.class_names, None, area_ranges, max_dets)          # ValueError on bad ranges / max_dets
+        if views is not None:
+            tiling.check_views(views)
+            views = list(views)
+        if int(tile_candidates) < 1:
+            raise ValueError(f'evaluate_coco: tile_candidates must be >= 1, got {tile_candidates}')
+        if tiled:
+            if not 0.0 <= float(overlap) < 1.0:
+                raise ValueError(f'evaluate_coco: overlap must lie in [0, 1), got {overlap}')
+            if tile is not None and (np.ndim(tile) > 1 or np.size(tile) not in (1, 2) or np.min(tile) < 1):
+                raise ValueError(f'evaluate_coco: tile must be a positive int or (th, tw), got {tile!r}')
+        elif tile is not None:
+            raise ValueError('evaluate_coco: tile= needs tiled=True')
+        self._ensure_tuned()
+        eng = self.engine
+        iou, score = self._thresholds
+        A = len(acc.area_ranges)
+        for i0, part, raws, gt_dev, scale_dev, count_dev in self._eval_batches(items, paths, bs, channel_order):
+            n = len(part)
+            flat, outs, cand_count, match_out = eng.alloc_coco_outputs_flat(n, A, MAP_MAX_GT)
+            group_cap = None
+            if tiled:
+                group_cap = eng.predict_tiled_device(raws, tile, overlap, full_image, self._letterbox, self._pad_value, iou, score,
+                                                     tile_candidates, views, outputs=(flat, outs, cand_count))[3]
+            elif views is not None:
+                group_cap = eng.predict_tta_device(raws, views, self._letterbox, self._pad_value, iou, score, tile_candidates,
+                                                   outputs=(flat, outs, cand_count))[3]
+            else:
+                imgs, box_map = eng.preprocess_u8_batch(raws, letterbox=self._letterbox, pad_value=self._pad_value)
+                eng.forward_device(imgs)
+                eng.decode_nms_device(n, outs, iou, score, box_map=box_map if self._letterbox else None)
+            eng.coco_match_device(outs, scale_dev, gt_dev, count_dev, acc.iou_thresholds, acc.area_ranges, out=match_out)
+            scores, classes, valid, cand, rank, dm, di, gi = eng.coco_outputs_to_host(flat, n, A, MAP_MAX_GT)
+            if group_cap is not None:
+                self._check_candidates('evaluate_coco', i0, cand, group_cap)
+            acc.add(scores, classes, valid, rank, dm, di, [boxes[:, 4] for _, _, boxes in part], gi)
         return acc.result()
 
     # ---- reference models.py:95-98

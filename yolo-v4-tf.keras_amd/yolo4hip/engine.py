@@ -606,10 +606,13 @@ class Engine:
                          ext.ptr(b), ext.ptr(s), ext.ptr(c), ext.ptr(v), ext.ptr(k), ext.stream_ptr()))
         return outs, cand_count
 
-    def _rows_device(self, who, raw_imgs, rows_of, views, pad_value, iou_threshold, score_threshold, tile_candidates):
+    def _rows_device(self, who, raw_imgs, rows_of, views, pad_value, iou_threshold, score_threshold, tile_candidates,
+                     outputs=None):
         """The loop of `predict_tiled_device` and `predict_tta_device`: rows_of(h, w) -> the base rows (window, rect, map) of a
         photo.  views=None: the rows as they are, through y4_window_u8_ragged and y4_decode_gather; a view list: every row under
-        every view (tiling.view_rows, slot = its index there), through y4_view_u8_ragged and y4_decode_gather_views."""
+        every view (tiling.view_rows, slot = its index there), through y4_view_u8_ragged and y4_decode_gather_views.
+        outputs: None, or the (flat, outs, cand_count) of a block the caller allocated for len(raw_imgs) photos
+        (`alloc_coco_outputs_flat`) in place of `alloc_tiled_outputs_flat`'s."""
         torch = self.torch
         raw_imgs, pad_value = self._check_ragged(raw_imgs, pad_value, who)
         if int(tile_candidates) < 1:
@@ -644,7 +647,7 @@ class Engine:
         # a photo cannot yield more candidates than its rows have (box, class) pairs: no larger list is ever needed
         group_cap = int(min(int(tile_candidates), max_slots * self.num_boxes * self.num_classes))
         state = self.gather_begin(P, max_slots, group_cap)
-        flat, outs, cand_count = self.alloc_tiled_outputs_flat(P)
+        flat, outs, cand_count = self.alloc_tiled_outputs_flat(P) if outputs is None else outputs
         step = C.sizeof(Desc)
         with torch.cuda.device(self.device):
             canvas = torch.empty((min(R, self.max_batch), H, W, 3), dtype=torch.uint8, device=self.device)
@@ -668,7 +671,7 @@ class Engine:
         return res if with_indices else res[:4]
 
     def predict_tiled_device(self, raw_imgs, tile=None, overlap=0.2, full_image=True, letterbox=False, pad_value=128,
-                             iou_threshold=-1.0, score_threshold=-1.0, tile_candidates=1 << 18, views=None):
+                             iou_threshold=-1.0, score_threshold=-1.0, tile_candidates=1 << 18, views=None, outputs=None):
         """`predict_tiled` with the results left on the device: -> (flat, outs, cand_count, group_cap) in the form of
         `alloc_tiled_outputs_flat(len(raw_imgs))` -- outs are what `decode_nms_device` returns for that many images, boxes
         normalised to each photo, ready for `map_match_device`.  The caller checks cand_count <= group_cap.  Asynchronous."""
@@ -676,7 +679,7 @@ class Engine:
         tile_hw = None if tile is None else ((int(tile), int(tile)) if np.ndim(tile) == 0 else (int(tile[0]), int(tile[1])))
         return self._rows_device("predict_tiled", raw_imgs,
                                  lambda h, w: tiling.tile_rows(h, w, (H, W), tile_hw, overlap, full_image, letterbox),
-                                 views, pad_value, iou_threshold, score_threshold, tile_candidates)
+                                 views, pad_value, iou_threshold, score_threshold, tile_candidates, outputs)
 
     def predict_tiled(self, raw_imgs, tile=None, overlap=0.2, full_image=True, letterbox=False, pad_value=128,
                       iou_threshold=-1.0, score_threshold=-1.0, tile_candidates=1 << 18, with_indices=False, views=None):
@@ -698,13 +701,13 @@ class Engine:
         return self._rows_to_host("predict_tiled", res, len(raws), with_indices)
 
     def predict_tta_device(self, raw_imgs, views=tiling.DEFAULT_VIEWS, letterbox=False, pad_value=128, iou_threshold=-1.0, score_threshold=-1.0,
-                           tile_candidates=1 << 18):
+                           tile_candidates=1 << 18, outputs=None):
         """`predict_tta` with the results left on the device, in the form of `predict_tiled_device`: -> (flat, outs, cand_count,
         group_cap), boxes normalised to each photo, ready for `map_match_device`."""
         H, W = self.img_hw
         return self._rows_device("predict_tta", raw_imgs,
                                  lambda h, w: tiling.tile_rows(h, w, (H, W), None, 0.0, True, letterbox)[-1:],
-                                 views, pad_value, iou_threshold, score_threshold, tile_candidates)
+                                 views, pad_value, iou_threshold, score_threshold, tile_candidates, outputs)
 
     def predict_tta(self, raw_imgs, views=tiling.DEFAULT_VIEWS, letterbox=False, pad_value=128, iou_threshold=-1.0, score_threshold=-1.0,
                     tile_candidates=1 << 18, with_indices=False):
@@ -878,6 +881,71 @@ class Engine:
                                             ext.ptr(scale_dev), ext.ptr(gt_dev), ext.ptr(gt_count_dev), max_gt, arr, len(thr),
                                             ext.ptr(tp_mask), ext.ptr(best), ext.ptr(match), ext.ptr(used), ext.stream_ptr()))
         return (tp_mask, best, match, used) if debug else tp_mask
+
+    # ---------------------------------------------------------------- COCO matching
+    def _coco_fields(self, n, n_areas, max_gt, mask_dtype):
+        T = self.T
+        return [("float32", (n, T)), ("float32", (n, T)), ("int32", (n,)), ("int32", (n,)), ("int32", (n, T)),
+                (mask_dtype, (n, n_areas, T)), (mask_dtype, (n, n_areas, T)), (mask_dtype, (n, max_gt))]
+
+    def alloc_coco_outputs_flat(self, n, n_areas, max_gt):
+        """What `Yolov4.evaluate_coco` needs of a batch as views of ONE int32 device block -- scores, classes, valid, the
+        candidate counts of the tiled paths, and cls_rank, dt_match, dt_ignore, gt_ignore of `coco_match_device` -- so that they
+        reach the host in a single copy (`coco_outputs_to_host`); the boxes are a tensor of their own and stay on the device.
+        -> (flat int32 tensor, outs for `decode_nms_device` / `predict_tiled_device(outputs=)` (boxes, scores, classes, valid, no
+        kept indices -- with `nms_merge` a tensor outside the block), cand_count int32 view [n], (cls_rank [n,max_total],
+        dt_match [n,n_areas,max_total], dt_ignore, gt_ignore [n,max_gt]) int32 views)."""
+        flat, (scores, classes, valid, cand, rank, dm, di, gi) = self._alloc_block(self._coco_fields(n, n_areas, max_gt, "int32"))
+        boxes = self.torch.empty((n, self.T, 4), dtype=self.torch.float32, device=self.device)
+        kept = self.torch.empty((n, self.T), dtype=self.torch.int32, device=self.device) if self.nms_merge else None
+        return flat, (boxes, scores, classes, valid, kept), cand, (rank, dm, di, gi)
+
+    def coco_outputs_to_host(self, flat, n, n_areas, max_gt):
+        """The one copy of `alloc_coco_outputs_flat`'s block -> (scores float32 [n,T], classes float32 [n,T], valid int32 [n],
+        cand_count int32 [n], cls_rank int32 [n,T], dt_match uint32 [n,A,T], dt_ignore uint32 [n,A,T], gt_ignore uint32
+        [n,max_gt]) as numpy views of it."""
+        return tuple(_block_views(flat.cpu().numpy(), self._coco_fields(n, n_areas, max_gt, "uint32")))
+
+    def coco_match_device(self, outs, scale_dev, gt_dev, gt_count_dev, iou_thresholds, area_ranges, debug=False, out=None):
+        """y4_coco_match on the outputs of `decode_nms_device` / `predict_tiled_device` / `predict_tta_device` (outs = boxes,
+        scores, classes, valid, ...): the kept boxes of each image, scaled to raw-image pixels by scale_dev (float32 cuda [n,2]:
+        w, h), are matched against gt_dev (float32 cuda [n,max_gt,5]; gt_count_dev int32 [n]) by COCO's rule (csrc/coco_match.hip),
+        once per area range (1..4 rows [lo, hi]) and IoU threshold (1..16).  -> (cls_rank int32 [n,max_total], dt_match int32
+        [n,A,max_total] with bit t "matched at iou_thresholds[t]", dt_ignore likewise, gt_ignore int32 [n,max_gt] with bit a) as
+        cuda tensors -- `out`, the views of `alloc_coco_outputs_flat`, when given; with debug=True also match_row int32
+        [n,A,T,max_total].  Asynchronous."""
+        torch = self.torch
+        boxes, scores, classes, valid = outs[:4]
+        n, T = scores.shape
+        thr = [float(t) for t in iou_thresholds]
+        rng = np.asarray(area_ranges, dtype=np.float64)
+        if rng.ndim != 2 or rng.shape[1] != 2:
+            raise ValueError(f"area_ranges must be rows [lo, hi], got shape {rng.shape}")
+        A = len(rng)
+        if gt_dev.dim() != 3 or gt_dev.shape[0] != n or gt_dev.shape[2] != 5 or gt_dev.dtype != torch.float32 \
+                or not gt_dev.is_contiguous():
+            raise ValueError(f"gt_dev must be a contiguous float32 tensor [{n},max_gt,5], got {gt_dev.dtype} {tuple(gt_dev.shape)}")
+        if tuple(scale_dev.shape) != (n, 2) or scale_dev.dtype != torch.float32 or not scale_dev.is_contiguous():
+            raise ValueError(f"scale_dev must be a contiguous float32 tensor [{n},2], got {scale_dev.dtype} {tuple(scale_dev.shape)}")
+        if tuple(gt_count_dev.shape) != (n,) or gt_count_dev.dtype != torch.int32 or not gt_count_dev.is_contiguous():
+            raise ValueError(f"gt_count_dev must be a contiguous int32 tensor [{n}], got {gt_count_dev.dtype} {tuple(gt_count_dev.shape)}")
+        max_gt = gt_dev.shape[1]
+        shapes = ((n, T), (n, A, T), (n, A, T), (n, max_gt))
+        if out is None:
+            out = tuple(torch.empty(shape, dtype=torch.int32, device=self.device) for shape in shapes)
+        elif len(out) != 4 or any(tuple(o.shape) != shape or o.dtype != torch.int32 or not o.is_contiguous()
+                                  for o, shape in zip(out, shapes)):
+            raise ValueError(f"out must be contiguous int32 tensors of shapes {shapes}")
+        rank, dm, di, gi = out
+        rows = torch.empty((n, A, len(thr), T), dtype=torch.int32, device=self.device) if debug else None
+        thr_arr = (C.c_double * max(len(thr), 1))(*thr)
+        rng_arr = (C.c_double * max(rng.size, 1))(*rng.reshape(-1).tolist())
+        with torch.cuda.device(self.device):
+            ext.check(self.lib.y4_coco_match(ext.ptr(boxes), ext.ptr(scores), ext.ptr(classes), ext.ptr(valid), n, T,
+                                             ext.ptr(scale_dev), ext.ptr(gt_dev), ext.ptr(gt_count_dev), max_gt, rng_arr, A,
+                                             thr_arr, len(thr), ext.ptr(dm), ext.ptr(di), ext.ptr(rank), ext.ptr(gi),
+                                             ext.ptr(rows), ext.stream_ptr()))
+        return (rank, dm, di, gi, rows) if debug else (rank, dm, di, gi)
 
     def predict_device(self, imgs_dev, outs=None):
         """The whole hot path on device buffers: forward + decode + NMS (async on the current stream).  With `nms_merge` on:
