@@ -178,6 +178,35 @@ int y4_decode_nms_mapped(y4_handle h, int n, float iou_threshold, float score_th
  * returned before this call existed. */
 int y4_set_nms_rule(y4_handle h, int kind, float beta, int agnostic);
 int y4_get_nms_rule(y4_handle h, int* kind, float* beta, int* agnostic);
+/* Soft-NMS (Bodla et al. 2017): a kept box multiplies the scores of its neighbours by a factor below 1 instead of deleting them; the
+ * next box to keep is the maximum of the CURRENT scores.  method 0 (the default) is off: every entry point runs the NMS kernel it
+ * ran before this call existed, bit for bit.  With method 1 / 2 / 3 every entry point that reads y4_set_nms_rule (see there; the
+ * merged forms included) runs this rule instead, per candidate list (an image's, or a gathered group's), on the same keys and
+ * unclipped boxes, under the same pair rule (kind, beta, agnostic), max_total, max_per_class and the call's iou_threshold:
+ *   1. Participants P: the top_k largest keys of the list (score descending, then box index, then class), or all when the list
+ *      is shorter.  Candidates outside P take no part -- a defined pre-NMS top-k, not an error: no status bit.  top_k <= 4096.
+ *   2. Working scores w_j = s_j.
+ *   3. While fewer than max_total boxes are kept: among the j of P that are neither kept nor turned away and have w_j > min_score
+ *      (strict), take k with the largest key (w_j, then box index ascending, then class ascending); none: stop.
+ *   4. If k's class already has max_per_class kept boxes, k is turned away: not kept, decays nothing.
+ *   5. Otherwise k is kept with OUTPUT SCORE w_k, and for every other live j of k's class (of every class under agnostic 1), with
+ *      m = the measure of y4_set_nms_rule of (B_j, B_k) in float32 (for kind 1 the penalty applies to every pair),
+ *          method 1, gaussian:  w_j *= m > 0 ? expf(-(m * m) / sigma) : 1       (a NaN or negative measure decays nothing)
+ *          method 2, linear:    w_j *= m > iou_threshold ? 1 - m : 1            (strict)
+ *          method 3, hard:      w_j *= m > iou_threshold ? 0 : 1
+ *      one float32 rounding per kept neighbour, in pick order.
+ * Outputs keep their form: boxes through the box map and the clip, scores = w at the pick (non-increasing), classes, valid,
+ * kept_idx, zero / -1 padded; the list's counter is reset and the overflow status bit set as by the NMS kernel.  Method 3 with
+ * every list no longer than top_k returns the bits of method 0.  The same call gives the same bits (picks are by unique key; no
+ * floating-point atomics).  The merged entry points run the merge behind it unchanged -- members are decided on the original boxes
+ * and weighted with the original scores -- so only the boxes move.
+ * min_score < 0: the config's score_threshold (the convention of iou_threshold < 0); a run-time score threshold of a call does not
+ * change it.  Host-only state like y4_set_nms_rule: settable at any time, no effect on the workspace, not carried by
+ * y4_copy_schedule, not in a checkpoint.  Y4_EINVAL, with nothing changed: a method outside 0 .. 3; sigma not finite or <= 0
+ * (validated for every method); min_score NaN, infinite or >= 1; top_k outside 1 .. 4096; a null getter argument.  A call whose
+ * (top_k, max_total, num_classes) needs more than 160 KB of LDS fails with Y4_EINVAL at the launch.  Default (0, 0.5, -1, 4096). */
+int y4_set_nms_soft(y4_handle h, int method /* 0 off, 1 gaussian, 2 linear, 3 hard */, float sigma, float min_score, int top_k);
+int y4_get_nms_soft(y4_handle h, int* method, float* sigma, float* min_score, int* top_k);
 /* ---- Gathered decode + NMS: ONE NMS over the candidates of several batch rows (tiled inference: the rows are windows of one
  * photo, see y4_window_u8_ragged).  Row i belongs to group g = row_group_dev[i] (a photo), has slot t = row_slot_dev[i] in it
  * (0 <= t < max_slots, distinct among a group's rows) and the map m = row_map_dev[i] = {ax, bx, ay, by} from its canvas-normalised

@@ -199,6 +199,11 @@ struct y4_ctx {
     int nms_kind = 0;
     float nms_beta = 1.0f;
     int nms_agnostic = 0;
+    // y4_set_nms_soft: Soft-NMS instead of hard suppression in nms_over (soft_nms.hip); method 0 is off.  Host-only, as the rule
+    int soft_method = 0;
+    float soft_sigma = 0.5f;
+    float soft_min_score = -1.0f;    // < 0: the config's score_threshold
+    int soft_top_k = 4096;
     // is the head's output of this run written to HBM?  (an LDS pair in front of a head conv: also when that conv's input is retained)
     bool stores_x(const Chain& ch) const { return ch.store_x || (ch.lds_pair && retain_head_in && ops[ch.tail[0]].out_f32); }
 };
@@ -914,7 +919,10 @@ int nms_over(y4_handle h, const CandStore& c, int n, float iou_thr, const NmsOut
     k.status = c.status; k.div_c = c.div_c;
     k.box_map = box_map;
     k.kind = h->nms_kind; k.beta = h->nms_beta; k.agnostic = h->nms_agnostic;
-    return nms_launch(k, s);
+    if (h->soft_method == 0) return nms_launch(k, s);
+    // y4_set_nms_soft: the soft kernel over the same lists into the same outputs
+    const SoftNmsK sk{h->soft_method, h->soft_sigma, h->soft_min_score < 0.f ? cfg.score_threshold : h->soft_min_score, h->soft_top_k};
+    return soft_nms_launch(k, sk, s);
 }
 
 // ... of the workspace's lists, behind run_decode
@@ -1251,6 +1259,23 @@ int y4_get_nms_rule(y4_handle h, int* kind, float* beta, int* agnostic) {
     if (int r = check_handle(h)) return r;
     Y4_REQUIRE(kind && beta && agnostic, Y4_EINVAL, "y4_get_nms_rule: null argument");
     *kind = h->nms_kind; *beta = h->nms_beta; *agnostic = h->nms_agnostic;
+    return Y4_OK;
+}
+
+int y4_set_nms_soft(y4_handle h, int method, float sigma, float min_score, int top_k) {
+    if (int r = check_handle(h)) return r;
+    Y4_REQUIRE(method >= 0 && method <= 3, Y4_EINVAL, "y4_set_nms_soft: method %d (0: off, 1: gaussian, 2: linear, 3: hard)", method);
+    Y4_REQUIRE(std::isfinite(sigma) && sigma > 0.f, Y4_EINVAL, "y4_set_nms_soft: sigma %g must be finite and > 0", (double)sigma);
+    Y4_REQUIRE(std::isfinite(min_score) && min_score < 1.f, Y4_EINVAL, "y4_set_nms_soft: min_score %g must be finite and < 1", (double)min_score);
+    Y4_REQUIRE(top_k >= 1 && top_k <= 4096, Y4_EINVAL, "y4_set_nms_soft: top_k %d outside 1 .. 4096", top_k);
+    h->soft_method = method; h->soft_sigma = sigma; h->soft_min_score = min_score; h->soft_top_k = top_k;
+    return Y4_OK;
+}
+
+int y4_get_nms_soft(y4_handle h, int* method, float* sigma, float* min_score, int* top_k) {
+    if (int r = check_handle(h)) return r;
+    Y4_REQUIRE(method && sigma && min_score && top_k, Y4_EINVAL, "y4_get_nms_soft: null argument");
+    *method = h->soft_method; *sigma = h->soft_sigma; *min_score = h->soft_min_score; *top_k = h->soft_top_k;
     return Y4_OK;
 }
 

@@ -48,7 +48,7 @@ class Yolov4(object):
     def __init__(self, weight_path=None, class_name_path='coco_classes.txt', config=yolo_config, *,
                  dtype='f32', max_batch=32, synth_seed=0, device=None, device_preprocess=True, tune=None, share_schedule=None,
                  letterbox=False, pad_value=128, box_loss='giou', nms_kind='iou', nms_beta=0.6, nms_agnostic=False,
-                 nms_merge=False):
+                 nms_merge=False, nms_soft=None, nms_sigma=0.5, nms_soft_min_score=None, nms_top_k=4096):
         # (reference models.py:23 also asserts img_size[0] == img_size[1], 'not support yet': rectangles are supported here)
         assert config['img_size'][0] % config['strides'][-1] == 0, 'must be a multiple of last stride'
         assert config['img_size'][1] % config['strides'][-1] == 0, 'must be a multiple of last stride'
@@ -87,6 +87,14 @@ class Yolov4(object):
         # export_prediction, evaluate_map, fit(val_map=True), predict_tiled and predict_img_tiled, with and without letterbox, before
         # and after load_model and fit; it is no part of a checkpoint or a schedule.
         self.nms_merge = Engine._merge_flag(nms_merge)          # (raises ValueError)
+        # nms_soft='gaussian' | 'linear' | 'hard' (None: off): Soft-NMS (Engine.set_nms_soft) -- a kept box decays the scores of its
+        # neighbours under that pair rule instead of deleting them, with nms_sigma, the floor nms_soft_min_score (None: the config's
+        # score_threshold, whatever a call's run-time thresholds are) and the nms_top_k best candidates of a list taking part.  Like
+        # the rule it is state of both engines and in force for everything nms_kind is in force for, over tiles and views too; it
+        # is no part of a checkpoint or a schedule.
+        Engine._soft_mode(nms_soft, nms_sigma, nms_soft_min_score, nms_top_k)      # (raises ValueError)
+        self.nms_soft, self.nms_sigma, self.nms_top_k = nms_soft, float(nms_sigma), int(nms_top_k)
+        self.nms_soft_min_score = None if nms_soft_min_score is None else float(nms_soft_min_score)
         # letterbox=True: predict_img / predict / export_prediction resize each image with its aspect ratio kept, centred on a
         # canvas of uint8 level `pad_value` (Darknet's letterbox_image geometry; the resize is still cv2's uint8 arithmetic and the
         # pad a uint8 level, 128 = 0.502, where Darknet pads 0.5), and the boxes are mapped back to each raw image on the device.
@@ -116,7 +124,8 @@ class Yolov4(object):
         self.engine = Engine(self.num_classes, self.config, max_batch=self._max_batch, dtype=self._dtype,
                              device=self._device, alias_workspace=True, box_loss=self.box_loss,
                              nms_kind=self.nms_kind, nms_beta=self.nms_beta, nms_agnostic=self.nms_agnostic,
-                             nms_merge=self.nms_merge)
+                             nms_merge=self.nms_merge, nms_soft=self.nms_soft, nms_sigma=self.nms_sigma,
+                             nms_soft_min_score=self.nms_soft_min_score, nms_top_k=self.nms_top_k)
         self.yolo_model = _KerasLikeModel(self._tuned_first(self.engine.forward_heads), 'yolo_model')
         print(f"nms iou: {self.config['iou_threshold']} score: {self.config['score_threshold']}")
         self._thresholds = (-1.0, -1.0)  # what inference_model runs with (-1: the config's); load_model changes them
@@ -371,7 +380,8 @@ class Yolov4(object):
             eng = Engine(self.num_classes, self.config, max_batch=self._max_batch, dtype=self._dtype,
                          device=self._device, alias_workspace=True, retain_head_inputs=level, box_loss=self.box_loss,
                          nms_kind=self.nms_kind, nms_beta=self.nms_beta, nms_agnostic=self.nms_agnostic,
-                             nms_merge=self.nms_merge)
+                             nms_merge=self.nms_merge, nms_soft=self.nms_soft, nms_sigma=self.nms_sigma,
+                             nms_soft_min_score=self.nms_soft_min_score, nms_top_k=self.nms_top_k)
             setattr(self, name, eng)
         eng.load_weight_blob(self._flat)
         self.engine.copy_schedule_to(eng)

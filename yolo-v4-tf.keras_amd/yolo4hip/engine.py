@@ -68,19 +68,22 @@ def _block_views(flat, fields):
 class Engine:
     def __init__(self, num_classes, config=None, max_batch=32, dtype="f32", device=None, alias_workspace=False,
                  retain_head_inputs=False, *, max_per_class=100, max_total=100, box_loss="giou",
-                 nms_kind="iou", nms_beta=0.6, nms_agnostic=False, nms_merge=False):
+                 nms_kind="iou", nms_beta=0.6, nms_agnostic=False, nms_merge=False,
+                 nms_soft=None, nms_sigma=0.5, nms_soft_min_score=None, nms_top_k=4096):
         self._build(num_classes, config, max_batch, dtype, device, alias_workspace, retain_head_inputs, None,
                     max_per_class=max_per_class, max_total=max_total, box_loss=box_loss,
-                    nms_kind=nms_kind, nms_beta=nms_beta, nms_agnostic=nms_agnostic, nms_merge=nms_merge)
+                    nms_kind=nms_kind, nms_beta=nms_beta, nms_agnostic=nms_agnostic, nms_merge=nms_merge,
+                    nms_soft=nms_soft, nms_sigma=nms_sigma, nms_soft_min_score=nms_soft_min_score, nms_top_k=nms_top_k)
 
     def _build(self, num_classes, config, max_batch, dtype, device, alias_workspace, retain_head_inputs, parent, *,
                max_per_class=100, max_total=100, box_loss="giou", nms_kind="iou", nms_beta=0.6, nms_agnostic=False,
-               nms_merge=False):
+               nms_merge=False, nms_soft=None, nms_sigma=0.5, nms_soft_min_score=None, nms_top_k=4096):
         """What `__init__` and `sibling` share: the handle, its workspaces and every attribute.  `parent` is None for an engine
         with weights of its own, or the engine whose packed weights and schedule this one takes over."""
         box_kind = self._box_kind(box_loss)           # (an unknown name is refused before anything is loaded or created)
         nms_rule = self._nms_rule(nms_kind, nms_beta, nms_agnostic)      # (likewise)
         self.nms_merge = self._merge_flag(nms_merge)                     # (likewise); a sibling takes its parent's
+        soft_mode = self._soft_mode(nms_soft, nms_sigma, nms_soft_min_score, nms_top_k)      # (likewise)
         import torch
         self.torch = torch
         self.lib = ext.load()
@@ -105,6 +108,8 @@ class Engine:
         self.box_loss = self.BOX_LOSSES[box_kind]
         # nms_kind / nms_beta / nms_agnostic: the pair rule of the NMS stage (`set_nms_rule`); a sibling takes its parent's
         self._apply_nms_rule(nms_rule)
+        # nms_soft / nms_sigma / nms_soft_min_score / nms_top_k: Soft-NMS instead of hard suppression (`set_nms_soft`); likewise
+        self._apply_soft_mode(soft_mode)
         flops, nbox, hcs, wfl = C.c_int64(), C.c_int32(), C.c_int32(), C.c_int64()
         ext.check(self.lib.y4_model_info(self.handle, C.byref(flops), C.byref(nbox), C.byref(hcs), C.byref(wfl)))
         self.flops_per_image, self.num_boxes = flops.value, nbox.value
@@ -154,7 +159,9 @@ class Engine:
         e = Engine.__new__(Engine)
         e._build(self.num_classes, self.config, self.max_batch, self.dtype, self.device, self.alias_workspace, self.retain_level, self,
                  max_per_class=self.cfg.max_per_class, max_total=self.cfg.max_total, box_loss=self.box_loss,
-                 nms_kind=self.nms_kind, nms_beta=self.nms_beta, nms_agnostic=self.nms_agnostic, nms_merge=self.nms_merge)
+                 nms_kind=self.nms_kind, nms_beta=self.nms_beta, nms_agnostic=self.nms_agnostic, nms_merge=self.nms_merge,
+                 nms_soft=self.nms_soft, nms_sigma=self.nms_sigma, nms_soft_min_score=self.nms_soft_min_score,
+                 nms_top_k=self.nms_top_k)
         return e
 
     BOX_LOSSES = ("giou", "ciou")          # the kinds of y4_set_box_loss, by number
@@ -205,6 +212,53 @@ class Engine:
         self.nms_kind, self.nms_beta, self.nms_agnostic = self.NMS_KINDS[rule[0]], rule[1], bool(rule[2])
         for e in getattr(self, "_stream_siblings", []):
             e.set_nms_rule(kind, beta, agnostic)
+
+    SOFT_METHODS = (None, "gaussian", "linear", "hard")      # the methods of y4_set_nms_soft, by number
+    SOFT_TOP_K_MAX = 4096
+
+    @classmethod
+    def _soft_mode(cls, method, sigma, min_score, top_k):
+        """-> (method number, sigma, min_score or None, top_k), or ValueError.  Every value is validated for every method."""
+        if method is not None and not isinstance(method, str) or method not in cls.SOFT_METHODS:
+            raise ValueError(f"nms_soft must be one of {cls.SOFT_METHODS}, got {method!r}")
+        try:
+            sg = float(sigma)
+        except (TypeError, ValueError):
+            raise ValueError(f"nms_sigma must be a finite number > 0, got {sigma!r}") from None
+        if not (np.isfinite(sg) and sg > 0.0):
+            raise ValueError(f"nms_sigma must be a finite number > 0, got {sigma!r}")
+        ms = None
+        if min_score is not None:
+            try:
+                ms = float(min_score)
+            except (TypeError, ValueError):
+                raise ValueError(f"nms_soft_min_score must be None or a number in [0, 1), got {min_score!r}") from None
+            if not (np.isfinite(ms) and 0.0 <= ms < 1.0):
+                raise ValueError(f"nms_soft_min_score must be None or a number in [0, 1), got {min_score!r}")
+        if isinstance(top_k, (bool, np.bool_)) or not isinstance(top_k, (int, np.integer)) or not 1 <= int(top_k) <= cls.SOFT_TOP_K_MAX:
+            raise ValueError(f"nms_top_k must be an integer in 1 .. {cls.SOFT_TOP_K_MAX}, got {top_k!r}")
+        return cls.SOFT_METHODS.index(method), sg, ms, int(top_k)
+
+    def _apply_soft_mode(self, mode, force=False):
+        method, sigma, min_score, top_k = mode
+        if force or mode != (0, 0.5, None, self.SOFT_TOP_K_MAX):     # (that is the handle's own mode: nothing to set)
+            ext.check(self.lib.y4_set_nms_soft(self.handle, method, sigma, -1.0 if min_score is None else min_score, top_k))
+        self.nms_soft, self.nms_sigma, self.nms_soft_min_score, self.nms_top_k = self.SOFT_METHODS[method], sigma, min_score, top_k
+
+    def set_nms_soft(self, method, sigma=0.5, min_score=None, top_k=4096):
+        """Soft-NMS for every later predict / decode_nms / nms_gathered / predict_tiled / predict_tta call of this engine
+        (y4_set_nms_soft; host state of the handle, settable at any time).  method None: off, the hard kernel as before.
+        'gaussian': a kept box multiplies the score of every live neighbour of its class (of any class under an agnostic rule) by
+        exp(-m^2 / sigma), m the measure of `set_nms_rule`; 'linear': by 1 - m where m > iou_threshold; 'hard': by 0 there -- the
+        hard rule in this kernel, equal to method None bit for bit while no list is longer than top_k.  The next box kept is the one
+        with the best CURRENT score, output scores are the decayed ones, a box whose score falls to `min_score` or below is gone
+        (None: the config's score_threshold; a run-time score threshold of a call does not change it), and only the `top_k` best
+        candidates of a list take part (at most 4096).  Every value is validated for every method.  With `nms_merge` on, the
+        merge runs behind it unchanged: only the boxes move.  The stream siblings this engine already has follow; siblings made
+        later inherit it."""
+        self._apply_soft_mode(self._soft_mode(method, sigma, min_score, top_k), force=True)
+        for e in getattr(self, "_stream_siblings", []):
+            e.set_nms_soft(method, sigma, min_score, top_k)
 
     @staticmethod
     def _merge_flag(on):
