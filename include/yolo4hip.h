@@ -207,6 +207,39 @@ int y4_get_nms_rule(y4_handle h, int* kind, float* beta, int* agnostic);
  * (top_k, max_total, num_classes) needs more than 160 KB of LDS fails with Y4_EINVAL at the launch.  Default (0, 0.5, -1, 4096). */
 int y4_set_nms_soft(y4_handle h, int method /* 0 off, 1 gaussian, 2 linear, 3 hard */, float sigma, float min_score, int top_k);
 int y4_get_nms_soft(y4_handle h, int* method, float* sigma, float* min_score, int* top_k);
+/* Matrix-NMS (Wang et al., SOLOv2, 2020): score decay like Soft-NMS, but every decayed score is a closed-form function of the pair
+ * measures and the ORIGINAL score order -- no pick sequence.  method 0 (the default) is off: every entry point runs what it ran
+ * before this call existed, bit for bit.  With method 1 / 2 every entry point that reads y4_set_nms_rule (the merged and gathered
+ * forms included) runs this rule instead, per candidate list (an image's, or a gathered group's), on the same keys and unclipped
+ * boxes, under the same pair rule (kind, beta, agnostic), max_total and max_per_class:
+ *   1. Participants P: the top_k largest keys of the list, or all when the list is shorter (the select of y4_set_nms_soft: a
+ *      defined pre-NMS top-k, no status bit).  top_k <= 4096.
+ *   2. Order: by key, largest first (score descending, then box index ascending, then class ascending); i < j: i comes earlier.
+ *      i and j interact iff they have the same class (always under agnostic 1).
+ *   3. Pair measure: m_ij = the measure of y4_set_nms_rule of (B_i, B_j) in float32 (for kind 1 the penalty applies to every pair);
+ *      only its positive part counts, m+ = m > 0 ? m : 0, so a NaN or negative measure decays nothing.
+ *   4. Compensation: c_i = the maximum of m+_ki over the interacting k < i; 0 without such a k.
+ *   5. Decay: d_j = the minimum of t_ij over the interacting i < j; 1 without such an i.
+ *          method 1, gaussian:  t_ij = expf((c_i * c_i - m+_ij * m+_ij) / sigma)
+ *          method 2, linear:    t_ij = (1 - m+_ij) / (1 - c_i) where c_i < 1; a term with c_i >= 1 is left out
+ *      every product, difference, quotient and expf rounds once, in float32.
+ *   6. Output score w_j = s_j * d_j, one rounding.  The call's iou_threshold plays no part in the decay (the merged entry points
+ *      still decide with it which candidates a kept box absorbs).
+ *   7. Result: the candidates with w_j > min_score (strict) are walked by key (w_j, then box index ascending, then class ascending),
+ *      largest first; one whose class already holds max_per_class boxes is skipped (it has decayed the others all the same: decay
+ *      is one-shot); the walk stops at max_total boxes.
+ * Outputs keep their form: boxes through the box map and the clip, scores = w (non-increasing), classes, valid, kept_idx, zero / -1
+ * padded; the list's counter is reset and the overflow status bit set as by the NMS kernel.  The same call gives the same bits
+ * whatever order the list was written in (no floating-point atomics).  On a class of two candidates gaussian equals method 1 of
+ * y4_set_nms_soft bit for bit (c = 0, and 0 * 0 - x is -x exactly).
+ * min_score < 0: the config's score_threshold; a run-time score threshold of a call does not change it.  Host-only state like
+ * y4_set_nms_soft: settable at any time, not carried by y4_copy_schedule, not in a checkpoint.  The two decay modes exclude each
+ * other: Y4_EINVAL for method != 0 here while y4_set_nms_soft's method is != 0, and for y4_set_nms_soft(method != 0) while this
+ * method is != 0.  Y4_EINVAL, with nothing changed, also for: a method outside 0 .. 2; sigma not finite or <= 0 (validated for every
+ * method); min_score NaN, infinite or >= 1; top_k outside 1 .. 4096; a null getter argument.  A call whose (max_total, num_classes)
+ * needs more than 160 KB of LDS fails with Y4_EINVAL at the launch.  Default (0, 0.5, -1, 4096). */
+int y4_set_nms_matrix(y4_handle h, int method /* 0 off, 1 gaussian, 2 linear */, float sigma, float min_score, int top_k);
+int y4_get_nms_matrix(y4_handle h, int* method, float* sigma, float* min_score, int* top_k);
 /* ---- Gathered decode + NMS: ONE NMS over the candidates of several batch rows (tiled inference: the rows are windows of one
  * photo, see y4_window_u8_ragged).  Row i belongs to group g = row_group_dev[i] (a photo), has slot t = row_slot_dev[i] in it
  * (0 <= t < max_slots, distinct among a group's rows) and the map m = row_map_dev[i] = {ax, bx, ay, by} from its canvas-normalised

@@ -166,6 +166,15 @@ struct SoftNmsK {
 };
 int soft_nms_launch(const NmsK& k, const SoftNmsK& s, hipStream_t stream);
 
+// matrix_nms.hip: Matrix-NMS over the same lists, with the same outputs, counter reset and status bit (y4_set_nms_matrix)
+struct MatrixNmsK {
+    int method;                      // 1 gaussian, 2 linear (0, off, never gets here: nms_over calls nms_launch or soft_nms_launch)
+    float sigma;                     // gaussian: t = expf((c * c - m * m) / sigma)
+    float min_score;                 // a candidate is a result only if its decayed score is > min_score (resolved: >= 0)
+    int top_k;                       // participants: the top_k largest keys of the list, 1 .. SORT_CAP
+};
+int matrix_nms_launch(const NmsK& k, const MatrixNmsK& s, hipStream_t stream);
+
 // tiled.hip: the decode stage's per-row candidate lists -> one list per group
 struct GatherK {
     const float* dboxes;             // [n, nbox, 4] what the decode stage wrote (canvas-normalised)

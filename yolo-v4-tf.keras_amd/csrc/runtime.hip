@@ -204,6 +204,11 @@ struct y4_ctx {
     float soft_sigma = 0.5f;
     float soft_min_score = -1.0f;    // < 0: the config's score_threshold
     int soft_top_k = 4096;
+    // y4_set_nms_matrix: Matrix-NMS in nms_over (matrix_nms.hip); method 0 is off.  Host-only; excludes soft_method != 0
+    int matrix_method = 0;
+    float matrix_sigma = 0.5f;
+    float matrix_min_score = -1.0f;  // < 0: the config's score_threshold
+    int matrix_top_k = 4096;
     // is the head's output of this run written to HBM?  (an LDS pair in front of a head conv: also when that conv's input is retained)
     bool stores_x(const Chain& ch) const { return ch.store_x || (ch.lds_pair && retain_head_in && ops[ch.tail[0]].out_f32); }
 };
@@ -919,6 +924,11 @@ int nms_over(y4_handle h, const CandStore& c, int n, float iou_thr, const NmsOut
     k.status = c.status; k.div_c = c.div_c;
     k.box_map = box_map;
     k.kind = h->nms_kind; k.beta = h->nms_beta; k.agnostic = h->nms_agnostic;
+    if (h->matrix_method != 0) {
+        // y4_set_nms_matrix: the matrix kernel over the same lists into the same outputs
+        const MatrixNmsK mk{h->matrix_method, h->matrix_sigma, h->matrix_min_score < 0.f ? cfg.score_threshold : h->matrix_min_score, h->matrix_top_k};
+        return matrix_nms_launch(k, mk, s);
+    }
     if (h->soft_method == 0) return nms_launch(k, s);
     // y4_set_nms_soft: the soft kernel over the same lists into the same outputs
     const SoftNmsK sk{h->soft_method, h->soft_sigma, h->soft_min_score < 0.f ? cfg.score_threshold : h->soft_min_score, h->soft_top_k};
@@ -1268,6 +1278,7 @@ int y4_set_nms_soft(y4_handle h, int method, float sigma, float min_score, int t
     Y4_REQUIRE(std::isfinite(sigma) && sigma > 0.f, Y4_EINVAL, "y4_set_nms_soft: sigma %g must be finite and > 0", (double)sigma);
     Y4_REQUIRE(std::isfinite(min_score) && min_score < 1.f, Y4_EINVAL, "y4_set_nms_soft: min_score %g must be finite and < 1", (double)min_score);
     Y4_REQUIRE(top_k >= 1 && top_k <= 4096, Y4_EINVAL, "y4_set_nms_soft: top_k %d outside 1 .. 4096", top_k);
+    Y4_REQUIRE(method == 0 || h->matrix_method == 0, Y4_EINVAL, "y4_set_nms_soft: method %d while Matrix-NMS is on (y4_set_nms_matrix)", method);
     h->soft_method = method; h->soft_sigma = sigma; h->soft_min_score = min_score; h->soft_top_k = top_k;
     return Y4_OK;
 }
@@ -1276,6 +1287,24 @@ int y4_get_nms_soft(y4_handle h, int* method, float* sigma, float* min_score, in
     if (int r = check_handle(h)) return r;
     Y4_REQUIRE(method && sigma && min_score && top_k, Y4_EINVAL, "y4_get_nms_soft: null argument");
     *method = h->soft_method; *sigma = h->soft_sigma; *min_score = h->soft_min_score; *top_k = h->soft_top_k;
+    return Y4_OK;
+}
+
+int y4_set_nms_matrix(y4_handle h, int method, float sigma, float min_score, int top_k) {
+    if (int r = check_handle(h)) return r;
+    Y4_REQUIRE(method >= 0 && method <= 2, Y4_EINVAL, "y4_set_nms_matrix: method %d (0: off, 1: gaussian, 2: linear)", method);
+    Y4_REQUIRE(std::isfinite(sigma) && sigma > 0.f, Y4_EINVAL, "y4_set_nms_matrix: sigma %g must be finite and > 0", (double)sigma);
+    Y4_REQUIRE(std::isfinite(min_score) && min_score < 1.f, Y4_EINVAL, "y4_set_nms_matrix: min_score %g must be finite and < 1", (double)min_score);
+    Y4_REQUIRE(top_k >= 1 && top_k <= 4096, Y4_EINVAL, "y4_set_nms_matrix: top_k %d outside 1 .. 4096", top_k);
+    Y4_REQUIRE(method == 0 || h->soft_method == 0, Y4_EINVAL, "y4_set_nms_matrix: method %d while Soft-NMS is on (y4_set_nms_soft)", method);
+    h->matrix_method = method; h->matrix_sigma = sigma; h->matrix_min_score = min_score; h->matrix_top_k = top_k;
+    return Y4_OK;
+}
+
+int y4_get_nms_matrix(y4_handle h, int* method, float* sigma, float* min_score, int* top_k) {
+    if (int r = check_handle(h)) return r;
+    Y4_REQUIRE(method && sigma && min_score && top_k, Y4_EINVAL, "y4_get_nms_matrix: null argument");
+    *method = h->matrix_method; *sigma = h->matrix_sigma; *min_score = h->matrix_min_score; *top_k = h->matrix_top_k;
     return Y4_OK;
 }
 

@@ -48,7 +48,7 @@ class Yolov4(object):
     def __init__(self, weight_path=None, class_name_path='coco_classes.txt', config=yolo_config, *,
                  dtype='f32', max_batch=32, synth_seed=0, device=None, device_preprocess=True, tune=None, share_schedule=None,
                  letterbox=False, pad_value=128, box_loss='giou', nms_kind='iou', nms_beta=0.6, nms_agnostic=False,
-                 nms_merge=False, nms_soft=None, nms_sigma=0.5, nms_soft_min_score=None, nms_top_k=4096):
+                 nms_merge=False, nms_soft=None, nms_sigma=0.5, nms_soft_min_score=None, nms_top_k=4096, nms_matrix=None):
         # (reference models.py:23 also asserts img_size[0] == img_size[1], 'not support yet': rectangles are supported here)
         assert config['img_size'][0] % config['strides'][-1] == 0, 'must be a multiple of last stride'
         assert config['img_size'][1] % config['strides'][-1] == 0, 'must be a multiple of last stride'
@@ -95,6 +95,12 @@ class Yolov4(object):
         Engine._soft_mode(nms_soft, nms_sigma, nms_soft_min_score, nms_top_k)      # (raises ValueError)
         self.nms_soft, self.nms_sigma, self.nms_top_k = nms_soft, float(nms_sigma), int(nms_top_k)
         self.nms_soft_min_score = None if nms_soft_min_score is None else float(nms_soft_min_score)
+        # nms_matrix='gaussian' | 'linear' (None: off): Matrix-NMS (Engine.set_nms_matrix) -- one-shot score decay by the earlier
+        # candidates of a class, no pick sequence; nms_sigma, nms_soft_min_score and nms_top_k parameterise whichever of nms_soft /
+        # nms_matrix is set, and the two exclude each other.  In force wherever nms_soft would be.
+        if Engine._matrix_mode(nms_matrix, nms_sigma, nms_soft_min_score, nms_top_k)[0] and nms_soft is not None:      # (raises ValueError)
+            raise ValueError(f"nms_soft={nms_soft!r} and nms_matrix={nms_matrix!r} exclude each other")
+        self.nms_matrix = nms_matrix
         # letterbox=True: predict_img / predict / export_prediction resize each image with its aspect ratio kept, centred on a
         # canvas of uint8 level `pad_value` (Darknet's letterbox_image geometry; the resize is still cv2's uint8 arithmetic and the
         # pad a uint8 level, 128 = 0.502, where Darknet pads 0.5), and the boxes are mapped back to each raw image on the device.
@@ -125,7 +131,7 @@ class Yolov4(object):
                              device=self._device, alias_workspace=True, box_loss=self.box_loss,
                              nms_kind=self.nms_kind, nms_beta=self.nms_beta, nms_agnostic=self.nms_agnostic,
                              nms_merge=self.nms_merge, nms_soft=self.nms_soft, nms_sigma=self.nms_sigma,
-                             nms_soft_min_score=self.nms_soft_min_score, nms_top_k=self.nms_top_k)
+                             nms_soft_min_score=self.nms_soft_min_score, nms_top_k=self.nms_top_k, nms_matrix=self.nms_matrix)
         self.yolo_model = _KerasLikeModel(self._tuned_first(self.engine.forward_heads), 'yolo_model')
         print(f"nms iou: {self.config['iou_threshold']} score: {self.config['score_threshold']}")
         self._thresholds = (-1.0, -1.0)  # what inference_model runs with (-1: the config's); load_model changes them
@@ -381,7 +387,7 @@ class Yolov4(object):
                          device=self._device, alias_workspace=True, retain_head_inputs=level, box_loss=self.box_loss,
                          nms_kind=self.nms_kind, nms_beta=self.nms_beta, nms_agnostic=self.nms_agnostic,
                              nms_merge=self.nms_merge, nms_soft=self.nms_soft, nms_sigma=self.nms_sigma,
-                             nms_soft_min_score=self.nms_soft_min_score, nms_top_k=self.nms_top_k)
+                             nms_soft_min_score=self.nms_soft_min_score, nms_top_k=self.nms_top_k, nms_matrix=self.nms_matrix)
             setattr(self, name, eng)
         eng.load_weight_blob(self._flat)
         self.engine.copy_schedule_to(eng)

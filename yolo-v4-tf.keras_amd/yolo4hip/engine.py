@@ -69,21 +69,28 @@ class Engine:
     def __init__(self, num_classes, config=None, max_batch=32, dtype="f32", device=None, alias_workspace=False,
                  retain_head_inputs=False, *, max_per_class=100, max_total=100, box_loss="giou",
                  nms_kind="iou", nms_beta=0.6, nms_agnostic=False, nms_merge=False,
-                 nms_soft=None, nms_sigma=0.5, nms_soft_min_score=None, nms_top_k=4096):
+                 nms_soft=None, nms_sigma=0.5, nms_soft_min_score=None, nms_top_k=4096, nms_matrix=None):
         self._build(num_classes, config, max_batch, dtype, device, alias_workspace, retain_head_inputs, None,
                     max_per_class=max_per_class, max_total=max_total, box_loss=box_loss,
                     nms_kind=nms_kind, nms_beta=nms_beta, nms_agnostic=nms_agnostic, nms_merge=nms_merge,
-                    nms_soft=nms_soft, nms_sigma=nms_sigma, nms_soft_min_score=nms_soft_min_score, nms_top_k=nms_top_k)
+                    nms_soft=nms_soft, nms_sigma=nms_sigma, nms_soft_min_score=nms_soft_min_score, nms_top_k=nms_top_k,
+                    nms_matrix=nms_matrix)
 
     def _build(self, num_classes, config, max_batch, dtype, device, alias_workspace, retain_head_inputs, parent, *,
                max_per_class=100, max_total=100, box_loss="giou", nms_kind="iou", nms_beta=0.6, nms_agnostic=False,
-               nms_merge=False, nms_soft=None, nms_sigma=0.5, nms_soft_min_score=None, nms_top_k=4096):
+               nms_merge=False, nms_soft=None, nms_sigma=0.5, nms_soft_min_score=None, nms_top_k=4096, nms_matrix=None,
+               matrix_params=None):
         """What `__init__` and `sibling` share: the handle, its workspaces and every attribute.  `parent` is None for an engine
         with weights of its own, or the engine whose packed weights and schedule this one takes over."""
         box_kind = self._box_kind(box_loss)           # (an unknown name is refused before anything is loaded or created)
         nms_rule = self._nms_rule(nms_kind, nms_beta, nms_agnostic)      # (likewise)
         self.nms_merge = self._merge_flag(nms_merge)                     # (likewise); a sibling takes its parent's
         soft_mode = self._soft_mode(nms_soft, nms_sigma, nms_soft_min_score, nms_top_k)      # (likewise)
+        # nms_sigma / nms_soft_min_score / nms_top_k parameterise whichever of nms_soft / nms_matrix is set (a sibling hands over
+        # its parent's Matrix-NMS values in `matrix_params`)
+        matrix_mode = self._matrix_mode(nms_matrix, *(matrix_params or (nms_sigma, nms_soft_min_score, nms_top_k)))
+        if soft_mode[0] and matrix_mode[0]:
+            raise ValueError(f"nms_soft={nms_soft!r} and nms_matrix={nms_matrix!r} exclude each other")
         import torch
         self.torch = torch
         self.lib = ext.load()
@@ -110,6 +117,8 @@ class Engine:
         self._apply_nms_rule(nms_rule)
         # nms_soft / nms_sigma / nms_soft_min_score / nms_top_k: Soft-NMS instead of hard suppression (`set_nms_soft`); likewise
         self._apply_soft_mode(soft_mode)
+        # nms_matrix: Matrix-NMS (`set_nms_matrix`); likewise
+        self._apply_matrix_mode(matrix_mode)
         flops, nbox, hcs, wfl = C.c_int64(), C.c_int32(), C.c_int32(), C.c_int64()
         ext.check(self.lib.y4_model_info(self.handle, C.byref(flops), C.byref(nbox), C.byref(hcs), C.byref(wfl)))
         self.flops_per_image, self.num_boxes = flops.value, nbox.value
@@ -161,7 +170,8 @@ class Engine:
                  max_per_class=self.cfg.max_per_class, max_total=self.cfg.max_total, box_loss=self.box_loss,
                  nms_kind=self.nms_kind, nms_beta=self.nms_beta, nms_agnostic=self.nms_agnostic, nms_merge=self.nms_merge,
                  nms_soft=self.nms_soft, nms_sigma=self.nms_sigma, nms_soft_min_score=self.nms_soft_min_score,
-                 nms_top_k=self.nms_top_k)
+                 nms_top_k=self.nms_top_k, nms_matrix=self.nms_matrix,
+                 matrix_params=(self.nms_matrix_sigma, self.nms_matrix_min_score, self.nms_matrix_top_k))
         return e
 
     BOX_LOSSES = ("giou", "ciou")          # the kinds of y4_set_box_loss, by number
@@ -256,9 +266,46 @@ class Engine:
         candidates of a list take part (at most 4096).  Every value is validated for every method.  With `nms_merge` on, the
         merge runs behind it unchanged: only the boxes move.  The stream siblings this engine already has follow; siblings made
         later inherit it."""
-        self._apply_soft_mode(self._soft_mode(method, sigma, min_score, top_k), force=True)
+        mode = self._soft_mode(method, sigma, min_score, top_k)
+        if mode[0] and getattr(self, "nms_matrix", None) is not None:
+            raise ValueError(f"nms_soft={method!r} while nms_matrix={self.nms_matrix!r}: the two decay modes exclude each other")
+        self._apply_soft_mode(mode, force=True)
         for e in getattr(self, "_stream_siblings", []):
             e.set_nms_soft(method, sigma, min_score, top_k)
+
+    MATRIX_METHODS = (None, "gaussian", "linear")      # the methods of y4_set_nms_matrix, by number
+
+    @classmethod
+    def _matrix_mode(cls, method, sigma, min_score, top_k):
+        """-> (method number, sigma, min_score or None, top_k), or ValueError.  Every value is validated for every method."""
+        if method is not None and not isinstance(method, str) or method not in cls.MATRIX_METHODS:
+            raise ValueError(f"nms_matrix must be one of {cls.MATRIX_METHODS}, got {method!r}")
+        _, sg, ms, k = cls._soft_mode(None, sigma, min_score, top_k)      # (the same ranges)
+        return cls.MATRIX_METHODS.index(method), sg, ms, k
+
+    def _apply_matrix_mode(self, mode, force=False):
+        method, sigma, min_score, top_k = mode
+        if force or mode != (0, 0.5, None, self.SOFT_TOP_K_MAX):     # (that is the handle's own mode: nothing to set)
+            ext.check(self.lib.y4_set_nms_matrix(self.handle, method, sigma, -1.0 if min_score is None else min_score, top_k))
+        self.nms_matrix, self.nms_matrix_sigma = self.MATRIX_METHODS[method], sigma
+        self.nms_matrix_min_score, self.nms_matrix_top_k = min_score, top_k
+
+    def set_nms_matrix(self, method, sigma=0.5, min_score=None, top_k=4096):
+        """Matrix-NMS (Wang et al. 2020) for every later predict / decode_nms / nms_gathered / predict_tiled / predict_tta call of
+        this engine (y4_set_nms_matrix; host state of the handle, settable at any time).  method None: off.  'gaussian' / 'linear':
+        the `top_k` best candidates of a list (at most 4096), ordered by score, decay each other in one shot -- candidate j's score
+        is multiplied by the minimum over the earlier candidates i of its class (of any class under an agnostic rule) of
+        exp((c_i^2 - m_ij^2) / sigma), or of (1 - m_ij) / (1 - c_i), m the positive part of the measure of `set_nms_rule` and c_i
+        the largest m of i against anything earlier -- and the results are the decayed scores above `min_score` (None: the
+        config's score_threshold) in their new order, under max_per_class and max_total.  iou_threshold plays no part in the
+        decay.  It excludes Soft-NMS: ValueError when `nms_soft` is on (and `set_nms_soft` refuses while this is on).  The
+        stream siblings this engine already has follow; siblings made later inherit it."""
+        mode = self._matrix_mode(method, sigma, min_score, top_k)
+        if mode[0] and self.nms_soft is not None:
+            raise ValueError(f"nms_matrix={method!r} while nms_soft={self.nms_soft!r}: the two decay modes exclude each other")
+        self._apply_matrix_mode(mode, force=True)
+        for e in getattr(self, "_stream_siblings", []):
+            e.set_nms_matrix(method, sigma, min_score, top_k)
 
     @staticmethod
     def _merge_flag(on):

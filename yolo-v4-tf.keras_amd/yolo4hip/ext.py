@@ -106,6 +106,8 @@ SYMBOLS = {
     "y4_get_nms_rule": (_I, [_VP, C.POINTER(C.c_int), C.POINTER(C.c_float), C.POINTER(C.c_int)]),
     "y4_set_nms_soft": (_I, [_VP, _I, C.c_float, C.c_float, _I]),
     "y4_get_nms_soft": (_I, [_VP, C.POINTER(C.c_int), C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_int)]),
+    "y4_set_nms_matrix": (_I, [_VP, _I, C.c_float, C.c_float, _I]),
+    "y4_get_nms_matrix": (_I, [_VP, C.POINTER(C.c_int), C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_int)]),
     "y4_set_retain_head_inputs": (_I, [_VP, _I]),
     "y4_loss_grad": (_I, [_VP, _I, _VP, _VP, _VP, _I, _F, _VP, _VP, _VP, _VP, _VP]),
     "y4_head_grad_scratch_floats": (_I, [_VP, _I, C.POINTER(C.c_size_t)]),
