@@ -2,7 +2,9 @@
 """Loss fixtures written by the REFERENCE'S OWN PYTHON (runs only where /root/reference exists; nothing of it is copied).
 
   python tests/golden/make_loss_fixtures.py          writes tests/golden/loss_<case>.npz for every case of tests/loss_cases.py
+                                                     (CASES, and LABEL_CASES: other max_boxes and class counts)
   python tests/golden/make_loss_fixtures.py --seeds  prints, per case, the first seed that passes check_case
+  (case names after the options restrict either to those cases)
 
 The reference's `loss.py` and `utils.py` are imported UNMODIFIED.  `tensorflow` is a module of eager torch-CPU float32
 functions made here (the ~20 names loss.py touches; tests/golden/tf_standin.py is not involved), `cv2` an empty placeholder.
@@ -87,10 +89,37 @@ def import_reference():
 def run_case(name, mods, seed=None):
     """-> (arrays to store, problems: a list of failed conditions)."""
     import loss_cases as LC
-    import loss_oracle as LO
+    if name in LC.LABEL_CASES:
+        return run_label_case(name, mods, seed)
     if seed is not None:
         LC.CASES[name] = dict(LC.CASES[name], seed=seed)
     case = LC.make_case(name)
+    return run_reference(case, mods)
+
+
+def run_label_case(name, mods, seed=None):
+    """A case of loss_cases.LABEL_CASES (max_boxes and class counts beside 100 and {3, 80}): its conditions are check_case's."""
+    import loss_cases as LC
+    case = LC.make_label_case(name, seed)
+    try:
+        LC.check_case(name, case)
+    except AssertionError as err:
+        return None, [str(err) or repr(err)]
+    out, problems = run_reference(case, mods, structure=False)
+    # the host assignment the heads were made from is the reference's
+    from yolo4hip.data import dense_from_records
+    for s, y in enumerate(dense_from_records(case["records"], case["hw"], case["ncls"])):
+        ref = np.zeros(y.size, dtype=np.float32)
+        ref[out[f"label{s}_idx"]] = out[f"label{s}_val"]
+        if not np.array_equal(ref, y.reshape(-1)):
+            problems.append(f"scale {s}: the host records are not the reference's labels")
+    return out, problems
+
+
+def run_reference(case, mods, structure=True):
+    """The reference on a case's inputs -> (arrays to store, problems); structure: the conditions of the cases of 100 rows."""
+    import loss_cases as LC
+    import loss_oracle as LO
     hw, ncls, n = case["hw"], case["ncls"], case["n"]
     boxes, heads = case["boxes"], case["heads"]
     y_true, xywh = mods["utils"].preprocess_true_boxes(boxes.copy(), hw, LC.ANCHORS, ncls)
@@ -129,9 +158,9 @@ def run_case(name, mods, seed=None):
         problems.append("no image without boxes")
     if not valid.all(axis=1).any():
         problems.append("no image with exactly max_boxes boxes")
-    if not any(np.any(~v[:-1] & (np.cumsum(v[::-1])[::-1][1:] > 0)) and v[0] for v in valid):
+    if structure and not any(np.any(~v[:-1] & (np.cumsum(v[::-1])[::-1][1:] > 0)) and v[0] for v in valid):
         problems.append("no degenerate row between valid rows")
-    if not any(((y[..., 4] == 1) & (y[..., 5:].sum(axis=-1) > 1)).any() for y in y_true):
+    if structure and not any(((y[..., 4] == 1) & (y[..., 5:].sum(axis=-1) > 1)).any() for y in y_true):
         problems.append("no collision of two classes on one cell and anchor")
     out = dict(sha=np.array(case["sha"]), true_xywh=xywh, ref_img=ref_img, ref_batch=ref_batch, ref_total=ref_total,
                d_ref=d_ref, ignore_count=np.array(ignore, dtype=np.int64))
@@ -144,15 +173,16 @@ def run_case(name, mods, seed=None):
 def main():
     mods = import_reference()
     import loss_cases as LC
+    names = [a for a in sys.argv[1:] if not a.startswith("--")] or list(LC.CASES) + list(LC.LABEL_CASES)
     if "--seeds" in sys.argv:
-        for name in LC.CASES:
+        for name in names:
             for seed in range(1, 400):
                 _, problems = run_case(name, mods, seed)
                 if not problems:
                     print(name, "seed", seed)
                     break
         return
-    for name in LC.CASES:
+    for name in names:
         out, problems = run_case(name, mods)
         assert not problems, (name, problems)
         path = os.path.join(HERE, f"loss_{name}.npz")

@@ -34,12 +34,12 @@ def _iou_parts(b1, b2):
     return inter / (union + EPS), union, np.prod(np.maximum(hi1, hi2) - np.minimum(lo1, lo2), axis=-1)
 
 
-def decode(head, anchors_s, stride, ncls):
+def decode(head, anchors_s, stride, ncls, dtype=np.float64):
     n, gh, gw, _ = head.shape
-    t = np.asarray(head, dtype=np.float64).reshape(n, gh, gw, 3, 5 + ncls)
-    grid = np.stack(np.meshgrid(np.arange(gw), np.arange(gh)), axis=-1)[None, :, :, None, :].astype(np.float64)
-    xy = (_sigmoid(t[..., 0:2]) + grid) * stride
-    wh = np.exp(t[..., 2:4]) * np.asarray(anchors_s, dtype=np.float64)
+    t = np.asarray(head, dtype=dtype).reshape(n, gh, gw, 3, 5 + ncls)
+    grid = np.stack(np.meshgrid(np.arange(gw), np.arange(gh)), axis=-1)[None, :, :, None, :].astype(dtype)
+    xy = (_sigmoid(t[..., 0:2]) + grid) * dtype(stride)
+    wh = np.exp(t[..., 2:4]) * np.asarray(anchors_s, dtype=dtype)
     return t, np.concatenate([xy, wh], axis=-1)
 
 

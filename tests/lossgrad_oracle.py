@@ -17,19 +17,19 @@ import numpy as np
 import loss_oracle as LO
 
 
-def scale_grad(head, label, true_xywh, anchors_s, stride, ncls, thresh, input_area, img_weight):
-    """One scale -> float64 [n, gh, gw, 3 (5 + C)]."""
-    t, pred = LO.decode(head, anchors_s, stride, ncls)
-    label = np.asarray(label, dtype=np.float64)
-    w_img = np.asarray(img_weight, dtype=np.float64)[:, None, None, None]
+def scale_grad(head, label, true_xywh, anchors_s, stride, ncls, thresh, input_area, img_weight, dtype=np.float64):
+    """One scale -> `dtype` [n, gh, gw, 3 (5 + C)] (float32: every operation in single precision, which measures what it costs)."""
+    t, pred = LO.decode(head, anchors_s, stride, ncls, dtype)
+    label = np.asarray(label, dtype=dtype)
+    w_img = np.asarray(img_weight, dtype=dtype)[:, None, None, None]
     r = label[..., 4]
     g = np.zeros_like(t)
     # class
     g[..., 5:] = r[..., None] * (LO._sigmoid(t[..., 5:]) - label[..., 5:])
     # confidence
-    rows = np.asarray(true_xywh, dtype=np.float64)[:, None, None, None, :, :]
+    rows = np.asarray(true_xywh, dtype=dtype)[:, None, None, None, :, :]
     max_iou = LO._iou_parts(pred[..., None, :], rows)[0].max(axis=-1)
-    m = r + (1.0 - r) * (max_iou < thresh)
+    m = r + (1.0 - r) * (max_iou < dtype(thresh))
     q = LO._sigmoid(t[..., 4])
     d = r - q
     g[..., 4] = LO.WEIGHTS[1] * m * (-2.0 * d * q * (1.0 - q) * LO._bce(t[..., 4], r) + d * d * (q - r))
@@ -63,13 +63,13 @@ def scale_grad(head, label, true_xywh, anchors_s, stride, ncls, thresh, input_ar
     return g.reshape(head.shape)
 
 
-def loss_grad(heads, labels, true_xywh, anchors, strides, ncls, thresh, input_hw, img_weight=None):
-    """-> three float64 arrays [n, gh, gw, 3 (5 + C)]: d(sum_i img_weight[i] * loss_i) / d head (img_weight: 1 / n by default)."""
+def loss_grad(heads, labels, true_xywh, anchors, strides, ncls, thresh, input_hw, img_weight=None, dtype=np.float64):
+    """-> three `dtype` arrays [n, gh, gw, 3 (5 + C)]: d(sum_i img_weight[i] * loss_i) / d head (img_weight: 1 / n by default)."""
     anchors = np.asarray(anchors, dtype=np.float64).reshape(3, 3, 2)
     n = heads[0].shape[0]
     w = np.full(n, 1.0 / n) if img_weight is None else np.asarray(img_weight, dtype=np.float64)
     area = float(input_hw[0]) * float(input_hw[1])
-    return [scale_grad(heads[s], labels[s], true_xywh, anchors[s], strides[s], ncls, thresh, area, w) for s in range(3)]
+    return [scale_grad(heads[s], labels[s], true_xywh, anchors[s], strides[s], ncls, thresh, area, w, dtype) for s in range(3)]
 
 
 def head_wgrad(g, x, dtype=np.float64):
