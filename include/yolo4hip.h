@@ -810,6 +810,44 @@ int y4_coco_match(const float* boxes_dev,  /* [n, max_total, 4], x1 y1 x2 y2 nor
                   uint32_t* gt_ignore_dev,  /* [n, max_gt]: bit a = ignored under range a */
                   int32_t* match_row_dev,   /* [n, n_areas, n_thresholds, max_total] or NULL: the matched row, -1 */
                   void* stream);
+/* ---- Data-set anchors on the device: IoU k-means (Lloyd steps) and a mutate-and-select evolution over the (w, h) of a data set's
+ * label boxes at the network input (yolo4hip/anchors.py drives these; DESIGN.md "Dataset anchors").  No handle, no scratch.
+ *   - pair measure iou64(box, anchor): the IoU of the two rectangles centred on each other exactly as y4_loss_assign computes it
+ *     (one shared function): half sides (double)(w * 0.5f), box area (double)(w * h), a float32 product, the anchor widened to
+ *     float64; intersection, union and quotient in float64, no contraction.  Best anchor: the first arg-max over j = 0 .. k - 1.
+ *     The index a box gets here is therefore the anchor y4_loss_assign gives it under the same nine anchors;
+ *   - fitness of a set: F = sum over the boxes of llrint(iou64(best) * 2^30), an int64; average IoU = F / n / 2^30;
+ *   - Lloyd step: per anchor j over the boxes whose best anchor is j, cnt_j, SW_j = sum llrint((double)w * 2^16), SH_j likewise;
+ *     next_j = ((float)((double)SW_j / (double)cnt_j / 65536.0), the same for h); an anchor with cnt_j == 0 keeps its value;
+ *   - evolution, generation g: candidate p = fmaxf(best * mult[g][p], 1.0f) elementwise in float32; the winner is the first arg-max
+ *     of the P fitness values and replaces best / F_best only if its fitness is strictly larger than F_best (accepted[g] = its
+ *     index, else -1).  All G generations are enqueued without a host synchronise: per generation one fitness launch that builds
+ *     its candidates from best_dev itself and one select launch.
+ * Every sum is an integer sum (order-free): per-wave and per-workgroup partials and one 64-bit integer atomic per accumulator per
+ * workgroup.  The same call gives the same bits.  Sides are expected in (0, 16384]: with n <= 2^22 every sum stays below 2^52.
+ * Y4_EINVAL before any launch: n outside [1, 2^22], k outside [1, 16], P outside [1, 256], G outside [1, 4096], a null pointer
+ * (assign_dev may be NULL), wh_dev or an int64 array not 8-byte aligned. */
+int y4_anchor_step(const float* wh_dev,      /* [n, 2] (w, h) */
+                   int n,
+                   const float* anchors_dev, /* [k, 2] */
+                   int k,
+                   float* next_dev,          /* [k, 2]: the anchors after this step (not anchors_dev itself) */
+                   int64_t* stats_dev,       /* [1 + 3 k]: F, cnt[k], SW[k], SH[k] of anchors_dev */
+                   uint8_t* assign_dev,      /* [n] or NULL: the best anchor of every box */
+                   void* stream);
+int y4_anchor_fitness(const float* wh_dev, int n,
+                      const float* sets_dev, /* [P, k, 2] */
+                      int P, int k,
+                      int64_t* f_dev,        /* [P] */
+                      void* stream);
+int y4_anchor_evolve(const float* wh_dev, int n,
+                     float* best_dev,        /* [k, 2] in / out */
+                     int64_t* fbest_dev,     /* [1] in / out: the fitness of best_dev */
+                     const float* mult_dev,  /* [G, P, k, 2] */
+                     int G, int P, int k,
+                     int64_t* fhist_dev,     /* [G, P]: every candidate's fitness */
+                     int32_t* accepted_dev,  /* [G]: the winning index, or -1 */
+                     void* stream);
 /* SPP (custom_layers.py:130-134): x = buf[..., 3c:4c] -> buf[..., 0:c]=maxpool13, [c:2c]=maxpool9,
  * [2c:3c]=maxpool5 (stride 1, 'same'), buf is [n,side,side,4c] */
 int y4_spp(int dtype, void* buf_dev, int n, int side, int c, void* stream);

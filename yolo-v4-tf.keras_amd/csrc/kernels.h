@@ -91,6 +91,13 @@ int coco_match_launch(const float* boxes, const float* scores, const float* clas
                       int n_areas, const double* iou_thresholds, int n_thresholds, uint32_t* dt_match, uint32_t* dt_ignore,
                       int32_t* cls_rank, uint32_t* gt_ignore, int32_t* match_row, hipStream_t stream);
 
+// anchors.hip: the data-set anchor search -- one Lloyd step, the fitness of P anchor sets, G generations of mutate-and-select
+int anchor_step_launch(const float* wh, int n, const float* anchors, int k, float* next, int64_t* stats, uint8_t* assign,
+                       hipStream_t stream);
+int anchor_fitness_launch(const float* wh, int n, const float* sets, int P, int k, int64_t* f, hipStream_t stream);
+int anchor_evolve_launch(const float* wh, int n, float* best, int64_t* fbest, const float* mult, int G, int P, int k,
+                         int64_t* fhist, int32_t* accepted, hipStream_t stream);
+
 // stem_down.hip: convs 0+1 fused (16-bit dtypes), c0 stays in LDS
 bool stem_down_supported(int dtype, int S);
 int stem_down_launch(int dtype, const void* imgs, int img_u8, int n, int S, const void* stem_wk, const float* s0_scale,

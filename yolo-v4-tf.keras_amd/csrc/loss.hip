@@ -5,6 +5,7 @@
 // shuffle tree, the four waves of a workgroup are added in wave order, and a second kernel adds a scale's workgroup partials in
 // strip order.  The tree depends on the image's geometry only, so image i's nine sums are the same bits whatever the batch
 // size and wherever the image sits in the batch.
+#include "anchor_iou.h"
 #include "kernels.h"
 #include "loss_common.h"
 
@@ -44,18 +45,8 @@ __global__ __launch_bounds__(LOSS_THREADS) void loss_assign_kernel(LossAssignK p
     if (tid < nvalid) {
         const int j = s_vidx[tid];
         const float bw = s_w[j], bh = s_h[j];
-        const double hbw = (double)(bw * 0.5f), hbh = (double)(bh * 0.5f);
-        const double area_b = (double)(bw * bh);                          // a float32 product in the reference
-        double best = 0.0;
-        int best_a = 0;
-        for (int a = 0; a < 9; ++a) {
-            const double aw = (double)p.anchors[2 * a], ah = (double)p.anchors[2 * a + 1];
-            const double lo_x = fmax(-hbw, -(aw / 2.0)), hi_x = fmin(hbw, aw / 2.0);
-            const double lo_y = fmax(-hbh, -(ah / 2.0)), hi_y = fmin(hbh, ah / 2.0);
-            const double inter = fmax(hi_x - lo_x, 0.0) * fmax(hi_y - lo_y, 0.0);
-            const double iou = inter / (area_b + aw * ah - inter);
-            if (a == 0 || iou > best) { best = iou; best_a = a; }         // first arg-max on ties
-        }
+        double best;
+        const int best_a = best_anchor(bw, bh, p.anchors, 9, &best);      // anchor_iou.h: the centred IoU, first arg-max on ties
         const int s = best_a / 3, a = best_a % 3;
         const float xn = (float)((double)cx / (double)p.img_w), yn = (float)((double)cy / (double)p.img_h);
         const double fc = floor((double)xn * (double)p.gw[s]), fr = floor((double)yn * (double)p.gh[s]);

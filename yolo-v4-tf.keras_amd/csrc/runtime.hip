@@ -2348,6 +2348,20 @@ int y4_coco_match(const float* boxes_dev, const float* scores_dev, const float* 
                              gt_ignore_dev, match_row_dev, (hipStream_t)stream);
 }
 
+int y4_anchor_step(const float* wh_dev, int n, const float* anchors_dev, int k, float* next_dev, int64_t* stats_dev,
+                   uint8_t* assign_dev, void* stream) {
+    return anchor_step_launch(wh_dev, n, anchors_dev, k, next_dev, stats_dev, assign_dev, (hipStream_t)stream);
+}
+
+int y4_anchor_fitness(const float* wh_dev, int n, const float* sets_dev, int P, int k, int64_t* f_dev, void* stream) {
+    return anchor_fitness_launch(wh_dev, n, sets_dev, P, k, f_dev, (hipStream_t)stream);
+}
+
+int y4_anchor_evolve(const float* wh_dev, int n, float* best_dev, int64_t* fbest_dev, const float* mult_dev, int G, int P, int k,
+                     int64_t* fhist_dev, int32_t* accepted_dev, void* stream) {
+    return anchor_evolve_launch(wh_dev, n, best_dev, fbest_dev, mult_dev, G, P, k, fhist_dev, accepted_dev, (hipStream_t)stream);
+}
+
 int y4_preprocess_u8(const uint8_t* img_dev, int h, int w, float* out_dev, int out_h, int out_w, void* stream) {
     return preprocess_u8_launch(img_dev, h, w, out_dev, out_h, out_w, (hipStream_t)stream);
 }

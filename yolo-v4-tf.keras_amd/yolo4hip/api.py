@@ -20,6 +20,8 @@ path); `fit(..., trainable='heads')` fine-tunes the three detection convs on a f
 training every layer (the reference's `fit`) is out of scope and raises.  `predict_tiled` / `predict_img_tiled` (not in the reference)
 cut a photo much larger than the network input into overlapping windows and run one NMS per photo over all of them on the device;
 `predict_tta` / `predict_img_tta` (not in the reference either) run a photo under flipped and scaled views, again under one NMS.
+`rebase_anchors(trained_with)` (not in the reference) keeps the boxes of loaded weights when `config['anchors']` are not the ones
+they were trained with (yolo4hip/anchors.py fits anchors to a data set).
 """
 import json
 import os
@@ -222,6 +224,16 @@ class Yolov4(object):
         self.inference_model = _KerasLikeModel(
             self._tuned_first(lambda x: self.engine.predict(x, iou_threshold=0.413, score_threshold=0.3)), 'inference_model')
         self._thresholds = (0.413, 0.3)
+
+    def rebase_anchors(self, trained_with):
+        """For weights that were trained under the anchors `trained_with` (18 numbers) while this model decodes with
+        `self.anchors` (e.g. pretrained heads under anchors from `yolo4hip.anchors.fit_anchors`): adds log(old_w / new_w) and
+        log(old_h / new_h), computed in float64 and added in float32, to the tw / th biases of convs 93 / 101 / 109 in the host
+        weight stream and re-loads it.  Afterwards exp(t') * new == exp(t) * old up to rounding: the model predicts the boxes it
+        predicted under the old anchors.  Explicit, never automatic -- `load_model` and the constructor leave weights as they
+        are -- and not idempotent: call it once per loaded weight set."""
+        from .anchors import rebase_flat
+        self._set_weights(rebase_flat(self._flat, self.plan, self.num_classes, trained_with, self.anchors))
 
     # ---- reference models.py:100-107.  Training all 110 convs is out of scope (SURVEY.md section 2); what is here is the
     # fine-tuning of the three detection convs on a frozen backbone and neck: in Keras terms every layer trainable = False

@@ -163,6 +163,9 @@ SYMBOLS = {
     "y4_map_match": (_I, [_VP, _VP, _VP, _VP, _I, _I, _VP, _VP, _VP, _I, C.POINTER(C.c_double), _I, _VP, _VP, _VP, _VP, _VP]),
     "y4_coco_match": (_I, [_VP, _VP, _VP, _VP, _I, _I, _VP, _VP, _VP, _I, C.POINTER(C.c_double), _I, C.POINTER(C.c_double), _I, _VP, _VP,
                            _VP, _VP, _VP, _VP]),
+    "y4_anchor_step": (_I, [_VP, _I, _VP, _I, _VP, _VP, _VP, _VP]),
+    "y4_anchor_fitness": (_I, [_VP, _I, _VP, _I, _I, _VP, _VP]),
+    "y4_anchor_evolve": (_I, [_VP, _I, _VP, _VP, _VP, _I, _I, _I, _VP, _VP, _VP]),
     "y4_spp": (_I, [_I, _VP, _I, _I, _I, _VP]),
     "y4_spp_hw": (_I, [_I, _VP, _I, _I, _I, _I, _VP]),
 }
