@@ -490,6 +490,21 @@ def test_contract_round_trip_refusals_and_siblings():
     e.close()
 
 
+def test_sibling_takes_both_decay_modes_also_one_that_is_off_with_parameters():
+    from yolo4hip import ext
+    _, eng = DC._engine(96, 2, 1)
+    ext.check(eng.lib.y4_set_nms_matrix(eng.handle, 0, 0.25, 0.125, 77))
+    eng.set_nms_matrix(None, 0.25, 0.125, 77)
+    eng.set_nms_soft("linear", 0.75, 0.375, 512)
+    sib = eng.sibling()
+    assert _get(sib, "soft") == (2, 0.75, 0.375, 512) and _get(sib) == (0, 0.25, 0.125, 77)
+    for name, value in (("nms_soft", "linear"), ("nms_sigma", 0.75), ("nms_soft_min_score", 0.375), ("nms_top_k", 512), ("nms_matrix", None),
+                        ("nms_matrix_sigma", 0.25), ("nms_matrix_min_score", 0.125), ("nms_matrix_top_k", 77)):
+        assert getattr(eng, name) == value and getattr(sib, name) == value, name
+    sib.close()
+    eng.close()
+
+
 def test_off_restores_the_bits_and_stream_siblings_follow():
     size, ncls, mode, seed = MC.RANDOM_CASES[0]
     heads, _, _ = MC.random_case(size, ncls, seed)

@@ -104,12 +104,11 @@ int box_merge_launch(const MergeK& k, hipStream_t stream) {
     Y4_REQUIRE(k.cap < MERGE_MAX_CAP, Y4_EINVAL, "merge-NMS: a list capacity of %u keys is not below the 2^25 the int64 sums allow", k.cap);
     Y4_REQUIRE(k.N >= 1 && k.max_total >= 1 && (int64_t)k.N * k.max_total < (1ll << 31), Y4_EINVAL, "merge-NMS: %d lists of %d slots",
                k.N, k.max_total);
-    Y4_REQUIRE((k.kind == 0 || k.kind == 1) && (k.agnostic == 0 || k.agnostic == 1) && k.beta > 0.f, Y4_EINVAL,
-               "merge-NMS: rule (kind %d, beta %g, agnostic %d)", k.kind, (double)k.beta, k.agnostic);
+    if (int r = nms_rule_check("merge-NMS", k.kind, k.beta, k.agnostic)) return r;
     const dim3 grid((uint32_t)k.N * (uint32_t)k.max_total), block(MERGE_THREADS);
-    // the measure as nms_launch chooses it: kind 0 does not read beta, kind 1 with beta == 1 is its own measure
-    if (k.kind == 0) hipLaunchKernelGGL(box_merge_kernel<NMS_IOU>, grid, block, 0, stream, k);
-    else if (k.beta == 1.0f) hipLaunchKernelGGL(box_merge_kernel<NMS_DIOU1>, grid, block, 0, stream, k);
+    const int measure = nms_measure_index(k.kind, k.beta);      // (as the NMS launchers choose it)
+    if (measure == NMS_IOU) hipLaunchKernelGGL(box_merge_kernel<NMS_IOU>, grid, block, 0, stream, k);
+    else if (measure == NMS_DIOU1) hipLaunchKernelGGL(box_merge_kernel<NMS_DIOU1>, grid, block, 0, stream, k);
     else hipLaunchKernelGGL(box_merge_kernel<NMS_DIOU>, grid, block, 0, stream, k);
     Y4_CHECK_HIP(hipGetLastError());
     return Y4_OK;

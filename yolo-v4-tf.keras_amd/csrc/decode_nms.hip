@@ -251,8 +251,8 @@ __global__ __launch_bounds__(256) void decode_cell_kernel(const DecodeK p) {
 }
 
 // ------------------------------------------------------------------------------------------- NMS
-// the constants, the LDS layout, the selectors, the sorts, nms_load_boxes and nms_write_outputs: nms_phases.h (soft_nms.hip runs the
-// same copies)
+// the constants, the LDS layout, the list prologue, the selectors, the sorts, nms_load_boxes and nms_write_outputs: nms_phases.h
+// (soft_nms.hip and matrix_nms.hip run the same copies)
 
 // ---- greedy pass, ROUND-PARALLEL on every wave: the usual case (all of the image's candidates in one chunk of at most
 // NMS_THREADS; round 4).  One candidate per thread; in a round the lowest undecided candidate of every class (an LDS atomicMin per
@@ -399,6 +399,7 @@ __global__ __launch_bounds__(NMS_THREADS) void nms_kernel(const NmsK p) {
     extern __shared__ __attribute__((aligned(16))) char nsm[];
     const NmsLds L(nsm, p.max_total, p.C);
     const int n = blockIdx.x, tid = threadIdx.x;
+    // nms_list_begin (nms_phases.h), statement for statement: this kernel keeps its own copy, the call changes its listing
     uint32_t cnt = p.counts[(size_t)n * COUNT_STRIDE];
     if (cnt > p.cap) {
         if (tid == 0) atomicOr(p.status, 1u);
@@ -409,8 +410,6 @@ __global__ __launch_bounds__(NMS_THREADS) void nms_kernel(const NmsK p) {
     if (tid == 0) L.w->kept = 0;
     unsigned long long cutoff = ~0ull;           // exclusive upper bound of keys still to visit
     __syncthreads();
-    // every thread has read the image's candidate count: leave the counter at zero for the next step's decode (which therefore needs
-    // no memset launch in front of it; decode_launch clears only when a decode was NOT followed by its NMS)
     if (tid == 0) p.counts[(size_t)n * COUNT_STRIDE] = 0;
 
     while (true) {
@@ -442,6 +441,8 @@ __global__ __launch_bounds__(NMS_THREADS) void nms_kernel(const NmsK p) {
     nms_write_outputs(p, L, n, tid);
 }
 
+struct NmsKernel { template <int KIND, bool AGN, int> static constexpr auto kernel = nms_kernel<KIND, AGN>; };      // (no methods)
+
 size_t nms_lds_bytes(int max_total, int classes) { return nms_lds_layout(max_total, classes).bytes; }
 
 int decode_launch(const DecodeK& k, hipStream_t stream, int clear_images) {
@@ -467,17 +468,8 @@ int decode_launch(const DecodeK& k, hipStream_t stream, int clear_images) {
 int nms_launch(const NmsK& k, hipStream_t stream) {
     const size_t lds = nms_lds_bytes(k.max_total, k.C);
     Y4_REQUIRE(lds <= 160 * 1024 && k.max_total <= 1024, Y4_EINVAL, "nms: max_total %d needs %zu bytes of LDS", k.max_total, lds);
-    Y4_REQUIRE((k.kind == 0 || k.kind == 1) && (k.agnostic == 0 || k.agnostic == 1) && k.beta > 0.f, Y4_EINVAL,
-               "nms: rule (kind %d, beta %g, agnostic %d)", k.kind, (double)k.beta, k.agnostic);
-    // [measure][agnostic]; kind 0 does not read beta, kind 1 with beta == 1 is its own measure
-    using Launch = int (*)(int, dim3, dim3, size_t, hipStream_t, const NmsK&);
-    static const Launch table[3][2] = {
-        {launch_lds<nms_kernel<NMS_IOU, false>, NmsK>, launch_lds<nms_kernel<NMS_IOU, true>, NmsK>},
-        {launch_lds<nms_kernel<NMS_DIOU1, false>, NmsK>, launch_lds<nms_kernel<NMS_DIOU1, true>, NmsK>},
-        {launch_lds<nms_kernel<NMS_DIOU, false>, NmsK>, launch_lds<nms_kernel<NMS_DIOU, true>, NmsK>},
-    };
-    const int measure = k.kind == 0 ? NMS_IOU : (k.beta == 1.0f ? NMS_DIOU1 : NMS_DIOU);
-    return table[measure][k.agnostic](160 * 1024, dim3(k.N), dim3(NMS_THREADS), lds, stream, k);
+    if (int r = nms_rule_check("nms", k.kind, k.beta, k.agnostic)) return r;
+    return nms_dispatch<NmsKernel>(std::make_index_sequence<6>(), 1, lds, stream, k);
 }
 
 }  // namespace y4

@@ -163,24 +163,17 @@ int decode_launch(const DecodeK& k, hipStream_t stream, int clear_images);
 int l2_flush_launch(const void* p, size_t bytes, void* sink, hipStream_t stream);
 int nms_launch(const NmsK& k, hipStream_t stream);
 
-// soft_nms.hip: Soft-NMS over the same lists, with the same outputs, counter reset and status bit as nms_kernel (y4_set_nms_soft).
-// The mode travels beside NmsK, which nms_kernel keeps as it is.
-struct SoftNmsK {
-    int method;                      // 1 gaussian, 2 linear, 3 hard (0, off, never gets here: nms_over calls nms_launch)
-    float sigma;                     // gaussian: w *= expf(-(m * m) / sigma)
-    float min_score;                 // a candidate takes part while its working score is > min_score (resolved: >= 0)
+// soft_nms.hip (y4_set_nms_soft) and matrix_nms.hip (y4_set_nms_matrix): score decay over the same lists, with the same outputs,
+// counter reset and status bit as nms_kernel (nms_list_begin).  The mode travels beside NmsK, which nms_kernel keeps as it is.
+struct DecayK {
+    int method;                      // soft: 1 gaussian, 2 linear, 3 hard; matrix: 1 gaussian, 2 linear (0, off, never gets here: nms_over)
+    float sigma;                     // gaussian.  soft: w *= expf(-(m * m) / sigma); matrix: t = expf((c * c - m * m) / sigma)
+    float min_score;                 // resolved, >= 0.  soft: a candidate takes part while its working score is > min_score;
+                                     // matrix: a candidate is a result only if its decayed score is > min_score
     int top_k;                       // participants: the top_k largest keys of the list, 1 .. SORT_CAP
 };
-int soft_nms_launch(const NmsK& k, const SoftNmsK& s, hipStream_t stream);
-
-// matrix_nms.hip: Matrix-NMS over the same lists, with the same outputs, counter reset and status bit (y4_set_nms_matrix)
-struct MatrixNmsK {
-    int method;                      // 1 gaussian, 2 linear (0, off, never gets here: nms_over calls nms_launch or soft_nms_launch)
-    float sigma;                     // gaussian: t = expf((c * c - m * m) / sigma)
-    float min_score;                 // a candidate is a result only if its decayed score is > min_score (resolved: >= 0)
-    int top_k;                       // participants: the top_k largest keys of the list, 1 .. SORT_CAP
-};
-int matrix_nms_launch(const NmsK& k, const MatrixNmsK& s, hipStream_t stream);
+int soft_nms_launch(const NmsK& k, const DecayK& s, hipStream_t stream);
+int matrix_nms_launch(const NmsK& k, const DecayK& s, hipStream_t stream);
 
 // tiled.hip: the decode stage's per-row candidate lists -> one list per group
 struct GatherK {

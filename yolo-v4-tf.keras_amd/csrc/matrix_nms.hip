@@ -35,7 +35,6 @@
 namespace y4 {
 
 enum { MATRIX_GAUSSIAN = 1, MATRIX_LINEAR = 2 };
-constexpr int MX_NE = SORT_CAP / NMS_THREADS;            // positions per thread
 
 // nms_kernel's layout with [SORT_CAP] floats behind it, 16-byte aligned: c of every position
 __host__ __device__ inline uint32_t matrix_c_offset(int max_total, int C) { return (nms_lds_layout(max_total, C).bytes + 15u) & ~15u; }
@@ -54,33 +53,21 @@ __device__ __forceinline__ uint32_t matrix_first_of(const unsigned long long* or
 
 __device__ __forceinline__ void matrix_sort(const NmsLds& X, uint32_t m, uint32_t m2, int tid) {
     if (m2 <= (uint32_t)NMS_THREADS) nms_rank_sort(X, m, m2, tid);
-    else nms_sort_regs<MX_NE>(X.skey, X.xbuf(), m2, tid);
+    else nms_sort_regs<NMS_NE>(X.skey, X.xbuf(), m2, tid);
 }
 
 template <int KIND, bool AGN, int METHOD>
-__global__ __launch_bounds__(NMS_THREADS) void matrix_nms_kernel(const NmsK p, const MatrixNmsK mp) {
+__global__ __launch_bounds__(NMS_THREADS) void matrix_nms_kernel(const NmsK p, const DecayK mp) {
     extern __shared__ __attribute__((aligned(16))) char nsm[];
     const NmsLds L(nsm, p.max_total, p.C);
     float* const c_a = (float*)(nsm + matrix_c_offset(p.max_total, p.C));
     const int n = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
-    uint32_t cnt = p.counts[(size_t)n * COUNT_STRIDE];
-    if (cnt > p.cap) {
-        if (tid == 0) atomicOr(p.status, 1u);
-        cnt = p.cap;
-    }
-    const unsigned long long* gk = p.keys + (int64_t)n * p.cap;
-    const float* gb = p.dboxes + (int64_t)n * p.nbox * 4;
-    if (tid == 0) L.w->kept = 0;
-    __syncthreads();
-    // every thread has read the list's count: leave the counter at zero, as nms_kernel does
-    if (tid == 0) p.counts[(size_t)n * COUNT_STRIDE] = 0;
+    const NmsList list = nms_list_begin(p, L, n, tid);
+    const float* gb = list.gb;
 
     // ---- participants: exactly the top_k largest keys, sorted descending
-    const uint32_t top_k = (uint32_t)mp.top_k;
-    unsigned long long pivot = 0;
-    if (cnt > top_k) pivot = nms_select_pivot(L, gk, cnt, ~0ull, top_k, tid);
     uint32_t m2;
-    const uint32_t m = nms_take_chunk(L, gk, cnt, ~0ull, pivot, top_k, tid, &m2);
+    const uint32_t m = nms_take_top_k(L, list.gk, list.cnt, (uint32_t)mp.top_k, tid, &m2);
     matrix_sort(L, m, m2, tid);
 
     // ---- the ordered list in skey: the key order (AGN), or (class ascending, key descending)
@@ -92,15 +79,15 @@ __global__ __launch_bounds__(NMS_THREADS) void matrix_nms_kernel(const NmsK p, c
             X.skey[i] = i < m ? ((unsigned long long)(uint32_t)(p.C - cand_box_class(L.skey[i], p.C, p.div_c).cls) << 32) | (unsigned long long)(m2 - i) : 0ull;
         __syncthreads();
         matrix_sort(X, m, m2, tid);
-        unsigned long long moved[MX_NE];
+        unsigned long long moved[NMS_NE];
 #pragma unroll
-        for (int e = 0; e < MX_NE; ++e) {
+        for (int e = 0; e < NMS_NE; ++e) {
             const uint32_t q = (uint32_t)(tid + NMS_THREADS * e);
             moved[e] = q < m ? L.skey[m2 - (uint32_t)(X.skey[q] & 0xffffffffull)] : 0ull;
         }
         __syncthreads();
 #pragma unroll
-        for (int e = 0; e < MX_NE; ++e) {
+        for (int e = 0; e < NMS_NE; ++e) {
             const uint32_t q = (uint32_t)(tid + NMS_THREADS * e);
             if (q < m) L.skey[q] = moved[e];
         }
@@ -109,13 +96,13 @@ __global__ __launch_bounds__(NMS_THREADS) void matrix_nms_kernel(const NmsK p, c
     unsigned long long* const ord = L.skey;
     nms_load_boxes(L, gb, p, m, tid);                                  // sbox[q] = the box of ord[q]; ends with a barrier
 
-    unsigned long long key[MX_NE];
-    float4 box[MX_NE];
-    int cls[MX_NE];
-    uint32_t slo[MX_NE];                   // the first position of this candidate's segment
-    uint32_t lo[MX_NE], hi[MX_NE];         // wave-uniform: the positions this wave's pair loops visit for register e
+    unsigned long long key[NMS_NE];
+    float4 box[NMS_NE];
+    int cls[NMS_NE];
+    uint32_t slo[NMS_NE];                   // the first position of this candidate's segment
+    uint32_t lo[NMS_NE], hi[NMS_NE];        // wave-uniform: the positions this wave's pair loops visit for register e
 #pragma unroll
-    for (int e = 0; e < MX_NE; ++e) {
+    for (int e = 0; e < NMS_NE; ++e) {
         const uint32_t q = (uint32_t)(tid + NMS_THREADS * e), base = (uint32_t)((tid & ~63) + NMS_THREADS * e);
         const bool have = q < m;
         key[e] = have ? ord[q] : 0ull;
@@ -131,7 +118,7 @@ __global__ __launch_bounds__(NMS_THREADS) void matrix_nms_kernel(const NmsK p, c
 
     // ---- pass 1: c_j = the largest m+ against an earlier candidate of its segment
 #pragma unroll
-    for (int e = 0; e < MX_NE; ++e) {
+    for (int e = 0; e < NMS_NE; ++e) {
         const uint32_t q = (uint32_t)(tid + NMS_THREADS * e);
         float c = 0.f;
         for (uint32_t i = lo[e]; i < hi[e]; ++i) {
@@ -147,7 +134,7 @@ __global__ __launch_bounds__(NMS_THREADS) void matrix_nms_kernel(const NmsK p, c
     // ---- pass 2: d_j, and the decayed key
     const bool cap_binds = p.max_per_class < p.max_total;
 #pragma unroll
-    for (int e = 0; e < MX_NE; ++e) {
+    for (int e = 0; e < NMS_NE; ++e) {
         const uint32_t q = (uint32_t)(tid + NMS_THREADS * e);
         float d = 1.f;
         for (uint32_t i = lo[e]; i < hi[e]; ++i) {
@@ -172,18 +159,18 @@ __global__ __launch_bounds__(NMS_THREADS) void matrix_nms_kernel(const NmsK p, c
     if (cap_binds) {
         // ---- the class cap: a key with max_per_class larger keys of its class in front of it is turned away
 #pragma unroll
-        for (int e = 0; e < MX_NE; ++e)
+        for (int e = 0; e < NMS_NE; ++e)
             // (class-aware: the end of the last lane's segment, from the ORIGINAL keys -- before anybody overwrites them)
             hi[e] = hi[e] == 0 ? 0u : (AGN ? m : __shfl(matrix_first_of(ord, m, cls[e] + 1, p.C, p.div_c), (int)(hi[e] - 1u) & 63));
         __syncthreads();
 #pragma unroll
-        for (int e = 0; e < MX_NE; ++e) {
+        for (int e = 0; e < NMS_NE; ++e) {
             const uint32_t q = (uint32_t)(tid + NMS_THREADS * e);
             if (q < m) dkey[q] = key[e];
         }
         __syncthreads();
 #pragma unroll
-        for (int e = 0; e < MX_NE; ++e) {
+        for (int e = 0; e < NMS_NE; ++e) {
             // every position of the classes this wave holds (their decayed order is not the original one)
             int larger = 0;
             for (uint32_t i = lo[e]; i < hi[e]; ++i) {
@@ -198,7 +185,7 @@ __global__ __launch_bounds__(NMS_THREADS) void matrix_nms_kernel(const NmsK p, c
     __syncthreads();                               // (also: every pair loop has read its boxes; the sort takes their slots)
     uint32_t mine = 0;
 #pragma unroll
-    for (int e = 0; e < MX_NE; ++e) {
+    for (int e = 0; e < NMS_NE; ++e) {
         const uint32_t q = (uint32_t)(tid + NMS_THREADS * e);
         if (q < m) dkey[q] = key[e];
         mine += key[e] != 0ull ? 1u : 0u;
@@ -222,26 +209,16 @@ __global__ __launch_bounds__(NMS_THREADS) void matrix_nms_kernel(const NmsK p, c
     nms_write_outputs(p, L, n, tid);
 }
 
-int matrix_nms_launch(const NmsK& k, const MatrixNmsK& s, hipStream_t stream) {
+struct MatrixKernel { template <int KIND, bool AGN, int METHOD> static constexpr auto kernel = matrix_nms_kernel<KIND, AGN, METHOD>; };
+
+int matrix_nms_launch(const NmsK& k, const DecayK& s, hipStream_t stream) {
     const size_t lds = matrix_lds_bytes(k.max_total, k.C);
     Y4_REQUIRE(lds <= 160 * 1024 && k.max_total <= 1024 && s.top_k >= 1 && s.top_k <= SORT_CAP, Y4_EINVAL,
                "matrix nms: top_k %d, max_total %d and %d classes need %zu bytes of LDS", s.top_k, k.max_total, k.C, lds);
-    Y4_REQUIRE((k.kind == 0 || k.kind == 1) && (k.agnostic == 0 || k.agnostic == 1) && k.beta > 0.f, Y4_EINVAL,
-               "matrix nms: rule (kind %d, beta %g, agnostic %d)", k.kind, (double)k.beta, k.agnostic);
+    if (int r = nms_rule_check("matrix nms", k.kind, k.beta, k.agnostic)) return r;
     Y4_REQUIRE(s.method >= MATRIX_GAUSSIAN && s.method <= MATRIX_LINEAR && s.sigma > 0.f && s.min_score >= 0.f, Y4_EINVAL,
                "matrix nms: mode (method %d, sigma %g, min_score %g)", s.method, (double)s.sigma, (double)s.min_score);
-    // [measure][agnostic][method - 1]
-    using Launch = int (*)(int, dim3, dim3, size_t, hipStream_t, const NmsK&, const MatrixNmsK&);
-#define Y4_MATRIX_ROW(KIND, AGN)                                                                                                    \
-    {launch_lds<matrix_nms_kernel<KIND, AGN, MATRIX_GAUSSIAN>, NmsK, MatrixNmsK>, launch_lds<matrix_nms_kernel<KIND, AGN, MATRIX_LINEAR>, NmsK, MatrixNmsK>}
-    static const Launch table[3][2][2] = {
-        {Y4_MATRIX_ROW(NMS_IOU, false), Y4_MATRIX_ROW(NMS_IOU, true)},
-        {Y4_MATRIX_ROW(NMS_DIOU1, false), Y4_MATRIX_ROW(NMS_DIOU1, true)},
-        {Y4_MATRIX_ROW(NMS_DIOU, false), Y4_MATRIX_ROW(NMS_DIOU, true)},
-    };
-#undef Y4_MATRIX_ROW
-    const int measure = k.kind == 0 ? NMS_IOU : (k.beta == 1.0f ? NMS_DIOU1 : NMS_DIOU);
-    return table[measure][k.agnostic][s.method - 1](160 * 1024, dim3(k.N), dim3(NMS_THREADS), lds, stream, k, s);
+    return nms_dispatch<MatrixKernel>(std::make_index_sequence<6 * 2>(), s.method, lds, stream, k, s);
 }
 
 }  // namespace y4

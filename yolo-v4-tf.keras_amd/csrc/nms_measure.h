@@ -30,6 +30,14 @@ __device__ __forceinline__ float iou_tf(const float4 a, const float4 b) {
 // the pairs IoU-NMS would suppress, and for every other pair the value returned is iou, an upper bound of m that is not above thr
 // either -- the same decision on every pair (a NaN iou fails both tests), at IoU's cost for all but a few.
 enum { NMS_IOU = 0, NMS_DIOU1 = 1, NMS_DIOU = 2 };
+// Host side, for every launcher that instantiates on the measure: the rule of the handle -> the measure (kind 0 does not read beta,
+// kind 1 with beta == 1 is its own), behind the check of the rule; `who` opens the message
+inline int nms_measure_index(int kind, float beta) { return kind == 0 ? NMS_IOU : (beta == 1.0f ? NMS_DIOU1 : NMS_DIOU); }
+inline int nms_rule_check(const char* who, int kind, float beta, int agnostic) {
+    Y4_REQUIRE((kind == 0 || kind == 1) && (agnostic == 0 || agnostic == 1) && beta > 0.f, Y4_EINVAL,
+               "%s: rule (kind %d, beta %g, agnostic %d)", who, kind, (double)beta, agnostic);
+    return Y4_OK;
+}
 template <int KIND>
 __device__ __forceinline__ float nms_measure(const float4 a, const float4 b, float thr, float beta) {
     const float iou = iou_tf(a, b);

@@ -1,9 +1,13 @@
-// nms_phases.h -- the phases that nms_kernel (decode_nms.hip) and soft_nms_kernel (soft_nms.hip) share, the single copy: the LDS
-// carve-up of a workgroup that owns one candidate list, the selectors that extract the best keys of the list (count, histogram pivot,
-// exact radix select, gather), the sorts, the box gather and the output stage.  Device code; include it after candidates.h and kernels.h.
+// nms_phases.h -- the phases that nms_kernel (decode_nms.hip), soft_nms_kernel (soft_nms.hip) and matrix_nms_kernel (matrix_nms.hip)
+// share, the single copy: the LDS carve-up of a workgroup that owns one candidate list, the list prologue (count, overflow bit, counter
+// reset), the selectors that extract the best keys of the list (count, histogram pivot, exact radix select, gather), the sorts, the box
+// gather and the output stage; and the table their three launchers dispatch through.  Include it after candidates.h and kernels.h.
 #pragma once
+#include <utility>
+
 #include "candidates.h"
 #include "kernels.h"
+#include "nms_measure.h"
 
 #pragma clang fp contract(off)   // keep the reference's float32 op order (no fused multiply-add)
 
@@ -11,6 +15,7 @@ namespace y4 {
 
 constexpr int NMS_THREADS = 1024;
 constexpr int SORT_CAP = 4096;
+constexpr int NMS_NE = SORT_CAP / NMS_THREADS;      // keys per thread of a full chunk: the participants / positions a decay kernel holds in registers
 constexpr int PAR_MAX_C = 1024;      // class count up to which the round-parallel greedy pass has its per-class LDS words
 constexpr uint32_t PAR_NONE = 0xffffffffu;
 
@@ -147,6 +152,25 @@ struct NmsLds {
     }
 };
 
+// ---- the list of workgroup n: its length, clamped to the capacity (an overflow raises the status bit), its keys and its box table.
+// Zeroes the kept count and, once every thread has read the list's counter, the counter: it is left at zero for the next step's decode
+// (which therefore needs no memset launch in front of it; decode_launch clears only when a decode was NOT followed by its NMS), and
+// counts_clean, the gather path and the merged forms depend on every kernel over a list doing so.
+struct NmsList { uint32_t cnt; const unsigned long long* gk; const float* gb; };
+__device__ __forceinline__ NmsList nms_list_begin(const NmsK& p, const NmsLds& L, int n, int tid) {
+    uint32_t cnt = p.counts[(size_t)n * COUNT_STRIDE];
+    if (cnt > p.cap) {
+        if (tid == 0) atomicOr(p.status, 1u);
+        cnt = p.cap;
+    }
+    const unsigned long long* gk = p.keys + (int64_t)n * p.cap;
+    const float* gb = p.dboxes + (int64_t)n * p.nbox * 4;
+    if (tid == 0) L.w->kept = 0;
+    __syncthreads();
+    if (tid == 0) p.counts[(size_t)n * COUNT_STRIDE] = 0;
+    return NmsList{cnt, gk, gb};
+}
+
 // ---- how many keys remain below the cutoff?
 __device__ __forceinline__ uint32_t nms_count_below(const NmsLds& L, const unsigned long long* gk, uint32_t cnt, unsigned long long cutoff, int tid) {
     if (tid == 0) L.w->remaining = 0;
@@ -255,6 +279,15 @@ __device__ __forceinline__ uint32_t nms_take_chunk(const NmsLds& L, const unsign
     return m;
 }
 
+// ---- the participants of a decay kernel: EXACTLY the top_k largest keys of the list (all when it is shorter) -> skey[0 .. m),
+// unsorted -- the exact radix select, never the histogram pivot.  -> m
+__device__ __forceinline__ uint32_t nms_take_top_k(const NmsLds& L, const unsigned long long* gk, uint32_t cnt, uint32_t top_k, int tid,
+                                                   uint32_t* m2_out) {
+    unsigned long long pivot = 0;
+    if (cnt > top_k) pivot = nms_select_pivot(L, gk, cnt, ~0ull, top_k, tid);
+    return nms_take_chunk(L, gk, cnt, ~0ull, pivot, top_k, tid, m2_out);
+}
+
 // Rank sort of skey[0 .. m2), m2 <= NMS_THREADS, descending: a thread's key goes to position (number of larger keys); keys are
 // unique.  No dependent chain, two barriers.  In-kernel timestamps at ~1000 keys: 22 us, the same as the 55 dependent exchange
 // stages of a bitonic network in LDS or in registers with shuffles, and as broadcasting the keys with v_readlane instead of LDS
@@ -330,6 +363,19 @@ __device__ __forceinline__ void nms_write_outputs(const NmsK& p, const NmsLds& L
         if (p.out_idx) p.out_idx[(int64_t)n * p.max_total + i] = id;
     }
     if (tid == 0) p.out_valid[n] = kept;
+}
+
+// ---- host side: the launchers' dispatch.  F names a kernel template: F::kernel<KIND, AGN, METHOD> is its instantiation for a
+// measure (nms_measure.h), the agnostic flag and a method 1 .. NMETHODS; I counts the 6 * NMETHODS of them.  Launches the one of the
+// rule in `k` and of `method`, one workgroup per list, through launch_lds -- one table per kernel template,
+// [measure][agnostic][method - 1].  more: what the kernel takes behind NmsK
+template <class F, class... Args, size_t... I>
+int nms_dispatch(std::index_sequence<I...>, int method, size_t lds, hipStream_t stream, const NmsK& k, const Args&... more) {
+    constexpr size_t NM = sizeof...(I) / 6;
+    using Launch = int (*)(int, dim3, dim3, size_t, hipStream_t, const NmsK&, const Args&...);
+    static const Launch table[] = {launch_lds<F::template kernel<(int)(I / (2 * NM)), (I / NM) % 2 != 0, (int)(I % NM) + 1>, NmsK, Args...>...};
+    const size_t at = ((size_t)nms_measure_index(k.kind, k.beta) * 2 + (size_t)k.agnostic) * NM + (size_t)(method - 1);
+    return table[at](160 * 1024, dim3(k.N), dim3(NMS_THREADS), lds, stream, k, more...);
 }
 
 }  // namespace y4

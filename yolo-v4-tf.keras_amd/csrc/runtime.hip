@@ -116,6 +116,14 @@ struct TileEntry { int run, own; bool chained; };      // chained: entry <= 0
 static TileEntry decode_entry(int v) { return v < 0 ? TileEntry{(-v) % 1000, (-v) / 1000, true} : TileEntry{0, v, v == 0}; }
 static int encode_entry(int run, int own) { return -(run + 1000 * own); }
 
+// A score-decay mode of the NMS stage as the handle keeps it (y4_set_nms_soft, y4_set_nms_matrix)
+struct DecayMode {
+    int method = 0;              // 0: off
+    float sigma = 0.5f;
+    float min_score = -1.0f;     // < 0: the config's score_threshold
+    int top_k = 4096;
+};
+
 }  // namespace y4
 
 using namespace y4;
@@ -199,16 +207,9 @@ struct y4_ctx {
     int nms_kind = 0;
     float nms_beta = 1.0f;
     int nms_agnostic = 0;
-    // y4_set_nms_soft: Soft-NMS instead of hard suppression in nms_over (soft_nms.hip); method 0 is off.  Host-only, as the rule
-    int soft_method = 0;
-    float soft_sigma = 0.5f;
-    float soft_min_score = -1.0f;    // < 0: the config's score_threshold
-    int soft_top_k = 4096;
-    // y4_set_nms_matrix: Matrix-NMS in nms_over (matrix_nms.hip); method 0 is off.  Host-only; excludes soft_method != 0
-    int matrix_method = 0;
-    float matrix_sigma = 0.5f;
-    float matrix_min_score = -1.0f;  // < 0: the config's score_threshold
-    int matrix_top_k = 4096;
+    // y4_set_nms_soft / y4_set_nms_matrix: score decay instead of hard suppression in nms_over (soft_nms.hip, matrix_nms.hip).
+    // Host-only, as the rule.  At most one of the two is on; one that is off keeps its parameters
+    DecayMode soft, matrix;
     // is the head's output of this run written to HBM?  (an LDS pair in front of a head conv: also when that conv's input is retained)
     bool stores_x(const Chain& ch) const { return ch.store_x || (ch.lds_pair && retain_head_in && ops[ch.tail[0]].out_f32); }
 };
@@ -924,15 +925,11 @@ int nms_over(y4_handle h, const CandStore& c, int n, float iou_thr, const NmsOut
     k.status = c.status; k.div_c = c.div_c;
     k.box_map = box_map;
     k.kind = h->nms_kind; k.beta = h->nms_beta; k.agnostic = h->nms_agnostic;
-    if (h->matrix_method != 0) {
-        // y4_set_nms_matrix: the matrix kernel over the same lists into the same outputs
-        const MatrixNmsK mk{h->matrix_method, h->matrix_sigma, h->matrix_min_score < 0.f ? cfg.score_threshold : h->matrix_min_score, h->matrix_top_k};
-        return matrix_nms_launch(k, mk, s);
-    }
-    if (h->soft_method == 0) return nms_launch(k, s);
-    // y4_set_nms_soft: the soft kernel over the same lists into the same outputs
-    const SoftNmsK sk{h->soft_method, h->soft_sigma, h->soft_min_score < 0.f ? cfg.score_threshold : h->soft_min_score, h->soft_top_k};
-    return soft_nms_launch(k, sk, s);
+    // the decay mode that is on: matrix, else soft, else none -- its kernel over the same lists into the same outputs
+    const DecayMode& m = h->matrix.method != 0 ? h->matrix : h->soft;
+    if (m.method == 0) return nms_launch(k, s);
+    const DecayK dk{m.method, m.sigma, m.min_score < 0.f ? cfg.score_threshold : m.min_score, m.top_k};
+    return &m == &h->matrix ? matrix_nms_launch(k, dk, s) : soft_nms_launch(k, dk, s);
 }
 
 // ... of the workspace's lists, behind run_decode
@@ -954,6 +951,26 @@ int merge_over(y4_handle h, const CandStore& c, int n, float iou_thr, const NmsO
     k.box_map = box_map;
     k.kind = h->nms_kind; k.beta = h->nms_beta; k.agnostic = h->nms_agnostic;
     return box_merge_launch(k, s);
+}
+
+// The detection tail of every entry point: [decode ->] [save the lists' counts ->] NMS [-> merge], on one stream in this order.
+// gathered: the lists of a gather scratch (y4_nms_gathered*), which are there already; null: the workspace's lists, decoded here
+// (decoded: an event to record behind the decode, or null) and under run_nms's counter bookkeeping.  A threshold < 0 is the config's.
+enum { TAIL_COUNTS = 1, TAIL_MERGE = 2 };      // cand_count <- the raw counts, before the NMS zeroes the counters | merge_over behind
+int detect_tail(y4_handle h, const char* who, const CandStore* gathered, int n, float iou_threshold, float score_threshold, int flags,
+                int32_t* cand_count, const NmsOutputs& o, const float* box_map, hipStream_t s, hipEvent_t decoded = nullptr) {
+    const CandStore c = gathered ? *gathered : workspace_cands(h);
+    Y4_REQUIRE(!(flags & TAIL_MERGE) || c.cap < MERGE_MAX_CAP, Y4_EINVAL, "%s: a list capacity of %u keys is not below the 2^25 the merge allows",
+               who, c.cap);
+    const float iou = iou_threshold < 0.f ? h->cfg.iou_threshold : iou_threshold;
+    if (!gathered) {
+        if (int r = run_decode(h, n, score_threshold < 0.f ? h->cfg.score_threshold : score_threshold, s)) return r;
+        if (decoded) Y4_CHECK_HIP(hipEventRecord(decoded, s));
+    }
+    if (flags & TAIL_COUNTS)
+        if (int r = gather_counts_launch(c.counts, cand_count, n, s)) return r;
+    if (int r = gathered ? nms_over(h, c, n, iou, o, box_map, s) : run_nms(h, n, iou, o, box_map, s)) return r;
+    return flags & TAIL_MERGE ? merge_over(h, c, n, iou, o, cand_count, box_map, s) : Y4_OK;
 }
 
 }  // namespace
@@ -1234,26 +1251,16 @@ int y4_decode_nms_mapped(y4_handle h, int n, float iou_threshold, float score_th
                          float* scores, float* classes, int32_t* valid, int32_t* kept_idx, void* stream) {
     if (int r = check_ready(h, n)) return r;
     Y4_REQUIRE(boxes && scores && classes && valid, Y4_EINVAL, "y4_decode_nms: null output");
-    const float iou = iou_threshold < 0.f ? h->cfg.iou_threshold : iou_threshold;
-    const float sc = score_threshold < 0.f ? h->cfg.score_threshold : score_threshold;
-    if (int r = run_decode(h, n, sc, (hipStream_t)stream)) return r;
-    return run_nms(h, n, iou, NmsOutputs{boxes, scores, classes, valid, kept_idx}, box_map, (hipStream_t)stream);
+    return detect_tail(h, "y4_decode_nms", nullptr, n, iou_threshold, score_threshold, 0, nullptr, NmsOutputs{boxes, scores, classes, valid, kept_idx},
+                       box_map, (hipStream_t)stream);
 }
 
 int y4_decode_nms_merged(y4_handle h, int n, float iou_threshold, float score_threshold, const float* box_map, int32_t* cand_count,
                          float* boxes, float* scores, float* classes, int32_t* valid, int32_t* kept_idx, void* stream) {
     if (int r = check_ready(h, n)) return r;
     Y4_REQUIRE(cand_count && boxes && scores && classes && valid && kept_idx, Y4_EINVAL, "y4_decode_nms_merged: null output");
-    const CandStore c = workspace_cands(h);
-    Y4_REQUIRE(c.cap < MERGE_MAX_CAP, Y4_EINVAL, "y4_decode_nms_merged: %u candidate keys per image are not below the 2^25 the merge allows", c.cap);
-    const float iou = iou_threshold < 0.f ? h->cfg.iou_threshold : iou_threshold;
-    const float sc = score_threshold < 0.f ? h->cfg.score_threshold : score_threshold;
-    hipStream_t s = (hipStream_t)stream;
-    const NmsOutputs o{boxes, scores, classes, valid, kept_idx};
-    if (int r = run_decode(h, n, sc, s)) return r;
-    if (int r = gather_counts_launch(c.counts, cand_count, n, s)) return r;      // nms_kernel zeroes the counters it has read
-    if (int r = run_nms(h, n, iou, o, box_map, s)) return r;
-    return merge_over(h, c, n, iou, o, cand_count, box_map, s);
+    return detect_tail(h, "y4_decode_nms_merged", nullptr, n, iou_threshold, score_threshold, TAIL_COUNTS | TAIL_MERGE, cand_count,
+                       NmsOutputs{boxes, scores, classes, valid, kept_idx}, box_map, (hipStream_t)stream);
 }
 
 int y4_set_nms_rule(y4_handle h, int kind, float beta, int agnostic) {
@@ -1272,41 +1279,43 @@ int y4_get_nms_rule(y4_handle h, int* kind, float* beta, int* agnostic) {
     return Y4_OK;
 }
 
-int y4_set_nms_soft(y4_handle h, int method, float sigma, float min_score, int top_k) {
+// The two score-decay modes of the NMS stage: what y4_set_nms_soft and y4_set_nms_matrix differ in
+struct Decay {
+    const char* name;                  // y4_set_<name>, y4_get_<name>: for messages
+    int max_method;
+    const char* methods;               // ... spelled out
+    DecayMode y4_ctx::*own;
+    DecayMode y4_ctx::*other;          // the mode that must be off while this one is on
+    const char* other_name;
+};
+static const Decay SOFT{"nms_soft", 3, "0: off, 1: gaussian, 2: linear, 3: hard", &y4_ctx::soft, &y4_ctx::matrix,
+                        "Matrix-NMS is on (y4_set_nms_matrix)"};
+static const Decay MATRIX{"nms_matrix", 2, "0: off, 1: gaussian, 2: linear", &y4_ctx::matrix, &y4_ctx::soft,
+                          "Soft-NMS is on (y4_set_nms_soft)"};
+
+static int set_decay(y4_handle h, const Decay& d, int method, float sigma, float min_score, int top_k) {
     if (int r = check_handle(h)) return r;
-    Y4_REQUIRE(method >= 0 && method <= 3, Y4_EINVAL, "y4_set_nms_soft: method %d (0: off, 1: gaussian, 2: linear, 3: hard)", method);
-    Y4_REQUIRE(std::isfinite(sigma) && sigma > 0.f, Y4_EINVAL, "y4_set_nms_soft: sigma %g must be finite and > 0", (double)sigma);
-    Y4_REQUIRE(std::isfinite(min_score) && min_score < 1.f, Y4_EINVAL, "y4_set_nms_soft: min_score %g must be finite and < 1", (double)min_score);
-    Y4_REQUIRE(top_k >= 1 && top_k <= 4096, Y4_EINVAL, "y4_set_nms_soft: top_k %d outside 1 .. 4096", top_k);
-    Y4_REQUIRE(method == 0 || h->matrix_method == 0, Y4_EINVAL, "y4_set_nms_soft: method %d while Matrix-NMS is on (y4_set_nms_matrix)", method);
-    h->soft_method = method; h->soft_sigma = sigma; h->soft_min_score = min_score; h->soft_top_k = top_k;
+    Y4_REQUIRE(method >= 0 && method <= d.max_method, Y4_EINVAL, "y4_set_%s: method %d (%s)", d.name, method, d.methods);
+    Y4_REQUIRE(std::isfinite(sigma) && sigma > 0.f, Y4_EINVAL, "y4_set_%s: sigma %g must be finite and > 0", d.name, (double)sigma);
+    Y4_REQUIRE(std::isfinite(min_score) && min_score < 1.f, Y4_EINVAL, "y4_set_%s: min_score %g must be finite and < 1", d.name, (double)min_score);
+    Y4_REQUIRE(top_k >= 1 && top_k <= 4096, Y4_EINVAL, "y4_set_%s: top_k %d outside 1 .. 4096", d.name, top_k);
+    Y4_REQUIRE(method == 0 || (h->*d.other).method == 0, Y4_EINVAL, "y4_set_%s: method %d while %s", d.name, method, d.other_name);
+    h->*d.own = DecayMode{method, sigma, min_score, top_k};
     return Y4_OK;
 }
 
-int y4_get_nms_soft(y4_handle h, int* method, float* sigma, float* min_score, int* top_k) {
+static int get_decay(y4_handle h, const Decay& d, int* method, float* sigma, float* min_score, int* top_k) {
     if (int r = check_handle(h)) return r;
-    Y4_REQUIRE(method && sigma && min_score && top_k, Y4_EINVAL, "y4_get_nms_soft: null argument");
-    *method = h->soft_method; *sigma = h->soft_sigma; *min_score = h->soft_min_score; *top_k = h->soft_top_k;
+    Y4_REQUIRE(method && sigma && min_score && top_k, Y4_EINVAL, "y4_get_%s: null argument", d.name);
+    const DecayMode& m = h->*d.own;
+    *method = m.method; *sigma = m.sigma; *min_score = m.min_score; *top_k = m.top_k;
     return Y4_OK;
 }
 
-int y4_set_nms_matrix(y4_handle h, int method, float sigma, float min_score, int top_k) {
-    if (int r = check_handle(h)) return r;
-    Y4_REQUIRE(method >= 0 && method <= 2, Y4_EINVAL, "y4_set_nms_matrix: method %d (0: off, 1: gaussian, 2: linear)", method);
-    Y4_REQUIRE(std::isfinite(sigma) && sigma > 0.f, Y4_EINVAL, "y4_set_nms_matrix: sigma %g must be finite and > 0", (double)sigma);
-    Y4_REQUIRE(std::isfinite(min_score) && min_score < 1.f, Y4_EINVAL, "y4_set_nms_matrix: min_score %g must be finite and < 1", (double)min_score);
-    Y4_REQUIRE(top_k >= 1 && top_k <= 4096, Y4_EINVAL, "y4_set_nms_matrix: top_k %d outside 1 .. 4096", top_k);
-    Y4_REQUIRE(method == 0 || h->soft_method == 0, Y4_EINVAL, "y4_set_nms_matrix: method %d while Soft-NMS is on (y4_set_nms_soft)", method);
-    h->matrix_method = method; h->matrix_sigma = sigma; h->matrix_min_score = min_score; h->matrix_top_k = top_k;
-    return Y4_OK;
-}
-
-int y4_get_nms_matrix(y4_handle h, int* method, float* sigma, float* min_score, int* top_k) {
-    if (int r = check_handle(h)) return r;
-    Y4_REQUIRE(method && sigma && min_score && top_k, Y4_EINVAL, "y4_get_nms_matrix: null argument");
-    *method = h->matrix_method; *sigma = h->matrix_sigma; *min_score = h->matrix_min_score; *top_k = h->matrix_top_k;
-    return Y4_OK;
-}
+int y4_set_nms_soft(y4_handle h, int method, float sigma, float min_score, int top_k) { return set_decay(h, SOFT, method, sigma, min_score, top_k); }
+int y4_get_nms_soft(y4_handle h, int* method, float* sigma, float* min_score, int* top_k) { return get_decay(h, SOFT, method, sigma, min_score, top_k); }
+int y4_set_nms_matrix(y4_handle h, int method, float sigma, float min_score, int top_k) { return set_decay(h, MATRIX, method, sigma, min_score, top_k); }
+int y4_get_nms_matrix(y4_handle h, int* method, float* sigma, float* min_score, int* top_k) { return get_decay(h, MATRIX, method, sigma, min_score, top_k); }
 
 // ---- gathered decode + NMS (tiled inference).  The caller's scratch: [n_groups] counters, one per 256-byte line | the groups' key
 // lists [n_groups][group_cap] | the groups' box tables [n_groups][max_slots * nbox][4], each part 256-byte aligned.
@@ -1398,11 +1407,9 @@ int y4_nms_gathered(y4_handle h, int n_groups, int max_slots, uint32_t group_cap
     if (int r = gather_scratch_check("y4_nms_gathered", scratch_dev)) return r;
     Y4_REQUIRE(h->act, Y4_ESTATE, "workspace not bound (call y4_bind_workspace first)");
     Y4_REQUIRE(cand_count_dev && boxes_dev && scores_dev && classes_dev && valid_dev, Y4_EINVAL, "y4_nms_gathered: null output");
-    hipStream_t s = (hipStream_t)stream;
     const CandStore g = gathered_cands(h, scratch_dev, L, max_slots, group_cap);
-    if (int r = gather_counts_launch(g.counts, cand_count_dev, n_groups, s)) return r;
-    return nms_over(h, g, n_groups, iou_threshold < 0.f ? h->cfg.iou_threshold : iou_threshold,
-                    NmsOutputs{boxes_dev, scores_dev, classes_dev, valid_dev, kept_idx_dev}, nullptr, s);
+    return detect_tail(h, "y4_nms_gathered", &g, n_groups, iou_threshold, -1.f, TAIL_COUNTS, cand_count_dev,
+                       NmsOutputs{boxes_dev, scores_dev, classes_dev, valid_dev, kept_idx_dev}, nullptr, (hipStream_t)stream);
 }
 
 int y4_nms_gathered_merged(y4_handle h, int n_groups, int max_slots, uint32_t group_cap, float iou_threshold, void* scratch_dev,
@@ -1414,14 +1421,9 @@ int y4_nms_gathered_merged(y4_handle h, int n_groups, int max_slots, uint32_t gr
     Y4_REQUIRE(h->act, Y4_ESTATE, "workspace not bound (call y4_bind_workspace first)");
     Y4_REQUIRE(cand_count_dev && boxes_dev && scores_dev && classes_dev && valid_dev && kept_idx_dev, Y4_EINVAL,
                "y4_nms_gathered_merged: null output");
-    Y4_REQUIRE(group_cap < MERGE_MAX_CAP, Y4_EINVAL, "y4_nms_gathered_merged: group_cap %u is not below the 2^25 the merge allows", group_cap);
-    hipStream_t s = (hipStream_t)stream;
     const CandStore g = gathered_cands(h, scratch_dev, L, max_slots, group_cap);
-    const float iou = iou_threshold < 0.f ? h->cfg.iou_threshold : iou_threshold;
-    const NmsOutputs o{boxes_dev, scores_dev, classes_dev, valid_dev, kept_idx_dev};
-    if (int r = gather_counts_launch(g.counts, cand_count_dev, n_groups, s)) return r;
-    if (int r = nms_over(h, g, n_groups, iou, o, nullptr, s)) return r;
-    return merge_over(h, g, n_groups, iou, o, cand_count_dev, nullptr, s);
+    return detect_tail(h, "y4_nms_gathered_merged", &g, n_groups, iou_threshold, -1.f, TAIL_COUNTS | TAIL_MERGE, cand_count_dev,
+                       NmsOutputs{boxes_dev, scores_dev, classes_dev, valid_dev, kept_idx_dev}, nullptr, (hipStream_t)stream);
 }
 
 static void loss_geometry(y4_handle h, int* gh, int* gw, int* lane_base) {
@@ -1780,10 +1782,10 @@ static int predict_impl(y4_handle h, const void* imgs, int n, float* boxes, floa
         if (int r = run_op(h, l.op, imgs, l.cnt, s, l.img0)) return r;
         if (ev && h->t_rec[k]) Y4_CHECK_HIP(hipEventRecord(ev[++i], s));
     }
-    if (int r = run_decode(h, n, h->cfg.score_threshold, s)) return r;
-    if (ev) Y4_CHECK_HIP(hipEventRecord(ev[++i], s));
-    if (int r = run_nms(h, n, h->cfg.iou_threshold, NmsOutputs{boxes, scores, classes, valid, kept_idx}, nullptr, s)) return r;
-    if (ev) Y4_CHECK_HIP(hipEventRecord(ev[++i], s));
+    if (int r = detect_tail(h, "y4_predict", nullptr, n, -1.f, -1.f, 0, nullptr, NmsOutputs{boxes, scores, classes, valid, kept_idx}, nullptr, s,
+                            ev ? ev[i + 1] : nullptr))
+        return r;
+    if (ev) Y4_CHECK_HIP(hipEventRecord(ev[i += 2], s));
     return Y4_OK;
 }
 

@@ -28,7 +28,6 @@
 namespace y4 {
 
 enum { SOFT_GAUSSIAN = 1, SOFT_LINEAR = 2, SOFT_HARD = 3 };
-constexpr int SOFT_NE = SORT_CAP / NMS_THREADS;          // participants per thread
 constexpr int SOFT_WAVES = NMS_THREADS / 64;
 
 // what a wave publishes per pick: its best live key, where that candidate sits in the chunk, the kept boxes of its class so far
@@ -47,39 +46,25 @@ __device__ __forceinline__ float soft_factor(float m, float iou_thr, float sigma
 }
 
 template <int KIND, bool AGN, int METHOD>
-__global__ __launch_bounds__(NMS_THREADS) void soft_nms_kernel(const NmsK p, const SoftNmsK sp) {
+__global__ __launch_bounds__(NMS_THREADS) void soft_nms_kernel(const NmsK p, const DecayK sp) {
     extern __shared__ __attribute__((aligned(16))) char nsm[];
     const NmsLds L(nsm, p.max_total, p.C);
     SoftSlot* const slots = (SoftSlot*)(nsm + soft_slots_offset(p.max_total, p.C));
     const int n = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    uint32_t cnt = p.counts[(size_t)n * COUNT_STRIDE];
-    if (cnt > p.cap) {
-        if (tid == 0) atomicOr(p.status, 1u);
-        cnt = p.cap;
-    }
-    const unsigned long long* gk = p.keys + (int64_t)n * p.cap;
-    const float* gb = p.dboxes + (int64_t)n * p.nbox * 4;
-    if (tid == 0) L.w->kept = 0;
-    __syncthreads();
-    // every thread has read the list's count: leave the counter at zero, as nms_kernel does (counts_clean, the gather path and the
-    // merged forms depend on it)
-    if (tid == 0) p.counts[(size_t)n * COUNT_STRIDE] = 0;
+    const NmsList list = nms_list_begin(p, L, n, tid);
 
     // ---- participants: exactly the top_k largest keys, unsorted, and their boxes
-    const uint32_t top_k = (uint32_t)sp.top_k;
-    unsigned long long pivot = 0;
-    if (cnt > top_k) pivot = nms_select_pivot(L, gk, cnt, ~0ull, top_k, tid);
     uint32_t m2;
-    const uint32_t m = nms_take_chunk(L, gk, cnt, ~0ull, pivot, top_k, tid, &m2);
-    nms_load_boxes(L, gb, p, m, tid);
+    const uint32_t m = nms_take_top_k(L, list.gk, list.cnt, (uint32_t)sp.top_k, tid, &m2);
+    nms_load_boxes(L, list.gb, p, m, tid);
 
-    uint32_t id[SOFT_NE], same[SOFT_NE];
-    float w[SOFT_NE];
-    float4 box[SOFT_NE];
-    int cls[SOFT_NE];
-    bool live[SOFT_NE];
+    uint32_t id[NMS_NE], same[NMS_NE];
+    float w[NMS_NE];
+    float4 box[NMS_NE];
+    int cls[NMS_NE];
+    bool live[NMS_NE];
 #pragma unroll
-    for (int e = 0; e < SOFT_NE; ++e) {
+    for (int e = 0; e < NMS_NE; ++e) {
         const uint32_t pos = (uint32_t)(tid + NMS_THREADS * e);
         const bool have = pos < m;
         const unsigned long long key = have ? L.skey[pos] : 0ull;
@@ -98,7 +83,7 @@ __global__ __launch_bounds__(NMS_THREADS) void soft_nms_kernel(const NmsK p, con
         unsigned long long best = 0;
         uint32_t bpos = 0, bsame = 0;
 #pragma unroll
-        for (int e = 0; e < SOFT_NE; ++e) {
+        for (int e = 0; e < NMS_NE; ++e) {
             const unsigned long long k = live[e] ? cand_key(w[e], id[e]) : 0ull;
             if (k > best) { best = k; bpos = (uint32_t)(tid + NMS_THREADS * e); bsame = same[e]; }
         }
@@ -128,14 +113,14 @@ __global__ __launch_bounds__(NMS_THREADS) void soft_nms_kernel(const NmsK p, con
         const int wcls = cand_box_class(kmax, p.C, p.div_c).cls;
         // the winner leaves the pool, kept or turned away
 #pragma unroll
-        for (int e = 0; e < SOFT_NE; ++e)
+        for (int e = 0; e < NMS_NE; ++e)
             if ((uint32_t)(tid + NMS_THREADS * e) == wpos) live[e] = false;
         if (cap_binds && (int)wsame >= p.max_per_class) continue;    // its class is full: not kept, decays nothing
         const float4 kb = L.sbox[wpos];
         if (tid == 0) L.keep((uint32_t)kept, kb, wcls, kmax, cand_box_class(kmax, p.C, p.div_c).box);     // score = w at the pick
         ++kept;
 #pragma unroll
-        for (int e = 0; e < SOFT_NE; ++e) {
+        for (int e = 0; e < NMS_NE; ++e) {
             if (!live[e]) continue;
             const bool mine = cls[e] == wcls;
             if (mine) ++same[e];
@@ -151,27 +136,16 @@ __global__ __launch_bounds__(NMS_THREADS) void soft_nms_kernel(const NmsK p, con
     nms_write_outputs(p, L, n, tid);
 }
 
-int soft_nms_launch(const NmsK& k, const SoftNmsK& s, hipStream_t stream) {
+struct SoftKernel { template <int KIND, bool AGN, int METHOD> static constexpr auto kernel = soft_nms_kernel<KIND, AGN, METHOD>; };
+
+int soft_nms_launch(const NmsK& k, const DecayK& s, hipStream_t stream) {
     const size_t lds = soft_lds_bytes(k.max_total, k.C);
     Y4_REQUIRE(lds <= 160 * 1024 && k.max_total <= 1024 && s.top_k >= 1 && s.top_k <= SORT_CAP, Y4_EINVAL,
                "soft nms: top_k %d, max_total %d and %d classes need %zu bytes of LDS", s.top_k, k.max_total, k.C, lds);
-    Y4_REQUIRE((k.kind == 0 || k.kind == 1) && (k.agnostic == 0 || k.agnostic == 1) && k.beta > 0.f, Y4_EINVAL,
-               "soft nms: rule (kind %d, beta %g, agnostic %d)", k.kind, (double)k.beta, k.agnostic);
+    if (int r = nms_rule_check("soft nms", k.kind, k.beta, k.agnostic)) return r;
     Y4_REQUIRE(s.method >= SOFT_GAUSSIAN && s.method <= SOFT_HARD && s.sigma > 0.f && s.min_score >= 0.f, Y4_EINVAL,
                "soft nms: mode (method %d, sigma %g, min_score %g)", s.method, (double)s.sigma, (double)s.min_score);
-    // [measure][agnostic][method - 1]
-    using Launch = int (*)(int, dim3, dim3, size_t, hipStream_t, const NmsK&, const SoftNmsK&);
-#define Y4_SOFT_ROW(KIND, AGN)                                                                                                      \
-    {launch_lds<soft_nms_kernel<KIND, AGN, SOFT_GAUSSIAN>, NmsK, SoftNmsK>, launch_lds<soft_nms_kernel<KIND, AGN, SOFT_LINEAR>, NmsK, SoftNmsK>, \
-     launch_lds<soft_nms_kernel<KIND, AGN, SOFT_HARD>, NmsK, SoftNmsK>}
-    static const Launch table[3][2][3] = {
-        {Y4_SOFT_ROW(NMS_IOU, false), Y4_SOFT_ROW(NMS_IOU, true)},
-        {Y4_SOFT_ROW(NMS_DIOU1, false), Y4_SOFT_ROW(NMS_DIOU1, true)},
-        {Y4_SOFT_ROW(NMS_DIOU, false), Y4_SOFT_ROW(NMS_DIOU, true)},
-    };
-#undef Y4_SOFT_ROW
-    const int measure = k.kind == 0 ? NMS_IOU : (k.beta == 1.0f ? NMS_DIOU1 : NMS_DIOU);
-    return table[measure][k.agnostic][s.method - 1](160 * 1024, dim3(k.N), dim3(NMS_THREADS), lds, stream, k, s);
+    return nms_dispatch<SoftKernel>(std::make_index_sequence<6 * 3>(), s.method, lds, stream, k, s);
 }
 
 }  // namespace y4

@@ -30,7 +30,7 @@ import numpy as np
 
 from . import prepost, tiling, weights as W
 from .config import yolo_config
-from .engine import Engine
+from .engine import NMS_OPTIONS, Engine
 from .plan import build_plan
 
 
@@ -94,13 +94,13 @@ class Yolov4(object):
         # score_threshold, whatever a call's run-time thresholds are) and the nms_top_k best candidates of a list taking part.  Like
         # the rule it is state of both engines and in force for everything nms_kind is in force for, over tiles and views too; it
         # is no part of a checkpoint or a schedule.
-        Engine._soft_mode(nms_soft, nms_sigma, nms_soft_min_score, nms_top_k)      # (raises ValueError)
+        Engine._decay_mode("soft", nms_soft, nms_sigma, nms_soft_min_score, nms_top_k)      # (raises ValueError)
         self.nms_soft, self.nms_sigma, self.nms_top_k = nms_soft, float(nms_sigma), int(nms_top_k)
         self.nms_soft_min_score = None if nms_soft_min_score is None else float(nms_soft_min_score)
         # nms_matrix='gaussian' | 'linear' (None: off): Matrix-NMS (Engine.set_nms_matrix) -- one-shot score decay by the earlier
         # candidates of a class, no pick sequence; nms_sigma, nms_soft_min_score and nms_top_k parameterise whichever of nms_soft /
         # nms_matrix is set, and the two exclude each other.  In force wherever nms_soft would be.
-        if Engine._matrix_mode(nms_matrix, nms_sigma, nms_soft_min_score, nms_top_k)[0] and nms_soft is not None:      # (raises ValueError)
+        if Engine._decay_mode("matrix", nms_matrix, nms_sigma, nms_soft_min_score, nms_top_k)[0] and nms_soft is not None:      # (raises ValueError)
             raise ValueError(f"nms_soft={nms_soft!r} and nms_matrix={nms_matrix!r} exclude each other")
         self.nms_matrix = nms_matrix
         # letterbox=True: predict_img / predict / export_prediction resize each image with its aspect ratio kept, centred on a
@@ -126,14 +126,15 @@ class Yolov4(object):
         self._tune_eager = tune is True
         self.build_model(load_pretrained=True if self.weight_path else False)
 
+    def nms_options(self):
+        """The `nms_*` keywords both engines are built with: this object's attributes of those names."""
+        return {k: getattr(self, k) for k in NMS_OPTIONS}
+
     def build_model(self, load_pretrained=True):
         self.plan = build_plan(self.img_size[:2], self.num_classes)
         # alias_workspace: like the reference's Keras model, the facade keeps no intermediate activations (2.7x less HBM)
         self.engine = Engine(self.num_classes, self.config, max_batch=self._max_batch, dtype=self._dtype,
-                             device=self._device, alias_workspace=True, box_loss=self.box_loss,
-                             nms_kind=self.nms_kind, nms_beta=self.nms_beta, nms_agnostic=self.nms_agnostic,
-                             nms_merge=self.nms_merge, nms_soft=self.nms_soft, nms_sigma=self.nms_sigma,
-                             nms_soft_min_score=self.nms_soft_min_score, nms_top_k=self.nms_top_k, nms_matrix=self.nms_matrix)
+                             device=self._device, alias_workspace=True, box_loss=self.box_loss, **self.nms_options())
         self.yolo_model = _KerasLikeModel(self._tuned_first(self.engine.forward_heads), 'yolo_model')
         print(f"nms iou: {self.config['iou_threshold']} score: {self.config['score_threshold']}")
         self._thresholds = (-1.0, -1.0)  # what inference_model runs with (-1: the config's); load_model changes them
@@ -397,9 +398,7 @@ class Yolov4(object):
         if eng is None:
             eng = Engine(self.num_classes, self.config, max_batch=self._max_batch, dtype=self._dtype,
                          device=self._device, alias_workspace=True, retain_head_inputs=level, box_loss=self.box_loss,
-                         nms_kind=self.nms_kind, nms_beta=self.nms_beta, nms_agnostic=self.nms_agnostic,
-                             nms_merge=self.nms_merge, nms_soft=self.nms_soft, nms_sigma=self.nms_sigma,
-                             nms_soft_min_score=self.nms_soft_min_score, nms_top_k=self.nms_top_k, nms_matrix=self.nms_matrix)
+                         **self.nms_options())
             setattr(self, name, eng)
         eng.load_weight_blob(self._flat)
         self.engine.copy_schedule_to(eng)

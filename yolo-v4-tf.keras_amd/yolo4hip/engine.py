@@ -65,30 +65,27 @@ def _block_views(flat, fields):
     return views
 
 
+# the keywords of the NMS stage, of Engine and of Yolov4 alike
+NMS_OPTIONS = ("nms_kind", "nms_beta", "nms_agnostic", "nms_merge", "nms_soft", "nms_sigma", "nms_soft_min_score", "nms_top_k", "nms_matrix")
+
+
 class Engine:
     def __init__(self, num_classes, config=None, max_batch=32, dtype="f32", device=None, alias_workspace=False,
-                 retain_head_inputs=False, *, max_per_class=100, max_total=100, box_loss="giou",
-                 nms_kind="iou", nms_beta=0.6, nms_agnostic=False, nms_merge=False,
-                 nms_soft=None, nms_sigma=0.5, nms_soft_min_score=None, nms_top_k=4096, nms_matrix=None):
-        self._build(num_classes, config, max_batch, dtype, device, alias_workspace, retain_head_inputs, None,
-                    max_per_class=max_per_class, max_total=max_total, box_loss=box_loss,
-                    nms_kind=nms_kind, nms_beta=nms_beta, nms_agnostic=nms_agnostic, nms_merge=nms_merge,
-                    nms_soft=nms_soft, nms_sigma=nms_sigma, nms_soft_min_score=nms_soft_min_score, nms_top_k=nms_top_k,
-                    nms_matrix=nms_matrix)
+                 retain_head_inputs=False, **kw):
+        """**kw: the keyword-only arguments of `_build`, where their defaults are written."""
+        self._build(num_classes, config, max_batch, dtype, device, alias_workspace, retain_head_inputs, None, **kw)
 
     def _build(self, num_classes, config, max_batch, dtype, device, alias_workspace, retain_head_inputs, parent, *,
                max_per_class=100, max_total=100, box_loss="giou", nms_kind="iou", nms_beta=0.6, nms_agnostic=False,
-               nms_merge=False, nms_soft=None, nms_sigma=0.5, nms_soft_min_score=None, nms_top_k=4096, nms_matrix=None,
-               matrix_params=None):
+               nms_merge=False, nms_soft=None, nms_sigma=0.5, nms_soft_min_score=None, nms_top_k=4096, nms_matrix=None):
         """What `__init__` and `sibling` share: the handle, its workspaces and every attribute.  `parent` is None for an engine
         with weights of its own, or the engine whose packed weights and schedule this one takes over."""
         box_kind = self._box_kind(box_loss)           # (an unknown name is refused before anything is loaded or created)
         nms_rule = self._nms_rule(nms_kind, nms_beta, nms_agnostic)      # (likewise)
         self.nms_merge = self._merge_flag(nms_merge)                     # (likewise); a sibling takes its parent's
-        soft_mode = self._soft_mode(nms_soft, nms_sigma, nms_soft_min_score, nms_top_k)      # (likewise)
-        # nms_sigma / nms_soft_min_score / nms_top_k parameterise whichever of nms_soft / nms_matrix is set (a sibling hands over
-        # its parent's Matrix-NMS values in `matrix_params`)
-        matrix_mode = self._matrix_mode(nms_matrix, *(matrix_params or (nms_sigma, nms_soft_min_score, nms_top_k)))
+        # nms_sigma / nms_soft_min_score / nms_top_k parameterise whichever of nms_soft / nms_matrix is set
+        soft_mode = self._decay_mode("soft", nms_soft, nms_sigma, nms_soft_min_score, nms_top_k)      # (likewise)
+        matrix_mode = self._decay_mode("matrix", nms_matrix, nms_sigma, nms_soft_min_score, nms_top_k)
         if soft_mode[0] and matrix_mode[0]:
             raise ValueError(f"nms_soft={nms_soft!r} and nms_matrix={nms_matrix!r} exclude each other")
         import torch
@@ -116,9 +113,9 @@ class Engine:
         # nms_kind / nms_beta / nms_agnostic: the pair rule of the NMS stage (`set_nms_rule`); a sibling takes its parent's
         self._apply_nms_rule(nms_rule)
         # nms_soft / nms_sigma / nms_soft_min_score / nms_top_k: Soft-NMS instead of hard suppression (`set_nms_soft`); likewise
-        self._apply_soft_mode(soft_mode)
-        # nms_matrix: Matrix-NMS (`set_nms_matrix`); likewise
-        self._apply_matrix_mode(matrix_mode)
+        self._apply_decay_mode("soft", soft_mode)
+        # nms_matrix: Matrix-NMS (`set_nms_matrix`); likewise -- and its own sigma, floor and top_k, which no keyword carries
+        self._apply_decay_mode("matrix", matrix_mode if parent is None else parent._decay_state("matrix"))
         flops, nbox, hcs, wfl = C.c_int64(), C.c_int32(), C.c_int32(), C.c_int64()
         ext.check(self.lib.y4_model_info(self.handle, C.byref(flops), C.byref(nbox), C.byref(hcs), C.byref(wfl)))
         self.flops_per_image, self.num_boxes = flops.value, nbox.value
@@ -167,11 +164,7 @@ class Engine:
         overlap the other batch's kernels.  Results are those of this engine, bit for bit."""
         e = Engine.__new__(Engine)
         e._build(self.num_classes, self.config, self.max_batch, self.dtype, self.device, self.alias_workspace, self.retain_level, self,
-                 max_per_class=self.cfg.max_per_class, max_total=self.cfg.max_total, box_loss=self.box_loss,
-                 nms_kind=self.nms_kind, nms_beta=self.nms_beta, nms_agnostic=self.nms_agnostic, nms_merge=self.nms_merge,
-                 nms_soft=self.nms_soft, nms_sigma=self.nms_sigma, nms_soft_min_score=self.nms_soft_min_score,
-                 nms_top_k=self.nms_top_k, nms_matrix=self.nms_matrix,
-                 matrix_params=(self.nms_matrix_sigma, self.nms_matrix_min_score, self.nms_matrix_top_k))
+                 max_per_class=self.cfg.max_per_class, max_total=self.cfg.max_total, box_loss=self.box_loss, **self.nms_options())
         return e
 
     BOX_LOSSES = ("giou", "ciou")          # the kinds of y4_set_box_loss, by number
@@ -205,9 +198,9 @@ class Engine:
             raise ValueError(f"nms_agnostic must be False or True, got {agnostic!r}")
         return cls.NMS_KINDS.index(kind), b, int(bool(agnostic))
 
-    def _apply_nms_rule(self, rule):
+    def _apply_nms_rule(self, rule, force=False):
         kind, beta, agnostic = rule
-        if rule != (0, 1.0, 0):                   # (that is the handle's own rule: 'iou' ignores beta, nothing to set)
+        if force or rule != (0, 1.0, 0):          # (that is the handle's own rule: 'iou' ignores beta, nothing to set)
             ext.check(self.lib.y4_set_nms_rule(self.handle, kind, 1.0 if kind == 0 else beta, agnostic))
         self.nms_kind, self.nms_beta, self.nms_agnostic = self.NMS_KINDS[kind], beta, bool(agnostic)
 
@@ -217,20 +210,23 @@ class Engine:
         or 'diou' -- iff IoU - (d^2 / c^2)^beta > iou_threshold (DIoU-NMS; Darknet's nms_kind=diounms, beta_nms=0.6); agnostic:
         a kept box suppresses later candidates of every class, not only its own.  `beta` is ignored by 'iou' but validated.
         The stream siblings this engine already has follow; siblings made later inherit it."""
-        rule = self._nms_rule(kind, beta, agnostic)
-        ext.check(self.lib.y4_set_nms_rule(self.handle, rule[0], 1.0 if rule[0] == 0 else rule[1], rule[2]))
-        self.nms_kind, self.nms_beta, self.nms_agnostic = self.NMS_KINDS[rule[0]], rule[1], bool(rule[2])
-        for e in getattr(self, "_stream_siblings", []):
-            e.set_nms_rule(kind, beta, agnostic)
+        self._apply_nms_rule(self._nms_rule(kind, beta, agnostic), force=True)
+        self._tell_siblings("set_nms_rule", kind, beta, agnostic)
 
     SOFT_METHODS = (None, "gaussian", "linear", "hard")      # the methods of y4_set_nms_soft, by number
+    MATRIX_METHODS = (None, "gaussian", "linear")            # the methods of y4_set_nms_matrix, by number
     SOFT_TOP_K_MAX = 4096
+    # the two score-decay modes: (method names, setter, the attributes of method / sigma / min_score / top_k -- the first is also the
+    # keyword of the method).  The keywords nms_sigma / nms_soft_min_score / nms_top_k serve both, so messages name those.
+    _DECAY = {"soft": (SOFT_METHODS, "y4_set_nms_soft", ("nms_soft", "nms_sigma", "nms_soft_min_score", "nms_top_k")),
+              "matrix": (MATRIX_METHODS, "y4_set_nms_matrix", ("nms_matrix", "nms_matrix_sigma", "nms_matrix_min_score", "nms_matrix_top_k"))}
 
     @classmethod
-    def _soft_mode(cls, method, sigma, min_score, top_k):
+    def _decay_mode(cls, family, method, sigma, min_score, top_k):
         """-> (method number, sigma, min_score or None, top_k), or ValueError.  Every value is validated for every method."""
-        if method is not None and not isinstance(method, str) or method not in cls.SOFT_METHODS:
-            raise ValueError(f"nms_soft must be one of {cls.SOFT_METHODS}, got {method!r}")
+        methods, _, attrs = cls._DECAY[family]
+        if method is not None and not isinstance(method, str) or method not in methods:
+            raise ValueError(f"{attrs[0]} must be one of {methods}, got {method!r}")
         try:
             sg = float(sigma)
         except (TypeError, ValueError):
@@ -247,13 +243,35 @@ class Engine:
                 raise ValueError(f"nms_soft_min_score must be None or a number in [0, 1), got {min_score!r}")
         if isinstance(top_k, (bool, np.bool_)) or not isinstance(top_k, (int, np.integer)) or not 1 <= int(top_k) <= cls.SOFT_TOP_K_MAX:
             raise ValueError(f"nms_top_k must be an integer in 1 .. {cls.SOFT_TOP_K_MAX}, got {top_k!r}")
-        return cls.SOFT_METHODS.index(method), sg, ms, int(top_k)
+        return methods.index(method), sg, ms, int(top_k)
 
-    def _apply_soft_mode(self, mode, force=False):
+    def _decay_state(self, family):
+        """The mode of `family` this engine is in, as `_decay_mode` returns it."""
+        methods, _, attrs = self._DECAY[family]
+        method, sigma, min_score, top_k = (getattr(self, a) for a in attrs)
+        return methods.index(method), sigma, min_score, top_k
+
+    def _apply_decay_mode(self, family, mode, force=False):
+        methods, setter, attrs = self._DECAY[family]
         method, sigma, min_score, top_k = mode
         if force or mode != (0, 0.5, None, self.SOFT_TOP_K_MAX):     # (that is the handle's own mode: nothing to set)
-            ext.check(self.lib.y4_set_nms_soft(self.handle, method, sigma, -1.0 if min_score is None else min_score, top_k))
-        self.nms_soft, self.nms_sigma, self.nms_soft_min_score, self.nms_top_k = self.SOFT_METHODS[method], sigma, min_score, top_k
+            ext.check(getattr(self.lib, setter)(self.handle, method, sigma, -1.0 if min_score is None else min_score, top_k))
+        for a, v in zip(attrs, (methods[method], sigma, min_score, top_k)):
+            setattr(self, a, v)
+
+    def _set_decay(self, family, method, sigma, min_score, top_k):
+        """`set_nms_soft` / `set_nms_matrix`: validate, refuse while the other mode is on, set, tell the stream siblings."""
+        mode = self._decay_mode(family, method, sigma, min_score, top_k)
+        own, other = self._DECAY[family][2][0], self._DECAY["matrix" if family == "soft" else "soft"][2][0]
+        if mode[0] and getattr(self, other, None) is not None:
+            raise ValueError(f"{own}={method!r} while {other}={getattr(self, other)!r}: the two decay modes exclude each other")
+        self._apply_decay_mode(family, mode, force=True)
+        self._tell_siblings("set_" + own, method, sigma, min_score, top_k)
+
+    def _tell_siblings(self, setter, *args):
+        """The stream siblings this engine already has follow a setter of NMS state."""
+        for e in getattr(self, "_stream_siblings", []):
+            getattr(e, setter)(*args)
 
     def set_nms_soft(self, method, sigma=0.5, min_score=None, top_k=4096):
         """Soft-NMS for every later predict / decode_nms / nms_gathered / predict_tiled / predict_tta call of this engine
@@ -266,29 +284,7 @@ class Engine:
         candidates of a list take part (at most 4096).  Every value is validated for every method.  With `nms_merge` on, the
         merge runs behind it unchanged: only the boxes move.  The stream siblings this engine already has follow; siblings made
         later inherit it."""
-        mode = self._soft_mode(method, sigma, min_score, top_k)
-        if mode[0] and getattr(self, "nms_matrix", None) is not None:
-            raise ValueError(f"nms_soft={method!r} while nms_matrix={self.nms_matrix!r}: the two decay modes exclude each other")
-        self._apply_soft_mode(mode, force=True)
-        for e in getattr(self, "_stream_siblings", []):
-            e.set_nms_soft(method, sigma, min_score, top_k)
-
-    MATRIX_METHODS = (None, "gaussian", "linear")      # the methods of y4_set_nms_matrix, by number
-
-    @classmethod
-    def _matrix_mode(cls, method, sigma, min_score, top_k):
-        """-> (method number, sigma, min_score or None, top_k), or ValueError.  Every value is validated for every method."""
-        if method is not None and not isinstance(method, str) or method not in cls.MATRIX_METHODS:
-            raise ValueError(f"nms_matrix must be one of {cls.MATRIX_METHODS}, got {method!r}")
-        _, sg, ms, k = cls._soft_mode(None, sigma, min_score, top_k)      # (the same ranges)
-        return cls.MATRIX_METHODS.index(method), sg, ms, k
-
-    def _apply_matrix_mode(self, mode, force=False):
-        method, sigma, min_score, top_k = mode
-        if force or mode != (0, 0.5, None, self.SOFT_TOP_K_MAX):     # (that is the handle's own mode: nothing to set)
-            ext.check(self.lib.y4_set_nms_matrix(self.handle, method, sigma, -1.0 if min_score is None else min_score, top_k))
-        self.nms_matrix, self.nms_matrix_sigma = self.MATRIX_METHODS[method], sigma
-        self.nms_matrix_min_score, self.nms_matrix_top_k = min_score, top_k
+        self._set_decay("soft", method, sigma, min_score, top_k)
 
     def set_nms_matrix(self, method, sigma=0.5, min_score=None, top_k=4096):
         """Matrix-NMS (Wang et al. 2020) for every later predict / decode_nms / nms_gathered / predict_tiled / predict_tta call of
@@ -300,12 +296,11 @@ class Engine:
         config's score_threshold) in their new order, under max_per_class and max_total.  iou_threshold plays no part in the
         decay.  It excludes Soft-NMS: ValueError when `nms_soft` is on (and `set_nms_soft` refuses while this is on).  The
         stream siblings this engine already has follow; siblings made later inherit it."""
-        mode = self._matrix_mode(method, sigma, min_score, top_k)
-        if mode[0] and self.nms_soft is not None:
-            raise ValueError(f"nms_matrix={method!r} while nms_soft={self.nms_soft!r}: the two decay modes exclude each other")
-        self._apply_matrix_mode(mode, force=True)
-        for e in getattr(self, "_stream_siblings", []):
-            e.set_nms_matrix(method, sigma, min_score, top_k)
+        self._set_decay("matrix", method, sigma, min_score, top_k)
+
+    def nms_options(self):
+        """The `nms_*` keywords an Engine in this one's NMS state is built with (`sibling`; `Yolov4.nms_options` is its twin)."""
+        return {k: getattr(self, k) for k in NMS_OPTIONS}
 
     @staticmethod
     def _merge_flag(on):
@@ -321,8 +316,7 @@ class Engine:
         bit for bit; only the boxes move.  Host state of this object: with the flag off every call is the plain entry point.
         The stream siblings this engine already has follow; siblings made later inherit it."""
         self.nms_merge = self._merge_flag(on)
-        for e in getattr(self, "_stream_siblings", []):
-            e.set_nms_merge(on)
+        self._tell_siblings("set_nms_merge", on)
 
     def _merge_counts(self, n):
         """The [n] int32 device words the merged entry points save the candidate counts in (kept for the engine's lifetime)."""
