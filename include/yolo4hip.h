@@ -749,6 +749,47 @@ typedef struct y4_mosaic_cut { int32_t cut_y, cut_x; } y4_mosaic_cut;   /* 8 byt
 int y4_mosaic_u8_ragged(const uint8_t* src_dev, const y4_augment_desc* tiles_dev /* [n][4] */,
                         const y4_mosaic_cut* cuts_dev /* [n] */, int n, uint8_t* out_dev, int H, int W, int pad_value,
                         void* stream);
+/* One 8-bit 4:2:0 video frame for y4_yuv_u8_ragged: a luma plane h x w with row pitch y_pitch at byte y_offset of the source
+ * buffer, and two chroma planes subsampled 2 x 2 -- ceil(h / 2) rows of ceil(w / 2) samples, so odd sizes are legal -- at
+ * u_offset and v_offset with row pitch c_pitch and c_step bytes between two samples of one plane:
+ *   NV12   v_offset = u_offset + 1, c_step = 2 (one interleaved UV plane);     NV21   u_offset = v_offset + 1, c_step = 2;
+ *   I420   c_step = 1, the U plane before the V plane;                         YV12   c_step = 1, V before U.
+ * A decoder surface with its own pitch is described in place.  out_h, out_w, pad_top, pad_left as y4_image_desc.
+ * `flags`: bit 0 selects the BT.709 matrix (0: BT.601), bit 1 full range (0: limited range, Y 16..235, chroma 16..240). */
+typedef struct y4_yuv_desc {
+    int64_t y_offset, u_offset, v_offset;
+    int32_t y_pitch, c_pitch, c_step;
+    int32_t h, w, out_h, out_w, pad_top, pad_left;
+    int32_t flags;
+} y4_yuv_desc;                                       /* 64 bytes */
+#define Y4_YUV_BT709 1
+#define Y4_YUV_FULL_RANGE 2
+/* Colour conversion and resize of video frames in one launch: frame i (desc_dev[i]) -> slot i of the uint8 [n,H,W,3] batch.
+ * Slot i holds the bytes y4_resize_u8_ragged writes, with the same out_h, out_w, pad_top, pad_left and pad_value, for the packed
+ * RGB frame that the following rule gives at SOURCE resolution:
+ *   chroma   source pixel (y, x) takes U = src[u_offset + (y >> 1) * c_pitch + (x >> 1) * c_step], V likewise: sample replication,
+ *            no siting and no chroma interpolation;
+ *   colour   integers only, sums in int32, arithmetic shift.  C = Y - y0 (y0 = 16 limited range, 0 full range), D = U - 128,
+ *            E = V - 128;
+ *              R = clamp8((cy C + crv E + 8192) >> 14)
+ *              G = clamp8((cy C + cgu D + cgv E + 8192) >> 14)
+ *              B = clamp8((cy C + cbu D + 8192) >> 14)
+ *            every coefficient is floor(c 2^14 + 0.5) of the real coefficient from (Kr, Kb); for limited range the luma scale is
+ *            255/219 and the chroma scale 255/224:
+ *                                  cy     crv    cgu     cgv    cbu
+ *              BT.601 limited   19077   26149  -6419  -13320  33050      (flags 0)
+ *              BT.601 full      16384   22970  -5638  -11700  29032      (flags 2)
+ *              BT.709 limited   19077   29372  -3494   -8731  34610      (flags 1)
+ *              BT.709 full      16384   25802  -3069   -7670  30402      (flags 3)
+ *   resize   each of the four bilinear taps is converted, then the arithmetic of y4_resize_u8 runs on the converted taps; a
+ *            frame with h == out_h and w == out_w is converted and copied.  Nothing is interpolated in YUV.
+ * yolo4hip/yuv.py: to_rgb is the rule in NumPy.  The arguments are checked on the host as in y4_resize_u8_ragged (NULL pointers,
+ * n in 1..65535, H, W > 0, pad_value in 0..255, an output of 2^31 bytes or more: Y4_EINVAL before any launch).  The descriptors
+ * live on the device and are NOT checked: the caller owns the table's correctness (every plane inside the source buffer, c_step
+ * 1 or 2, y_pitch >= w, c_pitch >= c_step * ceil(w / 2), h, w, out_h, out_w >= 1, the rectangle inside the canvas).  Bytes of the
+ * pitch padding are never read. */
+int y4_yuv_u8_ragged(const uint8_t* src_dev, const y4_yuv_desc* desc_dev, int n, uint8_t* out_dev, int H, int W, int pad_value,
+                     void* stream);
 /* ---- VOC mAP matching on the device: the per-image matching of `eval_map` (reference models.py:282-330; yolo4hip/evalmap.py) on
  * the boxes y4_decode_nms(_mapped) left on the device, so that a validation batch returns to the host as flags (yolo4hip/mapeval.py
  * turns them into AP).  No handle.  Per image, one workgroup:

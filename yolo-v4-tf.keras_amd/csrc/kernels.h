@@ -79,6 +79,9 @@ int augment_u8_ragged_launch(const uint8_t* src, const y4_augment_desc* desc, in
                              hipStream_t stream);
 int mosaic_u8_ragged_launch(const uint8_t* src, const y4_augment_desc* tiles, const y4_mosaic_cut* cuts, int n, uint8_t* out, int H,
                             int W, int pad, hipStream_t stream);
+// yuv_u8.hip: the same template on 8-bit 4:2:0 video frames, converted to RGB tap by tap
+int yuv_u8_ragged_launch(const uint8_t* src, const y4_yuv_desc* desc, int n, uint8_t* out, int H, int W, int pad,
+                         hipStream_t stream);
 
 // map_match.hip: VOC mAP matching of kept boxes against ground truth, one workgroup per image
 int map_match_launch(const float* boxes, const float* scores, const float* classes, const int32_t* valid, int n, int max_total,

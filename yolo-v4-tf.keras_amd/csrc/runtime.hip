@@ -2333,6 +2333,11 @@ int y4_mosaic_u8_ragged(const uint8_t* src_dev, const y4_augment_desc* tiles_dev
     return mosaic_u8_ragged_launch(src_dev, tiles_dev, cuts_dev, n, out_dev, H, W, pad_value, (hipStream_t)stream);
 }
 
+int y4_yuv_u8_ragged(const uint8_t* src_dev, const y4_yuv_desc* desc_dev, int n, uint8_t* out_dev, int H, int W, int pad_value,
+                     void* stream) {
+    return yuv_u8_ragged_launch(src_dev, desc_dev, n, out_dev, H, W, pad_value, (hipStream_t)stream);
+}
+
 int y4_map_match(const float* boxes_dev, const float* scores_dev, const float* classes_dev, const int32_t* valid_dev, int n,
                  int max_total, const float* scale_dev, const float* gt_dev, const int32_t* gt_count_dev, int max_gt,
                  const double* iou_thresholds, int n_thresholds, uint32_t* tp_mask_dev, double* best_iou_dev, int32_t* match_dev,

@@ -631,6 +631,18 @@ class Yolov4(object):
         iou, score = self._thresholds
         return self.engine.predict(imgs, iou_threshold=iou, score_threshold=score, box_map=box_map)
 
+    # ---- video frames: not in the reference.  8-bit YUV 4:2:0 frames as a decoder delivers them (yolo4hip/yuv.py: YuvFrame) are
+    # uploaded as they are, 1.5 bytes per pixel, and converted and resized in one launch (Engine.preprocess_yuv_batch).  Honours this
+    # object's letterbox / pad_value, thresholds and every NMS setting.
+    def predict_yuv(self, frames, *, matrix='bt601', full_range=False, fmt='nv12'):
+        """frames: one `YuvFrame` or a list of them, any mix of sizes, formats and pitches (a 2-D uint8 array [h + h // 2, w] with
+        even h, w is a frame of format `fmt`) -> (boxes [n,100,4] normalised to each frame, scores, classes, valid), the form of
+        inference_model.predict.  matrix: 'bt601' or 'bt709'; full_range: Y 0..255 instead of 16..235.  The detections are
+        those of the RGB frames `yuv.to_rgb` gives, bit for bit."""
+        imgs, box_map = self.engine.preprocess_yuv_batch(frames, letterbox=self._letterbox, pad_value=self._pad_value,
+                                                         matrix=matrix, full_range=full_range, fmt=fmt)
+        return self._predict_mapped(imgs, box_map)
+
     # ---- reference models.py:109-123 (raw_img: RGB)
     def predict_img(self, raw_img, random_color=True, plot_img=True, figsize=(10, 10), show_text=True,
                     return_output=False):

@@ -482,6 +482,36 @@ class Engine:
                                   pad_value)
         return out, dev[desc_bytes:head].view(torch.float32).view(n, 4)
 
+    def preprocess_yuv_batch(self, frames, letterbox=False, pad_value=128, matrix='bt601', full_range=False, fmt='nv12'):
+        """`preprocess_u8_batch` for 8-bit 4:2:0 video frames: `frames` is one `yuv.YuvFrame` or a list of them, of ANY mix of
+        sizes, formats (nv12, nv21, i420, yv12) and pitches; a 2-D uint8 array [h + h // 2, w] with even h, w (the rawvideo
+        layout) is a frame of format `fmt`.  The frames and their y4_yuv_desc table are packed into the one pinned staging buffer,
+        cross PCIe in one copy at 1.5 bytes per pixel, and one launch (`y4_yuv_u8_ragged`) converts and resizes: the batch is,
+        byte for byte, `preprocess_u8_batch` of `yuv.to_rgb(frame, matrix, full_range)`.
+        -> (uint8 cuda tensor [n,H,W,3], float32 cuda tensor [n,4] box map: prepost.box_map of each frame's h, w).
+        Asynchronous on the current stream."""
+        torch = self.torch
+        from . import prepost, yuv
+        frames = yuv.as_frames(frames, fmt)
+        word = yuv.flags(matrix, full_range)
+        pad_value = int(pad_value)
+        if not 0 <= pad_value <= 255:
+            raise ValueError(f"pad_value must be a uint8 level 0..255, got {pad_value}")
+        n = len(frames)
+        H, W = self.img_hw
+        desc = (ext.y4_yuv_desc * n)()
+        maps = np.empty((n, 4), np.float32)
+        for i, f in enumerate(frames):
+            rect = prepost.letterbox_rect(f.h, f.w, H, W) if letterbox else (H, W, 0, 0)
+            d = desc[i]
+            d.out_h, d.out_w, d.pad_top, d.pad_left = rect
+            maps[i] = prepost.box_map(f.h, f.w, H, W, rect)
+        dev, desc_bytes, head = self._upload_ragged([f.data[:f.nbytes] for f in frames], desc, maps,
+                                                    place=lambda d, k, off: frames[k].fill_desc(d, off, word))
+        out = self._canvas_launch(self.lib.y4_yuv_u8_ragged, C.c_void_p(dev.data_ptr() + head), (ext.ptr(dev),), n, None,
+                                  pad_value)
+        return out, dev[desc_bytes:head].view(torch.float32).view(n, 4)
+
     def augment_u8_batch(self, raw_imgs, params, pad_value=128):
         """The training input of `Yolov4.fit` on the device: uint8 RGB images [h,w,3] of any mix of sizes and one parameter row
         per image (yolo4hip.augment.PARAM_DTYPE: `draw_params`) -> the augmented uint8 cuda batch [n,H,W,3] for
@@ -559,13 +589,14 @@ class Engine:
                 raise ValueError(f"expected uint8 [h,w,3] images, got {getattr(a, 'dtype', type(a))} {getattr(a, 'shape', '')}")
         return raw_imgs, pad_value
 
-    def _upload_ragged(self, raw_imgs, desc, extra=None, rows=None, windows=None):
+    def _upload_ragged(self, raw_imgs, desc, extra=None, rows=None, windows=None, place=None):
         """The one upload of a ragged batch (`preprocess_u8_batch`, `augment_u8_batch`, `mosaic_u8_batch`, `predict_tiled`): fills
         offset, h, w of every row of `desc` (a ctypes array of y4_image_desc or y4_augment_desc; row k describes image k, or image
         rows[k] where `rows` is given: rows may share an image), packs descriptors | `extra` (a numpy array, or None) | the images
         into the pinned staging buffer (kept across calls) and copies it to a fresh device block in one copy.  With `windows` (one
         (y0, x0, wh, ww) per row, inside image rows[k]) `desc` is an array of y4_window_desc: offset is then the window's first
-        pixel, pitch the image's row, h and w the window's.
+        pixel, pitch the image's row, h and w the window's.  With `place` the sources are byte buffers of any layout (video frames)
+        and place(row, k, offset) fills row k's source fields itself.
         -> (device block, descriptor bytes, bytes before the first image); descriptor offsets count from the first image byte."""
         torch = self.torch
         n = len(raw_imgs)
@@ -574,7 +605,7 @@ class Engine:
         offs, off = [], 0
         for a in raw_imgs:
             offs.append(off)
-            off += a.shape[0] * a.shape[1] * 3
+            off += a.size
         if windows is not None:
             for d, k, (y0, x0, wh, ww) in zip(desc, rows, windows):
                 ih, iw = raw_imgs[k].shape[:2]
@@ -583,7 +614,10 @@ class Engine:
                 d.offset, d.pitch, d.h, d.w = offs[k] + (y0 * iw + x0) * 3, iw * 3, wh, ww
         else:
             for d, k in zip(desc, range(n) if rows is None else rows):
-                d.offset, d.h, d.w = offs[k], raw_imgs[k].shape[0], raw_imgs[k].shape[1]
+                if place is not None:
+                    place(d, k, offs[k])
+                else:
+                    d.offset, d.h, d.w = offs[k], raw_imgs[k].shape[0], raw_imgs[k].shape[1]
         total = head + off
         pin = getattr(self, "_batch_pin", None)
         if pin is None or pin.numel() < total:
@@ -624,6 +658,12 @@ class Engine:
         """y4_resize_u8_ragged on device buffers: `desc_dev` holds n y4_image_desc rows (offsets into `src_dev`), `out` is a
         uint8 cuda tensor of at least [n,H,W,3].  Asynchronous on the current stream; returns out[:n]."""
         return self._canvas_launch(self.lib.y4_resize_u8_ragged, ext.ptr(src_dev), (ext.ptr(desc_dev),), n, out, pad_value)
+
+    def yuv_u8_ragged(self, src_dev, desc_dev, n, out, pad_value=128):
+        """y4_yuv_u8_ragged on device buffers: `desc_dev` holds n y4_yuv_desc rows (planes of 4:2:0 frames in `src_dev`, a
+        decoder's surfaces for instance), `out` is a uint8 cuda tensor of at least [n,H,W,3].  Asynchronous on the current
+        stream; returns out[:n]."""
+        return self._canvas_launch(self.lib.y4_yuv_u8_ragged, ext.ptr(src_dev), (ext.ptr(desc_dev),), n, out, pad_value)
 
     def window_u8_ragged(self, src_dev, desc_dev, n, out, pad_value=128):
         """y4_window_u8_ragged on device buffers: `desc_dev` holds n y4_window_desc rows (windows of images in `src_dev`), `out`
@@ -1390,7 +1430,8 @@ class Engine:
         """Copy the master kernels of `state` back into the host stream `flat` (in place); the BatchNormalization vectors stay."""
         return self._group_weights_to_flat("blocks", state, flat)
 
-    def predict_stream(self, batches, with_indices=False, in_flight=None, letterbox=False, pad_value=128):
+    def predict_stream(self, batches, with_indices=False, in_flight=None, letterbox=False, pad_value=128, yuv=None,
+                       matrix='bt601', full_range=False):
         """Pipelined `inference_model.predict` over an iterable of uint8 batches ([n,h,w,3] numpy arrays or pinned torch
         tensors, n <= max_batch, any h,w): yields one result list per batch, in order.  A pinned tensor is uploaded from where
         it lies and may be refilled as soon as the generator yields (its upload is waited for before every yield).  While batch i computes, batch i+1 crosses PCIe as uint8
@@ -1405,9 +1446,19 @@ class Engine:
         aliased workspace and 1 with the plain one; pass `in_flight` to choose.
         letterbox=True: frames are letterboxed instead of stretched (`y4_resize_u8_ragged` with one descriptor per frame, all the
         same rectangle) and the boxes come back normalised to the frame (`y4_decode_nms_mapped`): what
-        `preprocess_u8_batch(letterbox=True)` + `predict(..., box_map=)` give, batch by batch."""
+        `preprocess_u8_batch(letterbox=True)` + `predict(..., box_map=)` give, batch by batch.
+        yuv='nv12' | 'nv21' | 'i420' | 'yv12': a batch is uint8 [n, h + h // 2, w] with even h, w -- n video frames in the
+        rawvideo layout, tight pitches -- and crosses PCIe as it is, 1.5 bytes per pixel instead of 3.  One launch
+        (`y4_yuv_u8_ragged`, the descriptor table built once per geometry) converts under `matrix` / `full_range` and writes the
+        network batch, stretched or letterboxed, also when the frame already has the network's size: the results are those of
+        this generator on the `yuv.to_rgb` frames.  yuv=None is the RGB path, launch for launch as before."""
         torch = self.torch
         dev = self.device
+        if yuv is not None:
+            from . import yuv as yuvmod
+            if yuv not in yuvmod.FORMATS:
+                raise ValueError(f"yuv must be None or one of {yuvmod.FORMATS}, got {yuv!r}")
+            yuv_flags = yuvmod.flags(matrix, full_range)
         copy_stream = torch.cuda.Stream(device=dev)        # uploads
         down_stream = torch.cuda.Stream(device=dev)        # results (its own stream: it waits for the compute stream)
         if in_flight is None:
@@ -1449,12 +1500,18 @@ class Engine:
             for bi, batch in enumerate(batches):
                 pinned_in = isinstance(batch, torch.Tensor) and batch.is_pinned() and batch.is_contiguous()
                 a = batch if pinned_in else np.ascontiguousarray(batch)
-                if a.dtype != (torch.uint8 if pinned_in else np.uint8) or a.ndim != 4 or a.shape[3] != 3 or not 1 <= a.shape[0] <= self.max_batch:
+                if yuv is not None:
+                    if a.dtype != (torch.uint8 if pinned_in else np.uint8) or a.ndim != 3 or not 1 <= a.shape[0] <= self.max_batch \
+                            or a.shape[1] < 3 or a.shape[1] % 3 or a.shape[2] < 2 or a.shape[2] % 2:
+                        raise ValueError(f"expected uint8 [n<={self.max_batch}, h + h // 2, w] {yuv} batches with even h, w, got "
+                                         f"{a.dtype} {tuple(a.shape)}")
+                elif a.dtype != (torch.uint8 if pinned_in else np.uint8) or a.ndim != 4 or a.shape[3] != 3 or not 1 <= a.shape[0] <= self.max_batch:
                     raise ValueError(f"expected uint8 [n<={self.max_batch},h,w,3] batches, got {a.dtype} {a.shape}")
                 sl = slots[bi % nslots]
                 eng, compute = engines[bi % in_flight], cstreams[bi % in_flight]     # batches alternate engines; slots rotate on their own
                 shape = tuple(a.shape)
-                key = (shape, bool(letterbox), int(pad_value))
+                key = (shape, bool(letterbox), int(pad_value)) if yuv is None else \
+                    (shape, bool(letterbox), int(pad_value), yuv, yuv_flags)
                 if sl.get("key") != key:                   # (re)allocate this slot's staging for the frame geometry
                     if "done" in sl:
                         sl["done"].synchronize()
@@ -1463,10 +1520,26 @@ class Engine:
                     sl["pin_np"] = sl["pin"].numpy()
                     sl["u8"] = torch.empty(shape, dtype=torch.uint8, device=dev)
                     # frames of another size are resized uint8 -> uint8 on the device; the /255 happens in the stem's load
-                    sl["net"] = None if shape[1:3] == tuple(self.img_hw) else \
+                    sl["net"] = None if yuv is None and shape[1:3] == tuple(self.img_hw) else \
                         torch.empty((self.max_batch, self.img_hw[0], self.img_hw[1], 3), dtype=torch.uint8, device=dev)
-                    sl["desc"] = sl["map"] = None
-                    if letterbox and sl["net"] is not None:
+                    sl["desc"] = sl["map"] = sl["yuv_desc"] = None
+                    if yuv is not None:
+                        # video frames: one y4_yuv_desc per frame, frame j at j * (h + h // 2) * w, every frame the same rectangle.
+                        # The boxes are mapped as on the RGB path: under letterbox, unless the frame has the network's size
+                        from . import prepost
+                        fh, fw = shape[1] // 3 * 2, shape[2]
+                        H, W = self.img_hw
+                        rect = prepost.letterbox_rect(fh, fw, H, W) if letterbox else (H, W, 0, 0)
+                        desc = (ext.y4_yuv_desc * self.max_batch)()
+                        layout = yuvmod.YuvFrame(np.empty((shape[1], fw), np.uint8), fmt=yuv)   # (the plane offsets of one frame)
+                        for j in range(self.max_batch):
+                            layout.fill_desc(desc[j], j * shape[1] * fw, yuv_flags)
+                            desc[j].out_h, desc[j].out_w, desc[j].pad_top, desc[j].pad_left = rect
+                        sl["yuv_desc"] = torch.from_numpy(np.frombuffer(desc, dtype=np.uint8).copy()).to(dev)
+                        if letterbox and (fh, fw) != (H, W):
+                            sl["map"] = torch.from_numpy(np.tile(prepost.box_map(fh, fw, H, W, rect), (self.max_batch, 1))).to(dev)
+                        torch.cuda.current_stream().synchronize()   # (read by the compute streams)
+                    elif letterbox and sl["net"] is not None:
                         # every frame of the slot has the same rectangle: one descriptor per frame, frame j at j * h * w * 3
                         from . import prepost
                         fh, fw = shape[1], shape[2]
@@ -1497,7 +1570,14 @@ class Engine:
                     sl["up"].record(copy_stream)
                 compute.wait_event(sl["up"])
                 with torch.cuda.stream(compute):
-                    if sl["desc"] is not None:             # letterbox: ragged resize, boxes mapped back to the frame in the NMS output
+                    if sl["yuv_desc"] is not None:         # video frames: convert + resize in one launch, always
+                        frames = eng.yuv_u8_ragged(sl["u8"], sl["yuv_desc"], n, sl["net"], pad_value)
+                        if sl["map"] is not None:
+                            eng.forward_device(frames)
+                            eng.decode_nms_device(n, tuple(t[:n] for t in sl["outs"]), box_map=sl["map"][:n])
+                        else:
+                            eng.predict_device(frames, tuple(t[:n] for t in sl["outs"]))
+                    elif sl["desc"] is not None:           # letterbox: ragged resize, boxes mapped back to the frame in the NMS output
                         frames = eng.resize_u8_ragged(sl["u8"], sl["desc"], n, sl["net"], pad_value)
                         eng.forward_device(frames)
                         eng.decode_nms_device(n, tuple(t[:n] for t in sl["outs"]), box_map=sl["map"][:n])

@@ -66,6 +66,12 @@ class y4_augment_desc(C.Structure):
     _fields_ = y4_image_desc._fields_ + [("flip", C.c_int32), ("hue", C.c_float), ("sat", C.c_float), ("val", C.c_float)]
 
 
+class y4_yuv_desc(C.Structure):
+    _fields_ = [("y_offset", C.c_int64), ("u_offset", C.c_int64), ("v_offset", C.c_int64), ("y_pitch", C.c_int32),
+                ("c_pitch", C.c_int32), ("c_step", C.c_int32), ("h", C.c_int32), ("w", C.c_int32), ("out_h", C.c_int32),
+                ("out_w", C.c_int32), ("pad_top", C.c_int32), ("pad_left", C.c_int32), ("flags", C.c_int32)]
+
+
 class y4_mosaic_cut(C.Structure):
     _fields_ = [("cut_y", C.c_int32), ("cut_x", C.c_int32)]
 
@@ -160,6 +166,7 @@ SYMBOLS = {
     "y4_nms_gathered_merged": (_I, [_VP, _I, _I, C.c_uint32, _F, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "y4_augment_u8_ragged": (_I, [_VP, _VP, _I, _VP, _I, _I, _I, _VP]),
     "y4_mosaic_u8_ragged": (_I, [_VP, _VP, _VP, _I, _VP, _I, _I, _I, _VP]),
+    "y4_yuv_u8_ragged": (_I, [_VP, _VP, _I, _VP, _I, _I, _I, _VP]),
     "y4_map_match": (_I, [_VP, _VP, _VP, _VP, _I, _I, _VP, _VP, _VP, _I, C.POINTER(C.c_double), _I, _VP, _VP, _VP, _VP, _VP]),
     "y4_coco_match": (_I, [_VP, _VP, _VP, _VP, _I, _I, _VP, _VP, _VP, _I, C.POINTER(C.c_double), _I, C.POINTER(C.c_double), _I, _VP, _VP,
                            _VP, _VP, _VP, _VP]),
