@@ -461,42 +461,49 @@ class Yolov4(object):
         boxes arrive normalised to each raw image and stay on the device for the matching.  RuntimeError when an image has more
         than tile_candidates candidates, as `predict_tiled`."""
         from .mapeval import MapAccumulator
-        items, paths, bs = self._eval_items('evaluate_map', data, img_folder_path, bs, channel_order)
-        if views is not None:
-            tiling.check_views(views)                      # ValueError before anything is uploaded
-            views = list(views)
+        items, paths, bs, views = self._eval_items('evaluate_map', data, img_folder_path, bs, channel_order, views)
         self._ensure_tuned()
         eng = self.engine
-        iou, score = self._thresholds
         acc = MapAccumulator(self.class_names, iou_thresholds)
         for i0, part, raws, gt_dev, scale_dev, count_dev in self._eval_batches(items, paths, bs, channel_order):
             n = len(part)
-            if views is None:
-                imgs, box_map = eng.preprocess_u8_batch(raws, letterbox=self._letterbox, pad_value=self._pad_value)
-                flat, outs, tp_mask = eng.alloc_map_outputs_flat(n)
-                eng.forward_device(imgs)
-                eng.decode_nms_device(n, outs, iou, score, box_map=box_map if self._letterbox else None)
-                eng.map_match_device(outs, scale_dev, gt_dev, count_dev, acc.iou_thresholds, tp_mask=tp_mask)
-                scores, classes, valid, tp = eng.map_outputs_to_host(flat, n)
-            else:
-                # the boxes arrive normalised to each raw image (no box map) and are matched where they lie; the block of
-                # predict_tta_device comes back in its one copy, the true-positive flags in a second small one
-                flat, outs, _, group_cap = eng.predict_tta_device(
-                    raws, views, letterbox=self._letterbox, pad_value=self._pad_value, iou_threshold=iou,
-                    score_threshold=score, tile_candidates=tile_candidates)
-                tp = eng.map_match_device(outs, scale_dev, gt_dev, count_dev, acc.iou_thresholds)
-                (_, scores, classes, valid, _), cand = eng.tiled_outputs_to_host(flat, n)
-                self._check_candidates('evaluate_map', i0, cand, group_cap)
-                tp = tp.cpu().numpy().view(np.uint32)
+            flat, outs, tp_mask = eng.alloc_map_outputs_flat(n)
+            # with views the map block still comes back in its one copy, the candidate counts (no field of it) in a second small one
+            cand = None if views is None else eng.torch.empty((n,), dtype=eng.torch.int32, device=eng.device)
+            group_cap = self._eval_infer(raws, (flat, outs, cand), views, tile_candidates=tile_candidates)
+            eng.map_match_device(outs, scale_dev, gt_dev, count_dev, acc.iou_thresholds, tp_mask=tp_mask)
+            scores, classes, valid, tp = eng.map_outputs_to_host(flat, n)
+            if group_cap is not None:
+                self._check_candidates('evaluate_map', i0, cand.cpu().numpy(), group_cap)
             acc.add([stem for _, stem, _ in part], scores, classes, valid, tp, [boxes[:, 4] for _, _, boxes in part])
         return acc.result()
 
-    def _eval_items(self, who, data, img_folder_path, bs, channel_order):
-        """The arguments `evaluate_map` and `evaluate_coco` share -> (items of `read_map_annotations`, image paths, bs);
-        ValueError before anything is read or uploaded."""
+    def _eval_infer(self, raws, outputs, views=None, tiled=False, tile=None, overlap=0.2, full_image=True, tile_candidates=1 << 18):
+        """The inference of one batch of `evaluate_map` / `evaluate_coco`, under this object's thresholds, letterbox and pad value,
+        into outputs = (flat, outs, cand_count): tiled -> `predict_tiled_device`, views -> `predict_tta_device` (both write cand_count),
+        else preprocess_u8_batch -> forward -> decode + NMS.  -> group_cap for `_check_candidates`, or None on the plain path."""
+        eng = self.engine
+        iou, score = self._thresholds
+        if tiled:
+            return eng.predict_tiled_device(raws, tile, overlap, full_image, self._letterbox, self._pad_value, iou, score,
+                                            tile_candidates, views, outputs=outputs)[3]
+        if views is not None:
+            return eng.predict_tta_device(raws, views, self._letterbox, self._pad_value, iou, score, tile_candidates,
+                                          outputs=outputs)[3]
+        imgs, box_map = eng.preprocess_u8_batch(raws, letterbox=self._letterbox, pad_value=self._pad_value)
+        eng.forward_device(imgs)
+        eng.decode_nms_device(len(raws), outputs[1], iou, score, box_map=box_map if self._letterbox else None)
+        return None
+
+    def _eval_items(self, who, data, img_folder_path, bs, channel_order, views):
+        """The arguments `evaluate_map` and `evaluate_coco` share -> (items of `read_map_annotations`, image paths, bs, views as a
+        list or None); ValueError before anything is read or uploaded."""
         from .data import read_map_annotations
         if channel_order not in ('rgb', 'bgr'):
             raise ValueError(f"channel_order must be 'rgb' or 'bgr', got {channel_order!r}")
+        if views is not None:
+            tiling.check_views(views)
+            views = list(views)
         if isinstance(data, (str, os.PathLike)):
             if img_folder_path is None:
                 raise ValueError(f'{who}: an annotation file needs img_folder_path')
@@ -512,7 +519,7 @@ class Yolov4(object):
             raise ValueError(f'{who}: bs {bs}')
         if not items:
             raise ValueError(f'{who}: no annotation lines')
-        return items, paths, bs
+        return items, paths, bs, views
 
     def _eval_batches(self, items, paths, bs, channel_order):
         """The batch loop `evaluate_map` and `evaluate_coco` share: `bs` images per batch in file order, a batch larger than the
@@ -572,11 +579,8 @@ class Yolov4(object):
         the model to compare with published tables."""
         from .cocoeval import CocoAccumulator
         from .data import MAP_MAX_GT
-        items, paths, bs = self._eval_items('evaluate_coco', data, img_folder_path, bs, channel_order)
+        items, paths, bs, views = self._eval_items('evaluate_coco', data, img_folder_path, bs, channel_order, views)
         acc = CocoAccumulator(self.class_names, None, area_ranges, max_dets)          # ValueError on bad ranges / max_dets
-        if views is not None:
-            tiling.check_views(views)
-            views = list(views)
         if int(tile_candidates) < 1:
             raise ValueError(f'evaluate_coco: tile_candidates must be >= 1, got {tile_candidates}')
         if tiled:
@@ -588,22 +592,11 @@ class Yolov4(object):
             raise ValueError('evaluate_coco: tile= needs tiled=True')
         self._ensure_tuned()
         eng = self.engine
-        iou, score = self._thresholds
         A = len(acc.area_ranges)
         for i0, part, raws, gt_dev, scale_dev, count_dev in self._eval_batches(items, paths, bs, channel_order):
             n = len(part)
             flat, outs, cand_count, match_out = eng.alloc_coco_outputs_flat(n, A, MAP_MAX_GT)
-            group_cap = None
-            if tiled:
-                group_cap = eng.predict_tiled_device(raws, tile, overlap, full_image, self._letterbox, self._pad_value, iou, score,
-                                                     tile_candidates, views, outputs=(flat, outs, cand_count))[3]
-            elif views is not None:
-                group_cap = eng.predict_tta_device(raws, views, self._letterbox, self._pad_value, iou, score, tile_candidates,
-                                                   outputs=(flat, outs, cand_count))[3]
-            else:
-                imgs, box_map = eng.preprocess_u8_batch(raws, letterbox=self._letterbox, pad_value=self._pad_value)
-                eng.forward_device(imgs)
-                eng.decode_nms_device(n, outs, iou, score, box_map=box_map if self._letterbox else None)
+            group_cap = self._eval_infer(raws, (flat, outs, cand_count), views, tiled, tile, overlap, full_image, tile_candidates)
             eng.coco_match_device(outs, scale_dev, gt_dev, count_dev, acc.iou_thresholds, acc.area_ranges, out=match_out)
             scores, classes, valid, cand, rank, dm, di, gi = eng.coco_outputs_to_host(flat, n, A, MAP_MAX_GT)
             if group_cap is not None:
@@ -648,22 +641,13 @@ class Yolov4(object):
                     return_output=False):
         print('img shape: ', raw_img.shape)
         if self._letterbox:
-            imgs, box_map = self._letterboxed([raw_img])
-            pred_output = self._predict_mapped(imgs, box_map)
+            pred_output = self._predict_mapped(*self._letterboxed([raw_img]))
         elif self._device_preprocess and getattr(raw_img, 'dtype', None) == np.uint8:
             # same arithmetic as preprocess_img (tests: bit-identical), on the GPU: the uint8 image crosses PCIe
-            imgs = self.engine.preprocess_u8(np.ascontiguousarray(raw_img))
-            pred_output = self.inference_model.predict(imgs)
+            pred_output = self.inference_model.predict(self.engine.preprocess_u8(np.ascontiguousarray(raw_img)))
         else:
-            img = self.preprocess_img(raw_img)
-            imgs = np.expand_dims(img, axis=0)
-            pred_output = self.inference_model.predict(imgs)
-        detections = prepost.get_detection_data(img=raw_img, model_outputs=pred_output, class_names=self.class_names)
-        output_img = prepost.draw_bbox(raw_img, detections, cmap=self.class_color, random_color=random_color,
-                                       figsize=figsize, show_text=show_text, show_img=plot_img)
-        if return_output:
-            return output_img, detections
-        return detections
+            pred_output = self.inference_model.predict(np.expand_dims(self.preprocess_img(raw_img), axis=0))
+        return self._show(raw_img, pred_output, random_color, plot_img, figsize, show_text, return_output)
 
     # ---- tiled (sliced) inference: not in the reference.  A photo much larger than the network input is cut into overlapping
     # windows at native resolution (yolo4hip/tiling.py), the windows run as batch rows, and one NMS per photo runs over all rows
@@ -677,19 +661,16 @@ class Yolov4(object):
         views: None, or (scale, flip) views every row also runs under (see `predict_tta`)."""
         self._ensure_tuned()
         iou, score = self._thresholds
-        b, s, c, v = self.engine.predict_tiled(raw_imgs, tile=tile, overlap=overlap, full_image=full_image,
+        return tuple(self.engine.predict_tiled(raw_imgs, tile=tile, overlap=overlap, full_image=full_image,
                                                letterbox=self._letterbox, pad_value=self._pad_value, iou_threshold=iou,
-                                               score_threshold=score, tile_candidates=tile_candidates, views=views)
-        return b, s, c, v
+                                               score_threshold=score, tile_candidates=tile_candidates, views=views))
 
     def _show(self, raw_img, pred_output, random_color, plot_img, figsize, show_text, return_output):
         """The DataFrame and drawing of `predict_img` for outputs normalised to the photo."""
         detections = prepost.get_detection_data(img=raw_img, model_outputs=pred_output, class_names=self.class_names)
         output_img = prepost.draw_bbox(raw_img, detections, cmap=self.class_color, random_color=random_color,
                                        figsize=figsize, show_text=show_text, show_img=plot_img)
-        if return_output:
-            return output_img, detections
-        return detections
+        return (output_img, detections) if return_output else detections
 
     def predict_img_tiled(self, raw_img, random_color=True, plot_img=True, figsize=(10, 10), show_text=True,
                           return_output=False, *, tile=None, overlap=0.2, full_image=True, views=None):
@@ -708,9 +689,8 @@ class Yolov4(object):
         'lrud'), at most 16, no duplicates; ((1.0, ''),) is `predict_img`'s own path."""
         self._ensure_tuned()
         iou, score = self._thresholds
-        b, s, c, v = self.engine.predict_tta(raw_imgs, views=views, letterbox=self._letterbox, pad_value=self._pad_value,
-                                             iou_threshold=iou, score_threshold=score, tile_candidates=tile_candidates)
-        return b, s, c, v
+        return tuple(self.engine.predict_tta(raw_imgs, views=views, letterbox=self._letterbox, pad_value=self._pad_value,
+                                             iou_threshold=iou, score_threshold=score, tile_candidates=tile_candidates))
 
     def predict_img_tta(self, raw_img, random_color=True, plot_img=True, figsize=(10, 10), show_text=True,
                         return_output=False, *, views=tiling.DEFAULT_VIEWS):

@@ -9,7 +9,7 @@ import os
 
 import numpy as np
 
-from . import ext, schedule, tiling
+from . import canvas, ext, schedule, tiling
 from .config import yolo_config
 
 
@@ -464,23 +464,9 @@ class Engine:
         kept and centred on a `pad_value` canvas (prepost.letterbox_rect / prepost.letterbox, bit for bit).
         -> (uint8 cuda tensor [n,H,W,3], float32 cuda tensor [n,4] box map for `predict(..., box_map=)`: the identity rows
         for stretch, prepost.box_map for letterbox).  Asynchronous on the current stream."""
-        torch = self.torch
-        from . import prepost
         raw_imgs, pad_value = self._check_ragged(raw_imgs, pad_value, "preprocess_u8_batch")
-        n = len(raw_imgs)
-        H, W = self.img_hw
-        desc = (ext.y4_image_desc * n)()
-        maps = np.empty((n, 4), np.float32)
-        for i, a in enumerate(raw_imgs):
-            h, w = a.shape[:2]
-            rect = prepost.letterbox_rect(h, w, H, W) if letterbox else (H, W, 0, 0)
-            d = desc[i]
-            d.out_h, d.out_w, d.pad_top, d.pad_left = rect
-            maps[i] = prepost.box_map(h, w, H, W, rect)
-        dev, desc_bytes, head = self._upload_ragged(raw_imgs, desc, maps)
-        out = self._canvas_launch(self.lib.y4_resize_u8_ragged, C.c_void_p(dev.data_ptr() + head), (ext.ptr(dev),), n, None,
-                                  pad_value)
-        return out, dev[desc_bytes:head].view(torch.float32).view(n, 4)
+        return self._fit_batch(self.lib.y4_resize_u8_ragged, ext.y4_image_desc, raw_imgs, [a.shape[:2] for a in raw_imgs],
+                               letterbox, pad_value)
 
     def preprocess_yuv_batch(self, frames, letterbox=False, pad_value=128, matrix='bt601', full_range=False, fmt='nv12'):
         """`preprocess_u8_batch` for 8-bit 4:2:0 video frames: `frames` is one `yuv.YuvFrame` or a list of them, of ANY mix of
@@ -490,27 +476,21 @@ class Engine:
         byte for byte, `preprocess_u8_batch` of `yuv.to_rgb(frame, matrix, full_range)`.
         -> (uint8 cuda tensor [n,H,W,3], float32 cuda tensor [n,4] box map: prepost.box_map of each frame's h, w).
         Asynchronous on the current stream."""
-        torch = self.torch
-        from . import prepost, yuv
+        from . import yuv
         frames = yuv.as_frames(frames, fmt)
         word = yuv.flags(matrix, full_range)
-        pad_value = int(pad_value)
-        if not 0 <= pad_value <= 255:
-            raise ValueError(f"pad_value must be a uint8 level 0..255, got {pad_value}")
-        n = len(frames)
-        H, W = self.img_hw
-        desc = (ext.y4_yuv_desc * n)()
-        maps = np.empty((n, 4), np.float32)
-        for i, f in enumerate(frames):
-            rect = prepost.letterbox_rect(f.h, f.w, H, W) if letterbox else (H, W, 0, 0)
-            d = desc[i]
-            d.out_h, d.out_w, d.pad_top, d.pad_left = rect
-            maps[i] = prepost.box_map(f.h, f.w, H, W, rect)
-        dev, desc_bytes, head = self._upload_ragged([f.data[:f.nbytes] for f in frames], desc, maps,
-                                                    place=lambda d, k, off: frames[k].fill_desc(d, off, word))
-        out = self._canvas_launch(self.lib.y4_yuv_u8_ragged, C.c_void_p(dev.data_ptr() + head), (ext.ptr(dev),), n, None,
-                                  pad_value)
-        return out, dev[desc_bytes:head].view(torch.float32).view(n, 4)
+        return self._fit_batch(self.lib.y4_yuv_u8_ragged, ext.y4_yuv_desc, [f.data[:f.nbytes] for f in frames],
+                               [(f.h, f.w) for f in frames], letterbox, self._check_pad(pad_value),
+                               place=lambda d, k, off: frames[k].fill_desc(d, off, word))
+
+    def _fit_batch(self, fn, Desc, sources, sizes, letterbox, pad_value, place=None):
+        """What `preprocess_u8_batch` and `preprocess_yuv_batch` share: the `Desc` table and box maps of sources of `sizes` (h, w)
+        fitted to the canvas, the one upload, the one launch of `fn` -> (uint8 cuda batch [n,H,W,3], float32 cuda box map [n,4])."""
+        n = len(sources)
+        desc, maps = canvas.fit_table(Desc, sizes, *self.img_hw, letterbox)
+        dev, desc_bytes, head = self._upload_ragged(sources, desc, maps, place=place)
+        out = self._canvas_launch(fn, C.c_void_p(dev.data_ptr() + head), (ext.ptr(dev),), n, None, pad_value)
+        return out, dev[desc_bytes:head].view(self.torch.float32).view(n, 4)
 
     def augment_u8_batch(self, raw_imgs, params, pad_value=128):
         """The training input of `Yolov4.fit` on the device: uint8 RGB images [h,w,3] of any mix of sizes and one parameter row
@@ -574,6 +554,12 @@ class Engine:
         return out[:n]
 
     @staticmethod
+    def _check_pad(pad_value):
+        if not 0 <= int(pad_value) <= 255:
+            raise ValueError(f"pad_value must be a uint8 level 0..255, got {int(pad_value)}")
+        return int(pad_value)
+
+    @staticmethod
     def _check_ragged(raw_imgs, pad_value, who):
         """One image or a list of them -> (list of uint8 [h,w,3] arrays, pad_value as an int), or ValueError."""
         if isinstance(raw_imgs, np.ndarray) and raw_imgs.ndim == 3:
@@ -581,53 +567,31 @@ class Engine:
         raw_imgs = list(raw_imgs)
         if len(raw_imgs) == 0:
             raise ValueError(f"{who}: no images")
-        pad_value = int(pad_value)
-        if not 0 <= pad_value <= 255:
-            raise ValueError(f"pad_value must be a uint8 level 0..255, got {pad_value}")
+        pad_value = Engine._check_pad(pad_value)
         for a in raw_imgs:
             if getattr(a, "dtype", None) != np.uint8 or a.ndim != 3 or a.shape[2] != 3 or a.shape[0] < 1 or a.shape[1] < 1:
                 raise ValueError(f"expected uint8 [h,w,3] images, got {getattr(a, 'dtype', type(a))} {getattr(a, 'shape', '')}")
         return raw_imgs, pad_value
 
     def _upload_ragged(self, raw_imgs, desc, extra=None, rows=None, windows=None, place=None):
-        """The one upload of a ragged batch (`preprocess_u8_batch`, `augment_u8_batch`, `mosaic_u8_batch`, `predict_tiled`): fills
-        offset, h, w of every row of `desc` (a ctypes array of y4_image_desc or y4_augment_desc; row k describes image k, or image
-        rows[k] where `rows` is given: rows may share an image), packs descriptors | `extra` (a numpy array, or None) | the images
-        into the pinned staging buffer (kept across calls) and copies it to a fresh device block in one copy.  With `windows` (one
-        (y0, x0, wh, ww) per row, inside image rows[k]) `desc` is an array of y4_window_desc: offset is then the window's first
-        pixel, pitch the image's row, h and w the window's.  With `place` the sources are byte buffers of any layout (video frames)
-        and place(row, k, offset) fills row k's source fields itself.
+        """The one upload of a ragged batch (`preprocess_u8_batch`, `augment_u8_batch`, `mosaic_u8_batch`, `predict_tiled`): the
+        source fields of every row of `desc` are filled by `canvas.place_sources` (which explains `rows`, `windows` and `place`), then
+        descriptors | `extra` (a numpy array, or None) | the images are packed into the pinned staging buffer (kept across calls)
+        and copied to a fresh device block in one copy.
         -> (device block, descriptor bytes, bytes before the first image); descriptor offsets count from the first image byte."""
         torch = self.torch
         n = len(raw_imgs)
         desc_bytes = C.sizeof(desc)
         head = desc_bytes + (extra.nbytes if extra is not None else 0)
-        offs, off = [], 0
-        for a in raw_imgs:
-            offs.append(off)
-            off += a.size
-        if windows is not None:
-            for d, k, (y0, x0, wh, ww) in zip(desc, rows, windows):
-                ih, iw = raw_imgs[k].shape[:2]
-                if not (0 <= y0 and 0 <= x0 and wh >= 1 and ww >= 1 and y0 + wh <= ih and x0 + ww <= iw):
-                    raise ValueError(f"window ({y0}, {x0}, {wh}, {ww}) is not inside its {ih} x {iw} image")
-                d.offset, d.pitch, d.h, d.w = offs[k] + (y0 * iw + x0) * 3, iw * 3, wh, ww
-        else:
-            for d, k in zip(desc, range(n) if rows is None else rows):
-                if place is not None:
-                    place(d, k, offs[k])
-                else:
-                    d.offset, d.h, d.w = offs[k], raw_imgs[k].shape[0], raw_imgs[k].shape[1]
-        total = head + off
+        offs = canvas.place_sources(desc, [a.shape for a in raw_imgs], rows, windows, place)
+        off, total = offs[-1], head + offs[-1]
         pin = getattr(self, "_batch_pin", None)
+        if pin is not None:
+            self._batch_pin_free.synchronize()              # the previous call's upload has left the buffer
         if pin is None or pin.numel() < total:
-            if pin is not None:
-                self._batch_pin_free.synchronize()
             pin = self._batch_pin = torch.empty(max(total, 1 << 20), dtype=torch.uint8).pin_memory()
             self._batch_pin_np = pin.numpy()
             self._batch_pin_free = torch.cuda.Event()
-        else:
-            self._batch_pin_free.synchronize()              # the previous call's upload has left the buffer
         buf = self._batch_pin_np
         buf[:desc_bytes] = np.frombuffer(desc, dtype=np.uint8)
         if extra is not None:
@@ -768,10 +732,9 @@ class Engine:
         R, P, max_slots = len(photo), len(raw_imgs), max(slot) + 1
         Desc, launch = ((ext.y4_window_desc, self.lib.y4_window_u8_ragged) if views is None
                         else (ext.y4_view_desc, self.lib.y4_view_u8_ragged))
-        desc = (Desc * R)()
-        for d, rect, bits in zip(desc, rects, flips):
-            d.out_h, d.out_w, d.pad_top, d.pad_left = rect
-            if views is not None:
+        desc = canvas.rect_table(Desc, rects)
+        if views is not None:
+            for d, bits in zip(desc, flips):
                 d.flip = bits
         # maps | groups | slots travel behind the descriptors in the one upload
         extra = np.concatenate([np.asarray(maps, np.float32).reshape(-1).view(np.int32), np.asarray(photo, np.int32),
@@ -785,11 +748,11 @@ class Engine:
         flat, outs, cand_count = self.alloc_tiled_outputs_flat(P) if outputs is None else outputs
         step = C.sizeof(Desc)
         with torch.cuda.device(self.device):
-            canvas = torch.empty((min(R, self.max_batch), H, W, 3), dtype=torch.uint8, device=self.device)
+            batch = torch.empty((min(R, self.max_batch), H, W, 3), dtype=torch.uint8, device=self.device)
             src = C.c_void_p(dev.data_ptr() + head)
             for r0 in range(0, R, self.max_batch):
                 n = min(self.max_batch, R - r0)
-                self.forward_device(self._canvas_launch(launch, src, (C.c_void_p(dev.data_ptr() + r0 * step),), n, canvas, pad_value))
+                self.forward_device(self._canvas_launch(launch, src, (C.c_void_p(dev.data_ptr() + r0 * step),), n, batch, pad_value))
                 self.decode_gather(state, n, row_group[r0:r0 + n], row_slot[r0:r0 + n], row_map[r0:r0 + n], score_threshold,
                                    oriented=views is not None)
             self.nms_gathered(state, outs, cand_count, iou_threshold)
@@ -982,6 +945,18 @@ class Engine:
         tp_mask uint32 [n,T]) as numpy views of it."""
         return tuple(_block_views(flat.cpu().numpy(), self._map_fields(n, "uint32")))
 
+    def _check_match_inputs(self, n, scale_dev, gt_dev, gt_count_dev):
+        """The ground-truth tensors of `map_match_device` and `coco_match_device` for n images -> max_gt, or ValueError."""
+        torch = self.torch
+        if gt_dev.dim() != 3 or gt_dev.shape[0] != n or gt_dev.shape[2] != 5 or gt_dev.dtype != torch.float32 \
+                or not gt_dev.is_contiguous():
+            raise ValueError(f"gt_dev must be a contiguous float32 tensor [{n},max_gt,5], got {gt_dev.dtype} {tuple(gt_dev.shape)}")
+        if tuple(scale_dev.shape) != (n, 2) or scale_dev.dtype != torch.float32 or not scale_dev.is_contiguous():
+            raise ValueError(f"scale_dev must be a contiguous float32 tensor [{n},2], got {scale_dev.dtype} {tuple(scale_dev.shape)}")
+        if tuple(gt_count_dev.shape) != (n,) or gt_count_dev.dtype != torch.int32 or not gt_count_dev.is_contiguous():
+            raise ValueError(f"gt_count_dev must be a contiguous int32 tensor [{n}], got {gt_count_dev.dtype} {tuple(gt_count_dev.shape)}")
+        return gt_dev.shape[1]
+
     def map_match_device(self, outs, scale_dev, gt_dev, gt_count_dev, iou_thresholds, debug=False, tp_mask=None):
         """y4_map_match on the outputs of `decode_nms_device` (outs = boxes, scores, classes, valid, ...): the kept boxes of
         each image, scaled to raw-image pixels by scale_dev (float32 cuda [n,2]: w, h), are matched against gt_dev (float32
@@ -993,14 +968,7 @@ class Engine:
         boxes, scores, classes, valid = outs[:4]
         n, T = scores.shape
         thr = [float(t) for t in iou_thresholds]
-        if gt_dev.dim() != 3 or gt_dev.shape[0] != n or gt_dev.shape[2] != 5 or gt_dev.dtype != torch.float32 \
-                or not gt_dev.is_contiguous():
-            raise ValueError(f"gt_dev must be a contiguous float32 tensor [{n},max_gt,5], got {gt_dev.dtype} {tuple(gt_dev.shape)}")
-        if tuple(scale_dev.shape) != (n, 2) or scale_dev.dtype != torch.float32 or not scale_dev.is_contiguous():
-            raise ValueError(f"scale_dev must be a contiguous float32 tensor [{n},2], got {scale_dev.dtype} {tuple(scale_dev.shape)}")
-        if tuple(gt_count_dev.shape) != (n,) or gt_count_dev.dtype != torch.int32 or not gt_count_dev.is_contiguous():
-            raise ValueError(f"gt_count_dev must be a contiguous int32 tensor [{n}], got {gt_count_dev.dtype} {tuple(gt_count_dev.shape)}")
-        max_gt = gt_dev.shape[1]
+        max_gt = self._check_match_inputs(n, scale_dev, gt_dev, gt_count_dev)
         if tp_mask is None:
             tp_mask = torch.empty((n, T), dtype=torch.int32, device=self.device)
         elif tuple(tp_mask.shape) != (n, T) or tp_mask.dtype != torch.int32 or not tp_mask.is_contiguous():
@@ -1057,14 +1025,7 @@ class Engine:
         if rng.ndim != 2 or rng.shape[1] != 2:
             raise ValueError(f"area_ranges must be rows [lo, hi], got shape {rng.shape}")
         A = len(rng)
-        if gt_dev.dim() != 3 or gt_dev.shape[0] != n or gt_dev.shape[2] != 5 or gt_dev.dtype != torch.float32 \
-                or not gt_dev.is_contiguous():
-            raise ValueError(f"gt_dev must be a contiguous float32 tensor [{n},max_gt,5], got {gt_dev.dtype} {tuple(gt_dev.shape)}")
-        if tuple(scale_dev.shape) != (n, 2) or scale_dev.dtype != torch.float32 or not scale_dev.is_contiguous():
-            raise ValueError(f"scale_dev must be a contiguous float32 tensor [{n},2], got {scale_dev.dtype} {tuple(scale_dev.shape)}")
-        if tuple(gt_count_dev.shape) != (n,) or gt_count_dev.dtype != torch.int32 or not gt_count_dev.is_contiguous():
-            raise ValueError(f"gt_count_dev must be a contiguous int32 tensor [{n}], got {gt_count_dev.dtype} {tuple(gt_count_dev.shape)}")
-        max_gt = gt_dev.shape[1]
+        max_gt = self._check_match_inputs(n, scale_dev, gt_dev, gt_count_dev)
         shapes = ((n, T), (n, A, T), (n, A, T), (n, max_gt))
         if out is None:
             out = tuple(torch.empty(shape, dtype=torch.int32, device=self.device) for shape in shapes)
@@ -1430,6 +1391,86 @@ class Engine:
         """Copy the master kernels of `state` back into the host stream `flat` (in place); the BatchNormalization vectors stay."""
         return self._group_weights_to_flat("blocks", state, flat)
 
+    def _check_stream_batch(self, a, u8, yuv):
+        """ValueError unless `a` (of dtype `u8`) is a batch `predict_stream` takes."""
+        if yuv is not None:
+            if a.dtype != u8 or a.ndim != 3 or not 1 <= a.shape[0] <= self.max_batch \
+                    or a.shape[1] < 3 or a.shape[1] % 3 or a.shape[2] < 2 or a.shape[2] % 2:
+                raise ValueError(f"expected uint8 [n<={self.max_batch}, h + h // 2, w] {yuv} batches with even h, w, got "
+                                 f"{a.dtype} {tuple(a.shape)}")
+        elif a.dtype != u8 or a.ndim != 4 or a.shape[3] != 3 or not 1 <= a.shape[0] <= self.max_batch:
+            raise ValueError(f"expected uint8 [n<={self.max_batch},h,w,3] batches, got {a.dtype} {a.shape}")
+
+    def _stream_setup(self, in_flight):
+        """-> (the engines that compute `in_flight` batches at a time: this one and its siblings, the in_flight + 1 staging slots)."""
+        sibs = getattr(self, "_stream_siblings", [])
+        while len(sibs) < in_flight - 1:
+            sibs.append(self.sibling())
+        self._stream_siblings = sibs
+        for e in sibs[:in_flight - 1]:
+            self.copy_schedule_to(e)                       # (the engine may have been re-tuned since the sibling was made)
+        nslots = in_flight + 1                             # one more staging slot than computing batches: the next upload runs ahead
+        # the staging slots (pinned host buffers, device frames, output blocks, events) outlive the call: pinning tens of MB
+        # costs milliseconds, which a short stream would pay again on every call
+        cache = getattr(self, "_stream_slots", None)
+        if cache is None or len(cache) != nslots:
+            for sl in cache or []:                         # an abandoned generator may have left copies in flight on these buffers
+                for ev in ("up", "ran", "done"):
+                    if ev in sl:
+                        sl[ev].synchronize()
+            cache = self._stream_slots = [{} for _ in range(nslots)]
+        for sl in cache:
+            if "done" in sl:
+                sl["done"].synchronize()
+        return [self] + sibs[:in_flight - 1], cache
+
+    def _stream_route(self, shape, letterbox, yuv, yuv_flags):
+        """How batches of `shape` reach the network and where their boxes go -> (launch, table, maps).  launch: None -- RGB frames of
+        the network's size are fed as they lie --, `Engine.resize_u8` -- equal RGB frames stretched, no table --, or the ragged method
+        that reads `table`, the rows the batch preprocessors build for max_batch equal sources back to back: `resize_u8_ragged` for
+        letterboxed RGB, `yuv_u8_ragged` for video, always.  maps: boxes are mapped under letterbox, unless the frame has the network's size."""
+        (H, W), B = self.img_hw, self.max_batch
+        if yuv is None:
+            fh, fw = shape[1:3]
+            if (fh, fw) == (H, W):
+                return None, None, None
+            if not letterbox:
+                return Engine.resize_u8, None, None
+            desc, maps = canvas.fit_table(ext.y4_image_desc, [(fh, fw)] * B, H, W, True)
+            canvas.place_sources(desc, [(fh, fw, 3)] * B)
+            return Engine.resize_u8_ragged, desc, maps
+        from . import yuv as yuvmod
+        layout = yuvmod.YuvFrame(np.empty(shape[1:], np.uint8), fmt=yuv)       # (the plane offsets of one frame)
+        desc, maps = canvas.fit_table(ext.y4_yuv_desc, [(layout.h, layout.w)] * B, H, W, letterbox)
+        canvas.place_sources(desc, [(layout.nbytes,)] * B, place=lambda d, k, off: layout.fill_desc(d, off, yuv_flags))
+        return Engine.yuv_u8_ragged, desc, maps if letterbox and (layout.h, layout.w) != (H, W) else None
+
+    def _stream_rekey(self, sl, key, compute):
+        """(Re)allocate the staging of slot `sl` for key = (batch shape, letterbox, pad_value, yuv, yuv_flags)."""
+        torch, dev = self.torch, self.device
+        shape, letterbox, _, yuv, yuv_flags = key
+        if "done" in sl:
+            sl["done"].synchronize()
+        sl["key"] = key
+        sl["pin"] = torch.empty(shape, dtype=torch.uint8).pin_memory()
+        sl["pin_np"] = sl["pin"].numpy()
+        sl["u8"] = torch.empty(shape, dtype=torch.uint8, device=dev)
+        sl["launch"], table, maps = self._stream_route(shape, letterbox, yuv, yuv_flags)
+        # frames of another size are resized uint8 -> uint8 on the device; the /255 happens in the stem's load
+        sl["net"] = None if sl["launch"] is None else \
+            torch.empty((self.max_batch, self.img_hw[0], self.img_hw[1], 3), dtype=torch.uint8, device=dev)
+        sl["table"] = None if table is None else torch.from_numpy(np.frombuffer(table, dtype=np.uint8).copy()).to(dev)
+        sl["map"] = None if maps is None else torch.from_numpy(maps).to(dev)
+        if table is not None:
+            torch.cuda.current_stream().synchronize()      # (read by the compute streams)
+        # one flat int32 block per slot holds all five outputs, so that results return in ONE small D2H copy
+        fields = _detection_fields(self.max_batch, self.T)
+        sl["flat"], sl["outs"] = self._alloc_block(fields)
+        sl["flat_host"] = torch.empty(_block_len(fields), dtype=torch.int32).pin_memory()
+        sl["host"] = _block_views(sl["flat_host"], fields)
+        sl["up"], sl["done"], sl["free"], sl["ran"] = (torch.cuda.Event() for _ in range(4))
+        sl["free"].record(compute)
+
     def predict_stream(self, batches, with_indices=False, in_flight=None, letterbox=False, pad_value=128, yuv=None,
                        matrix='bt601', full_range=False):
         """Pipelined `inference_model.predict` over an iterable of uint8 batches ([n,h,w,3] numpy arrays or pinned torch
@@ -1454,6 +1495,7 @@ class Engine:
         this generator on the `yuv.to_rgb` frames.  yuv=None is the RGB path, launch for launch as before."""
         torch = self.torch
         dev = self.device
+        yuv_flags = 0
         if yuv is not None:
             from . import yuv as yuvmod
             if yuv not in yuvmod.FORMATS:
@@ -1464,31 +1506,9 @@ class Engine:
         if in_flight is None:
             in_flight = 2 if self.alias_workspace else 1
         in_flight = max(1, int(in_flight))
-        sibs = getattr(self, "_stream_siblings", [])
-        while len(sibs) < in_flight - 1:
-            sibs.append(self.sibling())
-        self._stream_siblings = sibs
-        for e in sibs[:in_flight - 1]:
-            self.copy_schedule_to(e)                       # (the engine may have been re-tuned since the sibling was made)
-        engines = [self] + sibs[:in_flight - 1]
-        nslots = in_flight + 1                             # one more staging slot than computing batches: the next upload runs ahead
-        # the staging slots (pinned host buffers, device frames, output blocks, events) outlive the call: pinning tens of MB
-        # costs milliseconds, which a short stream would pay again on every call
-        cache = getattr(self, "_stream_slots", None)
-        if cache is None or len(cache) != nslots:
-            for sl in cache or []:                         # an abandoned generator may have left copies in flight on these buffers
-                for ev in ("up", "ran", "done"):
-                    if ev in sl:
-                        sl[ev].synchronize()
-            cache = self._stream_slots = [{} for _ in range(nslots)]
-        slots = cache
-        for sl in slots:
-            if "done" in sl:
-                sl["done"].synchronize()
+        engines, slots = self._stream_setup(in_flight)
+        nslots = len(slots)
         pending = []
-
-        # one flat int32 block per slot holds all five outputs, so that results return in ONE small D2H copy
-        fields = _detection_fields(self.max_batch, self.T)
 
         def finish(sl):
             sl["done"].synchronize()
@@ -1500,65 +1520,13 @@ class Engine:
             for bi, batch in enumerate(batches):
                 pinned_in = isinstance(batch, torch.Tensor) and batch.is_pinned() and batch.is_contiguous()
                 a = batch if pinned_in else np.ascontiguousarray(batch)
-                if yuv is not None:
-                    if a.dtype != (torch.uint8 if pinned_in else np.uint8) or a.ndim != 3 or not 1 <= a.shape[0] <= self.max_batch \
-                            or a.shape[1] < 3 or a.shape[1] % 3 or a.shape[2] < 2 or a.shape[2] % 2:
-                        raise ValueError(f"expected uint8 [n<={self.max_batch}, h + h // 2, w] {yuv} batches with even h, w, got "
-                                         f"{a.dtype} {tuple(a.shape)}")
-                elif a.dtype != (torch.uint8 if pinned_in else np.uint8) or a.ndim != 4 or a.shape[3] != 3 or not 1 <= a.shape[0] <= self.max_batch:
-                    raise ValueError(f"expected uint8 [n<={self.max_batch},h,w,3] batches, got {a.dtype} {a.shape}")
+                self._check_stream_batch(a, torch.uint8 if pinned_in else np.uint8, yuv)
                 sl = slots[bi % nslots]
                 eng, compute = engines[bi % in_flight], cstreams[bi % in_flight]     # batches alternate engines; slots rotate on their own
-                shape = tuple(a.shape)
-                key = (shape, bool(letterbox), int(pad_value)) if yuv is None else \
-                    (shape, bool(letterbox), int(pad_value), yuv, yuv_flags)
-                if sl.get("key") != key:                   # (re)allocate this slot's staging for the frame geometry
-                    if "done" in sl:
-                        sl["done"].synchronize()
-                    sl["key"] = key
-                    sl["pin"] = torch.empty(shape, dtype=torch.uint8).pin_memory()
-                    sl["pin_np"] = sl["pin"].numpy()
-                    sl["u8"] = torch.empty(shape, dtype=torch.uint8, device=dev)
-                    # frames of another size are resized uint8 -> uint8 on the device; the /255 happens in the stem's load
-                    sl["net"] = None if yuv is None and shape[1:3] == tuple(self.img_hw) else \
-                        torch.empty((self.max_batch, self.img_hw[0], self.img_hw[1], 3), dtype=torch.uint8, device=dev)
-                    sl["desc"] = sl["map"] = sl["yuv_desc"] = None
-                    if yuv is not None:
-                        # video frames: one y4_yuv_desc per frame, frame j at j * (h + h // 2) * w, every frame the same rectangle.
-                        # The boxes are mapped as on the RGB path: under letterbox, unless the frame has the network's size
-                        from . import prepost
-                        fh, fw = shape[1] // 3 * 2, shape[2]
-                        H, W = self.img_hw
-                        rect = prepost.letterbox_rect(fh, fw, H, W) if letterbox else (H, W, 0, 0)
-                        desc = (ext.y4_yuv_desc * self.max_batch)()
-                        layout = yuvmod.YuvFrame(np.empty((shape[1], fw), np.uint8), fmt=yuv)   # (the plane offsets of one frame)
-                        for j in range(self.max_batch):
-                            layout.fill_desc(desc[j], j * shape[1] * fw, yuv_flags)
-                            desc[j].out_h, desc[j].out_w, desc[j].pad_top, desc[j].pad_left = rect
-                        sl["yuv_desc"] = torch.from_numpy(np.frombuffer(desc, dtype=np.uint8).copy()).to(dev)
-                        if letterbox and (fh, fw) != (H, W):
-                            sl["map"] = torch.from_numpy(np.tile(prepost.box_map(fh, fw, H, W, rect), (self.max_batch, 1))).to(dev)
-                        torch.cuda.current_stream().synchronize()   # (read by the compute streams)
-                    elif letterbox and sl["net"] is not None:
-                        # every frame of the slot has the same rectangle: one descriptor per frame, frame j at j * h * w * 3
-                        from . import prepost
-                        fh, fw = shape[1], shape[2]
-                        H, W = self.img_hw
-                        rect = prepost.letterbox_rect(fh, fw, H, W)
-                        desc = (ext.y4_image_desc * self.max_batch)()
-                        for j in range(self.max_batch):
-                            desc[j].offset, desc[j].h, desc[j].w = j * fh * fw * 3, fh, fw
-                            desc[j].out_h, desc[j].out_w, desc[j].pad_top, desc[j].pad_left = rect
-                        sl["desc"] = torch.from_numpy(np.frombuffer(desc, dtype=np.uint8).copy()).to(dev)
-                        sl["map"] = torch.from_numpy(np.tile(prepost.box_map(fh, fw, H, W, rect), (self.max_batch, 1))).to(dev)
-                        torch.cuda.current_stream().synchronize()   # (read by the compute streams)
-                    sl["flat"], sl["outs"] = self._alloc_block(fields)
-                    sl["flat_host"] = torch.empty(_block_len(fields), dtype=torch.int32).pin_memory()
-                    sl["host"] = _block_views(sl["flat_host"], fields)
-                    sl["up"], sl["done"], sl["free"], sl["ran"] = (torch.cuda.Event() for _ in range(4))
-                    sl["free"].record(compute)
-                n = a.shape[0]
-                sl["n"] = n
+                key = (tuple(a.shape), bool(letterbox), int(pad_value), yuv, yuv_flags)
+                if sl.get("key") != key:
+                    self._stream_rekey(sl, key, compute)
+                n = sl["n"] = a.shape[0]
                 sl["free"].synchronize()                   # the slot's previous uint8 frame has been consumed
                 # plain single-threaded memcpy into the pinned staging buffer: torch's multi-threaded host copy leaves
                 # its worker pool spinning, which stalls the HIP runtime's own threads for tens of ms (measured).
@@ -1570,20 +1538,18 @@ class Engine:
                     sl["up"].record(copy_stream)
                 compute.wait_event(sl["up"])
                 with torch.cuda.stream(compute):
-                    if sl["yuv_desc"] is not None:         # video frames: convert + resize in one launch, always
-                        frames = eng.yuv_u8_ragged(sl["u8"], sl["yuv_desc"], n, sl["net"], pad_value)
-                        if sl["map"] is not None:
-                            eng.forward_device(frames)
-                            eng.decode_nms_device(n, tuple(t[:n] for t in sl["outs"]), box_map=sl["map"][:n])
-                        else:
-                            eng.predict_device(frames, tuple(t[:n] for t in sl["outs"]))
-                    elif sl["desc"] is not None:           # letterbox: ragged resize, boxes mapped back to the frame in the NMS output
-                        frames = eng.resize_u8_ragged(sl["u8"], sl["desc"], n, sl["net"], pad_value)
-                        eng.forward_device(frames)
-                        eng.decode_nms_device(n, tuple(t[:n] for t in sl["outs"]), box_map=sl["map"][:n])
-                    else:
-                        frames = sl["u8"] if sl["net"] is None else eng.resize_u8(sl["u8"], sl["net"])
-                        eng.predict_device(frames[:n], tuple(t[:n] for t in sl["outs"]))
+                    if sl["launch"] is None:               # frames of the network's size: fed as they lie
+                        frames = sl["u8"]
+                    elif sl["table"] is None:              # equal frames, stretched: the non-ragged resize
+                        frames = eng.resize_u8(sl["u8"], sl["net"])
+                    else:                                  # one ragged launch over the slot's table (letterbox; video frames, always)
+                        frames = sl["launch"](eng, sl["u8"], sl["table"], n, sl["net"], pad_value)
+                    outs = tuple(t[:n] for t in sl["outs"])
+                    if sl["map"] is None:
+                        eng.predict_device(frames[:n], outs)
+                    else:                                  # boxes mapped back to the frame in the NMS output
+                        eng.forward_device(frames[:n])
+                        eng.decode_nms_device(n, outs, box_map=sl["map"][:n])
                 sl["free"].record(compute)                 # the stem has consumed the uint8 frames
                 sl["ran"].record(compute)
                 with torch.cuda.stream(down_stream):       # results leave on a third stream: compute and uploads never wait

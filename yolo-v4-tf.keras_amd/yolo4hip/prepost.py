@@ -7,6 +7,7 @@ installed on the build or GPU machines; these are PIL/NumPy counterparts with th
   resize_bilinear     reference models.py:96    cv2.resize(img, (W,H)) (INTER_LINEAR, plain stretch)
   preprocess_img      reference models.py:95-98 resize, then img / 255. (float64 in [0,1])
   letterbox_rect      -- (no reference counterpart) Darknet's letterbox_image geometry: aspect kept, centred, padded
+  fit_rect            -- the one placement rule: letterbox_rect, or the whole canvas for stretch
   letterbox           -- the letterbox restated in NumPy (the device path, y4_resize_u8_ragged, is bit-identical to it)
   box_map             -- per-image affine map canvas-normalised -> image-normalised boxes (y4_decode_nms_mapped)
   get_detection_data  reference utils.py:56-78  element 0 of the 4 NMS outputs -> pandas DataFrame
@@ -91,6 +92,11 @@ def letterbox_rect(h, w, H, W):
     else:
         out_h, out_w = H, max(1, (w * H) // h)
     return out_h, out_w, (H - out_h) // 2, (W - out_w) // 2
+
+
+def fit_rect(h, w, H, W, letterbox):
+    """The placement rule of every input path: `letterbox_rect` under letterbox, else the whole canvas (H, W, 0, 0)."""
+    return letterbox_rect(h, w, H, W) if letterbox else (int(H), int(W), 0, 0)
 
 
 def letterbox(img, size_hw, pad_value=128):

@@ -64,10 +64,10 @@ def tile_rows(h, w, canvas_hw, tile_hw=None, overlap=0.2, full_image=True, lette
         raise ValueError(f"tile_rows: tile {th} x {tw}")
     rows = []
     for win in tile_windows(h, w, (th, tw), overlap):
-        rect = prepost.letterbox_rect(win[2], win[3], H, W) if letterbox else (H, W, 0, 0)
+        rect = prepost.fit_rect(win[2], win[3], H, W, letterbox)
         rows.append((win, rect, window_map(h, w, H, W, win, rect)))
     if full_image:
-        rect = prepost.letterbox_rect(h, w, H, W) if letterbox else (H, W, 0, 0)
+        rect = prepost.fit_rect(h, w, H, W, letterbox)
         rows.append(((0, 0, h, w), rect, prepost.box_map(h, w, H, W, rect)))
     return rows
 
