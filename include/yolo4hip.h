@@ -480,6 +480,35 @@ int y4_block_grad_scaled(y4_handle h, int n, const int32_t* records_dev, const i
 int y4_block_adam(y4_handle h, const float* dk_dev, float* k_dev, float* m_dev, float* v_dev, size_t n_floats, float lr,
                   float beta1, float beta2, float epsilon, int t, void* stream);
 
+/* ---- Cached frozen features.  Everything in front of the trainable convs is frozen, so for an image whose pixels do not change
+ * the tensors the handle retains (y4_set_retain_head_inputs) are the same in every epoch.  A cache ROW is what one image
+ * contributes at the handle's retention level, dense (no channel stride) in the handle's storage dtype, the three scales back to
+ * back in the order of the heads (stride 8, 16, 32), each [rows, columns, channels]:
+ *     level 1: the outputs of convs 92 / 100 / 108 (the head convs' inputs),
+ *     level 2: the outputs of convs 91 / 99 / 107  (the inputs of convs 92 / 100 / 108).
+ * The cache is caller-owned device memory of cache_rows * row_bytes bytes, 16-byte aligned.  A step on cached rows is
+ * y4_feature_load -> y4_forward_tail -> y4_loss / y4_head_grad / y4_block_grad* / y4_get_heads / y4_decode_nms as after y4_forward;
+ * by the canonical K order (a conv gives the same bits in whatever launch it runs) the results have the bits of the full forward. */
+
+/* *row_bytes: the bytes of one row, a multiple of 256; offs[k]: the byte offset of scale k's tensor in it (each a multiple of
+ * 256; the bytes between one tensor's end and the next offset are padding that no call reads or writes).  Either may be null.
+ * Y4_ESTATE at retention level 0. */
+int y4_feature_row_bytes(y4_handle h, size_t* row_bytes, size_t offs[3]);
+/* After a forward of n images: image i's retained tensors are copied out of the workspace views into row slots_host[i] of the
+ * cache.  ONE launch for the three scales and the n images (per 256 images), no host synchronisation: slots_host is a HOST
+ * array that is read before the call returns and travels as a kernel argument.  A slot outside [0, cache_rows), a slot named
+ * twice, n outside [1, max_batch] or a null / misaligned cache: Y4_EINVAL before anything is launched. */
+int y4_feature_store(y4_handle h, int n, const int64_t* slots_host, void* cache_dev, size_t cache_rows, void* stream);
+/* The inverse: row slots_host[i] is written into batch position i of the same views (a row may be named more than once).
+ * Same launch, same refusals bar the repeated slot. */
+int y4_feature_load(y4_handle h, int n, const int64_t* slots_host, const void* cache_dev, size_t cache_rows, void* stream);
+/* Runs only the convs behind the cached tensors on what the workspace holds for n images -- level 1: convs 93 / 101 / 109;
+ * level 2: convs 92, 93, 100, 101, 108, 109, in plan order -- and leaves the raw heads, the objectness side array and, at level
+ * 2, the stored outputs of convs 92 / 100 / 108 as y4_forward leaves them.  A conv of the tail that the schedule fuses with a
+ * conv outside the tail runs as its own launch (level 1: the LDS pair 92 -> 93); a run wholly inside the tail runs as the
+ * schedule says.  Y4_ESTATE at retention level 0. */
+int y4_forward_tail(y4_handle h, int n, void* stream);
+
 /* Replaces inference_model.predict(imgs) (reference models.py:69-73,113,159) = forward + decode + NMS. */
 int y4_predict(y4_handle h, const float* imgs_nhwc_dev, int n, float* boxes_dev, float* scores_dev,
                float* classes_dev, int32_t* valid_dev, int32_t* kept_idx_dev, void* stream);

@@ -306,4 +306,23 @@ size_t block_grad_scratch_bytes(int dtype, int n, const int* gh, const int* gw, 
                                 size_t* part_off);
 int block_grad_launch(int dtype, const GradK& k, const BlockK& b, int n, hipStream_t stream);
 
+// feature_cache.hip: the retained tensors of a batch <-> dense cache rows, in 16-byte chunks.  A row is the three scales' tensors
+// back to back; chunk r of a row belongs to the scale k with first[k] <= r, lies at chunk (r - first[k]) of that scale's
+// tensor, i.e. in pixel (r - first[k]) / cpp[k] of the view, and at byte off[k] + 16 (r - first[k]) of the row.
+constexpr int FEATURE_MAX_IMAGES = 256;      // images of one launch: their slots travel in the kernel argument
+struct FeatureK {
+    char* view[3];                   // the view's buffer at batch position 0
+    uint64_t img_stride[3];          // bytes from one batch position of the buffer to the next
+    uint32_t pix_stride[3], coff[3]; // bytes from one pixel to the next, and of the view's first channel
+    uint32_t first[3];               // a scale's first chunk in the row (first[0] = 0)
+    uint32_t off[3];                 // a scale's byte offset in the row
+    FastDiv cpp[3];                  // chunks of one pixel (channels * element size / 16)
+    FastDiv row;                     // chunks of a row without its padding; d = their number
+    uint32_t total;                  // chunks of the launch: images * row.d < 2^31
+    uint64_t row_bytes;
+    char* cache;
+    int32_t slot[FEATURE_MAX_IMAGES];
+};
+int feature_copy_launch(const FeatureK& k, bool store, hipStream_t stream);
+
 }  // namespace y4

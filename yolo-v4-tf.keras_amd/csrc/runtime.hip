@@ -1741,6 +1741,113 @@ int y4_block_adam(y4_handle h, const float* dk, float* w, float* m, float* v, si
     return adam_step(h, BLOCKS, "y4_block_adam", dk, w, m, v, n_floats, lr, beta1, beta2, epsilon, t, stream);
 }
 
+// ---- cached frozen features (feature_cache.hip)
+
+// the op whose INPUT view scale i's part of a cache row mirrors: the head conv at level 1, the 3x3 conv in front of it at level 2
+static const Op* feature_op(y4_handle h, int i) { return h->retain_block_in ? block_op(h, i) : head_op(h, i); }
+
+// the row layout and, with k, the views' side of a copy
+static int feature_layout(y4_handle h, const char* who, FeatureK* k, size_t* row_bytes, size_t* offs) {
+    Y4_REQUIRE(h->retain_head_in, Y4_ESTATE, "%s: the handle retains nothing (y4_set_retain_head_inputs before the workspace is bound)", who);
+    size_t off = 0, chunks = 0;
+    for (int i = 0; i < 3; ++i) {
+        const Op* o = feature_op(h, i);
+        Y4_REQUIRE(o != nullptr, Y4_EINVAL, "%s: no conv in front of head %d", who, i);
+        const View& v = o->in;
+        const size_t px_bytes = (size_t)v.c * h->es, bytes = (size_t)v.h * v.w * px_bytes;
+        Y4_REQUIRE(px_bytes % 16 == 0 && ((size_t)v.cstride * h->es) % 16 == 0 && ((size_t)v.coff * h->es) % 16 == 0, Y4_EINVAL,
+                   "%s: scale %d's view (%d channels at %d of %d) is not made of 16-byte chunks", who, i, v.c, v.coff, v.cstride);
+        if (offs) offs[i] = off;
+        if (k) {
+            const Buffer& b = h->bufs[v.buf];
+            k->view[i] = h->act ? buf_ptr(h, v) : nullptr;
+            k->img_stride[i] = (uint64_t)b.h * b.w * b.channels * h->es;
+            k->pix_stride[i] = (uint32_t)(v.cstride * h->es);
+            k->coff[i] = (uint32_t)(v.coff * h->es);
+            k->first[i] = (uint32_t)chunks;
+            k->off[i] = (uint32_t)off;
+            k->cpp[i] = fastdiv_make((uint32_t)(px_bytes / 16));
+        }
+        chunks += bytes / 16;
+        off = align256(off + bytes);
+    }
+    Y4_REQUIRE(chunks < (1u << 30), Y4_EINVAL, "%s: a row of %zu bytes", who, off);
+    if (k) { k->row = fastdiv_make((uint32_t)chunks); k->row_bytes = off; }
+    if (row_bytes) *row_bytes = off;
+    return Y4_OK;
+}
+
+int y4_feature_row_bytes(y4_handle h, size_t* row_bytes, size_t offs[3]) {
+    if (int r = check_handle(h)) return r;
+    return feature_layout(h, "y4_feature_row_bytes", nullptr, row_bytes, offs);
+}
+
+// y4_feature_store / y4_feature_load: every refusal first, then one launch per FEATURE_MAX_IMAGES images and 2^31 chunks
+static int feature_copy(y4_handle h, const char* who, bool store, int n, const int64_t* slots, void* cache, size_t cache_rows, void* stream) {
+    if (int r = check_handle(h)) return r;
+    FeatureK k{};
+    if (int r = feature_layout(h, who, &k, nullptr, nullptr)) return r;
+    Y4_REQUIRE(h->act, Y4_ESTATE, "%s: workspace not bound (call y4_bind_workspace first)", who);
+    Y4_REQUIRE(n >= 1 && n <= h->cfg.max_batch, Y4_EINVAL, "%s: batch %d outside [1, max_batch=%d]", who, n, h->cfg.max_batch);
+    Y4_REQUIRE(slots && cache, Y4_EINVAL, "%s: null argument", who);
+    Y4_REQUIRE(((uintptr_t)cache & 15) == 0, Y4_EINVAL, "%s: the cache must be 16-byte aligned", who);
+    for (int i = 0; i < 3; ++i) Y4_REQUIRE(((uintptr_t)k.view[i] & 15) == 0, Y4_EINVAL, "%s: the workspace is not 16-byte aligned", who);
+    const int64_t rows = (int64_t)std::min<size_t>(cache_rows, (size_t)INT32_MAX);
+    for (int i = 0; i < n; ++i)
+        Y4_REQUIRE(slots[i] >= 0 && slots[i] < rows, Y4_EINVAL, "%s: slot %lld of image %d outside [0, %lld)", who, (long long)slots[i], i,
+                   (long long)rows);
+    if (store) {
+        std::vector<int64_t> seen(slots, slots + n);
+        std::sort(seen.begin(), seen.end());
+        const auto dup = std::adjacent_find(seen.begin(), seen.end());
+        Y4_REQUIRE(dup == seen.end(), Y4_EINVAL, "%s: slot %lld is named twice", who, dup == seen.end() ? 0ll : (long long)*dup);
+    }
+    k.cache = (char*)cache;
+    const int per_launch = (int)std::min<uint32_t>(FEATURE_MAX_IMAGES, ((1u << 31) - 1) / k.row.d);
+    for (int i0 = 0; i0 < n; i0 += per_launch) {
+        const int cnt = std::min(per_launch, n - i0);
+        FeatureK g = k;
+        for (int i = 0; i < 3; ++i) g.view[i] += (uint64_t)i0 * g.img_stride[i];
+        for (int i = 0; i < cnt; ++i) g.slot[i] = (int32_t)slots[i0 + i];
+        g.total = (uint32_t)cnt * g.row.d;
+        if (int r = feature_copy_launch(g, store, (hipStream_t)stream)) return r;
+    }
+    return Y4_OK;
+}
+
+int y4_feature_store(y4_handle h, int n, const int64_t* slots_host, void* cache_dev, size_t cache_rows, void* stream) {
+    return feature_copy(h, "y4_feature_store", true, n, slots_host, cache_dev, cache_rows, stream);
+}
+int y4_feature_load(y4_handle h, int n, const int64_t* slots_host, const void* cache_dev, size_t cache_rows, void* stream) {
+    return feature_copy(h, "y4_feature_load", false, n, slots_host, (void*)cache_dev, cache_rows, stream);
+}
+
+int y4_forward_tail(y4_handle h, int n, void* stream) {
+    if (int r = check_ready(h, n)) return r;
+    Y4_REQUIRE(h->retain_head_in, Y4_ESTATE, "y4_forward_tail: the handle retains nothing (y4_set_retain_head_inputs before the workspace is bound)");
+    std::vector<int> tail;                               // the ops behind the cached tensors, in plan order
+    for (int i = 0; i < 3; ++i) {
+        const Op* ho = head_op(h, i);
+        const Op* bo = h->retain_block_in ? block_op(h, i) : nullptr;
+        Y4_REQUIRE(ho && (bo || !h->retain_block_in), Y4_EINVAL, "y4_forward_tail: no conv in front of head %d", i);
+        tail.push_back((int)(ho - h->ops.data()));
+        if (bo) tail.push_back((int)(bo - h->ops.data()));
+    }
+    std::sort(tail.begin(), tail.end());
+    auto in_tail = [&](int oi) { return oi < 0 || std::find(tail.begin(), tail.end(), oi) != tail.end(); };
+    // a run executes as one kernel here only when it lies wholly inside the tail; any other fusion would run convs in front of it
+    auto fused_here = [&](const Chain& ch) { return h->chain_active(ch) && in_tail(ch.head) && in_tail(ch.tail[0]) && in_tail(ch.tail[1]); };
+    for (int oi : tail) {
+        const OpExec ex = resolve_op(h, oi, true);
+        bool ran_with_head = false;
+        if (ex.kind == EX_SKIP)
+            for (const Chain& ch : h->chains) ran_with_head |= (ch.tail[0] == oi || ch.tail[1] == oi) && fused_here(ch);
+        if (ran_with_head) continue;
+        if (int r = run_op(h, oi, nullptr, n, (hipStream_t)stream, 0, ex.chain != nullptr && fused_here(*ex.chain))) return r;
+    }
+    return Y4_OK;
+}
+
 // forward + decode + NMS; when `ev` is given, ev[0] is recorded before the first op and ev[i+1] after op i
 static int predict_impl(y4_handle h, const void* imgs, int n, float* boxes, float* scores, float* classes,
                         int32_t* valid, int32_t* kept_idx, hipStream_t s, hipEvent_t* ev) {

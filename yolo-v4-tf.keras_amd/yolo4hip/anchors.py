@@ -36,7 +36,6 @@ def dataset_wh(annotation_lines, folder_path, img_size, letterbox=False):
     scale of `prepost.letterbox_rect` on both axes, applied as `augment.transform_boxes` applies it (float32-rounded scale, product
     and pad offset in float64, one cast to float32), then x2 - x1 in float32.  Every box is kept -- no shuffle, no cut to
     max_boxes, no clipping -- except rows with w <= 0 or h <= 0; a side that is not finite or exceeds 16384 raises ValueError."""
-    from PIL import Image
     if isinstance(img_size, (tuple, list, np.ndarray)):
         H, W = int(img_size[0]), int(img_size[1])
     else:
@@ -49,8 +48,7 @@ def dataset_wh(annotation_lines, folder_path, img_size, letterbox=False):
         boxes = np.array([[float(v) for v in f.split(',')] for f in fields[1:]], dtype=np.float32).reshape(-1, 5)
         if len(boxes) == 0:
             continue
-        with Image.open(os.path.join(folder_path, fields[0])) as im:
-            iw, ih = im.size                                              # the header: no pixel is decoded
+        ih, iw = prepost.image_hw(os.path.join(folder_path, fields[0]))   # the header: no pixel is decoded
         if letterbox:
             out_h, out_w, top, left = prepost.letterbox_rect(ih, iw, H, W)
             sx, sy = float(np.float32(out_w / iw)), float(np.float32(out_h / ih))

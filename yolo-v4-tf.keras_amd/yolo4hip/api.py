@@ -240,7 +240,7 @@ class Yolov4(object):
     # fine-tuning of the three detection convs on a frozen backbone and neck: in Keras terms every layer trainable = False
     # except conv 93 / 101 / 109.
     def fit(self, train_data_gen, epochs, val_data_gen=None, initial_epoch=0, callbacks=None, *, trainable=None,
-            learning_rate=1e-4, loss_scale=None, val_map=False):
+            learning_rate=1e-4, loss_scale=None, val_map=False, cache_features=False):
         """trainable='heads': Adam (the reference's compile, models.py:83; `learning_rate` replaces its 1e-4) on the weights and
         biases of the three detection convs.  Per batch: `train_data_gen.boxes(i)` -> one upload -> forward in chunks of
         max_batch -> labels assigned on the device -> y4_head_grad accumulated over the chunks (each image weighs 1 / batch
@@ -276,9 +276,32 @@ class Yolov4(object):
         LearningRateScheduler pattern) is asked at the start of every epoch; its result is that epoch's learning rate.
 
         val_map=True (needs `val_data_gen`): every epoch's logs and `.history` also hold 'val_mAP', `evaluate_map(val_data_gen)`'s
-        mAP at IoU 0.5 with the epoch's weights."""
+        mAP at IoU 0.5 with the epoch's weights.
+
+        cache_features=True, or an int byte budget (Keras' "bottleneck features"): everything in front of the trainable convs is
+        frozen, so with a generator that does not augment it computes the same tensors for an image in every epoch.  The first
+        epoch of the call runs as above and, after each chunk's forward, `Engine.store_features` copies what the engine retains
+        -- the head convs' inputs, with trainable='head_blocks' the inputs of convs 92 / 100 / 108 -- into a device cache, one row
+        per image at its annotation-line index (`train_data_gen.indexes`).  Every later epoch asks `train_data_gen.labels(i)`
+        instead of `boxes(i)` -- no photo is read, no image uploaded -- and per chunk runs `Engine.load_features` ->
+        `Engine.forward_tail_device` -> the same assignment, loss, gradient and Adam calls: `.history` and the trained weights
+        have the bits of the uncached call.  The cache lives for this call only (`load_model` may change the frozen weights
+        between calls).  Refused before any update: an augmenting generator and one without `indexes`, `batch_size` and
+        `labels` (ValueError); a cache larger than the budget, or with True than the free device memory (MemoryError naming the
+        bytes needed and the bytes per image).  `val_data_gen` is not cached.  False (default): the path above, call for call."""
         if val_map and val_data_gen is None:
             raise ValueError('fit: val_map=True needs val_data_gen')
+        caching = cache_features is not False
+        if caching:
+            if not isinstance(cache_features, (bool, int, np.integer)) or int(cache_features) < 1:
+                raise ValueError(f'fit: cache_features is False, True or a positive byte budget, got {cache_features!r}')
+            if getattr(train_data_gen, 'augment', None) is not None:
+                raise ValueError('fit: cache_features needs a generator that does not augment: an augmented image has other '
+                                 'pixels in every epoch, so there is nothing to cache')
+            missing = [a for a in ('indexes', 'batch_size', 'labels') if not hasattr(train_data_gen, a)]
+            if missing:
+                raise ValueError(f"fit: cache_features needs a generator with `indexes`, `batch_size` and `labels(i)` "
+                                 f"(yolo4hip.data.DataGenerator); this one lacks {', '.join(missing)}")
         if trainable not in ('heads', 'head_blocks'):
             raise NotImplementedError("training every layer is out of scope of the MI355X path; fit(..., trainable='heads') "
                                       "fine-tunes the three detection convs on a frozen backbone and neck, "
@@ -303,6 +326,19 @@ class Yolov4(object):
         grad = {g: torch.empty((eng._group_floats(g),), dtype=torch.float32, device=eng.device) for g in groups}
         augment = getattr(train_data_gen, 'augment', None)
         mosaic = augment is not None and getattr(augment, 'mosaic', 0) > 0
+        cache = None
+        if caching:
+            rows, row_bytes = int(np.max(train_data_gen.indexes)) + 1, eng.feature_row_bytes()[0]
+            if cache_features is True:
+                with torch.cuda.device(eng.device):       # what the driver has free and what torch holds without using it
+                    budget = torch.cuda.mem_get_info()[0] + torch.cuda.memory_reserved() - torch.cuda.memory_allocated()
+                what = 'bytes of device memory are free'
+            else:
+                budget, what = int(cache_features), 'bytes is the budget (cache_features)'
+            if rows * row_bytes > budget:
+                raise MemoryError(f'fit: the feature cache needs {rows * row_bytes} bytes ({rows} images, {row_bytes} bytes per '
+                                  f'image at {self.img_size} in {self._dtype} with trainable={trainable!r}); {budget} {what}')
+            cache = eng.alloc_feature_cache(rows)
         history = {'loss': []}
         if val_data_gen is not None:
             history['val_loss'] = []
@@ -316,8 +352,14 @@ class Yolov4(object):
                 if hasattr(cb, 'schedule'):
                     learning_rate = float(cb.schedule(epoch, learning_rate))
             total, images, skipped = 0.0, 0, 0
+            cached = cache is not None and epoch > int(initial_epoch)      # the first epoch of the call fills the cache
             for i in range(len(train_data_gen)):
-                if mosaic:
+                if cache is not None:                   # the batch's rows: the annotation-line indices of its images
+                    bs = int(train_data_gen.batch_size)
+                    idxs = np.asarray(train_data_gen.indexes[i * bs:(i + 1) * bs], dtype=np.int64)
+                if cached:
+                    boxes = train_data_gen.labels(i)
+                elif mosaic:
                     raws, tile_src, params, cuts, boxes = train_data_gen.raw_mosaic(i)
                 elif augment is not None:
                     raws, params, boxes = train_data_gen.raw(i)
@@ -329,16 +371,26 @@ class Yolov4(object):
                 elif augment is not None:
                     X = eng.augment_u8_batch(raws, params, pad_value=augment.pad_value)
                 count = boxes_dev.shape[0]
+                if cache is not None and len(idxs) != count:
+                    raise ValueError(f'labels for {count} images, but the generator names {len(idxs)} of them in `indexes`')
                 weight = torch.full((count,), 1.0 / count, dtype=torch.float32, device=eng.device)
                 parts, i0 = [], 0
                 if policy is not None:
                     overflow.zero_()
                 scaled = {'blocks': (policy.scale, overflow)} if policy is not None else {}
-                for chunk in eng._chunks(X):
-                    n = chunk.shape[0]
-                    if i0 + n > count:
-                        raise ValueError(f'labels for {count} images, the images are more')
-                    eng.forward_device(chunk)
+                # a cached epoch: a chunk is a range of cache rows, loaded where the forward would have left them
+                for chunk in (range(0, count, eng.max_batch) if cached else eng._chunks(X)):
+                    if cached:
+                        n = min(eng.max_batch, count - chunk)
+                        eng.load_features(cache, idxs[i0:i0 + n])
+                        eng.forward_tail_device(n)
+                    else:
+                        n = chunk.shape[0]
+                        if i0 + n > count:
+                            raise ValueError(f'labels for {count} images, the images are more')
+                        eng.forward_device(chunk)
+                        if cache is not None:
+                            eng.store_features(cache, idxs[i0:i0 + n])
                     labels = eng.assign_device(boxes_dev[i0:i0 + n])
                     for g in groups:
                         eng._group_grad_device(g, n, None, labels, self.iou_loss_thresh, weight[i0:i0 + n], grad[g], i0 > 0,

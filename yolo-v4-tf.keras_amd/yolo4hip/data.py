@@ -250,6 +250,7 @@ class DataGenerator:
         self.max_boxes = max_boxes
         self.augment = augment
         self.rng = np.random.default_rng(seed)              # augmentation parameters only
+        self._sizes = {}                                    # path field -> (h, w) of the image as first read (`labels`)
         self.on_epoch_end()
 
     def __len__(self):
@@ -344,11 +345,26 @@ class DataGenerator:
         own pixels, shuffled (global np.random) and cut to max_boxes)."""
         fields = annotation_line.split()
         img = prepost.imread_rgb(os.path.join(self.folder_path, fields[0]))
+        self._sizes[fields[0]] = img.shape[:2]
+        return img, self._read_boxes(fields)
+
+    def _read_boxes(self, fields):
+        """The boxes of one split annotation line, shuffled (global np.random: one draw per line with a box) and cut to max_boxes."""
         boxes = np.array([[float(v) for v in f.split(',')] for f in fields[1:]], dtype=np.float32)
         if len(boxes) > 0:
             np.random.shuffle(boxes)
             boxes = boxes[:self.max_boxes]
-        return img, boxes
+        return boxes
+
+    def _stretch_boxes(self, boxes, ih, iw):
+        """Boxes in the pixels of an ih x iw image -> [max_boxes, 5] at the network input (float32 products, zero padded)."""
+        h, w = self.target_img_size[:2]
+        box_data = np.zeros((self.max_boxes, 5))
+        if len(boxes) > 0:
+            boxes[:, [0, 2]] = boxes[:, [0, 2]] * (w / iw)
+            boxes[:, [1, 3]] = boxes[:, [1, 3]] * (h / ih)
+            box_data[:len(boxes)] = boxes
+        return box_data
 
     def get_data(self, annotation_line):
         """One annotation line "path x1,y1,x2,y2,cls ..." -> (image [H, W, 3] in [0, 1], boxes [max_boxes, 5] scaled to it)."""
@@ -356,9 +372,22 @@ class DataGenerator:
         ih, iw = img.shape[:2]
         h, w = self.target_img_size[:2]
         image_data = prepost.resize_bilinear(img, (w, h)) / 255.
-        box_data = np.zeros((self.max_boxes, 5))
-        if len(boxes) > 0:
-            boxes[:, [0, 2]] = boxes[:, [0, 2]] * (w / iw)
-            boxes[:, [1, 3]] = boxes[:, [1, 3]] * (h / ih)
-            box_data[:len(boxes)] = boxes
-        return image_data, box_data
+        return image_data, self._stretch_boxes(boxes, ih, iw)
+
+    def labels(self, index):
+        """Batch `index` -> boxes float32 [n, max_boxes, 5]: `boxes(index)[1]` bit for bit, without decoding a photo, and with the
+        same draws from the global np.random in the same order (the per-image box shuffle), so that a run that calls `labels`
+        where another calls `boxes` stays aligned with it -- what `Yolov4.fit(cache_features=True)` does from its second epoch
+        on.  The image size the stretch needs is the one this generator saw when it first read the line; for a line it has not
+        read, the image header (`prepost.image_hw`: no pixel is decoded).  An augmenting generator raises ValueError: its boxes
+        follow parameters drawn per batch, and its pixels differ every epoch."""
+        if self.augment is not None:
+            raise ValueError("DataGenerator.labels: this generator augments; its boxes come with its pixels (raw / boxes)")
+        idxs = self.indexes[index * self.batch_size:(index + 1) * self.batch_size]
+        y_bbox = np.empty((len(idxs), self.max_boxes, 5), dtype=np.float32)
+        for i, j in enumerate(idxs):
+            fields = self.annotation_lines[j].split()
+            if fields[0] not in self._sizes:
+                self._sizes[fields[0]] = prepost.image_hw(os.path.join(self.folder_path, fields[0]))
+            y_bbox[i] = self._stretch_boxes(self._read_boxes(fields), *self._sizes[fields[0]])
+        return y_bbox

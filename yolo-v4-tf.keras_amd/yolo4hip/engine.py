@@ -860,6 +860,50 @@ class Engine:
         with self.torch.cuda.device(self.device):
             ext.check(self.lib.y4_forward_until(self.handle, ext.ptr(imgs_dev), n, int(last_conv), ext.stream_ptr()))
 
+    # ---------------------------------------------------------------- cached frozen features
+    def feature_row_bytes(self):
+        """y4_feature_row_bytes -> (bytes of one cache row, the three scales' byte offsets in it): what one image contributes at
+        this engine's retention level -- level 1 the head convs' inputs, level 2 the inputs of convs 92 / 100 / 108 -- dense, in
+        the engine's dtype.  An engine that retains nothing raises Y4Error (Y4_ESTATE)."""
+        row, offs = C.c_size_t(), (C.c_size_t * 3)()
+        ext.check(self.lib.y4_feature_row_bytes(self.handle, C.byref(row), offs))
+        return row.value, tuple(int(o) for o in offs)
+
+    def alloc_feature_cache(self, rows):
+        """A cache of `rows` rows: a uint8 cuda tensor [rows, row_bytes] that owns the memory (not initialised)."""
+        rows = int(rows)
+        if rows < 1:
+            raise ValueError(f"alloc_feature_cache: {rows} rows")
+        return self.torch.empty((rows, self.feature_row_bytes()[0]), dtype=self.torch.uint8, device=self.device)
+
+    def _feature_copy(self, fn, who, cache, slots):
+        torch = self.torch
+        row = self.feature_row_bytes()[0]
+        if not isinstance(cache, torch.Tensor) or cache.dtype != torch.uint8 or cache.dim() != 2 or cache.shape[1] != row \
+                or not cache.is_contiguous() or cache.device != self.device:
+            raise ValueError(f"{who}: the cache must be a contiguous uint8 tensor [rows, {row}] on {self.device} (alloc_feature_cache)")
+        slots = np.ascontiguousarray(slots, dtype=np.int64).reshape(-1)      # host memory: read before the call returns
+        with torch.cuda.device(self.device):
+            ext.check(fn(self.handle, len(slots), slots.ctypes.data_as(C.POINTER(C.c_int64)), ext.ptr(cache), cache.shape[0],
+                         ext.stream_ptr()))
+
+    def store_features(self, cache, slots):
+        """After `forward_device` of len(slots) images: image i's retained tensors -> row slots[i] of `cache` (y4_feature_store, one
+        launch, asynchronous on the current stream).  A slot outside the cache or named twice raises Y4Error before any launch."""
+        self._feature_copy(self.lib.y4_feature_store, "store_features", cache, slots)
+
+    def load_features(self, cache, slots):
+        """Row slots[i] of `cache` -> batch position i of the retained tensors in the workspace (y4_feature_load); follow it with
+        `forward_tail_device(len(slots))`."""
+        self._feature_copy(self.lib.y4_feature_load, "load_features", cache, slots)
+
+    def forward_tail_device(self, n):
+        """y4_forward_tail: only the convs behind the cached tensors, on what the workspace holds for n images.  Afterwards the
+        raw heads are those `forward_device` of the same images leaves, bit for bit, and `loss_device`, the gradient calls,
+        `heads_device` and `decode_nms_device` work as after it."""
+        with self.torch.cuda.device(self.device):
+            ext.check(self.lib.y4_forward_tail(self.handle, int(n), ext.stream_ptr()))
+
     def heads_device(self, n):
         torch = self.torch
         outs = [torch.empty((n, gh, gw, self.nout), dtype=torch.float32, device=self.device) for gh, gw in self.grids_hw]

@@ -123,6 +123,10 @@ SYMBOLS = {
     "y4_block_grad": (_I, [_VP, _I, _VP, _VP, _VP, _I, _F, _VP, _VP, C.c_size_t, _VP, C.c_size_t, _I, _VP]),
     "y4_block_grad_scaled": (_I, [_VP, _I, _VP, _VP, _VP, _I, _F, _VP, _F, _VP, _VP, C.c_size_t, _VP, C.c_size_t, _I, _VP]),
     "y4_block_adam": (_I, [_VP, _VP, _VP, _VP, _VP, C.c_size_t, _F, _F, _F, _F, _I, _VP]),
+    "y4_feature_row_bytes": (_I, [_VP, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
+    "y4_feature_store": (_I, [_VP, _I, C.POINTER(C.c_int64), _VP, C.c_size_t, _VP]),
+    "y4_feature_load": (_I, [_VP, _I, C.POINTER(C.c_int64), _VP, C.c_size_t, _VP]),
+    "y4_forward_tail": (_I, [_VP, _I, _VP]),
     "y4_predict": (_I, [_VP, _VP, _I, _VP, _VP, _VP, _VP, _VP, _VP]),
     "y4_predict_u8": (_I, [_VP, _VP, _I, _VP, _VP, _VP, _VP, _VP, _VP]),
     "y4_profile": (_I, [_VP, _VP, _I, _VP, _VP, _I, C.POINTER(_I), _VP]),

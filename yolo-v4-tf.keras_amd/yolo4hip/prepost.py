@@ -30,6 +30,14 @@ def imread_rgb(path):
         raise TypeError("'NoneType' object is not subscriptable") from None
 
 
+def image_hw(path):
+    """(height, width) of an image file from its header: no pixel is decoded."""
+    from PIL import Image
+    with Image.open(path) as im:
+        iw, ih = im.size
+    return ih, iw
+
+
 def _linear_coeffs(dst, src):
     scale = src / dst
     f = (np.arange(dst, dtype=np.float64) + 0.5) * scale - 0.5
