@@ -289,156 +289,29 @@ class Yolov4(object):
         between calls).  Refused before any update: an augmenting generator and one without `indexes`, `batch_size` and
         `labels` (ValueError); a cache larger than the budget, or with True than the free device memory (MemoryError naming the
         bytes needed and the bytes per image).  `val_data_gen` is not cached.  False (default): the path above, call for call."""
-        if val_map and val_data_gen is None:
-            raise ValueError('fit: val_map=True needs val_data_gen')
-        caching = cache_features is not False
-        if caching:
-            if not isinstance(cache_features, (bool, int, np.integer)) or int(cache_features) < 1:
-                raise ValueError(f'fit: cache_features is False, True or a positive byte budget, got {cache_features!r}')
-            if getattr(train_data_gen, 'augment', None) is not None:
-                raise ValueError('fit: cache_features needs a generator that does not augment: an augmented image has other '
-                                 'pixels in every epoch, so there is nothing to cache')
-            missing = [a for a in ('indexes', 'batch_size', 'labels') if not hasattr(train_data_gen, a)]
-            if missing:
-                raise ValueError(f"fit: cache_features needs a generator with `indexes`, `batch_size` and `labels(i)` "
-                                 f"(yolo4hip.data.DataGenerator); this one lacks {', '.join(missing)}")
-        if trainable not in ('heads', 'head_blocks'):
-            raise NotImplementedError("training every layer is out of scope of the MI355X path; fit(..., trainable='heads') "
-                                      "fine-tunes the three detection convs on a frozen backbone and neck, "
-                                      "trainable='head_blocks' also the 3x3 convs in front of them")
-        groups = ('heads', 'blocks') if trainable == 'head_blocks' else ('heads',)
-        scaling = 'blocks' in groups and self._dtype == 'f16'
-        if scaling and loss_scale is None:
-            raise NotImplementedError("fit(trainable='head_blocks') on an f16 model: a 16-bit gradient in fp16 needs loss scaling; "
-                                      "pass loss_scale='dynamic' or a power of two (or use dtype 'bf16' or 'f32')")
-        if loss_scale is not None and not scaling:
-            raise ValueError("fit: loss_scale is for trainable='head_blocks' on an f16 model; there is nothing to scale on "
-                             f"a {self._dtype} model with trainable={trainable!r}")
-        from .engine import combine_loss
-        from .loss_scale import make_loss_scale
-        policy = make_loss_scale(loss_scale) if scaling else None
+        from . import fitloop
+        groups, policy = fitloop.check_arguments(train_data_gen, val_data_gen, trainable, loss_scale, val_map, cache_features,
+                                                 self._dtype, self.max_boxes)
         self._ensure_tuned()
-        if getattr(train_data_gen, 'max_boxes', self.max_boxes) != self.max_boxes:
-            raise ValueError(f"the generator's max_boxes {train_data_gen.max_boxes} != config['max_boxes'] {self.max_boxes}")
         eng = self._train_engine(2 if 'blocks' in groups else 1)
-        torch = eng.torch
         state = {g: eng._group_state(g, self._flat) for g in groups}
-        grad = {g: torch.empty((eng._group_floats(g),), dtype=torch.float32, device=eng.device) for g in groups}
-        augment = getattr(train_data_gen, 'augment', None)
-        mosaic = augment is not None and getattr(augment, 'mosaic', 0) > 0
+        grad = {g: eng.torch.empty((eng._group_floats(g),), dtype=eng.torch.float32, device=eng.device) for g in groups}
         cache = None
-        if caching:
-            rows, row_bytes = int(np.max(train_data_gen.indexes)) + 1, eng.feature_row_bytes()[0]
-            if cache_features is True:
-                with torch.cuda.device(eng.device):       # what the driver has free and what torch holds without using it
-                    budget = torch.cuda.mem_get_info()[0] + torch.cuda.memory_reserved() - torch.cuda.memory_allocated()
-                what = 'bytes of device memory are free'
-            else:
-                budget, what = int(cache_features), 'bytes is the budget (cache_features)'
-            if rows * row_bytes > budget:
-                raise MemoryError(f'fit: the feature cache needs {rows * row_bytes} bytes ({rows} images, {row_bytes} bytes per '
-                                  f'image at {self.img_size} in {self._dtype} with trainable={trainable!r}); {budget} {what}')
-            cache = eng.alloc_feature_cache(rows)
-        history = {'loss': []}
-        if val_data_gen is not None:
-            history['val_loss'] = []
-            if val_map:
-                history['val_mAP'] = []
-        if policy is not None:
-            history['loss_scale'], history['skipped_steps'] = [], []
-            overflow = torch.zeros((1,), dtype=torch.int32, device=eng.device)
-        for epoch in range(int(initial_epoch), int(epochs)):
-            for cb in callbacks or []:
-                if hasattr(cb, 'schedule'):
-                    learning_rate = float(cb.schedule(epoch, learning_rate))
-            total, images, skipped = 0.0, 0, 0
-            cached = cache is not None and epoch > int(initial_epoch)      # the first epoch of the call fills the cache
-            for i in range(len(train_data_gen)):
-                if cache is not None:                   # the batch's rows: the annotation-line indices of its images
-                    bs = int(train_data_gen.batch_size)
-                    idxs = np.asarray(train_data_gen.indexes[i * bs:(i + 1) * bs], dtype=np.int64)
-                if cached:
-                    boxes = train_data_gen.labels(i)
-                elif mosaic:
-                    raws, tile_src, params, cuts, boxes = train_data_gen.raw_mosaic(i)
-                elif augment is not None:
-                    raws, params, boxes = train_data_gen.raw(i)
-                else:
-                    X, boxes = train_data_gen.boxes(i)
-                boxes_dev = torch.from_numpy(eng._check_boxes(boxes)).to(eng.device)     # ValueError before any update
-                if mosaic:
-                    X = eng.mosaic_u8_batch(raws, tile_src, params, cuts, pad_value=augment.pad_value)
-                elif augment is not None:
-                    X = eng.augment_u8_batch(raws, params, pad_value=augment.pad_value)
-                count = boxes_dev.shape[0]
-                if cache is not None and len(idxs) != count:
-                    raise ValueError(f'labels for {count} images, but the generator names {len(idxs)} of them in `indexes`')
-                weight = torch.full((count,), 1.0 / count, dtype=torch.float32, device=eng.device)
-                parts, i0 = [], 0
-                if policy is not None:
-                    overflow.zero_()
-                scaled = {'blocks': (policy.scale, overflow)} if policy is not None else {}
-                # a cached epoch: a chunk is a range of cache rows, loaded where the forward would have left them
-                for chunk in (range(0, count, eng.max_batch) if cached else eng._chunks(X)):
-                    if cached:
-                        n = min(eng.max_batch, count - chunk)
-                        eng.load_features(cache, idxs[i0:i0 + n])
-                        eng.forward_tail_device(n)
-                    else:
-                        n = chunk.shape[0]
-                        if i0 + n > count:
-                            raise ValueError(f'labels for {count} images, the images are more')
-                        eng.forward_device(chunk)
-                        if cache is not None:
-                            eng.store_features(cache, idxs[i0:i0 + n])
-                    labels = eng.assign_device(boxes_dev[i0:i0 + n])
-                    for g in groups:
-                        eng._group_grad_device(g, n, None, labels, self.iou_loss_thresh, weight[i0:i0 + n], grad[g], i0 > 0,
-                                               *scaled.get(g, ()))
-                    parts.append(eng.loss_device(n, records=labels, iou_loss_thresh=self.iou_loss_thresh))
-                    i0 += n
-                if i0 != count:
-                    raise ValueError(f'labels for {count} images, but {i0} images')
-                # heads first, and every gradient of the batch before the first step: y4_block_grad must see the head weights
-                # the forward used.  The steps share their t.  An overflow of the scaled block gradient skips the step of both.
-                if policy is not None:
-                    parts.append(overflow.to(torch.float32).expand(1, *parts[0].shape[1:]))
-                losses = torch.cat(parts).cpu().numpy()                     # one copy: the loss and the overflow word
-                if policy is None or policy.update(bool(losses[-1].flat[0] != 0)):
-                    for g in groups:
-                        eng._group_adam_step(g, state[g], grad[g], lr=learning_rate)
-                else:
-                    skipped += 1
-                total += float(combine_loss(losses[:-1] if policy is not None else losses)[0].sum())
-                images += count
-            if images == 0:
-                raise ValueError('fit: the generator is empty')
-            # the trained heads reach the host stream and the inference engine at the end of every epoch
-            for g in groups:
-                eng._group_weights_to_flat(g, state[g], self._flat)
-            self.engine.load_weight_blob(self._flat)
-            logs = {'loss': total / images}
+        if cache_features is not False:
+            cache = fitloop.alloc_feature_cache(eng, train_data_gen, cache_features,
+                                                f'at {self.img_size} in {self._dtype} with trainable={trainable!r}')
+        val_names = () if val_data_gen is None else ('val_loss', 'val_mAP') if val_map else ('val_loss',)
+
+        def validate():
+            logs = {}
             if val_data_gen is not None:
                 logs['val_loss'] = self.evaluate(val_data_gen)['loss']
                 if val_map:
                     logs['val_mAP'] = self.evaluate_map(val_data_gen)['mAP']
-            for k, v in logs.items():
-                history[k].append(v)
-            if policy is not None:
-                history['loss_scale'].append(policy.scale)
-                history['skipped_steps'].append(skipped)
-            print(f'Epoch {epoch + 1}/{int(epochs)} - ' + ' - '.join(f'{k}: {v:.4f}' for k, v in logs.items()))
-            if hasattr(train_data_gen, 'on_epoch_end'):
-                train_data_gen.on_epoch_end()
-            for cb in callbacks or []:
-                if hasattr(cb, 'on_epoch_end'):
-                    cb.on_epoch_end(epoch, logs)
-
-        class History:
-            pass
-        out = History()
-        out.history, out.epoch = history, list(range(int(initial_epoch), int(epochs)))
-        return out
+            return logs
+        return fitloop.run(eng, train_data_gen, groups, state, grad, self._flat, self.iou_loss_thresh,
+                           self.engine.load_weight_blob, validate, val_names, epochs, initial_epoch, callbacks, learning_rate,
+                           policy, cache)
 
     def _train_engine(self, level=1):
         """The engine `fit` runs on: created on the first `fit`, with the head convs' inputs retained (the inference engine keeps

@@ -1110,6 +1110,21 @@ class Engine:
         for i in range(0, t.shape[0], self.max_batch):     # Keras predict() chunks too (batch_size=32), invisibly
             yield t[i:i + self.max_batch]
 
+    def _paired_chunks(self, imgs, count, rows="labels"):
+        """`_chunks(imgs)` walked beside `count` per-image rows (the labels; rows="box_map": predict's map rows) -> (index of the
+        chunk's first image, chunk).  ValueError before a chunk is handed out that has no rows, and at the end when rows are left
+        over.  count None: nothing to pair, nothing refused."""
+        more, left = {"labels": ("labels for {count} images, the images are more", "labels for {count} images, but {i0} images"),
+                      "box_map": ("box_map has {count} rows, the images are more", "box_map has {count} rows for {i0} images")}[rows]
+        i0 = 0
+        for chunk in self._chunks(imgs):
+            if count is not None and i0 + chunk.shape[0] > count:
+                raise ValueError(more.format(count=count))
+            yield i0, chunk
+            i0 += chunk.shape[0]
+        if count is not None and i0 != count:
+            raise ValueError(left.format(count=count, i0=i0))
+
     def forward_heads(self, imgs):
         """yolo_model.predict(imgs): list of 3 float32 numpy arrays [N,g,g,3(C+5)] (raw logits)."""
         parts = [[], [], []]
@@ -1129,19 +1144,13 @@ class Engine:
             torch = self.torch
             bm = box_map if isinstance(box_map, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(box_map, np.float32))
             box_map = bm.to(self.device, dtype=torch.float32).contiguous()
-        i0 = 0
-        for chunk in self._chunks(imgs):
+        for i0, chunk in self._paired_chunks(imgs, None if box_map is None else box_map.shape[0], "box_map"):
             n = chunk.shape[0]
             self.forward_device(chunk)
             bm = None if box_map is None else box_map[i0:i0 + n]
-            if bm is not None and bm.shape[0] != n:
-                raise ValueError(f"box_map has {box_map.shape[0]} rows, the images are more")
             outs = self.decode_nms_device(n, None, iou_threshold, score_threshold, box_map=bm)
-            i0 += n
             for i, o in enumerate(outs):
                 acc[i].append(o.cpu().numpy())
-        if box_map is not None and i0 != box_map.shape[0]:
-            raise ValueError(f"box_map has {box_map.shape[0]} rows for {i0} images")
         res = [np.concatenate(p, axis=0) for p in acc]
         return res if with_indices else res[:4]
 
@@ -1232,20 +1241,15 @@ class Engine:
         else:
             triple = self.upload_records(records, true_xywh)
             count = len(records)
-        parts, i0 = [], 0
-        for chunk in self._chunks(imgs):
+        parts = []
+        for i0, chunk in self._paired_chunks(imgs, count):
             n = chunk.shape[0]
-            if i0 + n > count:
-                raise ValueError(f"labels for {count} images, the images are more")
             self.forward_device(chunk)
             if boxes is not None:
                 out = self.loss_device(n, boxes_dev=boxes_dev[i0:i0 + n], iou_loss_thresh=iou_loss_thresh)
             else:
                 out = self.loss_device(n, records=tuple(t[i0:i0 + n] for t in triple), iou_loss_thresh=iou_loss_thresh)
             parts.append(out.cpu().numpy())
-            i0 += n
-        if i0 != count:
-            raise ValueError(f"labels for {count} images, but {i0} images")
         return np.concatenate(parts, axis=0)
 
     # ---------------------------------------------------------------- fine-tuning (csrc/head_train.hip, csrc/block_train.hip)
