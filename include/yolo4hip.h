@@ -103,6 +103,41 @@ int y4_set_workspace_aliasing(y4_handle h, int on);
 int y4_workspace_bytes(y4_handle h, size_t* act_bytes, size_t* wts_bytes);
 int y4_bind_workspace(y4_handle h, void* act_dev, size_t act_bytes, void* wts_dev, size_t wts_bytes);
 
+/* A read-only map of the `act` workspace under the handle's current layout (aliasing, retention): one row per region, sorted by
+ * offset; the rows cover [0, act_bytes) up to alignment gaps of at most 255 bytes.  Host-only, valid before the workspace is bound.
+ *   Y4_WS_ZERO     the library keeps these bytes zero between calls: the zero page (never written), the candidate counters (the NMS
+ *                  kernel of a list resets its counter; a decode not followed by its NMS makes the next decode clear them), the NMS
+ *                  status word (only ever OR-ed, on a list overflow that the worst-case capacity rules out; nothing resets it),
+ *                  the split-K tile counters (the last workgroup to arrive at a tile resets its counter)
+ *   Y4_WS_ACT      one activation buffer, [max_batch] images of image_bytes each; first_op / last_op: its lifetime in op-index time as
+ *                  the aliasing layout reads it (ACT rows share bytes under y4_set_workspace_aliasing, and only then)
+ *   Y4_WS_TAIL     state of the detection tail: decoded boxes, candidate keys, the objectness side array (per image), and the
+ *                  output scratch of y4_profile (image_bytes 0: packed for the n of the call)
+ *   Y4_WS_SCRATCH  meaningless between calls: the split-K partial sums
+ * Every region but the ZERO ones may hold anything when a call begins: no result depends on it. */
+#define Y4_WS_ZERO 0
+#define Y4_WS_ACT 1
+#define Y4_WS_TAIL 2
+#define Y4_WS_SCRATCH 3
+typedef struct y4_workspace_row {
+    char name[24];
+    int32_t kind;              /* Y4_WS_* */
+    int32_t buffer;            /* ACT: the buffer's number in the plan (row name "act<buffer>"); else -1 */
+    int32_t first_op, last_op; /* ACT: lifetime, op indices (last_op = the op count: outlives the forward); else -1 */
+    uint64_t offset, bytes;    /* bytes: what the region holds for max_batch images, without alignment slack */
+    uint64_t image_bytes;      /* bytes == max_batch * image_bytes where the region is per image, else 0 */
+} y4_workspace_row;                                  /* 64 bytes */
+/* Writes min(capacity, count) rows and the row count (rows_out may be NULL with capacity 0). */
+int y4_workspace_map(y4_handle h, y4_workspace_row* rows_out, int capacity, int* count_out);
+/* Where conv `conv_idx` stores its output: the index of its ACT row in y4_workspace_map's order, and the channel offset and
+ * channel stride (elements) of its view in that buffer's NHWC pixels -- what y4_get_conv_output reads.  materialised (may be NULL):
+ * 1 when a forward under the current fusion switches writes that view, 0 while a fused kernel keeps the tensor on chip -- conv 0
+ * under stem fusion, convs 2 .. 6 under the stage kernel, the 1x1 conv of a residual-block kernel, and inside a run that executes
+ * as one kernel everything but its last conv and a head whose output has other readers.  y4_get_conv_output refuses the first
+ * three; for a conv inside a run it copies the view as it is, i.e. what an earlier call left there.  Host-only. */
+int y4_conv_output_view(y4_handle h, int conv_idx, int32_t* row, int32_t* channel_offset, int32_t* channel_stride,
+                        int32_t* materialised);
+
 /* Replaces utils.load_weights (reference utils.py:12-53) + Keras set_weights: `darknet_floats_dev` is the
  * float32 stream of a Darknet .weights file after its 20-byte header, already on the device: for conv
  * 0..109, [beta,gamma,mean,var] x cout (or cout biases for convs 93/101/109), then cout*cin*k*k weights in

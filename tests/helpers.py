@@ -216,9 +216,11 @@ def tap_snapshot(eng, n):
         eng._lt = eng.layer_table()
     snap = {}
     if not eng.alias_workspace:
+        dims = (C.c_int32 * 4)()
         for i, lt in enumerate(eng._lt):
-            side = lt["out_side"] * (2 if i in (78, 85) else 1)
-            out = torch.empty((n, side, side, lt["cout"]), dtype=torch.float32, device=eng.device)
+            ext.check(eng.lib.y4_layer_dims(eng.handle, i, dims))          # (out_side is -1 on a rectangular engine)
+            up = 2 if i in (78, 85) else 1
+            out = torch.empty((n, dims[2] * up, dims[3] * up, lt["cout"]), dtype=torch.float32, device=eng.device)
             if eng.lib.y4_get_conv_output(eng.handle, i, n, ext.ptr(out), out.numel(), ext.stream_ptr()) == 0:
                 snap[f"conv{i}"] = out
     for k, h in enumerate(eng.heads_device(n)):
@@ -250,3 +252,136 @@ def first_tap_difference(a, b, eng=None):
             msg += f" [k{lt['ksize']} s{lt['stride']} {lt['cin']}->{lt['cout']} @{lt['out_side']}]"
         return msg
     return None
+
+
+# ---------------------------------------------------------------- poisoned workspace (tests/test_gpu_poisoned_workspace.py)
+# Two byte patterns, because each alone is blind: 0xFF.. is a NaN in float32, bfloat16 and float16, which fmaxf, the packed max of
+# SPP and every `score > threshold` compare drop silently; 0x47.. is finite and positive (5.1e4 in float32 and bfloat16, 7.3 in
+# float16), survives a max and passes every threshold.
+POISON_NAN, POISON_FINITE = 0xFF, 0x47
+KEY_SCORE_BITS = 0x3F800000          # 1.0f: no real score (obj * class probability, both sigmoids) is larger
+
+
+def key_poison(words, id_limit, device):
+    """`words` candidate keys no decode wrote, as int64: a poison that is harmless as an address.  A key is (score bits << 32) | ~id,
+    id = box * C + class (csrc/candidates.h), and the NMS kernels gather a box by the index they decode from it WITHOUT a range
+    check (nms_phases.h: nms_load_boxes), so plain bytes (0xFF..: id 0 happens to be valid; 0x47..: id 0xB8B8B8B8 is far outside
+    any table) will not do.  Word i holds id i % id_limit -- inside the table for every list the suite builds, and unique within
+    a list as the sorts assume (nms_rank_sort) -- under the best score a key can have, 1.0: a kernel that reads one stale key
+    sorts it to the FRONT of its list and keeps it, so the result changes, but no index leaves its buffer."""
+    import torch
+    ids = torch.arange(words, dtype=torch.int64, device=device) % int(id_limit)
+    return (KEY_SCORE_BITS << 32) | (~ids & 0xFFFFFFFF)
+
+
+def _gaps(rows, act_bytes):
+    """the alignment slack between the regions: [(offset, bytes)] of what no row covers"""
+    out, covered = [], 0
+    for r in rows:
+        if r["offset"] > covered:
+            out.append((covered, r["offset"] - covered))
+        covered = max(covered, r["offset"] + r["bytes"])
+    if act_bytes > covered:
+        out.append((covered, act_bytes - covered))
+    return out
+
+
+def _poison_row(eng, r, byte):
+    act = eng.act
+    part = act[r["offset"]:r["offset"] + r["bytes"]]
+    if r["name"] == "keys":            # per image a list of cap = nbox * C keys: every id below cap is a (box, class) of the table
+        cap = r["image_bytes"] // 8
+        part.view(eng.torch.int64).view(-1, cap).copy_(key_poison(cap, cap, act.device).expand(eng.max_batch, cap))
+    else:
+        part.fill_(byte)
+
+
+def poison(eng, kinds, byte):
+    """Fill every row of `eng.workspace_map()` whose kind is in `kinds` ('act', 'tail', 'scratch'), and the alignment gaps between
+    the regions, with `byte` -- the candidate keys with `key_poison` instead.  'zero' rows are the library's own and are refused.
+    -> bytes poisoned."""
+    assert kinds and set(kinds) <= {"act", "tail", "scratch"}, kinds
+    rows = eng.workspace_map()
+    total = 0
+    spans = []
+    for r in rows:
+        if r["kind"] in kinds:
+            _poison_row(eng, r, byte)
+            spans.append((r["offset"], r["offset"] + r["bytes"]))
+    for off, nbytes in _gaps(rows, eng.act_bytes):
+        eng.act[off:off + nbytes].fill_(byte)
+        spans.append((off, off + nbytes))
+    covered = 0
+    for lo, hi in sorted(spans):       # (ACT rows of an aliased layout share bytes: count each byte once)
+        total += max(0, hi - max(lo, covered))
+        covered = max(covered, hi)
+    eng.torch.cuda.synchronize()
+    return total
+
+
+def unowned_bytes_intact(eng, n, byte, kinds=("act", "tail")):
+    """After calls on n images of a NON-aliased engine whose workspace was poisoned with `byte`: the image slots >= n of every ACT
+    row and of every per-image TAIL row (`kinds`: where only some were poisoned), and every gap between regions, still hold the
+    poison byte for byte -- no kernel stored past what the call owns.  (That they do also shows the poison lay where a stray read would have met it.)
+    -> (bytes checked, None) or (bytes checked, a description of the first row that was written to)."""
+    torch = eng.torch
+    assert not eng.alias_workspace, "slots >= n of an aliased row are other tensors' memory"
+    rows = eng.workspace_map()
+    checked = 0
+    for r in rows:
+        if r["kind"] not in kinds or not r["image_bytes"]:
+            continue
+        part = eng.act[r["offset"] + n * r["image_bytes"]:r["offset"] + r["bytes"]]
+        if not part.numel():
+            continue
+        if r["name"] == "keys":
+            cap = r["image_bytes"] // 8
+            bad = part.view(torch.int64).view(-1, cap) != key_poison(cap, cap, part.device)
+        else:
+            bad = part != byte
+        checked += part.numel()
+        if bool(bad.any()):
+            at = int(bad.reshape(-1).nonzero()[0]) * (8 if r["name"] == "keys" else 1)
+            return checked, (f"row {r['name']} ({r['kind']}, {r['image_bytes']} B per image): {int(bad.sum())} "
+                             f"{'keys' if r['name'] == 'keys' else 'bytes'} of images >= {n} were overwritten, the first at byte {at} of "
+                             f"that part = image {n + at // r['image_bytes']}, byte {at % r['image_bytes']}")
+    for off, nbytes in _gaps(rows, eng.act_bytes):
+        part = eng.act[off:off + nbytes]
+        checked += nbytes
+        if bool((part != byte).any()):
+            return checked, f"the {nbytes} B gap at offset {off} was written to"
+    return checked, None
+
+
+def fresh_bind(eng):
+    """Bind the engine's workspaces again: y4_bind_workspace zeroes the whole activation workspace, the packed weights stay."""
+    from yolo4hip import ext
+    ext.check(eng.lib.y4_bind_workspace(eng.handle, ext.ptr(eng.act), eng.act_bytes, ext.ptr(eng.wts), eng.wts_bytes))
+    eng.adopt_packed()
+
+
+class PoisonedEmpty:
+    """`with PoisonedEmpty(eng, byte):` every tensor the engine's methods allocate with torch.empty inside the block -- the loss
+    scratch, the head-gradient partials, `_block_scratch`, and the outputs -- starts as `byte`s, not as what the caching allocator
+    happens to hand out."""
+    def __init__(self, eng, byte):
+        self.eng, self.byte, self.bytes, self.real = eng, byte, 0, eng.torch
+
+    def __getattr__(self, name):
+        return getattr(self.real, name)
+
+    def empty(self, *a, **kw):
+        t = self.real.empty(*a, **kw)
+        if t.is_cuda and t.numel():
+            t.view(-1).view(self.real.uint8).fill_(self.byte)
+            self.bytes += t.numel() * t.element_size()
+        return t
+
+    def __enter__(self):
+        self.real = self.eng.torch
+        self.eng.torch = self
+        return self
+
+    def __exit__(self, *exc):
+        self.eng.torch = self.real
+        return False

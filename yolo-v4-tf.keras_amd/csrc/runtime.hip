@@ -1075,6 +1075,83 @@ int y4_workspace_bytes(y4_handle h, size_t* act_bytes, size_t* wts_bytes) {
     return Y4_OK;
 }
 
+// Does the forward write conv `conv_idx`'s output view under the current switches?  Not while a fused kernel keeps it on chip: conv 0
+// under stem fusion, convs 2 .. 6 under the stage kernel, the 1x1 conv of a residual-block kernel, and inside a run that executes as
+// one kernel everything but its last tail and -- where it has other readers (stores_x) -- its head.
+static bool conv_materialised(y4_handle h, int oi, int conv_idx) {
+    if (h->sched.fuse_stem && conv_idx == 0) return false;
+    if (h->stage_active() && oi >= h->stage_first && oi < h->stage_last) return false;
+    if (h->heads_res(oi)) return false;
+    for (const Chain& ch : h->chains) {
+        if (!h->chain_active(ch) || resolve_op(h, ch.head, true).chain != &ch) continue;
+        if (ch.head == oi && (ch.alt_of >= 0 || !h->stores_x(ch))) return false;
+        if (ch.tail[0] == oi && ch.tail[1] >= 0) return false;
+    }
+    return true;
+}
+
+// The regions layout() placed, sorted by offset (ACT rows of an aliased layout share bytes; rows at one offset: the larger first).
+static void workspace_rows(const y4_ctx& c, std::vector<y4_workspace_row>& rows) {
+    rows.clear();
+    auto add = [&](const char* name, int kind, size_t off, size_t bytes, size_t image_bytes, int buf = -1, int first = -1, int last = -1) {
+        y4_workspace_row r{};
+        snprintf(r.name, sizeof(r.name), "%s", name);
+        r.kind = kind; r.buffer = buf; r.first_op = first; r.last_op = last;
+        r.offset = off; r.bytes = bytes; r.image_bytes = image_bytes;
+        rows.push_back(r);
+    };
+    const size_t nb = (size_t)c.cfg.max_batch;
+    std::vector<int> first, last;
+    buffer_lifetimes(c, first, last);
+    add("zero_page", Y4_WS_ZERO, c.zero_off, ZERO_PAGE_BYTES, 0);
+    for (size_t i = 0; i < c.bufs.size(); ++i) {
+        char name[16];
+        snprintf(name, sizeof(name), "act%zu", i);
+        add(name, Y4_WS_ACT, c.bufs[i].offset, c.bufs[i].bytes, c.bufs[i].bytes / nb, (int)i, first[i], last[i]);
+    }
+    add("boxes", Y4_WS_TAIL, c.dbox_off, nb * c.nbox * 16, (size_t)c.nbox * 16);
+    add("keys", Y4_WS_TAIL, c.keys_off, nb * (size_t)c.cand_cap * 8, (size_t)c.cand_cap * 8);
+    add("counts", Y4_WS_ZERO, c.counts_off, nb * 4 * COUNT_STRIDE, 4 * COUNT_STRIDE);
+    add("status", Y4_WS_ZERO, c.status_off, 256, 0);
+    // (y4_profile's outputs: five arrays packed for the n of the call, so no fixed bytes per image)
+    add("nms_scratch", Y4_WS_TAIL, c.scratch_off, nb * (size_t)c.cfg.max_total * 28 + nb * 4, 0);
+    add("splitk_counters", Y4_WS_ZERO, c.splitk_off, SPLITK_CNT_BYTES, 0);
+    add("splitk_partials", Y4_WS_SCRATCH, c.splitk_off + SPLITK_CNT_BYTES, SPLITK_WS_BYTES - SPLITK_CNT_BYTES, 0);
+    add("objectness", Y4_WS_TAIL, c.obj_off, nb * (size_t)c.cells_per_img * 16, (size_t)c.cells_per_img * 16);
+    std::stable_sort(rows.begin(), rows.end(), [](const y4_workspace_row& a, const y4_workspace_row& b) {
+        return a.offset != b.offset ? a.offset < b.offset : a.bytes > b.bytes;
+    });
+}
+
+int y4_workspace_map(y4_handle h, y4_workspace_row* rows_out, int capacity, int* count_out) {
+    if (int r = check_handle(h)) return r;
+    Y4_REQUIRE(count_out && capacity >= 0 && (rows_out || capacity == 0), Y4_EINVAL, "y4_workspace_map: null argument");
+    std::vector<y4_workspace_row> rows;
+    workspace_rows(*h, rows);
+    *count_out = (int)rows.size();
+    for (int i = 0; i < capacity && i < (int)rows.size(); ++i) rows_out[i] = rows[i];
+    return Y4_OK;
+}
+
+int y4_conv_output_view(y4_handle h, int conv_idx, int32_t* row, int32_t* channel_offset, int32_t* channel_stride, int32_t* materialised) {
+    if (int r = check_handle(h)) return r;
+    Y4_REQUIRE(row && channel_offset && channel_stride, Y4_EINVAL, "y4_conv_output_view: null argument");
+    for (const Op& op : h->ops) {
+        if (op.kind == OP_SPP || (op.conv != conv_idx && op.conv2 != conv_idx)) continue;
+        const View& v = op.conv == conv_idx ? op.out : op.out2;
+        std::vector<y4_workspace_row> rows;
+        workspace_rows(*h, rows);
+        for (size_t i = 0; i < rows.size(); ++i)
+            if (rows[i].kind == Y4_WS_ACT && rows[i].buffer == v.buf) {
+                *row = (int32_t)i; *channel_offset = v.coff; *channel_stride = v.cstride;
+                if (materialised) *materialised = conv_materialised(h, (int)(&op - h->ops.data()), conv_idx) ? 1 : 0;
+                return Y4_OK;
+            }
+    }
+    set_error("no conv with index %d", conv_idx);
+    return Y4_EINVAL;
+}
+
 int y4_bind_workspace(y4_handle h, void* act_dev, size_t act_bytes, void* wts_dev, size_t wts_bytes) {
     if (int r = check_handle(h)) return r;
     Y4_REQUIRE(act_dev && wts_dev, Y4_EINVAL, "y4_bind_workspace: null workspace");

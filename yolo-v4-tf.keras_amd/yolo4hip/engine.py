@@ -396,6 +396,15 @@ class Engine:
     def adopt_packed(self):
         ext.check(self.lib.y4_adopt_packed_weights(self.handle))
 
+    def workspace_map(self):
+        """The regions of `self.act` (y4_workspace_map): a list of dicts sorted by offset, see `ext.workspace_map`."""
+        return ext.workspace_map(self.lib, self.handle)
+
+    def conv_output_view(self, conv_idx):
+        """(row index in `workspace_map`, channel offset, channel stride, materialised) of the view conv `conv_idx` stores its
+        output in; materialised is False while a fused kernel keeps that tensor on chip (`conv_output` then shows stale bytes)"""
+        return ext.conv_output_view(self.lib, self.handle, conv_idx)
+
     def layer_table(self):
         n = self.lib.y4_num_layers(self.handle)
         out = []

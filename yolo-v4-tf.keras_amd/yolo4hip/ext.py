@@ -37,6 +37,15 @@ class y4_layer_desc(C.Structure):
                 ("out_side", C.c_int32), ("weight_offset", C.c_int64)]
 
 
+WS_ZERO, WS_ACT, WS_TAIL, WS_SCRATCH = 0, 1, 2, 3
+WS_KIND_NAMES = {WS_ZERO: "zero", WS_ACT: "act", WS_TAIL: "tail", WS_SCRATCH: "scratch"}
+
+
+class y4_workspace_row(C.Structure):
+    _fields_ = [("name", C.c_char * 24), ("kind", C.c_int32), ("buffer", C.c_int32), ("first_op", C.c_int32),
+                ("last_op", C.c_int32), ("offset", C.c_uint64), ("bytes", C.c_uint64), ("image_bytes", C.c_uint64)]
+
+
 class y4_conv_desc(C.Structure):
     _fields_ = [("dtype", C.c_int32), ("n", C.c_int32), ("h", C.c_int32), ("w", C.c_int32), ("cin", C.c_int32),
                 ("cout", C.c_int32), ("ksize", C.c_int32), ("stride", C.c_int32), ("act", C.c_int32),
@@ -92,6 +101,8 @@ SYMBOLS = {
                            C.POINTER(C.c_int64)]),
     "y4_workspace_bytes": (_I, [_VP, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
     "y4_bind_workspace": (_I, [_VP, _VP, C.c_size_t, _VP, C.c_size_t]),
+    "y4_workspace_map": (_I, [_VP, C.POINTER(y4_workspace_row), _I, C.POINTER(_I)]),
+    "y4_conv_output_view": (_I, [_VP, _I, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "y4_pack_weights": (_I, [_VP, _VP, C.c_size_t, _VP]),
     "y4_adopt_packed_weights": (_I, [_VP]),
     "y4_forward": (_I, [_VP, _VP, _I, _VP]),
@@ -201,6 +212,25 @@ def load():
             fn.restype, fn.argtypes = res, args
         _lib = lib
     return _lib
+
+
+def workspace_map(lib, handle):
+    """y4_workspace_map as a list of dicts in the library's order (sorted by offset): name, kind ('zero' | 'act' | 'tail' |
+    'scratch'), buffer, first_op, last_op, offset, bytes, image_bytes.  Host-only: works on a handle with no workspace bound."""
+    count = C.c_int()
+    check(lib.y4_workspace_map(handle, None, 0, C.byref(count)))
+    rows = (y4_workspace_row * count.value)()
+    check(lib.y4_workspace_map(handle, rows, count.value, C.byref(count)))
+    return [dict(name=r.name.decode(), kind=WS_KIND_NAMES[r.kind], buffer=r.buffer, first_op=r.first_op, last_op=r.last_op,
+                 offset=int(r.offset), bytes=int(r.bytes), image_bytes=int(r.image_bytes)) for r in rows]
+
+
+def conv_output_view(lib, handle, conv_idx):
+    """y4_conv_output_view -> (row index in `workspace_map`, channel offset, channel stride, materialised) of conv `conv_idx`'s
+    output; materialised: does a forward under the current fusion switches write it?"""
+    row, coff, cstride, stored = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32()
+    check(lib.y4_conv_output_view(handle, conv_idx, C.byref(row), C.byref(coff), C.byref(cstride), C.byref(stored)))
+    return row.value, coff.value, cstride.value, bool(stored.value)
 
 
 def check(rc):
