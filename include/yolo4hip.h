@@ -629,6 +629,15 @@ int y4_set_res_fusion(y4_handle h, int on);
 int y4_get_res_fusion(y4_handle h);
 int y4_set_res_fusion_mask(y4_handle h, int mask);
 
+/* Host only (no device is touched): the tile table the residual-block kernel walks for a batch of n maps of h x w pixels with
+ * c (64 | 128) channels on `slots` workgroups (a multiple of 8: slots / 8 per XCD).  int32 quadruples: a header {grid, stride, a, b}
+ * -- workgroups of the launch, entries per list, and the two constants of a tile's cost a + b * rows -- followed by `grid` lists of
+ * `stride` entries {image, first output row, rows, tile column (16 pixels)}; a list ends at its first entry with rows = 0, and list i
+ * runs on XCD i % 8.  Every column of every image is cut into heights from {16, 12, 8, 4} (c = 128) or {16, 8} (c = 64) that cover
+ * its rows exactly once; only a column's last tile may hang over the lower edge, by less than the smallest height.
+ * Returns the number of int32 values of the table (> 0), written to `out` when cap is at least that; < 0 on error. */
+int y4_rb_tile_table(int32_t n, int32_t h, int32_t w, int32_t c, int32_t slots, int32_t* out, int32_t cap);
+
 /* Kernel launches of one y4_predict under the current fusion / tile settings (whole batch, no sub-batching):
  * `conv_family` = launches of the conv kernels other than the stem (what bench.py's roofline is quoted on),
  * `total` = all launches including stem, SPP, decode and NMS. */

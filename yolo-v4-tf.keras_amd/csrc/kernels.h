@@ -122,6 +122,8 @@ int pack_resblock(int dtype, int c, const float* w1, const float* scale1, const 
                   const float* shift3, void* blob, hipStream_t stream);
 int resblock_launch(int dtype, int c, const void* in, int n, int h, int w, int in_cstride, int in_coff, const void* blob, void* out,
                     int out_cstride, int out_coff, hipStream_t stream);
+// host only: the tile table of an (n, h, w) map with c channels on `slots` workgroups, as the kernel reads it (y4_rb_tile_table)
+int rb_tile_table(int n, int h, int w, int c, int slots, int32_t* out, int cap);
 
 // decode_nms.hip
 // Per-image candidate counters are spaced one per 256 bytes: packed into one cache line, the ~10^3 appends per

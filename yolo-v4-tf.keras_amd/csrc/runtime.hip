@@ -2306,6 +2306,10 @@ int y4_set_res_fusion_mask(y4_handle h, int mask) {
     return Y4_OK;
 }
 
+int y4_rb_tile_table(int32_t n, int32_t h, int32_t w, int32_t c, int32_t slots, int32_t* out, int32_t cap) {
+    return rb_tile_table(n, h, w, c, slots, out, cap);
+}
+
 int y4_set_splitk(y4_handle h, int on) {
     if (int r = check_handle(h)) return r;
     h->allow_splitk = on != 0;

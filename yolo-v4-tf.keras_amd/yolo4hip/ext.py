@@ -155,6 +155,7 @@ SYMBOLS = {
     "y4_set_res_fusion": (_I, [_VP, _I]),
     "y4_get_res_fusion": (_I, [_VP]),
     "y4_set_res_fusion_mask": (_I, [_VP, _I]),
+    "y4_rb_tile_table": (_I, [_I, _I, _I, _I, _I, C.POINTER(C.c_int32), _I]),
     "y4_launch_counts": (_I, [_VP, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "y4_timing_begin": (_I, [_VP, _I, _I]),
     "y4_timing_end": (_I, [_VP, _VP, _VP, _I, C.POINTER(_I), C.POINTER(_I), _VP]),
